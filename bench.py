@@ -1,13 +1,15 @@
 #!/usr/bin/env python
 """bench.py -- preintegration windows/sec on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--scaling weak|strong] [--no-extra] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--scaling weak|strong] [--dump-outputs DIR]
+                    [--full [--no-extra] [--no-cpu]]
 
 A "step" is one pass of the hot path (one cpi_preintegrate_batch / cpi_factor_eval_batch call) over one batch of
 synthetic windows already resident in HBM.  The default workload is BASELINE.json configs[1]: 10 000 windows x 50
 samples, CPI model 1, mean-only.  Successive steps walk a pool of distinct batches larger than the 256 MiB Infinity
 Cache, so the inputs really stream from HBM.  The K timed steps are replayed as ONE HIP graph (K kernel nodes, captured
-from the same calls; `config.launch_mode` says which mode ran -- eager launches are the fall-back).  Prints ONE JSON line
+from the same calls; beyond GRAPH_MAX_STEPS as replays of a graph of that many steps; `config.launch_mode` says which mode
+ran -- eager launches are the fall-back).  Prints ONE JSON line
 (rank 0).
 
 N > 1: one rank per GPU over RCCL.  Launched either by the driver (`python -m torch.distributed.run ... bench.py --gpus N`,
@@ -30,14 +32,17 @@ expected wall time of the timed region under the schedule in use, from the kerne
 exchange (`value_without_gather`) are reported beside `value`.  `--workload cfg5_mean | cfg5_full` is BASELINE configs[4]:
 1 M windows x 100 samples per GPU, generated on the device.
 
-Output contract (rank 0): the LAST stdout line is ONE JSON object of < 6 KB -- the headline (metric, value, ms_per_step,
-config, `roofline`, `cpu_baseline`), `value_full_integrator` (= configs2.value: `value` is the LIGHTEST configuration, mean-only) and
-`value_overlapped`, `goal_40pct_hbm`, a compact `configs2` object (BASELINE configs[2]), the end-to-end route
-table of a 1 M x 50 batch held as one IMU stream (`routes_1M_x_50`) and one [launch ms, roofline fraction] pair per extra row.
-The full extra rows (45 workloads incl. the SURVEY 8(f) rows, the packed-triangle rows of ABI 3 and the reference's own window
-lengths -- 10 / 20 samples, keyed `...@1Mx10` --, each with its own `roofline`, counters and `cpu_baseline`) are
-written to bench_extra.json beside this file (copied to gpurun_out/ when that directory exists); tests/test_gpu_bench.py runs
-the driver's command verbatim and checks both.  N > 1 adds `config.rccl` (what the collective library saw), `value_kernel_only`
+Output contract (rank 0): the LAST stdout line is ONE JSON object of < 6 KB.  A plain run sets up, warms up, times the K
+steps, writes the outputs of the last one (`--dump-outputs DIR`: DIR/<name>.npy, float64, a fixed sample of rows beyond 64 MB)
+and prints the headline: metric, value, unit, higher_is_better, dtype, ms_per_step (wall time of the K steps / K), config and
+the `roofline` of the timed kernel.  `--full` measures everything else in the same run: the CPU baseline (`cpu_baseline`), the
+overlapped rate of the headline workload (`overlapped`, `value_overlapped`) and the extra rows, with `value_full_integrator`
+(= configs2.value: `value` is the LIGHTEST configuration, mean-only), a compact `configs2` object (BASELINE configs[2]), the
+end-to-end route table of a 1 M x 50 batch held as one IMU stream (`routes_1M_x_50`) and one [launch ms, roofline fraction]
+pair per extra row in the line.  The full extra rows (45 workloads incl. the SURVEY 8(f) rows, the packed-triangle rows of
+ABI 3 and the reference's own window lengths -- 10 / 20 samples, keyed `...@1Mx10` --, each with its own `roofline`, counters
+and `cpu_baseline`) are written to bench_extra.json beside this file; tests/test_gpu_bench.py runs the driver's command
+verbatim, and with --full, and checks both.  N > 1 adds `config.rccl` (what the collective library saw), `value_kernel_only`
 and `gather_verified` (rank 0 recomputes every rank's last-step batch and compares the gathered blocks bitwise).
 """
 import argparse
@@ -64,6 +69,11 @@ PMC_FILE = os.path.join(ROOT, "profiles", "r06_pmc.json")
 # xGMI: AMD quotes 153.6 GB/s per Infinity Fabric link BIDIRECTIONAL (the "7 links x ~153 GB/s" of the MI355X platform); a gather
 # moves data ONE way, each peer over its own link into the root: 76.8 GB/s per peer is the wire's ceiling, before protocol overhead
 XGMI_LINK_GBS_ONE_WAY = 76.8
+# steps per captured HIP graph: a longer run replays it (capturing 400 000 steps as one graph crashed the process on the
+# MI355X, 100 000 did not); it is the default K, so runs up to it time ONE graph as before
+GRAPH_MAX_STEPS = 5000
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000   # --dump-outputs: the whole dump, .npy headers included
+DUMP_SAMPLE_SEED = 20190101           # --dump-outputs: the rows kept when the outputs are larger
 
 # name -> kind, model, default units per step, samples, algorithmic HBM bytes per unit at 50 samples (SURVEY.md 8(d):
 # read + write, f64, compulsory traffic only), dominant kernel.  kinds: "pre" preintegration (dense layout), "tiled" the
@@ -159,8 +169,14 @@ def parse(argv=None):
                          "cpi_group_gather_chunk)")
     ap.add_argument("--gather-chunks", type=int, default=8, help="sub-blocks per step of the chunked schedule")
     ap.add_argument("--eager", action="store_true", help="issue the K timed steps as K launches instead of replaying one HIP graph")
-    ap.add_argument("--no-extra", action="store_true", help="skip the additional BASELINE configs")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline legs, the overlapped rate and the additional "
+                         "BASELINE configs (bench_extra.json)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the additional BASELINE configs")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float64; a fixed sample of rows when they exceed "
+                         "%d MB)" % (DUMP_LIMIT_BYTES // 1000000))
     return ap.parse_args(argv)
 
 
@@ -297,6 +313,13 @@ class Workload:
         """The outputs step number i writes."""
         return self.out if self.is_factor else self.outs[i % len(self.outs)]
 
+    def outputs_of(self, i):
+        """What a caller of step number i receives: output name -> device tensor, one row per window / factor."""
+        out = self.out_of(i)
+        if isinstance(out, dict):
+            return {k: v for k, v in out.items() if not k.startswith("_")}
+        return {{"sqrt_info": "R", "predict": "x_j"}.get(self.kind, self.variant): out}    # the packed / Hessian sweeps: "packed", "hessian"
+
     def step(self):
         if self.is_factor:
             e = self.eng
@@ -318,6 +341,14 @@ class Workload:
         self.calls[self.i % len(self.calls)]()
         self.i += 1
         return out
+
+    def graph_steps(self, steps):
+        """Steps per captured graph for a run of `steps`: all of them up to GRAPH_MAX_STEPS, else a multiple of the walk's period
+        (the pre-bound (batch, output set) pairs), so that every replay starts where the next steps of one long graph would."""
+        if steps <= GRAPH_MAX_STEPS:
+            return steps
+        period = 1 if self.is_factor else len(self.calls)
+        return max(1, GRAPH_MAX_STEPS // period) * period
 
     def capture(self, steps):
         """The next `steps` steps as ONE HIP graph (a kernel node per launch; "V1 full" forks its side stream inside the
@@ -372,10 +403,15 @@ def time_steps(wl, steps, warmup, dist_on=False, gather="root", schedule="final"
     do_gather = dist_on and gather != "none" and not wl.is_factor
     pipelined = do_gather and schedule == "pipelined" and len(wl.outs) >= 2
     chunked = do_gather and schedule == "chunked" and getattr(wl, "k", 0) >= 1 and gather == "root"
-    g = wl.capture(steps) if (graph and not pipelined and not chunked) else None
-    if g is not None:
+    plan = []                                                # [(graph, replays)]: the K steps as replays of at most two graphs
+    if graph and not pipelined and not chunked:
+        per = wl.graph_steps(steps)
+        plan = [(wl.capture(n), reps) for n, reps in ((per, steps // per), (steps % per, 1)) if n]
+        if any(g is None for g, _ in plan):
+            plan = []                                        # a capture failed: eager launches
+    for g, _ in plan:
         g.replay()                                           # untimed: the first replay of a graph uploads it
-        torch.cuda.synchronize()
+    torch.cuda.synchronize()
     recv, side, gathered = [None, None], None, None
     if dist_on:
         if do_gather:
@@ -460,8 +496,10 @@ def time_steps(wl, steps, warmup, dist_on=False, gather="root", schedule="final"
         cur.wait_stream(side)
         e2.record(cur)
     else:
-        if g is not None:
-            g.replay()
+        if plan:
+            for g, reps in plan:
+                for _ in range(reps):
+                    g.replay()
             wl.i = i0 + steps
         else:
             for _ in range(steps):
@@ -475,8 +513,27 @@ def time_steps(wl, steps, warmup, dist_on=False, gather="root", schedule="final"
         dist.barrier()                               # closing barrier: outside the timed region
         torch.cuda.synchronize()
     return {"wall": wall, "kernel_ms": e0.elapsed_time(e1), "gather_ms": e1.elapsed_time(e2) if do_gather else 0.0,
-            "mode": ("chunked-eager" if chunked else ("pipelined-eager" if pipelined else ("graph" if g is not None else "eager"))),
-            "gathered": gathered, "last_step": i0 + steps - 1}
+            "mode": ("chunked-eager" if chunked else ("pipelined-eager" if pipelined else ("graph" if plan else "eager"))),
+            "graph_steps": wl.graph_steps(steps) if plan else 0, "gathered": gathered, "last_step": i0 + steps - 1}
+
+
+def dump_outputs(arrays, path, limit=DUMP_LIMIT_BYTES, seed=DUMP_SAMPLE_SEED):
+    """--dump-outputs: every array (name -> tensor, one row per window / factor, the same number of rows in all) as
+    path/<name>.npy in float64.  When the arrays together exceed `limit` bytes, the same fixed, seeded sample of rows (in
+    ascending order) is kept from each, so that two builds run with the same arguments write files that compare row for row."""
+    import numpy as np
+    rows = {t.shape[0] for t in arrays.values()}
+    assert len(rows) == 1, "the outputs of one step have one row per window / factor: %r" % {k: tuple(t.shape) for k, t in arrays.items()}
+    R = rows.pop()
+    row_bytes = sum(t[:1].numel() * 8 for t in arrays.values())
+    keep = min(R, (limit - 256 * len(arrays)) // row_bytes)          # 256 bytes per file for the .npy header (128 in practice)
+    idx = None if keep == R else torch.from_numpy(np.sort(np.random.default_rng(seed).choice(R, keep, replace=False)))
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        if idx is not None:
+            t = t.index_select(0, idx.to(t.device))
+        np.save(os.path.join(path, name + ".npy"), t.to(torch.float64).cpu().numpy())
+    return keep
 
 
 # ------------------------------------------------------------------------------------------------ CPU legs
@@ -853,7 +910,7 @@ def main():
         else:
             dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
     import cpi_amd
-    from cpi_amd.dist import shard_bounds
+    from cpi_amd.dist import shard_bounds, unshard
     eng = cpi_amd.Engine(device=local_rank)
     build_id = (eng.lib.cpi_build_id() or b"").decode()
     pmc_rows, pmc_note = load_pmc(build_id)
@@ -884,6 +941,10 @@ def main():
     preramp(wl, PRERAMP_MS)
     wl.i = 0     # the pre-ramp runs for a TIME, i.e. a rank-dependent number of steps: every rank walks the batch pool from the same index
     tm = time_steps(wl, a.steps, a.warmup, dist_on, a.gather, schedule, graph=not a.eager)
+    if a.dump_outputs and rank == 0:
+        # what the caller of the timed path holds after its last step: the gathered blocks at the root, else this rank's outputs
+        got = tm["gathered"]
+        dump_outputs(unshard(got, total_units) if got else wl.outputs_of(tm["last_step"]), a.dump_outputs)
     wall, kern_ms, gather_ms = tm["wall"], tm["kernel_ms"], tm["gather_ms"]
     wall_ng = None
     if do_gather:     # the same K steps without the exchange step, beside it
@@ -912,7 +973,8 @@ def main():
         "data": "synthetic" if not rehearsal else "synthetic (REHEARSAL: all ranks on one GPU, gloo exchange -- not a measurement)",
         "config": {"workload": "%s: %d %s x %d samples per GPU per step%s" % (a.workload, W, unit, N, cfg_note),
                    "pool_batches": wl.nbatch, "clock_preramp_ms": PRERAMP_MS, "library_build": build_id,
-                   "launch_mode": {"graph": "%d timed steps replayed as ONE HIP graph (one kernel node per step)" % a.steps,
+                   "launch_mode": {"graph": ("%d timed steps replayed as ONE HIP graph (one kernel node per step)" % a.steps if tm["graph_steps"] == a.steps else
+                                             "%d timed steps replayed as HIP graphs of %d steps (one kernel node per step)" % (a.steps, tm["graph_steps"])),
                                    "eager": "%d eager launches" % a.steps,
                                    "pipelined-eager": "%d eager launches, each followed by its gather on a side stream" % a.steps,
                                    "chunked-eager": "%d steps of %d sub-block launches, each sub-block's slab gathered on a side stream while the next "
@@ -929,8 +991,8 @@ def main():
         # batch alone takes 8.2 us = 0.45); said here, in the line, not only in prose
         res["goal_40pct_hbm"] = bool(res["roofline"]["frac"] >= 0.40)
         res["goal_note"] = ("north_star asks >= 0.40 of 8 TB/s: reached from ~17 k windows per launch (30 k: 0.47, 1 M: 0.57) or with several "
-                            "batches in flight (`overlapped`, this run); one 10 k-window launch is launch / first-burst bound")
-        if rank == 0 and world == 1 and not a.no_extra and W == 10000:
+                            "batches in flight (`overlapped`, measured with --full); one 10 k-window launch is launch / first-burst bound")
+        if rank == 0 and world == 1 and a.full and not a.no_extra and W == 10000:
             # the same workload issued through 2 / 3 / 4 engine contexts (HIP streams): consecutive launches overlap
             try:
                 per, gper = overlapped_rate(W, N, (2, 3, 4), 3000)
@@ -981,9 +1043,9 @@ def main():
     if do_gather and a.gather == "root":
         res["config"].update(verify_gather(eng, wl, tm, world, rank, base_seed, rehearsal))
     extra = None
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu:
         res["cpu_baseline"] = cpu_baseline(wl, 8.0)
-    if rank == 0 and world == 1 and not a.no_extra:
+    if rank == 0 and world == 1 and a.full and not a.no_extra:
         extra = []
         del wl
         torch.cuda.empty_cache()

@@ -97,3 +97,38 @@ def test_every_global_name_bench_py_uses_is_defined():
             local_scopes.add(node.name)
     missing = sorted({n.id for n in ast.walk(tree) if isinstance(n, ast.Name) and isinstance(n.ctx, ast.Load)} - defined - local_scopes)
     assert not missing, missing
+
+
+def test_parse_keeps_a_plain_run_plain():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert a.steps == 7 and a.warmup == 3 and not a.full and a.dump_outputs is None
+    a = bench.parse(["--steps", "7", "--full", "--no-cpu", "--dump-outputs", "d"])
+    assert a.full and a.no_cpu and not a.no_extra and a.dump_outputs == "d"
+
+
+def test_dump_outputs_whole_or_a_fixed_sample_of_rows(tmp_path):
+    """--dump-outputs: float64 .npy files named after the outputs; beyond the size limit the SAME seeded rows of every array, in
+    ascending order, and the same rows on every call."""
+    import os
+
+    import numpy as np
+    import torch
+    W = 1000
+    arrays = {"DT": torch.arange(W, dtype=torch.float64), "alpha": torch.arange(3 * W, dtype=torch.float64).view(W, 3) * 0.5,
+              "q": torch.arange(4 * W, dtype=torch.float32).view(W, 4)}
+    assert bench.dump_outputs(arrays, str(tmp_path / "whole")) == W
+    got = {f[:-4]: np.load(str(tmp_path / "whole" / f)) for f in os.listdir(str(tmp_path / "whole"))}
+    assert set(got) == set(arrays)
+    for k, v in arrays.items():
+        assert got[k].dtype == np.float64 and np.array_equal(got[k], v.double().numpy()), k
+    limit = 20000
+    for d in ("s1", "s2"):
+        keep = bench.dump_outputs(arrays, str(tmp_path / d), limit=limit)
+        assert 0 < keep < W
+        assert sum(os.path.getsize(str(tmp_path / d / f)) for f in os.listdir(str(tmp_path / d))) <= limit
+    s1 = {f[:-4]: np.load(str(tmp_path / "s1" / f)) for f in os.listdir(str(tmp_path / "s1"))}
+    s2 = {f[:-4]: np.load(str(tmp_path / "s2" / f)) for f in os.listdir(str(tmp_path / "s2"))}
+    rows = s1["DT"].astype(np.int64)
+    assert len(rows) == keep and (np.diff(rows) > 0).all()
+    assert np.array_equal(s1["alpha"], arrays["alpha"].numpy()[rows]) and np.array_equal(s1["q"], arrays["q"].double().numpy()[rows])
+    assert all(np.array_equal(s1[k], s2[k]) for k in s1)

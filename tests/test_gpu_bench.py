@@ -1,7 +1,9 @@
-"""GPU: the DRIVER's bench command, verbatim (`python bench.py --gpus 1 --steps 20 --warmup 5`, no shortening flags): the
-LAST stdout line is one JSON object small enough for the driver to keep whole (< 6 KB; round 3's line had grown to 33 KB and
-`BENCH_r03.parsed` came back null), carries the contract's keys, the roofline of the dominant kernel, the CPU baseline, a
-compact BASELINE configs[2] object, and names the file that holds the full extra rows."""
+"""GPU: the DRIVER's bench command, verbatim (`python bench.py --gpus 1 --steps 20 --warmup 5`, no shortening flags) and the
+same command with `--full`: the LAST stdout line is one JSON object small enough for the driver to keep whole (< 6 KB; round
+3's line had grown to 33 KB and `BENCH_r03.parsed` came back null) and carries the contract's keys and the roofline of the
+dominant kernel; the plain run measures nothing else, the --full run adds the CPU baseline, a compact BASELINE configs[2]
+object, and names the file that holds the full extra rows.  `--dump-outputs` writes the last step's outputs, the same ones
+from run to run."""
 import json
 import os
 import subprocess
@@ -15,21 +17,31 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DRIVER_ARGS = ["--gpus", "1", "--steps", "20", "--warmup", "5"]
 
 
-@pytest.fixture(scope="module")
-def driver_run():
+def _bench(args, timeout):
     extra_path = os.path.join(ROOT, "bench_extra.json")
     if os.path.exists(extra_path):
         os.remove(extra_path)
     t0 = time.perf_counter()
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + DRIVER_ARGS, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                       text=True, timeout=1500, cwd=ROOT)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       text=True, timeout=timeout, cwd=ROOT)
     wall = time.perf_counter() - t0
     assert p.returncode == 0, p.stderr[-3000:]
     return p.stdout, wall, extra_path
 
 
-def test_the_last_stdout_line_of_the_drivers_command_parses_and_is_small(driver_run):
-    stdout, wall, _ = driver_run
+@pytest.fixture(scope="module")
+def driver_run():
+    out = _bench(DRIVER_ARGS, 600)
+    assert not os.path.exists(out[2]), "a plain run measures the headline only"
+    return out
+
+
+@pytest.fixture(scope="module")
+def full_run():
+    return _bench(DRIVER_ARGS + ["--full"], 1500)
+
+
+def _contract_line(stdout, wall):
     lines = [ln for ln in stdout.splitlines() if ln.strip()]
     line = lines[-1]
     assert len(line) < 6000, len(line)
@@ -52,6 +64,18 @@ def test_the_last_stdout_line_of_the_drivers_command_parses_and_is_small(driver_
     assert abs(rf["achieved"] - rf["algorithmic_bytes_per_launch"] / (rf["launch_us"] * 1e-6) / 1e9) < 1e-6 * rf["achieved"]
     assert rf["launch_us"] * 1e-3 <= r["ms_per_step"] * 1.001                                      # kernel time <= step time
     assert rf["traffic"] is None or rf["traffic"] > 0.9 * rf["algorithmic_bytes_per_launch"]
+    return r
+
+
+def test_the_last_stdout_line_of_the_drivers_command_parses_and_is_small(driver_run, full_run):
+    plain = _contract_line(*driver_run[:2])
+    # the plain run: the headline and nothing that takes runs of its own
+    for k in ("cpu_baseline", "overlapped", "configs2", "routes_1M_x_50", "extra_rows", "extra_file"):
+        assert k not in plain, k
+    assert plain["value_full_integrator"] is None and plain["value_overlapped"] is None
+    assert plain["goal_40pct_hbm"] == (plain["roofline"]["frac"] >= 0.40)
+    r = _contract_line(*full_run[:2])
+    rf = r["roofline"]
     cb = r["cpu_baseline"]
     assert cb["kind"] in ("reference", "port") and cb["cores"] >= 1 and cb["value"] > 0 and cb["unit"] == "windows/s"
     assert cb["single_core_value"] > 0 and 0 < len(cb["sample"]) <= 200 and cb["sparse_port"]["value"] > 0
@@ -75,8 +99,8 @@ def test_the_last_stdout_line_of_the_drivers_command_parses_and_is_small(driver_
     assert "bench_extra.json" in r["extra_file"]
 
 
-def test_the_full_extra_rows_land_in_bench_extra_json(driver_run):
-    stdout, _, extra_path = driver_run
+def test_the_full_extra_rows_land_in_bench_extra_json(full_run):
+    stdout, _, extra_path = full_run
     r = json.loads([ln for ln in stdout.splitlines() if ln.strip()][-1])
     doc = json.load(open(extra_path))
     rows = doc["rows"]
@@ -107,10 +131,56 @@ def test_the_full_extra_rows_land_in_bench_extra_json(driver_run):
 
 
 def test_no_extra_no_cpu_still_prints_one_contract_line():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "50", "--warmup", "10", "--no-extra", "--no-cpu"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "50", "--warmup", "10", "--full", "--no-extra", "--no-cpu"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
     r = json.loads(lines[0])
     assert r["steps"] == 50 and "configs2" not in r and "cpu_baseline" not in r and "overlapped" not in r and r["roofline"]["frac"] > 0.05
+
+
+def test_dump_outputs_writes_the_last_steps_outputs_the_same_from_run_to_run(tmp_path):
+    """`--dump-outputs DIR`: the arrays the timed path returns in its last step (mean-only: DT, alpha, beta, q of the 10 k windows), float64,
+    bitwise the same in two runs with the same arguments (seeded inputs, one pass of the same kernels), and equal to an independent
+    recompute of the batch that LAST step reads.  K = 22, W = 5: the last step is step 26 of the walk, whose batch is neither the first
+    warm-up step's nor the first timed step's, so a dump of any step other than the last one of the walk's period fails."""
+    import numpy as np
+    import torch
+
+    import cpi_amd
+    from cpi_amd import synth
+    steps, warmup = 22, 5
+    args = ["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup)]
+    got = []
+    for d in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--dump-outputs", str(tmp_path / d)],
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-3000:]
+        r = json.loads(p.stdout.strip().splitlines()[-1])
+        assert r["steps"] == steps and r["warmup"] == warmup
+        got.append({f[:-4]: np.load(str(tmp_path / d / f)) for f in sorted(os.listdir(str(tmp_path / d)))})
+    a, b = got
+    assert set(a) == {"DT", "alpha", "beta", "q"}, sorted(a)
+    for k, v in a.items():
+        assert v.dtype == np.float64 and v.shape[0] == 10000 and np.isfinite(v).all(), k
+        assert np.array_equal(v, b[k]), k
+    assert (a["DT"] > 0).all() and np.allclose(np.linalg.norm(a["q"].reshape(10000, 4), axis=1), 1.0, atol=1e-12)
+    # the independent recompute: the pool's batch b is synth.make_windows(seed = 20190101 + 101 b) (bench.main: base_seed(rank 0) and
+    # Workload), the walk starts at step 0 after the clock pre-ramp, so step `warmup + steps - 1` reads batch (warmup + steps - 1) % pool
+    nb = r["config"]["pool_batches"]
+    last = warmup + steps - 1
+    assert last % nb not in (0, warmup % nb), nb
+    eng = cpi_amd.Engine(device=0)
+
+    def recompute(batch):
+        kn, lin, q = synth.make_windows(10000, 50, seed=20190101 + 101 * batch, device=eng.device)
+        out = eng.preintegrate(kn, lin, q, eng.make_params(1), want=("mean",))
+        torch.cuda.synchronize()
+        return {k: out[k].cpu().numpy().reshape(a[k].shape) for k in a}
+
+    want = recompute(last % nb)
+    for k, v in a.items():
+        assert np.abs(v - want[k]).max() <= 1e-12 * max(1.0, np.abs(want[k]).max()), k
+    before = recompute((last - 1) % nb)
+    assert not np.array_equal(before["alpha"], a["alpha"])      # the check tells the steps apart
