@@ -149,6 +149,10 @@ def load():
     lib.cpi_factor_hessian_batch.argtypes = [vp, i32, C.POINTER(C.c_double), i64, C.POINTER(CpiOutputs), dp, dp, dp, i64, vp, vp, dp, dp]
     lib.cpi_predict_batch.argtypes = [vp, i32, C.POINTER(C.c_double), i64, C.POINTER(CpiOutputs), dp, i64, vp, dp]
     lib.cpi_preintegrate_batch_host.argtypes = [vp, C.POINTER(CpiParams), i64, i32, dp, vp, vp, i64, dp, dp, C.POINTER(CpiOutputs)]
+    lib.cpi_carry_doubles.argtypes = [i32]
+    lib.cpi_carry_doubles.restype = C.c_size_t
+    lib.cpi_preintegrate_resume.argtypes = [vp, C.POINTER(CpiParams), i64, i32, dp, vp, vp, dp, dp, dp, dp, C.POINTER(CpiOutputs)]
+    lib.cpi_preintegrate_resume_host.argtypes = [vp, C.POINTER(CpiParams), i64, i32, dp, vp, vp, i64, dp, dp, dp, dp, C.POINTER(CpiOutputs)]
     lib.cpi_host_alloc.argtypes = [C.c_size_t]
     lib.cpi_host_alloc.restype = C.c_void_p
     lib.cpi_host_free.argtypes = [vp]
@@ -160,7 +164,8 @@ def load():
               lib.cpi_preintegrate_tiled_batch, lib.cpi_tile_knots, lib.cpi_group_create, lib.cpi_group_gather, lib.cpi_group_synchronize, lib.cpi_group_size, lib.cpi_ctx_set_stream,
               lib.cpi_tile_windows, lib.cpi_assemble_tiles, lib.cpi_preintegrate_tiled_batch_host, lib.cpi_outputs_bind_slab,
               lib.cpi_group_last_gather_messages, lib.cpi_preintegrate_stream_host, lib.cpi_sqrt_information_packed_batch,
-              lib.cpi_factor_eval_whitened_tri_batch, lib.cpi_factor_hessian_tri_batch, lib.cpi_group_gather_chunk):
+              lib.cpi_factor_eval_whitened_tri_batch, lib.cpi_factor_hessian_tri_batch, lib.cpi_group_gather_chunk,
+              lib.cpi_preintegrate_resume, lib.cpi_preintegrate_resume_host):
         f.restype = C.c_int
     _lib = lib
     return lib

@@ -358,6 +358,97 @@ static int preintegrate_impl(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int
     return CPI_OK;
 }
 
+// Resumable preintegration: cpi_preintegrate_batch from and to carry records (include/cpi_amd.h).  The same ownership rules
+// and lane choice as the batch entry, except that the means are always computed (into carry_out); the kernels are the
+// CARRY instantiations of the batch kernels (cpi_mean_carry_kernel / cpi_cov_carry_kernel), so a NULL carry_in reproduces
+// the batch call bit for bit.
+extern "C" size_t cpi_carry_doubles(int32_t model) { return (model == CPI_MODEL_V1 || model == CPI_MODEL_V2) ? (size_t)carry::doubles(model) : 0; }
+extern "C" int cpi_preintegrate_resume(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                       const double *knots, const int64_t *first, const int32_t *count,
+                                       const double *lin, const double *q_k_lin, const double *carry_in, double *carry_out,
+                                       const cpi_outputs *out) {
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (!prm || !out) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_resume: prm/out is NULL");
+    if (prm->model != CPI_MODEL_V1 && prm->model != CPI_MODEL_V2)
+        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_resume: model must be 1 or 2 (the Forster comparator cannot be resumed)");
+    if (!carry_out) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_resume: carry_out is NULL");
+    if (W < 0 || N < 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_resume: negative size");
+    const int CD = carry::doubles(prm->model);
+    if (carry_in && carry_in < carry_out + W * CD && carry_out < carry_in + W * CD)
+        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_resume: carry_in and carry_out overlap");
+    if (W == 0) return CPI_OK;
+    if (!knots || !lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_resume: knots/lin is NULL");
+    if (prm->model == CPI_MODEL_V2 && !q_k_lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_resume: model 2 needs q_k_lin");
+    if (!grid_ok(W)) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_resume: W exceeds 2^31 - 1 windows per call (32-bit grid)");
+    if (N > 65535) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_resume: N (intervals per window) must be <= 65535");
+    const int L = prm->lanes_per_window;
+    if (L != 0 && !launch::mean_lanes_supported(L)) return fail(ctx, CPI_ERR_INVALID, "lanes_per_window must be 0 or one of 1,2,3,4,5,6,8,12,16,32,64");
+
+    const bool want_mean = out->DT || out->alpha || out->beta || out->q;
+    const bool want_jac = out->J_q || out->J_a || out->J_b || out->H_a || out->H_b || out->O_a || out->O_b;
+    const bool want_cov = out->P != nullptr || out->P_sym != nullptr;
+    const bool avg = prm->imu_avg != 0;
+    const bool v2 = prm->model == CPI_MODEL_V2;
+    const bool stj = v2 && prm->state_transition_jacobians != 0;
+    // ownership as in preintegrate_impl; the means always run (carry_out holds them even when out asks for none)
+    const bool run_cov = want_cov || (stj && want_jac);
+    const bool mean_jac = want_jac && !stj;
+    const bool run_mean = mean_jac || !run_cov;
+    CarryArgs c;
+    const int hdr = 1 | (avg ? 8 : 0) | (stj ? 16 : 0) | (32 * prm->model);
+    c.in = carry_in;
+    c.out = carry_out;
+    c.need = hdr | (run_cov ? carry::TAG_P : 0) | (mean_jac ? carry::TAG_J : 0);
+    c.tag_out = c.need;
+
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    PreArgs a;
+    memset(&a, 0, sizeof a);
+    a.W = W; a.N = N; a.knots = knots; a.first = (const long long *)first; a.count = count;
+    a.lin = lin; a.qk = q_k_lin;
+    for (int i = 0; i < 3; i++) a.grav[i] = prm->grav[i];
+    a.q4[0] = prm->sigma_w * prm->sigma_w; a.q4[1] = prm->sigma_wb * prm->sigma_wb;
+    a.q4[2] = prm->sigma_a * prm->sigma_a; a.q4[3] = prm->sigma_ab * prm->sigma_ab;
+    a.out = *out;
+    // model 1 with Jacobians and covariance: the two kernels overlap on the side stream as in the batch entry.  They write
+    // disjoint parts of carry_out and both only read carry_in (which is why the two may not overlap).
+    hipStream_t mean_stream = ctx->stream;
+    const bool forked = run_cov && run_mean;
+    if (forked) {
+        if (!ctx->side) {
+            CPI_HIP(ctx, hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
+            CPI_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
+            CPI_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
+        }
+        CPI_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
+        CPI_HIP(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
+        mean_stream = ctx->side;
+    }
+    if (run_cov) {
+        PreArgs p = a;
+        p.write_means = want_mean ? 1 : 0;
+        p.write_jac = (stj && want_jac) ? 1 : 0;
+        CarryArgs cc = c;
+        cc.own_means = 1;
+        launch::cov_carry(prm->model, avg, p, cc, ctx->stream);
+    }
+    if (run_mean) {
+        PreArgs m = a;
+        m.write_means = (want_mean && !run_cov) ? 1 : 0;
+        m.write_jac = mean_jac ? 1 : 0;
+        CarryArgs cm = c;
+        cm.own_means = run_cov ? 0 : 1;
+        launch::mean_carry(prm->model, mean_jac, avg, pick_lanes(prm, W, N, mean_jac), m, cm, mean_stream);
+    }
+    if (forked) {
+        CPI_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->side));
+        CPI_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+    }
+    CPI_HIP(ctx, hipGetLastError());
+    return CPI_OK;
+}
+
 // Replaces the caller-side loop of GraphSolver::createimufactor_cpi_v1 / _v2 (GraphSolver_IMU.cpp:43-75, 97-130) for ALL the
 // windows of a trajectory at once, with ZERO copies of the IMU data: cpi_cut_windows_kernel finds, per update time, where the
 // reference's deque would stand (28 bytes per window into the caller's workspace), and the preintegration kernels read the
@@ -1212,6 +1303,48 @@ extern "C" int cpi_preintegrate_batch_host(cpi_ctx *ctx, const cpi_params *prm, 
     for (int k = 0; k < kOutFields; k++)
         if (*out_field(&h, k))
             CPI_HIP(ctx, hipMemcpyAsync(*out_field(&h, k), dout[k].p, (size_t)W * OUT_N[k] * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    CPI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CPI_OK;
+}
+
+extern "C" int cpi_preintegrate_resume_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                            const double *knots, const int64_t *first, const int32_t *count,
+                                            int64_t n_knots, const double *lin, const double *q_k_lin,
+                                            const double *carry_in, double *carry_out, const cpi_outputs *out) {
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (!prm || !out || !knots || !lin || !carry_out) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_resume_host: NULL argument");
+    if (W <= 0) return W == 0 ? CPI_OK : fail(ctx, CPI_ERR_INVALID, "negative size");
+    if (N < 0) return fail(ctx, CPI_ERR_INVALID, "negative size");
+    if (prm->model != CPI_MODEL_V1 && prm->model != CPI_MODEL_V2)
+        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_resume_host: model must be 1 or 2 (the Forster comparator cannot be resumed)");
+    const size_t cd = (size_t)carry::doubles(prm->model);
+    if (carry_in && carry_in < carry_out + W * cd && carry_out < carry_in + W * cd)
+        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_resume_host: carry_in and carry_out overlap");
+    if (!first) n_knots = W * (int64_t)(N + 1);
+    if (n_knots <= 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_resume_host: n_knots must be > 0");
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    DevBuf dk, df, dc, dl, dq, dci, dco, dout[kOutFields];
+    CPI_UP(dk, knots, (size_t)n_knots * 7 * sizeof(double));
+    CPI_UP(df, first, (size_t)W * sizeof(int64_t));
+    CPI_UP(dc, count, (size_t)W * sizeof(int32_t));
+    CPI_UP(dl, lin, (size_t)W * 6 * sizeof(double));
+    CPI_UP(dq, q_k_lin, (size_t)W * 4 * sizeof(double));
+    CPI_UP(dci, carry_in, (size_t)W * cd * sizeof(double));
+    CPI_HIP(ctx, hipMalloc(&dco.p, (size_t)W * cd * sizeof(double)));
+    cpi_outputs d = *out, h = *out;
+    for (int k = 0; k < kOutFields; k++)
+        if (*out_field(&h, k)) {
+            CPI_HIP(ctx, hipMalloc(&dout[k].p, (size_t)W * OUT_N[k] * sizeof(double)));
+            *out_field(&d, k) = (double *)dout[k].p;
+        }
+    int rc = cpi_preintegrate_resume(ctx, prm, W, N, (const double *)dk.p, (const int64_t *)df.p, (const int32_t *)dc.p,
+                                     (const double *)dl.p, (const double *)dq.p, (const double *)dci.p, (double *)dco.p, &d);
+    if (rc != CPI_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    for (int k = 0; k < kOutFields; k++)
+        if (*out_field(&h, k))
+            CPI_HIP(ctx, hipMemcpyAsync(*out_field(&h, k), dout[k].p, (size_t)W * OUT_N[k] * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    CPI_HIP(ctx, hipMemcpyAsync(carry_out, dco.p, (size_t)W * cd * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     CPI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CPI_OK;
 }

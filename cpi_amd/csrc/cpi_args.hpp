@@ -47,6 +47,24 @@ struct PreArgs {
     cpi_outputs out;
 };
 
+// Resumable preintegration (cpi_preintegrate_resume): the carry record of a window (include/cpi_amd.h).  Offsets in doubles;
+// the means block is written by whichever kernel owns the means of the call, the Jacobian block by the mean kernel, the
+// covariance block by the covariance kernel.  R is column-major.
+namespace carry {
+static const int TAG = 0, DT = 1, ALPHA = 2, BETA = 5, R = 8, JAC = 17;   // JAC: J_q J_a J_b H_a H_b (O_a O_b) column-major
+// tag bits: 1 always set, 2 = covariance state held, 4 = analytic Jacobians held, 8 = imu_avg, 16 = stj, 32 * model
+static const int TAG_P = 2, TAG_J = 4, TAG_HDR = ~(TAG_P | TAG_J);
+constexpr int cov_off(int model) { return JAC + (model == 2 ? 63 : 45); }
+constexpr int doubles(int model) { return model == 1 ? 288 : (model == 2 ? cov_off(2) + 27 * 18 : 0); }
+}  // namespace carry
+struct CarryArgs {
+    const double *in;   // [W][carry::doubles] or NULL = the zero state
+    double *out;        // [W][carry::doubles]
+    int need;           // tag bits carry_in must hold: the header + the parts this call continues
+    int tag_out;        // the tag this call leaves (written by the owner of the means)
+    int own_means;      // this kernel writes the tag and the means of the record
+};
+
 // tiles[b][s][k][i] = field k (t, w, a) of knot s of window 64 b + i (include/cpi_amd.h: cpi_preintegrate_tiled_batch)
 struct TiledArgs {
     long long W;
@@ -106,6 +124,7 @@ namespace launch {
 bool mean_lanes_supported(int L);
 int mean_lane_choices(const int **list);   // the supported L values, ascending
 void mean(int model, bool jac, bool avg, int L, const PreArgs &a, hipStream_t st);
+void mean_carry(int model, bool jac, bool avg, int L, const PreArgs &a, const CarryArgs &c, hipStream_t st);
 // S wavefronts per tile (1 = one wavefront owns the tile; > 1 = SPLIT); big_lds_set: per-context bit set of the
 // instantiations whose dynamic-LDS limit was already raised
 hipError_t mean_tiled(int model, bool avg, bool counted, int S, const TiledArgs &a, hipStream_t st, unsigned *big_lds_set);
@@ -115,6 +134,7 @@ void cut_windows(long long K, const double *stream, long long U, const double *u
                  double *tstart, double *tend, hipStream_t st);
 // ---- cpi_cov.hip
 void cov(int model, bool avg, const PreArgs &a, hipStream_t st);
+void cov_carry(int model, bool avg, const PreArgs &a, const CarryArgs &c, hipStream_t st);
 void forster(const PreArgs &a, hipStream_t st);
 // ---- cpi_factor.hip
 void factor(int model, bool whiten, int lpf, const FactorArgs &a, hipStream_t st);            // lpf 16 | 8 | 4

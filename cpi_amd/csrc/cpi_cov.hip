@@ -25,6 +25,16 @@ static void launch_cov(bool avg, const PreArgs &a, hipStream_t st) {
 void cov(int model, bool avg, const PreArgs &a, hipStream_t st) {
     if (model == CPI_MODEL_V2) launch_cov<2>(avg, a, st); else launch_cov<1>(avg, a, st);
 }
+template <int MODEL>
+static void launch_cov_carry(bool avg, const PreArgs &a, const CarryArgs &c, hipStream_t st) {
+    constexpr int G = 64 / CovDims<MODEL>::GROUP;
+    const long long nb = (a.W + G - 1) / G;
+    if (avg) hipLaunchKernelGGL((cpi_cov_carry_kernel<MODEL, true>), dim3((unsigned)nb), dim3(64), 0, st, a, c);
+    else     hipLaunchKernelGGL((cpi_cov_carry_kernel<MODEL, false>), dim3((unsigned)nb), dim3(64), 0, st, a, c);
+}
+void cov_carry(int model, bool avg, const PreArgs &a, const CarryArgs &c, hipStream_t st) {
+    if (model == CPI_MODEL_V2) launch_cov_carry<2>(avg, a, c, st); else launch_cov_carry<1>(avg, a, c, st);
+}
 void forster(const PreArgs &a, hipStream_t st) {   // one kernel owns everything; imu_avg, q_k_lin, grav play no part
     hipLaunchKernelGGL(cpi_forster_kernel, dim3((unsigned)((a.W + 3) / 4)), dim3(64), 0, st, a);
 }

@@ -17,8 +17,12 @@ namespace {
 #ifndef CPI_FORSTER_MEAN_LANES
 #define CPI_FORSTER_MEAN_LANES 6
 #endif
-template <int MODEL, bool AVG>
-__global__ __launch_bounds__(64, CPI_COV_WPS) void cpi_cov_kernel(PreArgs A) {
+// CARRY (cpi_cov_carry_kernel, cpi_preintegrate_resume): the carried rotation / means (gs) and every lane's column P0 start
+// from the window's carry record instead of identity / zero, and are written back to it at the end.  Nothing else depends
+// on the initial state: the exchange rows cov_exch_init fills are the constant process-noise rows, and phase A derives GS_R0
+// from GS_R.
+template <int MODEL, bool AVG, bool CARRY>
+__device__ __forceinline__ void cov_body(const PreArgs &A, const CarryArgs &CA) {
     typedef CovDims<MODEL> D;
     constexpr int GROUP = D::GROUP;   // lanes per window
     constexpr int G = 64 / GROUP;     // windows per wavefront
@@ -51,6 +55,18 @@ __global__ __launch_bounds__(64, CPI_COV_WPS) void cpi_cov_kernel(PreArgs A) {
     const int jj = cov_col_of_lane<MODEL>(j);  // column owned by this lane; idle lanes (NCOL) run as a harmless zero transition column
     CovLane<MODEL> Ln;
     cov_init(Ln, jj, q4);
+    constexpr int CD = carry::doubles(MODEL), CO = carry::cov_off(MODEL);
+    bool cbad = false;   // CARRY: the record does not hold what this call continues (its outputs become NaN)
+    if constexpr (CARRY) {
+        if (CA.in) {
+            const double *ci = CA.in + w * CD;
+            cbad = !carry_tag_ok(ci[carry::TAG], CA.need);
+            if (!cbad && jj < D::NCOL) {
+#pragma unroll
+                for (int i = 0; i < D::NR; i++) Ln.P0[i] = ci[CO + jj * D::NR + i];
+            }
+        }
+    }
     double *ex_g = exch + g * EXCH_WIN;
     // every row starts on a 16-B boundary; said explicitly, or the row reads degrade from ds_read_b128 to ds_read_b64
     const double *ex_row = exch + (cov_row_off<MODEL>(G, g, jj) & ~1);   // (the offset is even; the mask lets the compiler see it)
@@ -59,6 +75,15 @@ __global__ __launch_bounds__(64, CPI_COV_WPS) void cpi_cov_kernel(PreArgs A) {
     for (int i = lane; i < exch_doubles(G); i += 64) exch[i] = 0.0;
     if (j == 0) {
         cov_gs_init(gs);
+        if constexpr (CARRY) {
+            if (CA.in && !cbad) {
+                const double *ci = CA.in + w * CD;
+                rec_put_mat(gs, GS_R, ldm3_cm(ci + carry::R));
+                put3(gs + GS_ALPHA, ldv3(ci + carry::ALPHA));
+                put3(gs + GS_BETA, ldv3(ci + carry::BETA));
+                gs[GS_DT] = ci[carry::DT];
+            }
+        }
         if (MODEL == 2) put3(gs + GS_GK, mul(quat_2_Rot(ldq4(A.qk + w * 4)), mk(A.grav[0], A.grav[1], A.grav[2])));
     }
     __syncthreads();
@@ -209,6 +234,16 @@ __global__ __launch_bounds__(64, CPI_COV_WPS) void cpi_cov_kernel(PreArgs A) {
         wave_lds_fence();
     }
 
+    if constexpr (CARRY) {
+        if (cbad) {
+#pragma unroll
+            for (int i = 0; i < D::NR; i++) Ln.P0[i] = __builtin_nan("");
+            if (j == 0) {
+                const double x = __builtin_nan("");
+                rec_put_mat(gs, GS_R, nan3()); put3(gs + GS_ALPHA, mk(x, x, x)); put3(gs + GS_BETA, mk(x, x, x)); gs[GS_DT] = x;
+            }
+        }
+    }
     if (!valid) return;
     if (A.out.P && jj < 15) {
         double *p = A.out.P + w * 225 + jj * 15;
@@ -228,6 +263,7 @@ __global__ __launch_bounds__(64, CPI_COV_WPS) void cpi_cov_kernel(PreArgs A) {
             const Q4 q = rot_2_quat(rec_mat(gs, GS_R));
             double *p = A.out.q + w * 4;
             p[0] = q.x; p[1] = q.y; p[2] = q.z; p[3] = q.w;
+            if constexpr (CARRY) { if (cbad) p[0] = p[1] = p[2] = p[3] = __builtin_nan(""); }   // (rot_2_quat of NaN is not all NaN)
         }
     }
     if (MODEL == 2 && A.write_jac && jj >= D::NPCOL && jj < D::NCOL) {
@@ -248,6 +284,29 @@ __global__ __launch_bounds__(64, CPI_COV_WPS) void cpi_cov_kernel(PreArgs A) {
             if (A.out.O_b) stv3(A.out.O_b + w * 9 + c * 3, vv);
         }
     }
+    if constexpr (CARRY) {
+        double *co = CA.out + w * CD;
+        if (jj < D::NCOL) {
+#pragma unroll
+            for (int i = 0; i < D::NR; i++) co[CO + jj * D::NR + i] = Ln.P0[i];
+        }
+        if (j == 0 && CA.own_means) {
+            co[carry::TAG] = cbad ? __builtin_nan("") : (double)CA.tag_out;
+            co[carry::DT] = gs[GS_DT];
+            stv3(co + carry::ALPHA, rec_v3(gs, GS_ALPHA));
+            stv3(co + carry::BETA, rec_v3(gs, GS_BETA));
+            stm3_cm(co + carry::R, rec_mat(gs, GS_R));
+        }
+    }
+}
+template <int MODEL, bool AVG>
+__global__ __launch_bounds__(64, CPI_COV_WPS) void cpi_cov_kernel(PreArgs A) {
+    cov_body<MODEL, AVG, false>(A, CarryArgs());
+}
+// cpi_preintegrate_resume: cpi_cov_kernel from and to carry records
+template <int MODEL, bool AVG>
+__global__ __launch_bounds__(64, CPI_COV_WPS) void cpi_cov_carry_kernel(PreArgs A, CarryArgs C) {
+    cov_body<MODEL, AVG, true>(A, C);
 }
 
 // ============================================================================================

@@ -193,5 +193,56 @@ __device__ __forceinline__ long long readfirstlane64(long long v) {
 
 // (PreArgs: cpi_args.hpp)
 
+// ---- carry records of cpi_preintegrate_resume (layout: cpi_args.hpp, namespace carry)
+// A record continues this call when its tag is an integer with the call's header bits and at least the parts it needs.
+__device__ __forceinline__ bool carry_tag_ok(double t, int need) {
+    if (!(t >= 1.0 && t < 1024.0) || t != floor(t)) return false;   // NaN, 0 and garbage fail here
+    const int it = (int)t;
+    return (it & carry::TAG_HDR) == (need & carry::TAG_HDR) && (it & need) == need;
+}
+template <int MODEL, bool JAC>
+__device__ __forceinline__ void carry_load_mean(MeanState<JAC> &s, const double *c, bool jac) {
+    s.DT = c[carry::DT];
+    s.alpha = ldv3(c + carry::ALPHA);
+    s.beta = ldv3(c + carry::BETA);
+    s.R = ldm3_cm(c + carry::R);
+    if (JAC && jac) {
+        s.Jq = ldm3_cm(c + carry::JAC); s.Ja = ldm3_cm(c + carry::JAC + 9); s.Jb = ldm3_cm(c + carry::JAC + 18);
+        s.Ha = ldm3_cm(c + carry::JAC + 27); s.Hb = ldm3_cm(c + carry::JAC + 36);
+        if (MODEL == 2) { s.Oa = ldm3_cm(c + carry::JAC + 45); s.Ob = ldm3_cm(c + carry::JAC + 54); }
+    }
+}
+template <int MODEL, bool JAC>
+__device__ __forceinline__ void carry_store_mean(double *c, const MeanState<JAC> &s, bool means, double tag) {
+    if (means) {
+        c[carry::TAG] = tag;
+        c[carry::DT] = s.DT;
+        stv3(c + carry::ALPHA, s.alpha);
+        stv3(c + carry::BETA, s.beta);
+        stm3_cm(c + carry::R, s.R);
+    }
+    if (JAC) {
+        stm3_cm(c + carry::JAC, s.Jq); stm3_cm(c + carry::JAC + 9, s.Ja); stm3_cm(c + carry::JAC + 18, s.Jb);
+        stm3_cm(c + carry::JAC + 27, s.Ha); stm3_cm(c + carry::JAC + 36, s.Hb);
+        if (MODEL == 2) { stm3_cm(c + carry::JAC + 45, s.Oa); stm3_cm(c + carry::JAC + 54, s.Ob); }
+    }
+}
+__device__ __forceinline__ M3 nan3() {
+    const double x = __builtin_nan("");
+    M3 A;
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int k = 0; k < 3; k++) A.m[i][k] = x;
+    return A;
+}
+// A window whose carry record does not fit the call: its whole state becomes NaN, so every output and the record it leaves are NaN.
+template <bool JAC>
+__device__ __forceinline__ void mean_poison(MeanState<JAC> &s) {
+    const double x = __builtin_nan("");
+    s.R = nan3(); s.alpha = mk(x, x, x); s.beta = mk(x, x, x); s.DT = x;
+    if (JAC) { s.Jq = nan3(); s.Ja = nan3(); s.Jb = nan3(); s.Ha = nan3(); s.Hb = nan3(); s.Oa = nan3(); s.Ob = nan3(); }
+}
+
 
 }  // namespace

@@ -134,6 +134,7 @@ public:
         imu_avg = o.imu_avg; state_transition_jacobians = o.state_transition_jacobians;
         b_w_lin = o.b_w_lin; b_a_lin = o.b_a_lin; q_k_lin = o.q_k_lin; grav = o.grav;
         knots_ = o.knots_; model_ = o.model_; ctx_ = o.ctx_; dirty_ = o.dirty_; means_only_ = o.means_only_;
+        incremental_ = o.incremental_; carry_ = o.carry_;
         for (int i = 0; i < 4; i++) sig_[i] = o.sig_[i];
         put(o.peek());
         return *this;
@@ -148,6 +149,8 @@ public:
     // b_w_lin / b_a_lin / q_k_lin / grav / imu_avg directly is NOT tracked: call invalidate() afterwards.
     void setLinearizationPoints(const Vec3 &b_w_lin_, const Vec3 &b_a_lin_, const Vec4 &q_k_lin_ = Vec4{{0, 0, 0, 0}},
                                 const Vec3 &grav_ = Vec3{{0, 0, 0}}) {
+        if (incremental_ && !carry_.empty())
+            throw std::logic_error("setLinearizationPoints: an incremental preintegrator has already integrated intervals at the old point");
         b_w_lin = b_w_lin_; b_a_lin = b_a_lin_; q_k_lin = q_k_lin_; grav = grav_;
         if (!knots_.empty()) dirty_ = true;
     }
@@ -184,8 +187,19 @@ public:
         }
         push(t_1, w_m_1, a_m_1);
     }
+    // Incremental mode (cpi_preintegrate_resume): a read runs only the intervals fed since the previous read, continuing
+    // from the carried state, and keeps only the last knot -- O(1) per read instead of re-running the window.  Switch it on
+    // before the first feed_IMU; the linearisation point cannot change once intervals were integrated.  The carry record is
+    // host memory, so a copy of the preintegrator continues on its own.  The Forster comparator cannot be resumed.
+    void set_incremental(bool on) {
+        if (on && model_ == CPI_MODEL_FORSTER) throw std::logic_error("set_incremental: the Forster comparator cannot be resumed");
+        if (!knots_.empty() || !carry_.empty()) throw std::logic_error("set_incremental: call it before the first feed_IMU");
+        incremental_ = on;
+    }
+    bool incremental() const { return incremental_; }
     // Runs this single window on the GPU and fills the result members (what a first read of any member does by itself).
     void finalize(const Context &ctx) {
+        if (incremental_) { finalize_incremental(ctx); return; }
         cpi_params p = params();
         const double lin[6] = { b_w_lin[0], b_w_lin[1], b_w_lin[2], b_a_lin[0], b_a_lin[1], b_a_lin[2] };
         CpiResult r;
@@ -249,6 +263,20 @@ protected:
     void touch() { dirty_ = true; }              // a recorded knot was rewritten in place
     std::vector<double> knots_;
 private:
+    void finalize_incremental(const Context &ctx) {
+        cpi_params p = params();
+        const double lin[6] = { b_w_lin[0], b_w_lin[1], b_w_lin[2], b_a_lin[0], b_a_lin[1], b_a_lin[2] };
+        CpiResult r;
+        cpi_outputs o = outputs_of(r);   // everything, so that the carry holds every part a later read may need
+        const int32_t n = knots_.empty() ? 0 : (int32_t)(knots_.size() / 7 - 1);
+        static const double zero_knot[7] = { 0, 0, 0, 0, 0, 0, 0 };
+        std::vector<double> next(cpi_carry_doubles(model_));
+        ctx.check(cpi_preintegrate_resume_host(ctx.get(), &p, 1, n, knots_.empty() ? zero_knot : knots_.data(), nullptr, nullptr,
+                                               n + 1, lin, q_k_lin.data(), carry_.empty() ? nullptr : carry_.data(), next.data(), &o));
+        carry_.swap(next);
+        if (n > 0) knots_.erase(knots_.begin(), knots_.end() - 7);   // the next segment starts on this one's last knot
+        set_result(r);
+    }
     template <class T> friend class Lazy;
     // full: the member being read is a Jacobian / covariance (not one of the four means)
     void ensure(bool full = true) const { if (dirty_ || (full && means_only_)) const_cast<CpiBase *>(this)->finalize(ctx_ ? *ctx_ : default_context()); }
@@ -269,6 +297,8 @@ private:
     const Context *ctx_ = nullptr;
     bool dirty_ = false;                         // intervals recorded since the result members were last computed
     bool means_only_ = false;                    // the last computation (CpiBatch::flush_means) filled the four means only
+    bool incremental_ = false;                   // set_incremental
+    std::vector<double> carry_;                  // incremental: the carry record of the intervals integrated so far
 };
 template <class T> inline void Lazy<T>::sync() const { owner_->ensure(!mean_); }
 
@@ -316,7 +346,11 @@ private:
 // Collects many recorded windows (same model / flags / gravity) and runs them in ONE launch.
 class CpiBatch {
 public:
-    void add(CpiBase *w) { win_.push_back(w); }
+    void add(CpiBase *w) {
+        // (many incremental windows at once: cpi_preintegrate_resume / Engine.preintegrate_resume)
+        if (w->incremental()) throw std::logic_error("CpiBatch::add: an incremental preintegrator runs on its own");
+        win_.push_back(w);
+    }
     void flush(const Context &ctx) {
         if (win_.empty()) return;
         const int64_t W = (int64_t)win_.size();

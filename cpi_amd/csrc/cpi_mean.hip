@@ -102,6 +102,30 @@ void mean(int model, bool jac, bool avg, int L, const PreArgs &a, hipStream_t st
     if (model == CPI_MODEL_V2) launch_mean_M<2>(jac, avg, L, a, st); else launch_mean_M<1>(jac, avg, L, a, st);
 }
 
+// cpi_preintegrate_resume: the same lane split as the batch entry, always the plain-knot (CUT = 0, not BIG) instantiation
+template <int MODEL, bool JAC, bool AVG>
+static void launch_mean_carry_L(int L, const PreArgs &a, const CarryArgs &c, hipStream_t st) {
+#define CPI_LAUNCH_C(LL)                                                                         \
+    case LL:                                                                                     \
+        hipLaunchKernelGGL((cpi_mean_carry_kernel<MODEL, JAC, AVG, LL>), dim3((unsigned)((a.W + (64 / LL) - 1) / (64 / LL))), dim3(64), 0, st, a, c); \
+        break;
+    if constexpr (MODEL == 2 && JAC) { switch (L) { CPI_LAUNCH_C(1) default: break; } } else
+    switch (L) {
+        CPI_LAUNCH_C(1) CPI_LAUNCH_C(2) CPI_LAUNCH_C(3) CPI_LAUNCH_C(4) CPI_LAUNCH_C(5) CPI_LAUNCH_C(6) CPI_LAUNCH_C(8)
+        CPI_LAUNCH_C(12) CPI_LAUNCH_C(16) CPI_LAUNCH_C(32) CPI_LAUNCH_C(64)
+        default: break;
+    }
+#undef CPI_LAUNCH_C
+}
+template <int MODEL>
+static void launch_mean_carry_M(bool jac, bool avg, int L, const PreArgs &a, const CarryArgs &c, hipStream_t st) {
+    if (jac) { if (avg) launch_mean_carry_L<MODEL, true, true>(L, a, c, st); else launch_mean_carry_L<MODEL, true, false>(L, a, c, st); }
+    else     { if (avg) launch_mean_carry_L<MODEL, false, true>(L, a, c, st); else launch_mean_carry_L<MODEL, false, false>(L, a, c, st); }
+}
+void mean_carry(int model, bool jac, bool avg, int L, const PreArgs &a, const CarryArgs &c, hipStream_t st) {
+    if (model == CPI_MODEL_V2) launch_mean_carry_M<2>(jac, avg, L, a, c, st); else launch_mean_carry_M<1>(jac, avg, L, a, c, st);
+}
+
 hipError_t mean_tiled(int model, bool avg, bool counted, int S, const TiledArgs &a, hipStream_t st, unsigned *big_lds_set) {
     const unsigned nb = (unsigned)((a.W + 63) / 64);
     const size_t lds = (size_t)(S - 1) * (model == CPI_MODEL_V2 ? 34 : 16) * 64 * sizeof(double);

@@ -193,6 +193,37 @@ class Engine:
                                                     _ptr(lin), _ptr(q_k_lin), C.byref(o)))
         return out
 
+    def carry_doubles(self, model):
+        """Doubles per window of a carry record (cpi_carry_doubles): 0 for the Forster comparator or an invalid model."""
+        return int(self.lib.cpi_carry_doubles(int(model)))
+
+    def preintegrate_resume(self, knots, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), first=None, count=None,
+                            N=None, carry_in=None, carry_out=None, out=None):
+        """cpi_preintegrate_resume: continue every window from carry_in ([W, carry_doubles] float64 CUDA tensor, None = the
+        zero state) over these knots (layouts as in preintegrate).  Returns (out, carry_out); out holds the measurement of all
+        the intervals so far, carry_out (allocated when not given) the state to continue from.  Asynchronous."""
+        params = params or self.make_params()
+        if first is None:
+            W, n1, seven = knots.shape
+            N = n1 - 1
+        else:
+            W = first.shape[0]
+            assert N is not None, "ragged layout needs N = max intervals per window"
+        for t in (knots, lin, q_k_lin, first, count, carry_in, carry_out):
+            assert t is None or (t.is_cuda and t.is_contiguous()), "inputs must be contiguous CUDA tensors"
+        cd = self.carry_doubles(params.model)
+        if carry_out is None and cd > 0:
+            carry_out = torch.empty((W, cd), dtype=torch.float64, device=self.device)
+        for t in (carry_in, carry_out):
+            assert t is None or (t.dtype == torch.float64 and t.numel() >= W * cd), "carry records are [W, carry_doubles] float64"
+        if out is None:
+            out = self.alloc_outputs(W, want, params.model)
+        o = self._outputs_struct(out)
+        self._sync_stream()
+        self._check(self.lib.cpi_preintegrate_resume(self.ctx, C.byref(params), W, N, _ptr(knots), _ptr(first), _ptr(count),
+                                                     _ptr(lin), _ptr(q_k_lin), _ptr(carry_in), _ptr(carry_out), C.byref(o)))
+        return out, carry_out
+
     def preintegrate_host(self, knots, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), count=None, pinned=True, out=None):
         """Dense batch held in HOST memory (CPU float64 tensors; pinned ones overlap upload / kernels / download):
         cpi_preintegrate_batch_host.  Returns a dict of CPU tensors (page-locked when pinned=True; out= re-uses the
@@ -542,8 +573,23 @@ class _CpiBase:
         self._iv = []      # (t0, t1, w0, a0, w1, a1)
         self._res = None
         self._engine = engine
+        self._incremental = False
+        self._carry = None   # incremental: the carry record (device tensor [1, carry_doubles]) of the intervals run so far
+        self._tail = None    # incremental: the last knot of the intervals run so far
+
+    def set_incremental(self, on=True):
+        """Incremental mode (Engine.preintegrate_resume): a read runs only the intervals fed since the previous read,
+        continuing from the carried state, and keeps only the last knot.  Before the first feed_IMU only; the linearisation
+        point cannot change once intervals were run.  Default off."""
+        if on and self._model == 3:
+            raise ValueError("set_incremental: the Forster comparator cannot be resumed")
+        if self._iv or self._tail is not None:
+            raise RuntimeError("set_incremental: call it before the first feed_IMU")
+        self._incremental = bool(on)
 
     def setLinearizationPoints(self, b_w_lin_, b_a_lin_, q_k_lin_=None, grav_=None):
+        if self._incremental and self._tail is not None:   # (a read before any feed_IMU integrates nothing)
+            raise RuntimeError("setLinearizationPoints: an incremental preintegrator has already run intervals at the old point")
         self.b_w_lin = np.asarray(b_w_lin_, dtype=np.float64).reshape(3)
         self.b_a_lin = np.asarray(b_a_lin_, dtype=np.float64).reshape(3)
         self.q_k_lin = np.zeros(4) if q_k_lin_ is None else np.asarray(q_k_lin_, dtype=np.float64).reshape(4)
@@ -562,7 +608,7 @@ class _CpiBase:
         reading equals this interval's w1/a1) share a knot.  The reference's feed_IMU only ever uses
         t1 - t0, so intervals need not chain: a knot whose time is NaN acts as a separator (both
         intervals touching it have a NaN dt and are skipped by the kernels)."""
-        rows = []
+        rows = [] if self._tail is None else [self._tail.copy()]
         for (t0, t1, w0, a0, w1, a1) in self._iv:
             if rows and not self.imu_avg and rows[-1][0] == t0:
                 # imu_avg == False: closing readings take no part in the arithmetic (CpiV1.h:77-86); when the TIMES chain the
@@ -586,6 +632,14 @@ class _CpiBase:
         lin = torch.from_numpy(np.concatenate([self.b_w_lin, self.b_a_lin])[None]).to(dev)
         q = torch.from_numpy(self.q_k_lin[None]).to(dev)
         prm = eng.make_params(self._model, self.imu_avg, self.state_transition_jacobians, self._sig, tuple(self.grav))
+        if self._incremental:
+            # every output requested, so that the carry holds every part a later read may need
+            out, self._carry = eng.preintegrate_resume(knots, lin, q, prm, carry_in=self._carry)
+            eng.synchronize()
+            if self._iv:
+                self._tail, self._iv = kn[-1], []
+            self._res = {k: v.cpu().numpy()[0] for k, v in out.items()}
+            return self._res
         out = eng.preintegrate(knots, lin, q, prm)
         eng.synchronize()
         self._res = {k: v.cpu().numpy()[0] for k, v in out.items()}

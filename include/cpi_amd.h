@@ -46,7 +46,9 @@ extern "C" {
                                round 4, a CONTRACT change without a new symbol: after cpi_preintegrate_stream the workspace
                                holds the true interval counts (cpi_stream_counts) and NOTHING ELSE a caller may read -- a
                                mean-only request runs no cut kernel, so the first / tstart / tend records round 3 left there
-                               are no longer written (they were never declared) */
+                               are no longer written (they were never declared);
+                               additions within 3 (new symbols only): cpi_carry_doubles, cpi_preintegrate_resume,
+                               cpi_preintegrate_resume_host (resumable preintegration) */
 
 enum { CPI_OK = 0, CPI_ERR_INVALID = 1, CPI_ERR_HIP = 2, CPI_ERR_NO_DEVICE = 3, CPI_ERR_RCCL = 4 };
 enum {
@@ -146,6 +148,42 @@ int cpi_ctx_synchronize(cpi_ctx *ctx);
 int cpi_preintegrate_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                            const double *knots, const int64_t *first, const int32_t *count,
                            const double *lin, const double *q_k_lin, const cpi_outputs *out);
+
+/* Resumable preintegration -- the incremental object of the reference (CpiBase::feed_IMU, CpiBase.h:99-124) for a batch:
+ * continue each window from a carried state and hand the state back.
+ *
+ * Call A on the knots [k0 .. km] of a window, then call B with carry_in = A's carry_out on [km .. kn]: B's outputs are the
+ * measurement of ALL the intervals so far and equal one cpi_preintegrate_batch call on [k0 .. kn] (up to the rounding of a
+ * different association; a NULL carry_in reproduces cpi_preintegrate_batch bit for bit).  Consecutive segments share their
+ * boundary knot (imu_avg needs it).  knots / first / count / N, dt <= 0 and NaN separators as in cpi_preintegrate_batch;
+ * a segment with count 0 passes the state through.  lin, q_k_lin, the sigmas, grav, model, imu_avg and
+ * state_transition_jacobians must stay the same along a chain (setLinearizationPoints comes before the first feed_IMU).
+ *
+ * carry_in   [W][cpi_carry_doubles(model)] or NULL = the zero state (CpiBase constructor)
+ * carry_out  [W][cpi_carry_doubles(model)], required; must not overlap carry_in (the two kernels of a model-1 "everything"
+ *            call run concurrently and both read carry_in)
+ * out        as in cpi_preintegrate_batch; the means are computed into carry_out even when out asks for none.
+ * CPI_MODEL_FORSTER, carry_out == NULL and overlapping carry ranges return CPI_ERR_INVALID.  No host synchronisation:
+ * the device entry can be captured into a graph.
+ *
+ * The carry record is opaque to callers; for binding authors (doubles, matrices column-major):
+ *   [0]        tag: an integer-valued double, 1 + 2 (covariance state held) + 4 (analytic Jacobians held) + 8 imu_avg
+ *              + 16 state_transition_jacobians + 32 model.  0 and NaN are never valid.
+ *   [1]        DT          [2..4] alpha     [5..7] beta     [8..16] R, the rotation the recursion carries (never a quaternion)
+ *   [17..]     J_q J_a J_b H_a H_b (+ O_a O_b, model 2), 9 each: when the call computes the analytic Jacobians
+ *   [62..286]  model 1: P, 15 x 15                                              (when the call runs the covariance kernel)
+ *   [80..565]  model 2: the 18 carried rows of the 18 covariance columns and of the 9 Discrete_J_b columns, 18 doubles per
+ *              column in the kernel's column order (the theta_klin unit block stays implicit)
+ * A call needs the parts it continues: the covariance state when it runs the covariance kernel (P / P_sym wanted, or model 2
+ * Jacobians with state_transition_jacobians), the analytic Jacobians when it computes them.  A window whose carry_in tag
+ * lacks a needed part or differs in model / imu_avg / state_transition_jacobians gets NaN in all its requested outputs and
+ * in its carry_out (the host cannot see device data: this is the guard against a silently wrong continuation); the other
+ * windows are unaffected. */
+size_t cpi_carry_doubles(int32_t model);   /* doubles per window of a carry record: 288 (model 1), 566 (model 2); 0 otherwise */
+int cpi_preintegrate_resume(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                            const double *knots, const int64_t *first, const int32_t *count,
+                            const double *lin, const double *q_k_lin, const double *carry_in, double *carry_out,
+                            const cpi_outputs *out);
 
 /* Replaces: the whole caller side of GraphSolver::createimufactor_cpi_v1 / _v2 (GraphSolver_IMU.cpp:43-75, 97-130) for every
  * window of a trajectory at once, reading ONE IMU stream IN PLACE: no knot is copied, for any model and any output.
@@ -367,6 +405,11 @@ int cpi_preintegrate_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, 
                                 const double *knots, const int64_t *first, const int32_t *count,
                                 int64_t n_knots, const double *lin, const double *q_k_lin,
                                 const cpi_outputs *out);
+/* cpi_preintegrate_resume from host memory: every pointer a host pointer, n_knots as in cpi_preintegrate_batch_host. */
+int cpi_preintegrate_resume_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                 const double *knots, const int64_t *first, const int32_t *count,
+                                 int64_t n_knots, const double *lin, const double *q_k_lin,
+                                 const double *carry_in, double *carry_out, const cpi_outputs *out);
 /* The tiled layout from HOST memory (tiles written by a host-side assembler), mean outputs only: same pipeline, chunks of
  * 1024 tiles. */
 int cpi_preintegrate_tiled_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N, const double *tiles,
