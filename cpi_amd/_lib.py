@@ -127,6 +127,10 @@ def load():
     lib.cpi_preintegrate_stream.argtypes = [vp, C.POINTER(CpiParams), i64, dp, i64, dp, i32, dp, dp, vp, C.POINTER(CpiOutputs)]
     lib.cpi_preintegrate_stream.restype = C.c_int
     lib.cpi_preintegrate_stream_host.argtypes = [vp, C.POINTER(CpiParams), i64, dp, i64, dp, i32, dp, dp, C.POINTER(CpiOutputs), vp]
+    lib.cpi_streams_workspace_bytes.argtypes = [i64, i64]
+    lib.cpi_streams_workspace_bytes.restype = C.c_size_t
+    lib.cpi_preintegrate_streams.argtypes = [vp, C.POINTER(CpiParams), i64, i64, dp, vp, i64, dp, vp, i32, dp, dp, vp, C.POINTER(CpiOutputs)]
+    lib.cpi_preintegrate_streams_host.argtypes = [vp, C.POINTER(CpiParams), i64, i64, dp, vp, i64, dp, vp, i32, dp, dp, C.POINTER(CpiOutputs), vp]
     lib.cpi_tile_windows.argtypes = [vp, i64, i32, dp, vp, vp, dp]
     lib.cpi_assemble_tiles.argtypes = [vp, i64, dp, i64, dp, i32, dp, vp]
     lib.cpi_preintegrate_tiled_batch_host.argtypes = [vp, C.POINTER(CpiParams), i64, i32, dp, vp, dp, dp, C.POINTER(CpiOutputs)]
@@ -165,7 +169,8 @@ def load():
               lib.cpi_tile_windows, lib.cpi_assemble_tiles, lib.cpi_preintegrate_tiled_batch_host, lib.cpi_outputs_bind_slab,
               lib.cpi_group_last_gather_messages, lib.cpi_preintegrate_stream_host, lib.cpi_sqrt_information_packed_batch,
               lib.cpi_factor_eval_whitened_tri_batch, lib.cpi_factor_hessian_tri_batch, lib.cpi_group_gather_chunk,
-              lib.cpi_preintegrate_resume, lib.cpi_preintegrate_resume_host):
+              lib.cpi_preintegrate_resume, lib.cpi_preintegrate_resume_host, lib.cpi_preintegrate_streams,
+              lib.cpi_preintegrate_streams_host):
         f.restype = C.c_int
     _lib = lib
     return lib

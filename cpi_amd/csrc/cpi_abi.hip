@@ -228,6 +228,7 @@ struct StreamCut {
     long long *first;
     int *count;
     double *tstart, *tend;
+    const RunArgs *runs;   // cpi_preintegrate_streams: the windows of many runs (NULL: one stream)
 };
 static int preintegrate_impl(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N, const double *knots, const int64_t *first,
                              const int32_t *count, const StreamCut *sc, const double *lin,
@@ -272,7 +273,8 @@ static int preintegrate_impl(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int
     const bool run_mean = !forster && (mean_jac || (want_mean && !run_cov));
     // A stream: the mean-only kernel cuts its own windows (fused; it still leaves the TRUE counts in the workspace); every
     // other kernel reads the cut that cpi_cut_windows_kernel leaves there.  Nothing asked for: the counts are still owed.
-    bool fused_cut = sc && anything && run_mean && !mean_jac && !run_cov && sc->K >= 4;
+    // (many runs: the kernel handles runs of any length itself -- the host cannot see them)
+    bool fused_cut = sc && anything && run_mean && !mean_jac && !run_cov && (sc->runs != nullptr || sc->K >= 4);
 #ifdef CPI_EXPERIMENTS
     if (expsw::no_fused_cut()) fused_cut = false;
 #endif
@@ -280,7 +282,8 @@ static int preintegrate_impl(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int
     DeviceGuard guard_;
     CPI_HIP(ctx, guard_.enter(ctx->device));
     if (sc && !fused_cut) {
-        launch::cut_windows(sc->K, knots, (long long)W, sc->update, (int)N, sc->first, sc->count, sc->tstart, sc->tend, ctx->stream);
+        if (sc->runs) launch::cut_runs(sc->K, knots, (long long)W, sc->update, *sc->runs, sc->first, sc->count, sc->tstart, sc->tend, ctx->stream);
+        else launch::cut_windows(sc->K, knots, (long long)W, sc->update, (int)N, sc->first, sc->count, sc->tstart, sc->tend, ctx->stream);
         CPI_HIP(ctx, hipGetLastError());
         first = reinterpret_cast<const int64_t *>(sc->first); count = sc->count;
     }
@@ -348,7 +351,10 @@ static int preintegrate_impl(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int
         if (!sc && !done && !mean_jac && LL == 1 && !first && !count && expsw::mean_line()) done = launch::mean_line(prm->model, avg, m, ctx->stream);
         if (done && done < W) m = shift_windows(m, done);
 #endif
-        if (done < W) launch::mean(prm->model, mean_jac, avg, LL, m, mean_stream);
+        if (done < W) {
+            if (fused_cut && sc->runs) launch::mean_runs(prm->model, avg, LL, m, *sc->runs, mean_stream);
+            else launch::mean(prm->model, mean_jac, avg, LL, m, mean_stream);
+        }
     }
     if (forked) {
         CPI_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->side));
@@ -462,6 +468,18 @@ extern "C" const int32_t *cpi_stream_counts(const void *workspace, int64_t U) {
     if (!workspace || U <= 0) return nullptr;
     return reinterpret_cast<const int32_t *>(static_cast<const char *>(workspace) + align16((size_t)U * 8) * 3);
 }
+// the workspace layout shared by the stream entries: first[U] (8 B), tstart[U], tend[U], count[U] (4 B), each 16-byte aligned
+static StreamCut stream_cut(int64_t K, const double *update_times, void *workspace, int64_t U, const RunArgs *runs) {
+    StreamCut sc;
+    char *ws = static_cast<char *>(workspace);
+    sc.K = (long long)K; sc.update = update_times;
+    sc.first = reinterpret_cast<long long *>(ws);
+    sc.tstart = reinterpret_cast<double *>(ws + align16((size_t)U * 8));
+    sc.tend = reinterpret_cast<double *>(ws + 2 * align16((size_t)U * 8));
+    sc.count = reinterpret_cast<int *>(ws + 3 * align16((size_t)U * 8));
+    sc.runs = runs;
+    return sc;
+}
 extern "C" int cpi_preintegrate_stream(cpi_ctx *ctx, const cpi_params *prm, int64_t K, const double *stream, int64_t U,
                                        const double *update_times, int32_t N, const double *lin, const double *q_k_lin,
                                        void *workspace, const cpi_outputs *out) {
@@ -481,13 +499,45 @@ extern "C" int cpi_preintegrate_stream(cpi_ctx *ctx, const cpi_params *prm, int6
     if (N > 65535) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_stream: N (intervals per window) must be <= 65535");
     if (prm->lanes_per_window != 0 && !launch::mean_lanes_supported(prm->lanes_per_window))
         return fail(ctx, CPI_ERR_INVALID, "lanes_per_window must be 0 or one of 1,2,3,4,5,6,8,12,16,32,64");
-    char *ws = static_cast<char *>(workspace);
-    StreamCut sc;
-    sc.K = (long long)K; sc.update = update_times;
-    sc.first = reinterpret_cast<long long *>(ws);
-    sc.tstart = reinterpret_cast<double *>(ws + align16((size_t)U * 8));
-    sc.tend = reinterpret_cast<double *>(ws + 2 * align16((size_t)U * 8));
-    sc.count = reinterpret_cast<int *>(ws + 3 * align16((size_t)U * 8));
+    const StreamCut sc = stream_cut(K, update_times, workspace, U, nullptr);
+    return preintegrate_impl(ctx, prm, U, N, stream, nullptr, nullptr, &sc, lin, q_k_lin, out);
+}
+
+// Many IMU streams in one call: run r owns the knots [stream_offsets[r], stream_offsets[r + 1]) and the windows
+// [update_offsets[r], update_offsets[r + 1]).  The offsets are device data: the kernels clamp them (cpi_mean_kernels.hpp:
+// run_of / run_window), the _host entry validates them.  The workspace is the single-stream entry's, so cpi_stream_counts
+// reads the counts of a multi-run call too.
+extern "C" size_t cpi_streams_workspace_bytes(int64_t R, int64_t U) {
+    (void)R;   // the layout depends on U alone: the run lookup needs no per-window record (it is redone in every prologue)
+    return cpi_stream_workspace_bytes(U);
+}
+extern "C" int cpi_preintegrate_streams(cpi_ctx *ctx, const cpi_params *prm, int64_t R, int64_t K, const double *stream,
+                                        const int64_t *stream_offsets, int64_t U, const double *update_times,
+                                        const int64_t *update_offsets, int32_t N, const double *lin, const double *q_k_lin,
+                                        void *workspace, const cpi_outputs *out) {
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (R < 0 || K < 0 || U < 0 || N < 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams: negative size");
+    if (U == 0) return CPI_OK;
+    if (R == 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams: U > 0 windows and no run");
+    if (R > 0x7ffffffeLL) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams: R exceeds 2^31 - 2 runs");
+    if (K == 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams: the streams hold no reading");
+    if (!stream || !stream_offsets || !update_times || !update_offsets || !workspace)
+        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams: NULL argument");
+    if (((uintptr_t)workspace & 15) != 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams: the workspace must be 16-byte aligned");
+    if (!grid_ok(U)) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams: U exceeds 2^31 - 1 windows per call");
+    // as in cpi_preintegrate_stream: everything preintegrate_impl would refuse is refused before the cut kernel is enqueued
+    if (!prm || !out || !lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams: prm/out/lin is NULL");
+    if (prm->model != CPI_MODEL_V1 && prm->model != CPI_MODEL_V2 && prm->model != CPI_MODEL_FORSTER)
+        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams: model must be 1, 2 or 3 (CPI_MODEL_FORSTER)");
+    if (prm->model == CPI_MODEL_V2 && !q_k_lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams: model 2 needs q_k_lin");
+    if (N > 65535) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams: N (intervals per window) must be <= 65535");
+    if (prm->lanes_per_window != 0 && !launch::mean_lanes_supported(prm->lanes_per_window))
+        return fail(ctx, CPI_ERR_INVALID, "lanes_per_window must be 0 or one of 1,2,3,4,5,6,8,12,16,32,64");
+    RunArgs ra;
+    ra.soff = reinterpret_cast<const long long *>(stream_offsets);
+    ra.uoff = reinterpret_cast<const long long *>(update_offsets);
+    ra.R = (int)R;
+    const StreamCut sc = stream_cut(K, update_times, workspace, U, &ra);
     return preintegrate_impl(ctx, prm, U, N, stream, nullptr, nullptr, &sc, lin, q_k_lin, out);
 }
 
@@ -1377,6 +1427,56 @@ extern "C" int cpi_preintegrate_stream_host(cpi_ctx *ctx, const cpi_params *prm,
         }
     const int rc = cpi_preintegrate_stream(ctx, prm, K, (const double *)ds.p, U, (const double *)du.p, N, (const double *)dl.p,
                                            (const double *)dq.p, dw.p, &d);
+    if (rc != CPI_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    for (int k = 0; k < kOutFields; k++)
+        if (*out_field(&h, k))
+            CPI_HIP(ctx, hipMemcpyAsync(*out_field(&h, k), dout[k].p, (size_t)U * OUT_N[k] * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (count) CPI_HIP(ctx, hipMemcpyAsync(count, cpi_stream_counts(dw.p, U), (size_t)U * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    CPI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CPI_OK;
+}
+
+// The multi-run entry from HOST memory.  Unlike the device entry it can read the offsets, and it validates them before anything is
+// enqueued: each array starts at 0, never decreases and ends at K (stream_offsets) / U (update_offsets).
+extern "C" int cpi_preintegrate_streams_host(cpi_ctx *ctx, const cpi_params *prm, int64_t R, int64_t K, const double *stream,
+                                             const int64_t *stream_offsets, int64_t U, const double *update_times,
+                                             const int64_t *update_offsets, int32_t N, const double *lin, const double *q_k_lin,
+                                             const cpi_outputs *out, int32_t *count) {
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (R < 0 || K < 0 || U < 0 || N < 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams_host: negative size");
+    if (U == 0) return CPI_OK;
+    if (R == 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams_host: U > 0 windows and no run");
+    if (K == 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams_host: the streams hold no reading");
+    if (!prm || !out || !stream || !stream_offsets || !update_times || !update_offsets || !lin)
+        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams_host: NULL argument");
+    if (prm->model == CPI_MODEL_V2 && !q_k_lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams_host: model 2 needs q_k_lin");
+    for (int pass = 0; pass < 2; pass++) {
+        const int64_t *o = pass ? update_offsets : stream_offsets;
+        const int64_t end = pass ? U : K;
+        const char *what = pass ? "update_offsets" : "stream_offsets";
+        if (o[0] != 0) return fail(ctx, CPI_ERR_INVALID, std::string("cpi_preintegrate_streams_host: ") + what + "[0] is not 0");
+        for (int64_t r = 0; r < R; r++)
+            if (o[r + 1] < o[r]) return fail(ctx, CPI_ERR_INVALID, std::string("cpi_preintegrate_streams_host: ") + what + " decrease at run " + std::to_string(r));
+        if (o[R] != end) return fail(ctx, CPI_ERR_INVALID, std::string("cpi_preintegrate_streams_host: ") + what + "[R] is not " + (pass ? "U" : "K"));
+    }
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    DevBuf ds, dso, du, duo, dl, dq, dw, dout[kOutFields];
+    CPI_UP(ds, stream, (size_t)K * 7 * sizeof(double));
+    CPI_UP(dso, stream_offsets, (size_t)(R + 1) * sizeof(int64_t));
+    CPI_UP(du, update_times, (size_t)U * sizeof(double));
+    CPI_UP(duo, update_offsets, (size_t)(R + 1) * sizeof(int64_t));
+    CPI_UP(dl, lin, (size_t)U * 6 * sizeof(double));
+    CPI_UP(dq, q_k_lin, (size_t)U * 4 * sizeof(double));
+    CPI_HIP(ctx, hipMalloc(&dw.p, cpi_streams_workspace_bytes(R, U)));
+    cpi_outputs d = *out, h = *out;
+    for (int k = 0; k < kOutFields; k++)
+        if (*out_field(&h, k)) {
+            CPI_HIP(ctx, hipMalloc(&dout[k].p, (size_t)U * OUT_N[k] * sizeof(double)));
+            *out_field(&d, k) = (double *)dout[k].p;
+        }
+    const int rc = cpi_preintegrate_streams(ctx, prm, R, K, (const double *)ds.p, (const int64_t *)dso.p, U, (const double *)du.p,
+                                            (const int64_t *)duo.p, N, (const double *)dl.p, (const double *)dq.p, dw.p, &d);
     if (rc != CPI_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
     for (int k = 0; k < kOutFields; k++)
         if (*out_field(&h, k))

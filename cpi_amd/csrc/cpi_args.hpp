@@ -65,6 +65,16 @@ struct CarryArgs {
     int own_means;      // this kernel writes the tag and the means of the record
 };
 
+// Many IMU streams in one call (cpi_preintegrate_streams): run r owns the knots [soff[r], soff[r + 1]) of PreArgs::knots and the
+// windows [uoff[r], uoff[r + 1]).  Both arrays live in device memory and are CLAMPED where they are read (cpi_mean_kernels.hpp:
+// run_of / run_window): a wrong offset gives wrong windows, never an out-of-bounds read.  A separate kernel argument, so that
+// PreArgs -- and with it the code of every existing kernel -- stays as it was.
+struct RunArgs {
+    const long long *soff;   // [R + 1]
+    const long long *uoff;   // [R + 1]
+    int R;                   // >= 1
+};
+
 // tiles[b][s][k][i] = field k (t, w, a) of knot s of window 64 b + i (include/cpi_amd.h: cpi_preintegrate_tiled_batch)
 struct TiledArgs {
     long long W;
@@ -132,6 +142,10 @@ void tile_knots(long long W, int N, const double *knots, const long long *first,
 void assemble_tiles(const AssembleArgs &a, hipStream_t st);
 void cut_windows(long long K, const double *stream, long long U, const double *update, int N, long long *first, int *count,
                  double *tstart, double *tend, hipStream_t st);
+// cpi_preintegrate_streams: the cut of cut_windows for windows of many runs, and the fused mean-only kernel (CUT = 3)
+void cut_runs(long long K, const double *stream, long long U, const double *update, const RunArgs &r, long long *first, int *count,
+              double *tstart, double *tend, hipStream_t st);
+void mean_runs(int model, bool avg, int L, const PreArgs &a, const RunArgs &r, hipStream_t st);
 // ---- cpi_cov.hip
 void cov(int model, bool avg, const PreArgs &a, hipStream_t st);
 void cov_carry(int model, bool avg, const PreArgs &a, const CarryArgs &c, hipStream_t st);

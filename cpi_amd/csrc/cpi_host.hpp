@@ -592,6 +592,72 @@ private:
     std::vector<double> knots_;
 };
 
+// Many trajectories at once: one ImuStream per run (e.g. per dataset of a Monte-Carlo batch), each with its own update times,
+// preintegrated by ONE call (cpi_preintegrate_streams_host) -- every run's clock may start at 0.  preintegrate() returns, per
+// run, one CpiResult per update time of that run, equal to what that run's ImuStream::preintegrate would return with the same
+// bound and lane split (prm.lanes_per_window: the automatic choice depends on the total number of windows).
+class ImuStreamSet {
+public:
+    // the run's readings and its update times (non-decreasing); lin [U_r][6] and q_k_lin [U_r][4] (model 2) per window
+    void add_run(const ImuStream &run, const std::vector<double> &update_times, const std::vector<double> &lin,
+                 const std::vector<double> &q_k_lin = std::vector<double>()) {
+        if (lin.size() != update_times.size() * 6) throw std::runtime_error("ImuStreamSet::add_run: lin must hold 6 doubles per update time");
+        if (!q_k_lin.empty() && q_k_lin.size() != update_times.size() * 4) throw std::runtime_error("ImuStreamSet::add_run: q_k_lin must hold 4 doubles per update time");
+        knots_.insert(knots_.end(), run.knots().begin(), run.knots().end());
+        ut_.insert(ut_.end(), update_times.begin(), update_times.end());
+        lin_.insert(lin_.end(), lin.begin(), lin.end());
+        qk_.insert(qk_.end(), q_k_lin.begin(), q_k_lin.end());
+        soff_.push_back((int64_t)(knots_.size() / 7));
+        uoff_.push_back((int64_t)ut_.size());
+        runs_.push_back(update_times.size());
+    }
+    size_t runs() const { return runs_.size(); }
+    // counts (optional) receives every window's interval count, per run.  A window longer than max_intervals (default: as
+    // long as the longest run) is an error, not a truncation.
+    std::vector<std::vector<CpiResult>> preintegrate(const Context &ctx, const cpi_params &prm,
+                                                     std::vector<std::vector<int32_t>> *counts = nullptr, int32_t max_intervals = 0) const {
+        const int64_t R = (int64_t)runs_.size(), K = (int64_t)(knots_.size() / 7), U = (int64_t)ut_.size();
+        std::vector<std::vector<CpiResult>> res((size_t)R);
+        for (int64_t r = 0; r < R; r++) res[r].resize(runs_[r]);
+        if (counts) { counts->assign((size_t)R, std::vector<int32_t>()); }
+        if (U == 0) return res;
+        if (!qk_.empty() && qk_.size() != ut_.size() * 4) throw std::runtime_error("ImuStreamSet::preintegrate: q_k_lin given for some runs and not for others");
+        int64_t longest = 1;
+        for (int64_t r = 0; r < R; r++) longest = std::max<int64_t>(longest, soff_[r + 1] - soff_[r]);
+        const int32_t N = max_intervals > 0 ? max_intervals : (int32_t)std::min<int64_t>(longest, 65535);
+        std::vector<double> DT(U), al(U * 3), be(U * 3), q(U * 4), Jq(U * 9), Ja(U * 9), Jb(U * 9), Ha(U * 9), Hb(U * 9), Oa(U * 9),
+            Ob(U * 9), P(U * 225);
+        cpi_outputs o{ DT.data(), al.data(), be.data(), q.data(), Jq.data(), Ja.data(), Jb.data(), Ha.data(), Hb.data(),
+                       prm.model == CPI_MODEL_V2 ? Oa.data() : nullptr, prm.model == CPI_MODEL_V2 ? Ob.data() : nullptr, P.data() };
+        std::vector<int32_t> cnt((size_t)U);
+        ctx.check(cpi_preintegrate_streams_host(ctx.get(), &prm, R, K, knots_.data(), soff_.data(), U, ut_.data(), uoff_.data(), N,
+                                                lin_.data(), qk_.empty() ? nullptr : qk_.data(), &o, cnt.data()));
+        for (int64_t u = 0; u < U; u++)
+            if (cnt[u] > N) throw std::runtime_error("ImuStreamSet::preintegrate: window " + std::to_string(u) + " holds " + std::to_string(cnt[u]) +
+                                                     " intervals, more than max_intervals = " + std::to_string(N));
+        for (int64_t r = 0; r < R; r++) {
+            for (int64_t j = 0; j < (int64_t)runs_[r]; j++) {
+                const int64_t w = uoff_[r] + j;
+                CpiResult &x = res[r][j];
+                x.DT = DT[w];
+                for (int i = 0; i < 3; i++) { x.alpha_tau[i] = al[w * 3 + i]; x.beta_tau[i] = be[w * 3 + i]; }
+                for (int i = 0; i < 4; i++) x.q_k2tau[i] = q[w * 4 + i];
+                for (int i = 0; i < 9; i++) {
+                    x.J_q[i] = Jq[w * 9 + i]; x.J_a[i] = Ja[w * 9 + i]; x.J_b[i] = Jb[w * 9 + i]; x.H_a[i] = Ha[w * 9 + i];
+                    x.H_b[i] = Hb[w * 9 + i]; x.O_a[i] = Oa[w * 9 + i]; x.O_b[i] = Ob[w * 9 + i];
+                }
+                for (int i = 0; i < 225; i++) x.P_meas[i] = P[w * 225 + i];
+            }
+            if (counts) (*counts)[r].assign(cnt.begin() + uoff_[r], cnt.begin() + uoff_[r + 1]);
+        }
+        return res;
+    }
+private:
+    std::vector<double> knots_, ut_, lin_, qk_;
+    std::vector<int64_t> soff_{0}, uoff_{0};   // [R + 1]
+    std::vector<size_t> runs_;                 // update times per run
+};
+
 // evaluateError-shaped evaluator (ImuFactorCPIv1.h:139 / ImuFactorCPIv2.h:151).  state = 16 doubles
 // [q(4) bg(3) v(3) ba(3) p(3)]; error[15]; H1/H2 column-major 15x15, may be nullptr.
 class ImuFactorCPI {

@@ -102,6 +102,33 @@ void mean(int model, bool jac, bool avg, int L, const PreArgs &a, hipStream_t st
     if (model == CPI_MODEL_V2) launch_mean_M<2>(jac, avg, L, a, st); else launch_mean_M<1>(jac, avg, L, a, st);
 }
 
+// cpi_preintegrate_streams, mean-only: the fused route of the single-stream entry (cut == 2 above) for many runs, with the
+// same BIG admission (thresholds of stream windows, a stream of < 2^26 readings) -- R = 1 takes the kernel shape the
+// single-stream call takes
+template <int MODEL, bool AVG>
+static void launch_mean_runs_L(int L, const PreArgs &a, const RunArgs &r, hipStream_t st) {
+    const long long wmin = MODEL == 2 ? (long long)CPI_MEAN_BIG_W_M2 : (long long)CPI_MEAN_BIG_W;
+    if (L == 1 && a.K > 0 && a.K < (1ll << 26) && a.W >= wmin && a.N >= CPI_MEAN_BIG_NMIN) {
+        hipLaunchKernelGGL((cpi_mean_runs_kernel<MODEL, AVG, 1, true>), dim3((unsigned)((a.W + 63) / 64)), dim3(64),
+                           (size_t)CPI_MEAN_BIG_LDS_PAD, st, a, r);
+        return;
+    }
+#define CPI_LAUNCH_R(LL)                                                                         \
+    case LL:                                                                                     \
+        hipLaunchKernelGGL((cpi_mean_runs_kernel<MODEL, AVG, LL, false>), dim3((unsigned)((a.W + (64 / LL) - 1) / (64 / LL))), dim3(64), 0, st, a, r); \
+        break;
+    switch (L) {
+        CPI_LAUNCH_R(1) CPI_LAUNCH_R(2) CPI_LAUNCH_R(3) CPI_LAUNCH_R(4) CPI_LAUNCH_R(5) CPI_LAUNCH_R(6) CPI_LAUNCH_R(8)
+        CPI_LAUNCH_R(12) CPI_LAUNCH_R(16) CPI_LAUNCH_R(32) CPI_LAUNCH_R(64)
+        default: break;
+    }
+#undef CPI_LAUNCH_R
+}
+void mean_runs(int model, bool avg, int L, const PreArgs &a, const RunArgs &r, hipStream_t st) {
+    if (model == CPI_MODEL_V2) { if (avg) launch_mean_runs_L<2, true>(L, a, r, st); else launch_mean_runs_L<2, false>(L, a, r, st); }
+    else                       { if (avg) launch_mean_runs_L<1, true>(L, a, r, st); else launch_mean_runs_L<1, false>(L, a, r, st); }
+}
+
 // cpi_preintegrate_resume: the same lane split as the batch entry, always the plain-knot (CUT = 0, not BIG) instantiation
 template <int MODEL, bool JAC, bool AVG>
 static void launch_mean_carry_L(int L, const PreArgs &a, const CarryArgs &c, hipStream_t st) {
@@ -167,6 +194,11 @@ void cut_windows(long long K, const double *stream, long long U, const double *u
                  double *tstart, double *tend, hipStream_t st) {
     (void)N;
     hipLaunchKernelGGL(cpi_cut_windows_kernel, dim3((unsigned)((U + 255) / 256)), dim3(256), 0, st, K, stream, U, update, first, count, tstart, tend);
+}
+
+void cut_runs(long long K, const double *stream, long long U, const double *update, const RunArgs &r, long long *first, int *count,
+              double *tstart, double *tend, hipStream_t st) {
+    hipLaunchKernelGGL(cpi_cut_runs_kernel, dim3((unsigned)((U + 255) / 256)), dim3(256), 0, st, K, stream, U, update, r, first, count, tstart, tend);
 }
 
 void assemble_tiles(const AssembleArgs &a, hipStream_t st) {

@@ -1,7 +1,7 @@
 // cpi_mean_body.inc -- the body of cpi_mean_kernel and cpi_mean_carry_kernel (cpi_mean_kernels.hpp), included inside both.
 // Shared as text rather than through a device function so that the batch kernels compile to exactly the code they had
 // before the carry path existed (a body function changes their scalar register allocation).  In scope where it is
-// included: MODEL, JAC, AVG, L, CUT, BIG, CARRY, the kernel arguments A (PreArgs) and CA (CarryArgs).
+// included: MODEL, JAC, AVG, L, CUT, BIG, CARRY, the kernel arguments A (PreArgs), CA (CarryArgs) and RA (RunArgs; CUT = 3 only).
     static_assert(!BIG || (L == 1 && !JAC), "BIG: one lane per window, mean-only");
     constexpr int WPB = 64 / L;       // windows per wavefront
     // knots staged per lane per chunk: measured on MI355X -- 2 when a lane has several intervals (L <= 8; 20 k x 50 with
@@ -28,7 +28,21 @@
     // knot less and builds that knot from its predecessor when it gets there.
     double t_start = 0.0, t_end = 0.0;
     bool tail = false;
-    if constexpr (CUT == 2) {
+    if constexpr (CUT == 3) {
+        // many runs: the run of the wavefront's first window, by a bisection on wave-uniform values (scalar loads); when the
+        // run also owns the wavefront's last window -- every wavefront but the few that straddle a run boundary -- that is
+        // every lane's run, otherwise each lane bisects for its own.  Then the CUT = 2 arithmetic on the run's readings.
+        const long long wb = (long long)blockIdx.x * WPB, we = min(wb + WPB, A.W) - 1;
+        int r = run_of(RA, wb);
+        if (!(RA.uoff[r + 1] > we)) r = run_of(RA, w);
+        const RunWindow c = run_window(A.knots, A.K, A.update, RA, r, w);
+        if (valid && l == 0) A.count_out[w] = c.cnt;                     // the TRUE count (cpi_stream_counts)
+        k0 = c.k0;
+        n = min(c.cnt, A.N);
+        t_start = c.t_start;
+        t_end = A.update[w];
+        tail = c.tail && c.cnt <= A.N;                                   // a truncated window has lost its tail
+    } else if constexpr (CUT == 2) {
         // the arithmetic of cpi_cut_windows_kernel (GraphSolver_IMU.cpp:50-69 as a closed form), per lane, in registers
         const double ts0 = A.knots[0], ts1 = A.knots[(A.K - 1) * 7];
         const double T = A.update[w], Tp = A.update[w > 0 ? w - 1 : 0];

@@ -58,6 +58,59 @@ __device__ __forceinline__ long long knots_not_after_near(const double *stream, 
     return r;
 }
 
+// ---- many streams in one call (cpi_preintegrate_streams; RunArgs: cpi_args.hpp)
+// The run that owns window u: the last r with uoff[r] <= u, by bisection over uoff[1 .. R - 1] -- whatever the offsets hold
+// (they live in device memory), the result lies in [0, R - 1].  log2(R) dependent loads of one small array.
+__device__ __forceinline__ int run_of(const RunArgs &RA, long long u) {
+    int lo = 0, hi = RA.R;                // the run lies in [lo, hi)
+    while (hi - lo > 1) {
+        const int mid = lo + ((hi - lo) >> 1);   // (lo + hi overflows an int for R > 2^30)
+        if (RA.uoff[mid] <= u) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+// knots_not_after_near for the n readings of one run, which may hold fewer than the four it probes
+__device__ __forceinline__ long long knots_in_run(const double *s, long long n, double t0, double t1, double T, double &last_stamp) {
+    if (n >= 4) return knots_not_after_near(s, n, t0, t1, T, last_stamp);
+    long long c = 0;
+    while (c < n && s[c * 7] <= T) c++;
+    last_stamp = c > 0 ? s[(c - 1) * 7] : t0;
+    return c;
+}
+// Window u of run r, cut the way cpi_cut_windows_kernel cuts window u - uoff[r] of a stream holding that run's readings alone
+// (its first window starts at the run's first reading).  The offsets are clamped into [0, K] (knots) and [0, u] (the run's
+// first window); a run without readings yields a window of 0 intervals based on a knot that exists (K >= 1: the entry
+// refuses an empty stream), so the kernels that read it stay inside the stream.
+struct RunWindow {
+    long long k0;      // the front reading (global knot index)
+    int cnt;           // TRUE intervals (whole + tail)
+    double t_start;    // stamp of the front reading
+    bool tail;         // the last interval is [stamp of the last real knot, T]
+};
+__device__ __forceinline__ RunWindow run_window(const double *stream, long long K, const double *update, const RunArgs &RA, int r, long long u) {
+    const long long kb = min(max(RA.soff[r], 0ll), K);
+    const long long kn = min(max(RA.soff[r + 1], kb), K) - kb;
+    // the run's first window -- or an offset past u, treated as one.  Window 0 is always a first window, whatever uoff[r] holds
+    // (a negative offset must not send it to update[-1]): every other window has a predecessor in update[].
+    const bool head = u <= max(RA.uoff[r], 0ll);
+    const double *rs = stream + kb * 7;
+    const double t0 = kn > 0 ? rs[0] : 0.0, t1 = kn > 0 ? rs[(kn - 1) * 7] : 0.0;
+    const double T = update[u], Tp = update[head ? u : u - 1];
+    double stT, stP;
+    const long long cT = knots_in_run(rs, kn, t0, t1, T, stT);
+    const long long cP = knots_in_run(rs, kn, t0, t1, Tp, stP);
+    const long long fp = head ? 0ll : max(cP - 1, 0ll);
+    RunWindow o;
+    o.t_start = head ? t0 : fmax(Tp, t0);
+    const long long fu = max(max(cT - 1, 0ll), fp);
+    const int m = (int)min(fu - fp, (long long)0x3fffffff);
+    const double front_t = (m > 0) ? stT : o.t_start;                   // m > 0: fu = cT - 1, whose stamp the search returned
+    o.tail = kn > 0 && (T - front_t) > 0;
+    o.cnt = m + (o.tail ? 1 : 0);
+    o.k0 = kn > 0 ? kb + fp : min(kb, K - 1);
+    return o;
+}
+
 // ============================================================================================
 // mean (+ analytic Jacobian) kernel
 // ============================================================================================
@@ -93,10 +146,14 @@ __device__ __forceinline__ long long knots_not_after_near(const double *stream, 
 // intervals" unchanged.  That holds for the model-2 segments with a gravity response (GSEG) too: lane 0 integrates with the
 // carried rotation, i.e. in the window-start frame, and its gravity response starts at zero because the carried means
 // already contain the gravity of the intervals before.  The window's final state is written back to the record.
+// CUT = 3 (cpi_mean_runs_kernel, mean-only requests of cpi_preintegrate_streams): CUT = 2 for windows of many runs -- the
+// prologue first finds the run of its window (RunArgs), then cuts the window out of that run's readings; everything after the
+// prologue is the CUT = 2 path on the whole stream.
 template <int MODEL, bool JAC, bool AVG, int L, int CUT, bool BIG = false>
 __global__ __launch_bounds__(64, BIG ? 2 : (((MODEL == 2 && !JAC) || (MODEL == 1 && JAC)) && L == 1 ? 2 : CPI_MEAN_WPS)) void cpi_mean_kernel(PreArgs A) {
     constexpr bool CARRY = false;
     [[maybe_unused]] const CarryArgs CA = {};
+    [[maybe_unused]] const RunArgs RA = {};
 #include "cpi_mean_body.inc"
 }
 // cpi_preintegrate_resume: the plain-knot path of cpi_mean_kernel<MODEL, JAC, AVG, L, 0> from and to carry records
@@ -105,6 +162,17 @@ __global__ __launch_bounds__(64, (((MODEL == 2 && !JAC) || (MODEL == 1 && JAC)) 
     constexpr bool CARRY = true;
     constexpr int CUT = 0;
     constexpr bool BIG = false;
+    [[maybe_unused]] const RunArgs RA = {};
+#include "cpi_mean_body.inc"
+}
+// cpi_preintegrate_streams, mean-only: cpi_mean_kernel<MODEL, false, AVG, L, 3, BIG> -- its own __global__ only because the run
+// offsets travel as a second argument (RunArgs) instead of growing PreArgs
+template <int MODEL, bool AVG, int L, bool BIG>
+__global__ __launch_bounds__(64, BIG ? 2 : ((MODEL == 2 && L == 1) ? 2 : CPI_MEAN_WPS)) void cpi_mean_runs_kernel(PreArgs A, RunArgs RA) {
+    constexpr bool JAC = false;
+    constexpr int CUT = 3;
+    constexpr bool CARRY = false;
+    [[maybe_unused]] const CarryArgs CA = {};
 #include "cpi_mean_body.inc"
 }
 
@@ -332,6 +400,16 @@ __global__ __launch_bounds__(256) void cpi_cut_windows_kernel(long long K, const
     const bool tail = (T - front_t) > 0;
     first[u] = fp; count[u] = m + (tail ? 1 : 0); tstart[u] = start_t;
     tend[u] = tail ? T : __builtin_nan("");
+}
+// The same 28 bytes per window for the windows of many runs (cpi_preintegrate_streams): first[u] indexes the whole stream, so
+// the covariance, Forster and analytic-Jacobian kernels read multi-run windows through their CUT = 1 path unchanged.
+__global__ __launch_bounds__(256) void cpi_cut_runs_kernel(long long K, const double *stream, long long U, const double *update, RunArgs RA,
+                                                           long long *first, int *count, double *tstart, double *tend) {
+    const long long u = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (u >= U) return;
+    const RunWindow c = run_window(stream, K, update, RA, run_of(RA, u), u);
+    first[u] = c.k0; count[u] = c.cnt; tstart[u] = c.t_start;
+    tend[u] = c.tail ? update[u] : __builtin_nan("");
 }
 // Rows leave as coalesced 512-byte stores (lane = window).  It is a copy with a transposition in it; designs measured on the
 // 1 M x 50 batch (profiles/r04_assembler.md):

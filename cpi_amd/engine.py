@@ -373,6 +373,118 @@ class Engine:
             raise ValueError("preintegrate_stream_host: a window has %d intervals, N = %d" % (int(cnt.max()), N))
         return (out, cnt) if return_counts else out
 
+    @staticmethod
+    def _runs(data, offsets, name, device):
+        """(one tensor, offsets) or a list of per-run tensors (offsets None) -> (tensor, int64 offsets [R + 1] on `device`)."""
+        if isinstance(data, (list, tuple)):
+            assert offsets is None, "%s: a list of per-run tensors carries its own offsets (pass None)" % name
+            lens = [int(t.shape[0]) for t in data]
+            data = torch.cat(list(data), dim=0).contiguous() if data else None
+            offsets = torch.tensor(np.concatenate([[0], np.cumsum(lens)]).astype(np.int64), device=device)
+            return data, offsets
+        assert offsets is not None, "%s: one tensor needs its run offsets [R + 1]" % name
+        if not torch.is_tensor(offsets):
+            offsets = torch.tensor(np.asarray(offsets, dtype=np.int64), device=device)
+        return data, offsets.to(device=device, dtype=torch.int64).contiguous()
+
+    def preintegrate_streams(self, stream, stream_offsets, update_times, update_offsets, lin, q_k_lin=None, params=None,
+                             want=("mean", "jac", "cov"), N=None, out=None, return_counts=False, check_counts=True, workspace=None):
+        """MANY IMU streams (runs, trajectories) cut at their update times and preintegrated in ONE call
+        (cpi_preintegrate_streams): run r owns the readings stream[stream_offsets[r]:stream_offsets[r + 1]] and the windows
+        [update_offsets[r], update_offsets[r + 1]); window u of run r equals window u - update_offsets[r] of preintegrate_stream on
+        run r alone (same N, params and lane split).  Stamps non-decreasing within a run, any order across runs.
+        stream [K, 7], update_times [U], lin [U, 6], q_k_lin [U, 4]: CUDA float64; the offsets [R + 1]: int64 tensors (moved to
+        the device) or sequences.  Convenience: stream may be a LIST of per-run [K_r, 7] tensors and update_times a list of per-run
+        [U_r] tensors (pass None as their offsets) -- they are concatenated ONCE, here (a copy of every reading, and offsets built
+        on the host: not graph-capturable).
+        N, return_counts, check_counts, workspace as in preintegrate_stream: N=None = streams_bound() (one host
+        synchronisation, NOT cached), N="loose" = min(K, 65535) (no synchronisation), an integer is used as given."""
+        params = params or self.make_params()
+        stream, soff = self._runs(stream, stream_offsets, "stream", self.device)
+        update_times, uoff = self._runs(update_times, update_offsets, "update_times", self.device)
+        if stream is None:
+            stream = torch.empty((0, 7), dtype=torch.float64, device=self.device)
+        if update_times is None:
+            update_times = torch.empty((0,), dtype=torch.float64, device=self.device)
+        R, K, U = soff.shape[0] - 1, stream.shape[0], update_times.shape[0]
+        assert uoff.shape[0] == R + 1, "stream_offsets and update_offsets must both hold R + 1 entries"
+        for t in (stream, update_times, lin, q_k_lin):
+            assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64), "inputs must be contiguous CUDA float64 tensors"
+        if N is None:
+            N = self.streams_bound(stream, soff, update_times, uoff)
+        elif isinstance(N, str):
+            assert N == "loose", 'N: an integer, None (exact bound, synchronises once) or "loose"'
+            N = max(1, min(K, 65535))
+        if out is None:
+            out = self.alloc_outputs(U, want, params.model)
+        ws = workspace if workspace is not None else self.streams_workspace(R, U)
+        o = self._outputs_struct(out)
+        self._sync_stream()
+        self._check(self.lib.cpi_preintegrate_streams(self.ctx, C.byref(params), R, K, _ptr(stream), _ptr(soff), U, _ptr(update_times),
+                                                      _ptr(uoff), int(N), _ptr(lin), _ptr(q_k_lin), _ptr(ws), C.byref(o)))
+        # the workspace and the offsets must outlive the kernels that read them (see preintegrate_stream)
+        if not self._follow and self.stream is not None:
+            for t in ((ws,) if workspace is None else ()) + (soff, uoff, stream, update_times):
+                t.record_stream(self.stream)
+        counts = torch.empty((0,), dtype=torch.int32, device=self.device)
+        if U and (return_counts or check_counts):
+            off = (self.lib.cpi_stream_counts(_ptr(ws), U) - ws.data_ptr()) // 4
+            with torch.cuda.stream(self.stream) if (not self._follow and self.stream is not None) else _nullctx():
+                counts = ws.view(torch.int32)[off:off + U].clone()
+            if check_counts and int(counts.max().item()) > N:
+                raise ValueError("preintegrate_streams: a window has %d intervals, more than N = %d" % (int(counts.max().item()), N))
+        return (out, counts) if return_counts else out
+
+    @staticmethod
+    def streams_bound(stream, stream_offsets, update_times, update_offsets):
+        """Longest window (whole intervals + a tail) that cutting every run at its update times can produce: stream_bound's closed
+        form of the deque loop run by run, the maximum over all runs (runs without readings or update times contribute nothing).
+        Works on CPU or CUDA tensors; reads the offsets on the host and ends in ONE host synchronisation.  Not cached: it is
+        recomputed on every call (a cache keyed by storage and version serves stale bounds to re-allocated buffers)."""
+        so = [int(v) for v in torch.as_tensor(stream_offsets).cpu().tolist()]
+        uo = [int(v) for v in torch.as_tensor(update_offsets).cpu().tolist()]
+        assert len(so) == len(uo) and len(so) >= 1, "offsets: R + 1 entries each"
+        stamps = stream[:, 0].contiguous()
+        best = []
+        for r in range(len(so) - 1):
+            if so[r + 1] <= so[r] or uo[r + 1] <= uo[r]:
+                continue
+            c = torch.searchsorted(stamps[so[r]:so[r + 1]].contiguous(), update_times[uo[r]:uo[r + 1]].contiguous(), right=True)
+            fp = torch.zeros_like(c)
+            fp[1:] = (c[:-1] - 1).clamp_min(0)
+            best.append((torch.maximum((c - 1).clamp_min(0), fp) - fp).max())
+        if not best:
+            return 1
+        return max(1, min(int(torch.stack(best).max().item()) + 1, 65535))
+
+    def streams_workspace(self, R, U):
+        """Device workspace of preintegrate_streams (cpi_streams_workspace_bytes; re-usable across calls)."""
+        return torch.empty((self.lib.cpi_streams_workspace_bytes(R, U) // 8 + 1,), dtype=torch.float64, device=self.device)
+
+    def preintegrate_streams_host(self, stream, stream_offsets, update_times, update_offsets, lin, q_k_lin=None, params=None,
+                                  want=("mean", "jac", "cov"), N=None, pinned=False, return_counts=False):
+        """preintegrate_streams from HOST memory (cpi_preintegrate_streams_host, which validates the offsets): CPU float64 tensors
+        and int64 offsets in, CPU tensors out; synchronous.  N defaults to streams_bound(); a longer window raises."""
+        params = params or self.make_params()
+        soff = torch.as_tensor(np.asarray(stream_offsets, dtype=np.int64))
+        uoff = torch.as_tensor(np.asarray(update_offsets, dtype=np.int64))
+        R, K, U = soff.shape[0] - 1, stream.shape[0], update_times.shape[0]
+        N = int(N) if N is not None else self.streams_bound(stream, soff, update_times, uoff)
+        for t in (stream, update_times, lin, q_k_lin):
+            assert t is None or (not t.is_cuda and t.is_contiguous() and t.dtype == torch.float64), "inputs must be contiguous CPU float64 tensors"
+        out = {}
+        for name, n in OUT_FIELDS:
+            if _group_of(name) in want and (params.model == 2 or name not in ("O_a", "O_b")):
+                out[name] = torch.empty((U,) if n == 1 else (U, n), dtype=torch.float64, pin_memory=pinned)
+        cnt = torch.empty((U,), dtype=torch.int32)
+        o = self._outputs_struct(out)
+        self._sync_stream()
+        self._check(self.lib.cpi_preintegrate_streams_host(self.ctx, C.byref(params), R, K, _ptr(stream), _ptr(soff), U, _ptr(update_times),
+                                                           _ptr(uoff), N, _ptr(lin), _ptr(q_k_lin), C.byref(o), _ptr(cnt)))
+        if U and int(cnt.max()) > N:
+            raise ValueError("preintegrate_streams_host: a window has %d intervals, N = %d" % (int(cnt.max()), N))
+        return (out, cnt) if return_counts else out
+
     def preintegrate_tiled_host(self, tiles, W, lin, q_k_lin=None, params=None, count=None, pinned=True, out=None):
         """Mean outputs from tiles held in HOST memory (cpi_preintegrate_tiled_batch_host: chunked upload / kernel /
         download pipeline).  CPU float64 tensors; returns CPU tensors; synchronous."""

@@ -48,7 +48,8 @@ extern "C" {
                                mean-only request runs no cut kernel, so the first / tstart / tend records round 3 left there
                                are no longer written (they were never declared);
                                additions within 3 (new symbols only): cpi_carry_doubles, cpi_preintegrate_resume,
-                               cpi_preintegrate_resume_host (resumable preintegration) */
+                               cpi_preintegrate_resume_host (resumable preintegration); cpi_streams_workspace_bytes,
+                               cpi_preintegrate_streams, cpi_preintegrate_streams_host (many IMU streams in one call) */
 
 enum { CPI_OK = 0, CPI_ERR_INVALID = 1, CPI_ERR_HIP = 2, CPI_ERR_NO_DEVICE = 3, CPI_ERR_RCCL = 4 };
 enum {
@@ -211,6 +212,38 @@ int cpi_preintegrate_stream(cpi_ctx *ctx, const cpi_params *prm, int64_t K, cons
                             const double *update_times, int32_t N, const double *lin, const double *q_k_lin,
                             void *workspace, const cpi_outputs *out);
 const int32_t *cpi_stream_counts(const void *workspace, int64_t U);   /* device pointer into the workspace: count[U] */
+
+/* Many trajectories at once: cpi_preintegrate_stream for R runs (IMU streams) in ONE call, every window cut in place.
+ *   stream          [K][7] the runs' readings back to back (device memory); run r owns the knots
+ *                   [stream_offsets[r], stream_offsets[r + 1]).  Stamps NON-DECREASING within a run; nothing is assumed across
+ *                   runs (every run may start its clock at 0)
+ *   stream_offsets  [R + 1] (device memory): 0 = stream_offsets[0] <= ... <= stream_offsets[R] = K
+ *   update_times    [U] (device memory); run r owns the windows u in [update_offsets[r], update_offsets[r + 1]), whose update
+ *                   times are non-decreasing
+ *   update_offsets  [R + 1] (device memory): 0 = update_offsets[0] <= ... <= update_offsets[R] = U
+ *   N, lin, q_k_lin, out   as in cpi_preintegrate_stream, indexed by the GLOBAL window u in [0, U)
+ *   workspace       cpi_streams_workspace_bytes(R, U) bytes of device memory, 16-byte aligned.  Its layout starts with that of
+ *                   cpi_stream_workspace_bytes(U), so cpi_stream_counts(workspace, U) holds the TRUE counts after the call;
+ *                   the rest of its contents is unspecified.  (Today the two sizes are equal for every R.)
+ * Window u of run r is, bit for bit, window u - update_offsets[r] of a cpi_preintegrate_stream call on the readings and update
+ * times of run r alone with the same N and params and the same lane split (cpi_params.lanes_per_window: the automatic choice
+ * depends on U, so only a pinned value gives the per-run call's split) -- except the covariance of model 3, which depends on
+ * the windows that share its wavefront in the last bits (~1e-22 of a covariance entry); the whole call is bit for bit
+ * cpi_preintegrate_batch on the windows the host assemblers cut out of every run, for every model: the first window of a run starts at that run's first
+ * reading, and the models (1, 2, 3 = Forster), the outputs, the tail interval and truncation to N intervals follow
+ * cpi_preintegrate_stream.  A run without readings yields windows of 0 intervals (the identity / zero state, count 0); a run
+ * without update times contributes nothing; runs of 1, 2 or 3 readings are fine.  K == 0 with U > 0 (no reading at all) and
+ * R == 0 with U > 0 return CPI_ERR_INVALID; U == 0 is a no-op.
+ * The offsets live in device memory and cannot be validated by the call: the kernels CLAMP them (into [0, K] / [0, U]) --
+ * wrong offsets give wrong windows, never an out-of-bounds read.  cpi_preintegrate_streams_host validates them.
+ * A mean-only request (models 1 and 2) runs ONE kernel: every wavefront finds the run of its windows (a bisection over
+ * update_offsets, done once per wavefront unless it straddles a run boundary) and cuts its windows in its prologue; every other
+ * request runs a cut kernel first, as cpi_preintegrate_stream does.  No host synchronisation: the call can be captured into a
+ * graph. */
+size_t cpi_streams_workspace_bytes(int64_t R, int64_t U);
+int cpi_preintegrate_streams(cpi_ctx *ctx, const cpi_params *prm, int64_t R, int64_t K, const double *stream,
+                             const int64_t *stream_offsets, int64_t U, const double *update_times, const int64_t *update_offsets,
+                             int32_t N, const double *lin, const double *q_k_lin, void *workspace, const cpi_outputs *out);
 
 /* The same loop for the mean outputs (DT, alpha, beta, q) on the TILED layout: the knots of 64 consecutive windows
  * interleaved per step,
@@ -423,6 +456,14 @@ int cpi_preintegrate_tiled_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64
 int cpi_preintegrate_stream_host(cpi_ctx *ctx, const cpi_params *prm, int64_t K, const double *stream, int64_t U,
                                  const double *update_times, int32_t N, const double *lin, const double *q_k_lin,
                                  const cpi_outputs *out, int32_t *count);
+/* cpi_preintegrate_streams with HOST pointers (pageable or pinned); count (may be NULL) receives the TRUE interval count of
+ * every window.  The offsets ARE validated here: an array that does not start at 0, decreases or does not end at K /
+ * U returns CPI_ERR_INVALID before anything is enqueued.  Uploads the runs once, whole; PCIe-inclusive, never the benchmarked
+ * path. */
+int cpi_preintegrate_streams_host(cpi_ctx *ctx, const cpi_params *prm, int64_t R, int64_t K, const double *stream,
+                                  const int64_t *stream_offsets, int64_t U, const double *update_times,
+                                  const int64_t *update_offsets, int32_t N, const double *lin, const double *q_k_lin,
+                                  const cpi_outputs *out, int32_t *count);
 void *cpi_host_alloc(size_t bytes);
 void cpi_host_free(void *p);
 int cpi_factor_eval_batch_host(cpi_ctx *ctx, int32_t model, const double grav[3], int64_t F,
