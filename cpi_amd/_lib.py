@@ -157,6 +157,8 @@ def load():
     lib.cpi_carry_doubles.restype = C.c_size_t
     lib.cpi_preintegrate_resume.argtypes = [vp, C.POINTER(CpiParams), i64, i32, dp, vp, vp, dp, dp, dp, dp, C.POINTER(CpiOutputs)]
     lib.cpi_preintegrate_resume_host.argtypes = [vp, C.POINTER(CpiParams), i64, i32, dp, vp, vp, i64, dp, dp, dp, dp, C.POINTER(CpiOutputs)]
+    lib.cpi_preintegrate_running.argtypes = [vp, C.POINTER(CpiParams), i64, i32, dp, vp, vp, dp, dp, C.POINTER(CpiOutputs)]
+    lib.cpi_preintegrate_running_host.argtypes = [vp, C.POINTER(CpiParams), i64, i32, dp, vp, vp, i64, dp, dp, C.POINTER(CpiOutputs)]
     lib.cpi_host_alloc.argtypes = [C.c_size_t]
     lib.cpi_host_alloc.restype = C.c_void_p
     lib.cpi_host_free.argtypes = [vp]
@@ -170,7 +172,7 @@ def load():
               lib.cpi_group_last_gather_messages, lib.cpi_preintegrate_stream_host, lib.cpi_sqrt_information_packed_batch,
               lib.cpi_factor_eval_whitened_tri_batch, lib.cpi_factor_hessian_tri_batch, lib.cpi_group_gather_chunk,
               lib.cpi_preintegrate_resume, lib.cpi_preintegrate_resume_host, lib.cpi_preintegrate_streams,
-              lib.cpi_preintegrate_streams_host):
+              lib.cpi_preintegrate_streams_host, lib.cpi_preintegrate_running, lib.cpi_preintegrate_running_host):
         f.restype = C.c_int
     _lib = lib
     return lib

@@ -7,7 +7,7 @@
     python -m cpi_amd.build --test-hooks         # additionally libcpi_amd_test.so (-DCPI_TEST_HOOKS: the two entries of
                                                  # include/cpi_amd_test.h; the PRODUCT library exports nothing but include/cpi_amd.h)
 
-The library is four translation units (cpi_amd/csrc/cpi_args.hpp) compiled IN PARALLEL into cpi_amd/csrc/_obj/*.o and
+The library is five translation units (cpi_amd/csrc/cpi_args.hpp) compiled IN PARALLEL into cpi_amd/csrc/_obj/*.o and
 linked into one shared object; an object is rebuilt only when the sources it includes (or the flags) change, so touching
 one kernel family costs one TU.  hipcc cross-compiles gfx950 without a GPU present; the .so is git-ignored but ships to
 the GPU box.
@@ -34,6 +34,7 @@ DEVICE = COMMON + ["cpi_math.hpp", "cpi_device_util.hpp"]
 # translation unit -> the files it includes (what its object depends on)
 UNITS = {
     "cpi_mean": DEVICE + ["cpi_mean.hip", "cpi_mean_kernels.hpp", "cpi_mean_body.inc"],
+    "cpi_running": DEVICE + ["cpi_running.hip", "cpi_running_kernels.hpp"],
     "cpi_cov": DEVICE + ["cpi_cov.hip", "cpi_cov_kernels.hpp"],
     "cpi_factor": DEVICE + ["cpi_factor.hip", "cpi_factor_kernels.hpp"],
     "cpi_abi": COMMON + ["cpi_abi.hip", "../../include/cpi_amd_test.h"],   # the test header: -DCPI_TEST_HOOKS builds only
@@ -219,7 +220,7 @@ def _build_locked(force, report, experiments, test_hooks):
     for variant, wanted in (("", True), ("exp", experiments), ("test", test_hooks)):
         if wanted and (force or stale(VARIANTS[variant][0], variant=variant)):
             todo.append(variant)
-    # every object of every wanted variant in ONE pool (the default build's four units + the units a variant compiles with its own
+    # every object of every wanted variant in ONE pool (the default build's five units + the units a variant compiles with its own
     # define): __graft_entry__.build() rebuilds three libraries in the time of the slowest translation unit
     jobs = {}
     for variant in todo:

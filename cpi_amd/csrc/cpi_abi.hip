@@ -455,6 +455,58 @@ extern "C" int cpi_preintegrate_resume(cpi_ctx *ctx, const cpi_params *prm, int6
     return CPI_OK;
 }
 
+// Running preintegration: the measurement after EVERY interval (include/cpi_amd.h).  rows holds W * N rows; the means and the
+// model-1 analytic Jacobians come from cpi_mean_running_kernel (the batch entry's lane choice, pick_lanes), the covariance rows
+// from cpi_cov_running_kernel.  The kernels run one after the other on the context's stream (no side stream: a capture of the
+// call is a chain), and unlike the batch entry the covariance kernel leaves the means to the mean kernel -- its own means
+// advance once per staged pass, not per interval.
+extern "C" int cpi_preintegrate_running(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                        const double *knots, const int64_t *first, const int32_t *count,
+                                        const double *lin, const double *q_k_lin, const cpi_outputs *rows) {
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (!prm || !rows) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running: prm/rows is NULL");
+    if (prm->model == CPI_MODEL_FORSTER)
+        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running: model must be 1 or 2 (the Forster comparator has no running form)");
+    if (prm->model != CPI_MODEL_V1 && prm->model != CPI_MODEL_V2)
+        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running: model must be 1 or 2");
+    const bool want_mean = rows->DT || rows->alpha || rows->beta || rows->q;
+    const bool want_jac = rows->J_q || rows->J_a || rows->J_b || rows->H_a || rows->H_b || rows->O_a || rows->O_b;
+    const bool want_cov = rows->P != nullptr || rows->P_sym != nullptr;
+    if (prm->model == CPI_MODEL_V2 && want_jac)
+        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running: the Jacobian fields (J_q ... O_b) are not available for model 2 "
+                                          "(they are read out of the state transition matrix at the end of the recursion)");
+    if (W < 0 || N < 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running: negative size");
+    if (W == 0 || N == 0) return CPI_OK;
+    if (!knots || !lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running: knots/lin is NULL");
+    if (prm->model == CPI_MODEL_V2 && !q_k_lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running: model 2 needs q_k_lin");
+    if (!grid_ok(W)) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running: W exceeds 2^31 - 1 windows per call (32-bit grid)");
+    if (N > 65535) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running: N (intervals per window) must be <= 65535");
+    const int Lp = prm->lanes_per_window;
+    if (Lp != 0 && !launch::mean_lanes_supported(Lp)) return fail(ctx, CPI_ERR_INVALID, "lanes_per_window must be 0 or one of 1,2,3,4,5,6,8,12,16,32,64");
+    if (!want_mean && !want_jac && !want_cov) return CPI_OK;
+    const bool avg = prm->imu_avg != 0;
+
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    PreArgs a;
+    memset(&a, 0, sizeof a);
+    a.W = W; a.N = N; a.knots = knots; a.first = (const long long *)first; a.count = count;
+    a.lin = lin; a.qk = q_k_lin;
+    for (int i = 0; i < 3; i++) a.grav[i] = prm->grav[i];
+    a.q4[0] = prm->sigma_w * prm->sigma_w; a.q4[1] = prm->sigma_wb * prm->sigma_wb;
+    a.q4[2] = prm->sigma_a * prm->sigma_a; a.q4[3] = prm->sigma_ab * prm->sigma_ab;
+    a.out = *rows;
+    if (want_mean || want_jac) {
+        PreArgs m = a;
+        m.write_means = want_mean ? 1 : 0;
+        m.write_jac = want_jac ? 1 : 0;
+        launch::mean_running(prm->model, want_jac, avg, pick_lanes(prm, W, N, want_jac), m, ctx->stream);
+    }
+    if (want_cov) launch::cov_running(prm->model, avg, a, ctx->stream);
+    CPI_HIP(ctx, hipGetLastError());
+    return CPI_OK;
+}
+
 // Replaces the caller-side loop of GraphSolver::createimufactor_cpi_v1 / _v2 (GraphSolver_IMU.cpp:43-75, 97-130) for ALL the
 // windows of a trajectory at once, with ZERO copies of the IMU data: cpi_cut_windows_kernel finds, per update time, where the
 // reference's deque would stand (28 bytes per window into the caller's workspace), and the preintegration kernels read the
@@ -1251,12 +1303,16 @@ extern "C" void *cpi_host_alloc(size_t bytes) {
 extern "C" void cpi_host_free(void *p) { if (p) (void)hipHostFree(p); }
 
 // tiled == false: knots[W][N+1][7];  tiled == true: tiles[ceil(W/64)][N+1][7][64] (chunks are whole tiles)
+// running: cpi_preintegrate_running -- N output rows per window instead of one, chunks of <= 65536 ROWS
 static int preintegrate_host_pipeline(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N, const double *knots, bool tiled,
-                                      const int32_t *count, const double *lin, const double *q_k_lin, const cpi_outputs *out) {
+                                      const int32_t *count, const double *lin, const double *q_k_lin, const cpi_outputs *out,
+                                      bool running = false) {
     int rc = host_pipe_get(ctx);
     if (rc != CPI_OK) return rc;
     HostPipe *hp = ctx->pipe;
-    const int64_t nch = (W + 65535) / 65536;
+    const size_t R = running ? (size_t)N : 1;            // output rows per window
+    const int64_t cw = running ? std::max<int64_t>(64, 65536 / (int64_t)R / 64 * 64) : 65536;
+    const int64_t nch = (W + cw - 1) / cw;
     const int64_t Wc = std::min<int64_t>(W, (((W + nch - 1) / nch) + 63) / 64 * 64);   // balanced chunks, whole wavefronts / tiles
     const int nslots = nch > 1 ? 2 : 1;
     const size_t knot_bytes = (size_t)(N + 1) * 7 * sizeof(double);
@@ -1268,7 +1324,7 @@ static int preintegrate_host_pipeline(cpi_ctx *ctx, const cpi_params *prm, int64
         for (int k = 0; k < 4; k++)
             if ((rc = host_pipe_reserve(ctx, hp->in[s][k], hp->in_cap[s][k], need[k])) != CPI_OK) return rc;
         for (int k = 0; k < kOutFields; k++)
-            if (*out_field(&h, k) && (rc = host_pipe_reserve(ctx, hp->out[s][k], hp->out_cap[s][k], (size_t)Wc * OUT_N[k] * sizeof(double))) != CPI_OK) return rc;
+            if (*out_field(&h, k) && (rc = host_pipe_reserve(ctx, hp->out[s][k], hp->out_cap[s][k], (size_t)Wc * R * OUT_N[k] * sizeof(double))) != CPI_OK) return rc;
     }
     // after the first enqueue nothing may return before the three streams are idle: copies into the caller's memory are in flight
     std::string err;
@@ -1287,7 +1343,10 @@ static int preintegrate_host_pipeline(cpi_ctx *ctx, const cpi_params *prm, int64
         cpi_outputs d;
         memset(&d, 0, sizeof d);
         for (int k = 0; k < kOutFields; k++) if (*out_field(&h, k)) *out_field(&d, k) = (double *)hp->out[s][k];
-        if (tiled)
+        if (running)
+            rc = cpi_preintegrate_running(ctx, prm, wn, N, (const double *)hp->in[s][0], nullptr, count ? (const int32_t *)hp->in[s][1] : nullptr,
+                                          (const double *)hp->in[s][2], q_k_lin ? (const double *)hp->in[s][3] : nullptr, &d);
+        else if (tiled)
             rc = cpi_preintegrate_tiled_batch(ctx, prm, wn, N, (const double *)hp->in[s][0], count ? (const int32_t *)hp->in[s][1] : nullptr,
                                               (const double *)hp->in[s][2], q_k_lin ? (const double *)hp->in[s][3] : nullptr, &d);
         else
@@ -1297,16 +1356,17 @@ static int preintegrate_host_pipeline(cpi_ctx *ctx, const cpi_params *prm, int64
         if (!hip_ok(hipEventRecord(hp->ev_done[s], ctx->stream), "hipEventRecord")) break;
         if (!hip_ok(hipStreamWaitEvent(hp->down, hp->ev_done[s], 0), "hipStreamWaitEvent")) break;
         for (int k = 0; k < kOutFields; k++)
-            if (*out_field(&h, k) && !hip_ok(hipMemcpyAsync(*out_field(&h, k) + (size_t)w0 * OUT_N[k], hp->out[s][k], (size_t)wn * OUT_N[k] * sizeof(double),
+            if (*out_field(&h, k) && !hip_ok(hipMemcpyAsync(*out_field(&h, k) + (size_t)w0 * R * OUT_N[k], hp->out[s][k], (size_t)wn * R * OUT_N[k] * sizeof(double),
                                                             hipMemcpyDeviceToHost, hp->down), "download")) break;
         if (!err.empty()) break;
         if (!hip_ok(hipEventRecord(hp->ev_out[s], hp->down), "hipEventRecord")) break;
     }
     const hipError_t e1 = hipStreamSynchronize(hp->up), e2 = hipStreamSynchronize(ctx->stream), e3 = hipStreamSynchronize(hp->down);
     if (rc != CPI_OK) return rc;   // message already set by the device-pointer entry
-    if (!err.empty()) return fail(ctx, CPI_ERR_HIP, "cpi_preintegrate_batch_host: " + err);
+    const char *who = running ? "cpi_preintegrate_running_host: " : "cpi_preintegrate_batch_host: ";
+    if (!err.empty()) return fail(ctx, CPI_ERR_HIP, who + err);
     hip_ok(e1, "hipStreamSynchronize(upload)"); hip_ok(e2, "hipStreamSynchronize"); hip_ok(e3, "hipStreamSynchronize(download)");
-    if (!err.empty()) return fail(ctx, CPI_ERR_HIP, "cpi_preintegrate_batch_host: " + err);
+    if (!err.empty()) return fail(ctx, CPI_ERR_HIP, who + err);
     return CPI_OK;
 }
 
@@ -1353,6 +1413,47 @@ extern "C" int cpi_preintegrate_batch_host(cpi_ctx *ctx, const cpi_params *prm, 
     for (int k = 0; k < kOutFields; k++)
         if (*out_field(&h, k))
             CPI_HIP(ctx, hipMemcpyAsync(*out_field(&h, k), dout[k].p, (size_t)W * OUT_N[k] * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    CPI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CPI_OK;
+}
+
+extern "C" int cpi_preintegrate_running_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                             const double *knots, const int64_t *first, const int32_t *count,
+                                             int64_t n_knots, const double *lin, const double *q_k_lin,
+                                             const cpi_outputs *rows) {
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (!prm || !rows || !knots || !lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_host: NULL argument");
+    if (W < 0 || N < 0) return fail(ctx, CPI_ERR_INVALID, "negative size");
+    if (prm->model != CPI_MODEL_V1 && prm->model != CPI_MODEL_V2)
+        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_host: model must be 1 or 2 (the Forster comparator has no running form)");
+    if (prm->model == CPI_MODEL_V2 && (rows->J_q || rows->J_a || rows->J_b || rows->H_a || rows->H_b || rows->O_a || rows->O_b))
+        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_host: the Jacobian fields (J_q ... O_b) are not available for model 2");
+    if (W == 0 || N == 0) return CPI_OK;
+    if (N > 65535) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_host: N (intervals per window) must be <= 65535");
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    if (!first) return preintegrate_host_pipeline(ctx, prm, W, N, knots, false, count, lin, q_k_lin, rows, true);
+    // ragged windows share one knot stream: staged whole, as in cpi_preintegrate_batch_host
+    if (n_knots <= 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_host: n_knots must be > 0");
+    DevBuf dk, df, dc, dl, dq, dout[kOutFields];
+    CPI_UP(dk, knots, (size_t)n_knots * 7 * sizeof(double));
+    CPI_UP(df, first, (size_t)W * sizeof(int64_t));
+    CPI_UP(dc, count, (size_t)W * sizeof(int32_t));
+    CPI_UP(dl, lin, (size_t)W * 6 * sizeof(double));
+    CPI_UP(dq, q_k_lin, (size_t)W * 4 * sizeof(double));
+    const size_t nrows = (size_t)W * (size_t)N;
+    cpi_outputs d = *rows, h = *rows;
+    for (int k = 0; k < kOutFields; k++)
+        if (*out_field(&h, k)) {
+            CPI_HIP(ctx, hipMalloc(&dout[k].p, nrows * OUT_N[k] * sizeof(double)));
+            *out_field(&d, k) = (double *)dout[k].p;
+        }
+    int rc = cpi_preintegrate_running(ctx, prm, W, N, (const double *)dk.p, (const int64_t *)df.p, (const int32_t *)dc.p,
+                                      (const double *)dl.p, (const double *)dq.p, &d);
+    if (rc != CPI_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    for (int k = 0; k < kOutFields; k++)
+        if (*out_field(&h, k))
+            CPI_HIP(ctx, hipMemcpyAsync(*out_field(&h, k), dout[k].p, nrows * OUT_N[k] * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     CPI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CPI_OK;
 }

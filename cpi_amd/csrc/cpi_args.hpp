@@ -1,8 +1,9 @@
 // cpi_args.hpp -- kernel argument blocks and the launcher interface between the translation units of libcpi_amd.so.
 //
-// The library is four translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
+// The library is five translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
 //   cpi_mean.hip    cpi_mean_kernel / cpi_mean_tiled_kernel / cpi_tile_*_kernel       (cpi_mean_kernels.hpp)
-//   cpi_cov.hip     cpi_cov_kernel<1|2> / cpi_forster_kernel                           (cpi_cov_kernels.hpp)
+//   cpi_running.hip cpi_mean_running_kernel: a row after every interval               (cpi_running_kernels.hpp)
+//   cpi_cov.hip     cpi_cov_kernel<1|2> / cpi_forster_kernel / cpi_cov_running_kernel  (cpi_cov_kernels.hpp)
 //   cpi_factor.hip  evaluateError sweeps, square-root information, Hessian blocks, state prediction
 //                                                                                      (cpi_factor_kernels.hpp)
 //   cpi_abi.hip     the C-ABI of include/cpi_amd.h: argument checks, launch heuristics, device sets (RCCL), the
@@ -146,7 +147,10 @@ void cut_windows(long long K, const double *stream, long long U, const double *u
 void cut_runs(long long K, const double *stream, long long U, const double *update, const RunArgs &r, long long *first, int *count,
               double *tstart, double *tend, hipStream_t st);
 void mean_runs(int model, bool avg, int L, const PreArgs &a, const RunArgs &r, hipStream_t st);
+// ---- cpi_running.hip (cpi_preintegrate_running: a.out holds W * N rows; L: any of mean_lane_choices)
+void mean_running(int model, bool jac, bool avg, int L, const PreArgs &a, hipStream_t st);
 // ---- cpi_cov.hip
+void cov_running(int model, bool avg, const PreArgs &a, hipStream_t st);   // P / P_sym rows only
 void cov(int model, bool avg, const PreArgs &a, hipStream_t st);
 void cov_carry(int model, bool avg, const PreArgs &a, const CarryArgs &c, hipStream_t st);
 void forster(const PreArgs &a, hipStream_t st);

@@ -21,7 +21,15 @@ namespace {
 // from the window's carry record instead of identity / zero, and are written back to it at the end.  Nothing else depends
 // on the initial state: the exchange rows cov_exch_init fills are the constant process-noise rows, and phase A derives GS_R0
 // from GS_R.
-template <int MODEL, bool AVG, bool CARRY>
+// RUNNING (cpi_cov_running_kernel, cpi_preintegrate_running): the read-out of the end (A.out.P / P_sym, columns jj < 15) after
+// EVERY interval, into row w N + i.  It is valid after every cov_end (after the column clone for model 2), and an interval past
+// the window's count is staged as an exact no-op, so the recursion simply runs over all N intervals and the rows past the count
+// repeat.  A row is 1 800 contiguous bytes (960 packed) of which a lane owns 120, stored straight from the column registers as at
+// the end of the batch kernel: the 15 lanes of a window complete the row's lines within 15 instructions.  (Parking the columns in
+// LDS for a flat copy with consecutive lanes on consecutive doubles was measured and is SLOWER -- its 11 / 5.5 KB cost the kernel
+// 3 / 2 of its 8 wavefronts per CU: 100 k x 20 model 1 1.63 -> 1.47 ms, model 2 2.21 -> 1.60 ms, 549 x 50 166 -> 84 us.)  The means
+// of the rows belong to cpi_mean_running_kernel.
+template <int MODEL, bool AVG, bool CARRY, bool RUNNING = false>
 __device__ __forceinline__ void cov_body(const PreArgs &A, const CarryArgs &CA) {
     typedef CovDims<MODEL> D;
     constexpr int GROUP = D::GROUP;   // lanes per window
@@ -45,7 +53,7 @@ __device__ __forceinline__ void cov_body(const PreArgs &A, const CarryArgs &CA) 
     if (!valid) w = A.W - 1;
     const int n = A.count ? min(max(A.count[w], 0), A.N) : A.N;
     const long long k0 = A.first ? A.first[w] : w * (long long)(A.N + 1);
-    const int nmax = wave_max(n);
+    const int nmax = RUNNING ? A.N : wave_max(n);
     // windows cut out of a stream in flight (PreArgs::tstart / tend): see the knot loads of phase A
     const bool cut = A.tstart != nullptr;
     const bool tail = cut && (A.tend[w] == A.tend[w]) && (A.count[w] <= A.N);
@@ -230,9 +238,25 @@ __device__ __forceinline__ void cov_body(const PreArgs &A, const CarryArgs &CA) 
 #pragma unroll
                 for (int i = 0; i < D::NR; i++) Ln.P0[i] = dpp_clone_shr4(Ln.P0[i]);
             }
+            if constexpr (RUNNING) {
+                const long long r = w * (long long)A.N + (base + sl);
+                if (valid && jj < 15) {
+                    if (A.out.P) {
+                        double *p = A.out.P + r * 225 + jj * 15;
+#pragma unroll
+                        for (int i = 0; i < 15; i++) p[i] = Ln.P0[i];
+                    }
+                    if (A.out.P_sym) {
+                        double *p = A.out.P_sym + r * CPI_TRI_DOUBLES + jj * (jj + 1) / 2;
+#pragma unroll
+                        for (int i = 0; i < 15; i++) if (i <= jj) p[i] = Ln.P0[i];
+                    }
+                }
+            }
         }
         wave_lds_fence();
     }
+    if constexpr (RUNNING) return;   // row N - 1 is the window's measurement
 
     if constexpr (CARRY) {
         if (cbad) {
@@ -307,6 +331,11 @@ __global__ __launch_bounds__(64, CPI_COV_WPS) void cpi_cov_kernel(PreArgs A) {
 template <int MODEL, bool AVG>
 __global__ __launch_bounds__(64, CPI_COV_WPS) void cpi_cov_carry_kernel(PreArgs A, CarryArgs C) {
     cov_body<MODEL, AVG, true>(A, C);
+}
+// cpi_preintegrate_running: cpi_cov_kernel with the covariance read-out after every interval
+template <int MODEL, bool AVG>
+__global__ __launch_bounds__(64, CPI_COV_WPS) void cpi_cov_running_kernel(PreArgs A) {
+    cov_body<MODEL, AVG, false, true>(A, CarryArgs());
 }
 
 // ============================================================================================

@@ -391,6 +391,57 @@ public:
         }
         win_.clear();
     }
+    // The reference's members after EVERY feed_IMU (cpi_preintegrate_running_host): for each added window one CpiResult per
+    // recorded knot interval, result[w][i] = the members after interval i (a skipped interval -- dt <= 0, the NaN separator
+    // feed_IMU places between intervals that do not chain -- repeats the previous one).  Models 1 and 2; the bias Jacobians
+    // are filled for model 1 only.  The windows stay added and their own result members are not touched: flush() still
+    // computes them.
+    std::vector<std::vector<CpiResult>> running(const Context &ctx) const {
+        std::vector<std::vector<CpiResult>> res(win_.size());
+        if (win_.empty()) return res;
+        const int64_t W = (int64_t)win_.size();
+        std::vector<double> knots, lin(W * 6), qk(W * 4);
+        std::vector<int64_t> first(W);
+        std::vector<int32_t> count(W);
+        int32_t N = 0;
+        for (int64_t w = 0; w < W; w++) {
+            const std::vector<double> &k = win_[w]->knots();
+            first[w] = (int64_t)(knots.size() / 7);
+            count[w] = k.empty() ? 0 : (int32_t)(k.size() / 7 - 1);
+            if (count[w] > N) N = count[w];
+            if (k.empty()) knots.insert(knots.end(), 7, 0.0); else knots.insert(knots.end(), k.begin(), k.end());
+            for (int i = 0; i < 3; i++) { lin[w * 6 + i] = win_[w]->b_w_lin[i]; lin[w * 6 + 3 + i] = win_[w]->b_a_lin[i]; }
+            for (int i = 0; i < 4; i++) qk[w * 4 + i] = win_[w]->q_k_lin[i];
+        }
+        if (N == 0) return res;
+        cpi_params p = win_[0]->params();
+        const bool jac = p.model == CPI_MODEL_V1;
+        const size_t M = (size_t)W * (size_t)N;
+        std::vector<double> DT(M), al(M * 3), be(M * 3), q(M * 4), Jq(jac ? M * 9 : 0), Ja(jac ? M * 9 : 0), Jb(jac ? M * 9 : 0),
+            Ha(jac ? M * 9 : 0), Hb(jac ? M * 9 : 0), P(M * 225);
+        cpi_outputs o{};
+        o.DT = DT.data(); o.alpha = al.data(); o.beta = be.data(); o.q = q.data(); o.P = P.data();
+        if (jac) { o.J_q = Jq.data(); o.J_a = Ja.data(); o.J_b = Jb.data(); o.H_a = Ha.data(); o.H_b = Hb.data(); }
+        ctx.check(cpi_preintegrate_running_host(ctx.get(), &p, W, N, knots.data(), first.data(), count.data(),
+                                                (int64_t)(knots.size() / 7), lin.data(), qk.data(), &o));
+        for (int64_t w = 0; w < W; w++) {
+            res[w].resize(count[w]);
+            for (int32_t i = 0; i < count[w]; i++) {
+                const size_t r = (size_t)w * N + i;
+                CpiResult &x = res[w][i];
+                x.DT = DT[r];
+                for (int k = 0; k < 3; k++) { x.alpha_tau[k] = al[r * 3 + k]; x.beta_tau[k] = be[r * 3 + k]; }
+                for (int k = 0; k < 4; k++) x.q_k2tau[k] = q[r * 4 + k];
+                if (jac)
+                    for (int k = 0; k < 9; k++) {
+                        x.J_q[k] = Jq[r * 9 + k]; x.J_a[k] = Ja[r * 9 + k]; x.J_b[k] = Jb[r * 9 + k];
+                        x.H_a[k] = Ha[r * 9 + k]; x.H_b[k] = Hb[r * 9 + k];
+                    }
+                for (int k = 0; k < 225; k++) x.P_meas[k] = P[r * 225 + k];
+            }
+        }
+        return res;
+    }
     // Mean outputs only (DT, alpha_tau, beta_tau, q_k2tau): the HBM-bound request.  The recorded windows are written
     // straight into the TILED layout (include/cpi_amd.h: tiles[ceil(W/64)][N+1][7][64], knot s of window w at
     // (((w / 64) (N+1) + s) 7 + k) 64 + w % 64 -- no dense copy is ever made) with their own interval counts, and go

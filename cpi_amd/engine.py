@@ -224,6 +224,64 @@ class Engine:
                                                      _ptr(lin), _ptr(q_k_lin), _ptr(carry_in), _ptr(carry_out), C.byref(o)))
         return out, carry_out
 
+    @staticmethod
+    def _running_want(want, model):
+        # model 2 has no running Jacobians (cpi_preintegrate_running refuses the fields): the default want drops them, an
+        # explicit request reaches the library and is refused there
+        return tuple(g for g in want if not (g == "jac" and model == 2 and want == ("mean", "jac", "cov")))
+
+    @staticmethod
+    def _running_views(flat, W, N):
+        return {k: (v if k.startswith("_") else v.view((W, N) + tuple(v.shape[1:]))) for k, v in flat.items()}
+
+    def preintegrate_running(self, knots, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), first=None,
+                             count=None, N=None, packed=False, out=None):
+        """cpi_preintegrate_running: the measurement after EVERY interval.  Inputs as in preintegrate.  Returns a dict of
+        tensors with leading shape [W, N]: entry [w, i] is what preintegrate returns for window w cut after interval i
+        (skipped intervals and i >= count repeat the previous row; [w, N - 1] is the window's measurement).  The tensors are
+        views of [W * N, ...] arrays, so {k: v.reshape(W * N, ...)} is an ordinary measurement dict for predict / factor_eval
+        (idx_i[row] = row // N).  Models 1 and 2; Jacobians for model 1 only (the default want drops them for model 2).
+        packed / out: as alloc_outputs(W * N, ..., packed) / the dict of an earlier call.  Asynchronous."""
+        params = params or self.make_params()
+        if first is None:
+            W, n1, seven = knots.shape
+            N = n1 - 1
+        else:
+            W = first.shape[0]
+            assert N is not None, "ragged layout needs N = max intervals per window"
+        for t in (knots, lin, q_k_lin, first, count):
+            assert t is None or (t.is_cuda and t.is_contiguous()), "inputs must be contiguous CUDA tensors"
+        assert knots.dtype == torch.float64 and lin.dtype == torch.float64
+        if out is None:
+            out = self._running_views(self.alloc_outputs(W * N, self._running_want(tuple(want), params.model), params.model, packed), W, N)
+        o = self._outputs_struct({k: v for k, v in out.items() if not k.startswith("_")})
+        self._sync_stream()
+        self._check(self.lib.cpi_preintegrate_running(self.ctx, C.byref(params), W, N, _ptr(knots), _ptr(first), _ptr(count),
+                                                      _ptr(lin), _ptr(q_k_lin), C.byref(o)))
+        return out
+
+    def preintegrate_running_host(self, knots, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), count=None,
+                                  pinned=True, out=None):
+        """preintegrate_running for a dense batch held in HOST memory (CPU float64 tensors): cpi_preintegrate_running_host.
+        Returns a dict of CPU tensors with leading shape [W, N]; synchronous."""
+        params = params or self.make_params()
+        W, n1, _ = knots.shape
+        N = n1 - 1
+        for t in (knots, lin, q_k_lin, count):
+            assert t is None or (not t.is_cuda and t.is_contiguous()), "inputs must be contiguous CPU tensors"
+        assert knots.dtype == torch.float64 and lin.dtype == torch.float64 and (count is None or count.dtype == torch.int32)
+        if out is None:
+            out = {}
+            groups = self._running_want(tuple(want), params.model)
+            for name, n in OUT_FIELDS:
+                if _group_of(name) in groups and (params.model == 2 or name not in ("O_a", "O_b")):
+                    out[name] = torch.empty((W, N) if n == 1 else (W, N, n), dtype=torch.float64, pin_memory=pinned)
+        o = self._outputs_struct(out)
+        self._sync_stream()
+        self._check(self.lib.cpi_preintegrate_running_host(self.ctx, C.byref(params), W, N, _ptr(knots), None, _ptr(count), 0,
+                                                           _ptr(lin), _ptr(q_k_lin), C.byref(o)))
+        return out
+
     def preintegrate_host(self, knots, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), count=None, pinned=True, out=None):
         """Dense batch held in HOST memory (CPU float64 tensors; pinned ones overlap upload / kernels / download):
         cpi_preintegrate_batch_host.  Returns a dict of CPU tensors (page-locked when pinned=True; out= re-uses the

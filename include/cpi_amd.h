@@ -49,7 +49,8 @@ extern "C" {
                                are no longer written (they were never declared);
                                additions within 3 (new symbols only): cpi_carry_doubles, cpi_preintegrate_resume,
                                cpi_preintegrate_resume_host (resumable preintegration); cpi_streams_workspace_bytes,
-                               cpi_preintegrate_streams, cpi_preintegrate_streams_host (many IMU streams in one call) */
+                               cpi_preintegrate_streams, cpi_preintegrate_streams_host (many IMU streams in one call);
+                               cpi_preintegrate_running, cpi_preintegrate_running_host (the measurement after every interval) */
 
 enum { CPI_OK = 0, CPI_ERR_INVALID = 1, CPI_ERR_HIP = 2, CPI_ERR_NO_DEVICE = 3, CPI_ERR_RCCL = 4 };
 enum {
@@ -185,6 +186,29 @@ int cpi_preintegrate_resume(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int3
                             const double *knots, const int64_t *first, const int32_t *count,
                             const double *lin, const double *q_k_lin, const double *carry_in, double *carry_out,
                             const cpi_outputs *out);
+
+/* Running preintegration -- the measurement after EVERY interval: the reference's public members (DT, alpha_tau, beta_tau,
+ * q_k2tau, the bias Jacobians, P_meas) as they stand after each feed_IMU, for a batch of windows in one call.
+ *
+ * Arguments as cpi_preintegrate_batch.  `rows` is an ordinary cpi_outputs whose arrays hold W * N rows: row w * N + i is what
+ * cpi_preintegrate_batch returns for window w cut after interval i (intervals 0 .. i), up to the rounding of a different
+ * association.  Row offsets are computed in 64 bits.
+ *   - a skipped interval (dt <= 0, a NaN-stamp separator) is an exact no-op: its row repeats the previous row bit for bit (row
+ *     0 of such a window is the zero state: DT = 0, alpha = beta = 0, q = [0 0 0 1], Jacobians and P zero);
+ *   - rows i >= count[w] repeat the window's final state, so row w * N + N - 1 is always the window's measurement; count is
+ *     clamped into [0, N]; count = 0 gives N zero-state rows;
+ *   - any pointer of rows may be NULL with the meaning it has in cpi_outputs; P and P_sym are independent, and a P_sym row is
+ *     bit for bit the upper triangle of the P row.
+ * Models 1 and 2, imu_avg 0 / 1, dense and ragged (first / count) layouts; lanes_per_window is honoured by the mean kernel.
+ * Means for both models, the five analytic bias Jacobians for model 1, the covariance for both models.  CPI_ERR_INVALID:
+ * CPI_MODEL_FORSTER, and any Jacobian field (J_q ... O_b) with model 2 (its Jacobians are read out of the state transition
+ * matrix at the end of the recursion).  W == 0 or N == 0 is a no-op; N <= 65535 and the 32-bit grid limit on W as in
+ * cpi_preintegrate_batch.  No host synchronisation and a single stream: the call can be captured into a graph.
+ * Composition: with F = W * N and idx_i[row] = row / N, cpi_predict_batch turns the rows into IMU-rate predicted states.
+ * Not provided: running rows from the stream entries (cpi_preintegrate_stream[s]) and from a carry record. */
+int cpi_preintegrate_running(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                             const double *knots, const int64_t *first, const int32_t *count,
+                             const double *lin, const double *q_k_lin, const cpi_outputs *rows);
 
 /* Replaces: the whole caller side of GraphSolver::createimufactor_cpi_v1 / _v2 (GraphSolver_IMU.cpp:43-75, 97-130) for every
  * window of a trajectory at once, reading ONE IMU stream IN PLACE: no knot is copied, for any model and any output.
@@ -438,6 +462,12 @@ int cpi_preintegrate_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, 
                                 const double *knots, const int64_t *first, const int32_t *count,
                                 int64_t n_knots, const double *lin, const double *q_k_lin,
                                 const cpi_outputs *out);
+/* cpi_preintegrate_running from host memory: every pointer a host pointer, n_knots as in cpi_preintegrate_batch_host; dense
+ * batches run through the same upload / kernels / download pipeline, in chunks of <= 65536 rows. */
+int cpi_preintegrate_running_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                  const double *knots, const int64_t *first, const int32_t *count,
+                                  int64_t n_knots, const double *lin, const double *q_k_lin,
+                                  const cpi_outputs *rows);
 /* cpi_preintegrate_resume from host memory: every pointer a host pointer, n_knots as in cpi_preintegrate_batch_host. */
 int cpi_preintegrate_resume_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                                  const double *knots, const int64_t *first, const int32_t *count,

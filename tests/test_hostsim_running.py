@@ -1,0 +1,188 @@
+"""CPU: host emulation of running preintegration (tests/hostsim/hostsim_running.cpp: the arithmetic and the association of
+cpi_mean_running_kernel / cpi_cov_running_kernel, from cpi_math.hpp) -- the segment pass, the ordered exclusive scan, the second
+walk and the fix-up of held-back rows for a given lane count L, and the per-interval covariance read-out.
+
+Every row of every window is compared: with the pinned traces of the compiled reference (tests/golden/trace_v1.npz /
+trace_v2.npz) at the regression gates of tests/tol.py, and with the C restatement's trace (oracle_py.oracle().trace) on seeded
+windows (cpi_amd.synth.make_windows) at the contractual gates.  Rows that must repeat the previous row (dt <= 0, a NaN-stamp
+separator, i >= count, count = 0) are checked for exact equality.  The largest error per field is printed."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from oracle import oracle_py as op
+from tests.tol import check_pre
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_SRC = os.path.join(_HERE, "hostsim", "hostsim_running.cpp")
+_LIB = os.path.join(_HERE, "hostsim", "libhostsim_running.so")
+_HDR = os.path.join(os.path.dirname(_HERE), "cpi_amd", "csrc", "cpi_math.hpp")
+GRAV = np.array([0.0, 0.0, 9.8])
+SIG = np.array([0.005, 4e-6, 0.01, 2e-4])
+LANES = [1, 2, 3, 4, 5, 6, 8, 12, 16, 32, 64]          # the kernels' lane choices (cpi_mean.hip: kMeanLanes)
+NS = [1, 2, 10, 20, 50, 80]
+MODES = [(1, 0), (1, 1), (2, 0), (2, 1)]
+MEAN = ("DT", "alpha", "beta", "q")
+JAC = ("J_q", "J_a", "J_b", "H_a", "H_b")
+
+
+@pytest.fixture(scope="module")
+def lib():
+    if (not os.path.exists(_LIB)) or os.path.getmtime(_LIB) < max(os.path.getmtime(_SRC), os.path.getmtime(_HDR)):
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-ffp-contract=off",
+                               "-o", _LIB, _SRC])
+    return C.CDLL(_LIB)
+
+
+def _dp(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def mean_rows(lib, model, jac, avg, L, kn, lin, q, N=None, n=None):
+    kn = np.ascontiguousarray(kn, dtype=np.float64)
+    n = kn.shape[0] - 1 if n is None else n
+    N = n if N is None else N
+    rows = np.full((N, 308), np.nan)
+    lin, q = np.ascontiguousarray(lin), np.ascontiguousarray(q)
+    assert lib.hsr_mean(model, int(jac), int(avg), L, N, n, _dp(kn), _dp(lin), _dp(q), _dp(GRAV), _dp(rows)) == 0
+    return op.split_out(rows)
+
+
+def cov_rows(lib, model, avg, kn, lin, q, N=None, n=None):
+    kn = np.ascontiguousarray(kn, dtype=np.float64)
+    n = kn.shape[0] - 1 if n is None else n
+    N = n if N is None else N
+    rows = np.full((N, 308), np.nan)
+    lin, q = np.ascontiguousarray(lin), np.ascontiguousarray(q)
+    assert lib.hsr_cov(model, int(avg), N, n, _dp(kn), _dp(lin), _dp(q), _dp(SIG), _dp(GRAV), _dp(rows)) == 0
+    return op.split_out(rows)
+
+
+class _Worst:
+    def __init__(self):
+        self.e = {}
+
+    def add(self, got, ref, keys):
+        for k in keys:
+            self.e[k] = max(self.e.get(k, 0.0), float(np.abs(got[k] - ref[k]).max()))
+
+    def report(self, label):
+        print("%s: largest error per field: %s" % (label, ", ".join("%s %.2e" % kv for kv in sorted(self.e.items()))))
+
+
+def test_hostsim_running_matches_the_golden_traces(lib, golden_dir):
+    """Compiled reference, every row, every lane count, regression gates."""
+    worst = _Worst()
+    for model in (1, 2):
+        d = np.load(os.path.join(golden_dir, "trace_v%d.npz" % model))
+        ref = {k: d[k] for k in d.files}
+        for L in LANES:
+            got = mean_rows(lib, model, False, 0, L, d["knots"], d["lin"], d["q_k_lin"])
+            check_pre(got, ref, what=("mean",), regression=True, label="golden m%d L%d" % (model, L))
+            worst.add(got, ref, MEAN)
+            if model == 1:
+                got = mean_rows(lib, 1, True, 0, L, d["knots"], d["lin"], d["q_k_lin"])
+                check_pre(got, ref, what=("mean", "jac"), regression=True, label="golden m1 jac L%d" % L)
+                worst.add(got, ref, MEAN + JAC)
+        got = cov_rows(lib, model, 0, d["knots"], d["lin"], d["q_k_lin"])
+        check_pre(got, ref, what=("cov",), regression=True, label="golden m%d cov" % model)
+        worst.add(got, ref, ("P",))
+    worst.report("hostsim running vs golden traces")
+
+
+@pytest.mark.parametrize("N", NS)
+def test_hostsim_running_matches_the_oracle_trace(lib, N):
+    """C restatement, seeded windows (edge cases included), every row, every lane count, contractual gates."""
+    from cpi_amd import synth
+    W = 12
+    kn, lin, q = (t.numpy() for t in synth.make_windows(W, N, seed=100 + N))
+    worst = _Worst()
+    for model, avg in MODES:
+        prm = op.make_params(model, avg, 1)
+        for w in range(W):
+            ref = op.oracle().trace(prm, kn[w], lin[w], q[w])
+            assert all(np.isfinite(ref[k]).all() for k in MEAN + JAC + ("P",))
+            for L in LANES:
+                got = mean_rows(lib, model, False, avg, L, kn[w], lin[w], q[w])
+                check_pre(got, ref, what=("mean",), label="m%d avg%d N%d w%d L%d" % (model, avg, N, w, L))
+                worst.add(got, ref, MEAN)
+                if model == 1:
+                    got = mean_rows(lib, 1, True, avg, L, kn[w], lin[w], q[w])
+                    check_pre(got, ref, what=("mean", "jac"), label="m1 jac avg%d N%d w%d L%d" % (avg, N, w, L))
+                    worst.add(got, ref, MEAN + JAC)
+            got = cov_rows(lib, model, avg, kn[w], lin[w], q[w])
+            check_pre(got, ref, what=("cov",), label="m%d avg%d N%d w%d cov" % (model, avg, N, w))
+            worst.add(got, ref, ("P",))
+    worst.report("hostsim running vs oracle.trace, N = %d" % N)
+
+
+def _edge_window(N, kind, seed):
+    from cpi_amd import synth
+    kn, lin, q = (t.numpy()[0] for t in synth.make_windows(1, N, seed=seed, edge_cases=False))
+    kn = kn.copy()
+    skipped = []
+    if kind == "dt0":            # repeated stamps: intervals 0, N // 2 (and the lane boundaries around it)
+        for i in sorted({0, N // 2, min(N - 1, N // 2 + 1)}):
+            kn[i + 1:, 0] -= kn[i + 1, 0] - kn[i, 0]
+            skipped.append(i)
+    elif kind == "negative":     # a stamp that steps back
+        i = N // 3
+        kn[i + 1:, 0] -= 2.0 * (kn[i + 1, 0] - kn[i, 0])
+        skipped.append(i)
+    elif kind == "nan":          # a NaN-stamp separator knot: the intervals on both sides of it are skipped
+        i = N // 2
+        kn[i] = 0.0
+        kn[i, 0] = np.nan
+        skipped += [i - 1, i] if i > 0 else [i]
+    return kn, lin, q, [i for i in skipped if 0 <= i < N]
+
+
+@pytest.mark.parametrize("kind", ["dt0", "negative", "nan"])
+def test_hostsim_running_skipped_intervals_repeat_the_previous_row(lib, kind):
+    for N in (2, 10, 20, 50):
+        kn, lin, q, skipped = _edge_window(N, kind, 7 + N)
+        assert skipped
+        for model, avg in MODES:
+            ref = op.oracle().trace(op.make_params(model, avg, 1), kn, lin, q)
+            outs = [(mean_rows(lib, model, model == 1, avg, L, kn, lin, q), ("mean", "jac") if model == 1 else ("mean",), L) for L in LANES]
+            outs.append((cov_rows(lib, model, avg, kn, lin, q), ("cov",), 0))
+            for got, what, L in outs:
+                keys = MEAN + (JAC if "jac" in what else ()) if "cov" not in what else ("P",)
+                check_pre(got, ref, what=what, label="%s N%d m%d avg%d L%d" % (kind, N, model, avg, L))
+                for i in skipped:
+                    for k in keys:
+                        if i == 0:
+                            zero = np.zeros_like(got[k][0])
+                            if k == "q":
+                                zero[3] = 1.0
+                            assert np.array_equal(got[k][0], zero), (kind, N, model, avg, L, k)
+                        else:
+                            assert np.array_equal(got[k][i], got[k][i - 1]), (kind, N, model, avg, L, i, k)
+
+
+def test_hostsim_running_rows_past_the_count_repeat_the_final_state(lib):
+    from cpi_amd import synth
+    N = 20
+    kn, lin, q = (t.numpy()[0] for t in synth.make_windows(1, N, seed=5, edge_cases=False))
+    for n in (0, 1, 7, 19, 20):
+        for model, avg in MODES:
+            prm = op.make_params(model, avg, 1)
+            ref = op.oracle().trace(prm, kn[:n + 1], lin, q) if n > 0 else None
+            for L in LANES:
+                got = mean_rows(lib, model, model == 1, avg, L, kn, lin, q, N=N, n=n)
+                got["P"] = cov_rows(lib, model, avg, kn, lin, q, N=N, n=n)["P"]
+                keys = MEAN + (JAC if model == 1 else ()) + ("P",)
+                if n > 0:
+                    head = {k: got[k][:n] for k in keys}
+                    check_pre(head, ref, what=("mean", "jac", "cov") if model == 1 else ("mean", "cov"), label="count %d m%d L%d" % (n, model, L))
+                for k in keys:
+                    if n == 0:
+                        zero = np.zeros_like(got[k][0])
+                        if k == "q":
+                            zero[3] = 1.0
+                        assert np.array_equal(got[k][0], zero), (n, model, avg, L, k)
+                    for i in range(max(n, 1), N):
+                        assert np.array_equal(got[k][i], got[k][i - 1]), (n, model, avg, L, i, k)
