@@ -159,6 +159,13 @@ def load():
     lib.cpi_preintegrate_resume_host.argtypes = [vp, C.POINTER(CpiParams), i64, i32, dp, vp, vp, i64, dp, dp, dp, dp, C.POINTER(CpiOutputs)]
     lib.cpi_preintegrate_running.argtypes = [vp, C.POINTER(CpiParams), i64, i32, dp, vp, vp, dp, dp, C.POINTER(CpiOutputs)]
     lib.cpi_preintegrate_running_host.argtypes = [vp, C.POINTER(CpiParams), i64, i32, dp, vp, vp, i64, dp, dp, C.POINTER(CpiOutputs)]
+    lib.cpi_preintegrate_stream_running.argtypes = lib.cpi_preintegrate_stream.argtypes
+    lib.cpi_preintegrate_stream_running_host.argtypes = lib.cpi_preintegrate_stream_host.argtypes
+    lib.cpi_preintegrate_streams_running.argtypes = lib.cpi_preintegrate_streams.argtypes
+    lib.cpi_preintegrate_streams_running_host.argtypes = lib.cpi_preintegrate_streams_host.argtypes
+    for f in (lib.cpi_preintegrate_stream_running, lib.cpi_preintegrate_stream_running_host, lib.cpi_preintegrate_streams_running,
+              lib.cpi_preintegrate_streams_running_host):
+        f.restype = C.c_int
     lib.cpi_host_alloc.argtypes = [C.c_size_t]
     lib.cpi_host_alloc.restype = C.c_void_p
     lib.cpi_host_free.argtypes = [vp]

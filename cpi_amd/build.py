@@ -34,7 +34,7 @@ DEVICE = COMMON + ["cpi_math.hpp", "cpi_device_util.hpp"]
 # translation unit -> the files it includes (what its object depends on)
 UNITS = {
     "cpi_mean": DEVICE + ["cpi_mean.hip", "cpi_mean_kernels.hpp", "cpi_mean_body.inc"],
-    "cpi_running": DEVICE + ["cpi_running.hip", "cpi_running_kernels.hpp"],
+    "cpi_running": DEVICE + ["cpi_running.hip", "cpi_running_kernels.hpp", "cpi_running_body.inc"],
     "cpi_cov": DEVICE + ["cpi_cov.hip", "cpi_cov_kernels.hpp"],
     "cpi_factor": DEVICE + ["cpi_factor.hip", "cpi_factor_kernels.hpp"],
     "cpi_abi": COMMON + ["cpi_abi.hip", "../../include/cpi_amd_test.h"],   # the test header: -DCPI_TEST_HOOKS builds only

@@ -593,6 +593,113 @@ extern "C" int cpi_preintegrate_streams(cpi_ctx *ctx, const cpi_params *prm, int
     return preintegrate_impl(ctx, prm, U, N, stream, nullptr, nullptr, &sc, lin, q_k_lin, out);
 }
 
+// Running rows from the stream entries (include/cpi_amd.h: cpi_preintegrate_stream_running / cpi_preintegrate_streams_running): the
+// cut kernel of cpi_preintegrate_stream[s] always runs, then cpi_mean_stream_running_kernel (means, model-1 Jacobians) and
+// cpi_cov_running_kernel (whose phase A reads cut windows when PreArgs::tstart is set) read the stream in place -- one after the
+// other on the context's stream, as in cpi_preintegrate_running.  The lane choice is pick_lanes(U, N, request), the function
+// cpi_preintegrate_running uses: the rows are bit for bit those of that entry on the host-assembled windows.
+// the request asks for Jacobian rows: the predicate of cpi_preintegrate_running (O_a / O_b included), shared by the checks, the
+// kernel choice and the lane choice of these entries
+static bool rows_want_jac(const cpi_outputs *rows) {
+    return rows->J_q || rows->J_a || rows->J_b || rows->H_a || rows->H_b || rows->O_a || rows->O_b;
+}
+static int stream_running_check(cpi_ctx *ctx, const std::string &who, const cpi_params *prm, bool many, int64_t R, int64_t K, int64_t U,
+                                int32_t N, const void *stream, const void *soff, const void *update_times, const void *uoff,
+                                const void *lin, const void *q_k_lin, const cpi_outputs *rows, bool &noop) {
+    noop = false;
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (!prm || !rows) return fail(ctx, CPI_ERR_INVALID, who + ": prm/rows is NULL");
+    if (prm->model == CPI_MODEL_FORSTER)
+        return fail(ctx, CPI_ERR_INVALID, who + ": model must be 1 or 2 (the Forster comparator has no running form)");
+    if (prm->model != CPI_MODEL_V1 && prm->model != CPI_MODEL_V2) return fail(ctx, CPI_ERR_INVALID, who + ": model must be 1 or 2");
+    if (prm->model == CPI_MODEL_V2 && rows_want_jac(rows))
+        return fail(ctx, CPI_ERR_INVALID, who + ": the Jacobian fields (J_q ... O_b) are not available for model 2 "
+                                                "(they are read out of the state transition matrix at the end of the recursion)");
+    if (R < 0 || K < 0 || U < 0 || N < 0) return fail(ctx, CPI_ERR_INVALID, who + ": negative size");
+    if (U == 0 || N == 0) { noop = true; return CPI_OK; }
+    if (many && R == 0) return fail(ctx, CPI_ERR_INVALID, who + ": U > 0 windows and no run");
+    if (many && R > 0x7ffffffeLL) return fail(ctx, CPI_ERR_INVALID, who + ": R exceeds 2^31 - 2 runs");
+    if (K == 0) return fail(ctx, CPI_ERR_INVALID, who + (many ? ": the streams hold no reading" : ": the stream is empty"));
+    if (!stream || !update_times || !lin || (many && (!soff || !uoff))) return fail(ctx, CPI_ERR_INVALID, who + ": NULL argument");
+    if (!grid_ok(U)) return fail(ctx, CPI_ERR_INVALID, who + ": U exceeds 2^31 - 1 windows per call");
+    if (prm->model == CPI_MODEL_V2 && !q_k_lin) return fail(ctx, CPI_ERR_INVALID, who + ": model 2 needs q_k_lin");
+    if (N > 65535) return fail(ctx, CPI_ERR_INVALID, who + ": N (intervals per window) must be <= 65535");
+    if (prm->lanes_per_window != 0 && !launch::mean_lanes_supported(prm->lanes_per_window))
+        return fail(ctx, CPI_ERR_INVALID, "lanes_per_window must be 0 or one of 1,2,3,4,5,6,8,12,16,32,64");
+    return CPI_OK;
+}
+// the running kernels on the windows [w0, w0 + wn) of a cut that is already in the workspace; rows: row 0 = window w0, interval 0.
+// L: the lane choice of the WHOLE call (a chunked download must not change it)
+static int stream_running_launch(cpi_ctx *ctx, const cpi_params *prm, const StreamCut &sc, const double *stream, int32_t N, int L,
+                                 const double *lin, const double *q_k_lin, const cpi_outputs *rows, int64_t w0, int64_t wn) {
+    const bool want_mean = rows->DT || rows->alpha || rows->beta || rows->q;
+    const bool want_jac = rows_want_jac(rows);
+    const bool want_cov = rows->P != nullptr || rows->P_sym != nullptr;
+    const bool avg = prm->imu_avg != 0;
+    PreArgs a;
+    memset(&a, 0, sizeof a);
+    a.W = wn; a.N = N; a.knots = stream; a.K = sc.K;
+    a.first = sc.first + w0; a.count = sc.count + w0; a.tstart = sc.tstart + w0; a.tend = sc.tend + w0;
+    a.lin = lin + w0 * 6; a.qk = q_k_lin ? q_k_lin + w0 * 4 : nullptr;
+    for (int i = 0; i < 3; i++) a.grav[i] = prm->grav[i];
+    a.q4[0] = prm->sigma_w * prm->sigma_w; a.q4[1] = prm->sigma_wb * prm->sigma_wb;
+    a.q4[2] = prm->sigma_a * prm->sigma_a; a.q4[3] = prm->sigma_ab * prm->sigma_ab;
+    a.out = *rows;
+    if (want_mean || want_jac) {
+        PreArgs m = a;
+        m.write_means = want_mean ? 1 : 0;
+        m.write_jac = want_jac ? 1 : 0;
+        launch::mean_stream_running(prm->model, want_jac, avg, L, m, ctx->stream);
+    }
+    if (want_cov) launch::cov_running(prm->model, avg, a, ctx->stream);
+    CPI_HIP(ctx, hipGetLastError());
+    return CPI_OK;
+}
+static int stream_running_cut(cpi_ctx *ctx, const StreamCut &sc, const double *stream, int64_t U, int32_t N) {
+    if (sc.runs) launch::cut_runs(sc.K, stream, (long long)U, sc.update, *sc.runs, sc.first, sc.count, sc.tstart, sc.tend, ctx->stream);
+    else launch::cut_windows(sc.K, stream, (long long)U, sc.update, (int)N, sc.first, sc.count, sc.tstart, sc.tend, ctx->stream);
+    CPI_HIP(ctx, hipGetLastError());
+    return CPI_OK;
+}
+static int stream_running_lanes(const cpi_params *prm, int64_t U, int32_t N, const cpi_outputs *rows) {
+    return pick_lanes(prm, U, N, rows_want_jac(rows));
+}
+static int stream_running_impl(cpi_ctx *ctx, const char *who, const cpi_params *prm, const RunArgs *runs, int64_t R, int64_t K,
+                               const double *stream, int64_t U, const double *update_times, int32_t N, const double *lin,
+                               const double *q_k_lin, void *workspace, const cpi_outputs *rows) {
+    bool noop;
+    const int rc = stream_running_check(ctx, who, prm, runs != nullptr, R, K, U, N, stream, runs ? runs->soff : nullptr, update_times,
+                                        runs ? runs->uoff : nullptr, lin, q_k_lin, rows, noop);
+    if (rc != CPI_OK || noop) return rc;
+    if (!workspace) return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": NULL argument");
+    if (((uintptr_t)workspace & 15) != 0) return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": the workspace must be 16-byte aligned");
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    RunArgs ra;
+    if (runs) { ra = *runs; ra.R = (int)R; }
+    const StreamCut sc = stream_cut(K, update_times, workspace, U, runs ? &ra : nullptr);
+    const int rcc = stream_running_cut(ctx, sc, stream, U, N);
+    if (rcc != CPI_OK) return rcc;
+    return stream_running_launch(ctx, prm, sc, stream, N, stream_running_lanes(prm, U, N, rows), lin, q_k_lin, rows, 0, U);
+}
+extern "C" int cpi_preintegrate_stream_running(cpi_ctx *ctx, const cpi_params *prm, int64_t K, const double *stream, int64_t U,
+                                               const double *update_times, int32_t N, const double *lin, const double *q_k_lin,
+                                               void *workspace, const cpi_outputs *rows) {
+    return stream_running_impl(ctx, "cpi_preintegrate_stream_running", prm, nullptr, 0, K, stream, U, update_times, N, lin, q_k_lin,
+                               workspace, rows);
+}
+extern "C" int cpi_preintegrate_streams_running(cpi_ctx *ctx, const cpi_params *prm, int64_t R, int64_t K, const double *stream,
+                                                const int64_t *stream_offsets, int64_t U, const double *update_times,
+                                                const int64_t *update_offsets, int32_t N, const double *lin, const double *q_k_lin,
+                                                void *workspace, const cpi_outputs *rows) {
+    RunArgs ra;
+    ra.soff = reinterpret_cast<const long long *>(stream_offsets);
+    ra.uoff = reinterpret_cast<const long long *>(update_offsets);
+    ra.R = 0;
+    return stream_running_impl(ctx, "cpi_preintegrate_streams_running", prm, &ra, R, K, stream, U, update_times, N, lin, q_k_lin,
+                               workspace, rows);
+}
+
 // ============================================================================================
 // re-linearisation sweeps
 // ============================================================================================
@@ -1585,6 +1692,85 @@ extern "C" int cpi_preintegrate_streams_host(cpi_ctx *ctx, const cpi_params *prm
     if (count) CPI_HIP(ctx, hipMemcpyAsync(count, cpi_stream_counts(dw.p, U), (size_t)U * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     CPI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CPI_OK;
+}
+
+// The running stream entries from HOST memory: the stream(s) are uploaded once, whole, and cut on the device; the U * N rows come
+// back in chunks of whole windows, never more than 2^18 rows per chunk (N <= 65535: at least 4 windows), the
+// kernels of a chunk and its download following each other on the context's stream.  The lane choice is that of the whole call,
+// so the rows do not depend on the chunking.
+static int stream_running_host_impl(cpi_ctx *ctx, const char *who, const cpi_params *prm, bool many, int64_t R, int64_t K,
+                                    const double *stream, const int64_t *stream_offsets, int64_t U, const double *update_times,
+                                    const int64_t *update_offsets, int32_t N, const double *lin, const double *q_k_lin,
+                                    const cpi_outputs *rows, int32_t *count) {
+    bool noop;
+    int rc = stream_running_check(ctx, who, prm, many, R, K, U, N, stream, stream_offsets, update_times, update_offsets, lin, q_k_lin, rows, noop);
+    if (rc != CPI_OK || noop) return rc;
+    if (many) {
+        for (int pass = 0; pass < 2; pass++) {
+            const int64_t *o = pass ? update_offsets : stream_offsets;
+            const int64_t end = pass ? U : K;
+            const char *what = pass ? "update_offsets" : "stream_offsets";
+            if (o[0] != 0) return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": " + what + "[0] is not 0");
+            for (int64_t r = 0; r < R; r++)
+                if (o[r + 1] < o[r]) return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": " + what + " decrease at run " + std::to_string(r));
+            if (o[R] != end) return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": " + what + "[R] is not " + (pass ? "U" : "K"));
+        }
+    }
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    DevBuf ds, dso, du, duo, dl, dq, dw, dout[kOutFields];
+    CPI_UP(ds, stream, (size_t)K * 7 * sizeof(double));
+    if (many) {
+        CPI_UP(dso, stream_offsets, (size_t)(R + 1) * sizeof(int64_t));
+        CPI_UP(duo, update_offsets, (size_t)(R + 1) * sizeof(int64_t));
+    }
+    CPI_UP(du, update_times, (size_t)U * sizeof(double));
+    CPI_UP(dl, lin, (size_t)U * 6 * sizeof(double));
+    CPI_UP(dq, q_k_lin, (size_t)U * 4 * sizeof(double));
+    CPI_HIP(ctx, hipMalloc(&dw.p, many ? cpi_streams_workspace_bytes(R, U) : cpi_stream_workspace_bytes(U)));
+    // windows per chunk: as many whole windows as 2^18 rows hold (whole wavefronts of one-lane windows when that is 64 or more;
+    // N <= 65535, so at least 4), never more than 2^18 rows of staging per output array
+    int64_t cw = std::max<int64_t>(1, ((int64_t)1 << 18) / N);
+    if (cw >= 64) cw = cw / 64 * 64;
+    cw = std::min<int64_t>(U, cw);
+    cpi_outputs d = *rows, h = *rows;
+    for (int k = 0; k < kOutFields; k++)
+        if (*out_field(&h, k)) {
+            CPI_HIP(ctx, hipMalloc(&dout[k].p, (size_t)cw * (size_t)N * OUT_N[k] * sizeof(double)));
+            *out_field(&d, k) = (double *)dout[k].p;
+        }
+    RunArgs ra;
+    ra.soff = (const long long *)dso.p; ra.uoff = (const long long *)duo.p; ra.R = (int)R;
+    const StreamCut sc = stream_cut(K, (const double *)du.p, dw.p, U, many ? &ra : nullptr);
+    rc = stream_running_cut(ctx, sc, (const double *)ds.p, U, N);
+    const int L = stream_running_lanes(prm, U, N, rows);
+    for (int64_t w0 = 0; w0 < U && rc == CPI_OK; w0 += cw) {
+        const int64_t wn = std::min<int64_t>(cw, U - w0);
+        rc = stream_running_launch(ctx, prm, sc, (const double *)ds.p, N, L, (const double *)dl.p, (const double *)dq.p, &d, w0, wn);
+        for (int k = 0; k < kOutFields && rc == CPI_OK; k++)
+            if (*out_field(&h, k)) {
+                const hipError_t e = hipMemcpyAsync(*out_field(&h, k) + (size_t)w0 * (size_t)N * OUT_N[k], dout[k].p,
+                                                    (size_t)wn * (size_t)N * OUT_N[k] * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+                if (e != hipSuccess) rc = fail(ctx, CPI_ERR_HIP, std::string(who) + ": download: " + hipGetErrorString(e));
+            }
+    }
+    if (rc != CPI_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }   // nothing returns while a copy is in flight
+    if (count) CPI_HIP(ctx, hipMemcpyAsync(count, cpi_stream_counts(dw.p, U), (size_t)U * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    CPI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CPI_OK;
+}
+extern "C" int cpi_preintegrate_stream_running_host(cpi_ctx *ctx, const cpi_params *prm, int64_t K, const double *stream, int64_t U,
+                                                    const double *update_times, int32_t N, const double *lin, const double *q_k_lin,
+                                                    const cpi_outputs *rows, int32_t *count) {
+    return stream_running_host_impl(ctx, "cpi_preintegrate_stream_running_host", prm, false, 0, K, stream, nullptr, U, update_times,
+                                    nullptr, N, lin, q_k_lin, rows, count);
+}
+extern "C" int cpi_preintegrate_streams_running_host(cpi_ctx *ctx, const cpi_params *prm, int64_t R, int64_t K, const double *stream,
+                                                     const int64_t *stream_offsets, int64_t U, const double *update_times,
+                                                     const int64_t *update_offsets, int32_t N, const double *lin, const double *q_k_lin,
+                                                     const cpi_outputs *rows, int32_t *count) {
+    return stream_running_host_impl(ctx, "cpi_preintegrate_streams_running_host", prm, true, R, K, stream, stream_offsets, U,
+                                    update_times, update_offsets, N, lin, q_k_lin, rows, count);
 }
 
 extern "C" int cpi_factor_eval_batch_host(cpi_ctx *ctx, int32_t model, const double grav[3], int64_t F,

@@ -2,7 +2,8 @@
 //
 // The library is five translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
 //   cpi_mean.hip    cpi_mean_kernel / cpi_mean_tiled_kernel / cpi_tile_*_kernel       (cpi_mean_kernels.hpp)
-//   cpi_running.hip cpi_mean_running_kernel: a row after every interval               (cpi_running_kernels.hpp)
+//   cpi_running.hip cpi_mean_running_kernel / cpi_mean_stream_running_kernel: a row after every interval, from plain knots /
+//                   from windows cut out of IMU stream(s) in place         (cpi_running_kernels.hpp, cpi_running_body.inc)
 //   cpi_cov.hip     cpi_cov_kernel<1|2> / cpi_forster_kernel / cpi_cov_running_kernel  (cpi_cov_kernels.hpp)
 //   cpi_factor.hip  evaluateError sweeps, square-root information, Hessian blocks, state prediction
 //                                                                                      (cpi_factor_kernels.hpp)
@@ -149,6 +150,9 @@ void cut_runs(long long K, const double *stream, long long U, const double *upda
 void mean_runs(int model, bool avg, int L, const PreArgs &a, const RunArgs &r, hipStream_t st);
 // ---- cpi_running.hip (cpi_preintegrate_running: a.out holds W * N rows; L: any of mean_lane_choices)
 void mean_running(int model, bool jac, bool avg, int L, const PreArgs &a, hipStream_t st);
+// cpi_preintegrate_stream[s]_running: the same rows for the windows that cut_windows / cut_runs left in a.first / count / tstart /
+// tend; a.knots = the stream of a.K readings, read in place
+void mean_stream_running(int model, bool jac, bool avg, int L, const PreArgs &a, hipStream_t st);
 // ---- cpi_cov.hip
 void cov_running(int model, bool avg, const PreArgs &a, hipStream_t st);   // P / P_sym rows only
 void cov(int model, bool avg, const PreArgs &a, hipStream_t st);

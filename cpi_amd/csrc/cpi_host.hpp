@@ -586,6 +586,58 @@ inline TiledWindowSet assemble_windows_tiled(const std::vector<double> &stream, 
     return ts;
 }
 
+// The longest window (whole intervals + tail) that cutting K readings at update_times gives: the deque loop of assemble_windows,
+// counts only -- the TIGHT row bound of ImuStream::running / ImuStreamSet::running (their output is U * N rows).
+inline int32_t longest_window(const double *stream, size_t K, const double *update_times, size_t U) {
+    if (K == 0) return 0;
+    size_t front = 0;
+    double front_t = stream[0];
+    int64_t longest = 0;
+    for (size_t u = 0; u < U; u++) {
+        const double T = update_times[u];
+        int64_t n = 0;
+        while (K - front > 1 && stream[(front + 1) * 7] <= T) { front++; front_t = stream[front * 7]; n++; }
+        if (T - front_t > 0) { front_t = T; n++; }
+        if (n > longest) longest = n;
+    }
+    return (int32_t)std::min<int64_t>(longest, 65535);
+}
+// The row arrays of a running call (U * N rows: means, P, the five bias Jacobians of model 1) and their unpacking into one
+// CpiResult per interval of a window's count.
+struct RunningRows {
+    std::vector<double> DT, al, be, q, Jq, Ja, Jb, Ha, Hb, P;
+    bool jac = false;
+    int32_t N = 0;
+    cpi_outputs bind(int model, int64_t U, int32_t N_) {
+        jac = model == CPI_MODEL_V1;
+        N = N_;
+        const size_t M = (size_t)U * (size_t)N;
+        DT.resize(M); al.resize(M * 3); be.resize(M * 3); q.resize(M * 4); P.resize(M * 225);
+        if (jac) { Jq.resize(M * 9); Ja.resize(M * 9); Jb.resize(M * 9); Ha.resize(M * 9); Hb.resize(M * 9); }
+        cpi_outputs o{};
+        o.DT = DT.data(); o.alpha = al.data(); o.beta = be.data(); o.q = q.data(); o.P = P.data();
+        if (jac) { o.J_q = Jq.data(); o.J_a = Ja.data(); o.J_b = Jb.data(); o.H_a = Ha.data(); o.H_b = Hb.data(); }
+        return o;
+    }
+    std::vector<CpiResult> window(int64_t w, int32_t count) const {
+        std::vector<CpiResult> res((size_t)count);
+        for (int32_t i = 0; i < count; i++) {
+            const size_t r = (size_t)w * N + i;
+            CpiResult &x = res[i];
+            x.DT = DT[r];
+            for (int k = 0; k < 3; k++) { x.alpha_tau[k] = al[r * 3 + k]; x.beta_tau[k] = be[r * 3 + k]; }
+            for (int k = 0; k < 4; k++) x.q_k2tau[k] = q[r * 4 + k];
+            if (jac)
+                for (int k = 0; k < 9; k++) {
+                    x.J_q[k] = Jq[r * 9 + k]; x.J_a[k] = Ja[r * 9 + k]; x.J_b[k] = Jb[r * 9 + k];
+                    x.H_a[k] = Ha[r * 9 + k]; x.H_b[k] = Hb[r * 9 + k];
+                }
+            for (int k = 0; k < 225; k++) x.P_meas[k] = P[r * 225 + k];
+        }
+        return res;
+    }
+};
+
 // ---- the caller's loop for MANY windows at once --------------------------------------------------------------------
 // What GraphSolver keeps between two states is a deque of IMU readings (GraphSolver.h: imu_times / imu_linaccs /
 // imu_angvel, filled by addmeasurement_imu); createimufactor_cpi_v1 / _v2 (GraphSolver_IMU.cpp:34-134) walk it up to the
@@ -635,6 +687,36 @@ public:
                 r.H_b[i] = Hb[w * 9 + i]; r.O_a[i] = Oa[w * 9 + i]; r.O_b[i] = Ob[w * 9 + i];
             }
             for (int i = 0; i < 225; i++) r.P_meas[i] = P[w * 225 + i];
+        }
+        if (counts) *counts = cnt;
+        return res;
+    }
+    // The reference's members after EVERY feed_IMU of every window (cpi_preintegrate_stream_running_host): result[u][i] = window u
+    // after interval i, one per interval of the window's TRUE count (as CpiBatch::running returns one per recorded interval); a
+    // skipped interval (dt <= 0) repeats the previous one.  Models 1 and 2; the bias Jacobians are filled for model 1 only.
+    // The call returns U * max_intervals rows, so the default bound (max_intervals = 0) is TIGHT: the longest window, found on
+    // the host from the stamps.  A window longer than max_intervals is an error, not a truncation.
+    std::vector<std::vector<CpiResult>> running(const Context &ctx, const cpi_params &prm, const std::vector<double> &update_times,
+                                                const std::vector<double> &lin, const std::vector<double> &q_k_lin = std::vector<double>(),
+                                                std::vector<int32_t> *counts = nullptr, int32_t max_intervals = 0) const {
+        const int64_t U = (int64_t)update_times.size(), K = (int64_t)size();
+        if ((int64_t)lin.size() != U * 6) throw std::runtime_error("ImuStream::running: lin must hold 6 doubles per update time");
+        if (!q_k_lin.empty() && (int64_t)q_k_lin.size() != U * 4) throw std::runtime_error("ImuStream::running: q_k_lin must hold 4 doubles per update time");
+        std::vector<std::vector<CpiResult>> res((size_t)U);
+        if (counts) counts->assign((size_t)U, 0);
+        if (U == 0) return res;
+        const int32_t N = max_intervals > 0 ? max_intervals : longest_window(knots_.data(), (size_t)K, update_times.data(), (size_t)U);
+        RunningRows rows;
+        cpi_outputs o = rows.bind(prm.model, U, N);
+        std::vector<int32_t> cnt((size_t)U, 0);
+        // (N == 0: no window holds an interval -- or the stream is empty, which the entry refuses as preintegrate()'s does)
+        if (N > 0 || K == 0)
+            ctx.check(cpi_preintegrate_stream_running_host(ctx.get(), &prm, K, knots_.data(), U, update_times.data(), std::max<int32_t>(N, 1),
+                                                           lin.data(), q_k_lin.empty() ? nullptr : q_k_lin.data(), &o, cnt.data()));
+        for (int64_t u = 0; u < U; u++) {
+            if (cnt[u] > N) throw std::runtime_error("ImuStream::running: window " + std::to_string(u) + " holds " + std::to_string(cnt[u]) +
+                                                     " intervals, more than max_intervals = " + std::to_string(N));
+            res[u] = rows.window(u, cnt[u]);
         }
         if (counts) *counts = cnt;
         return res;
@@ -701,6 +783,39 @@ public:
             }
             if (counts) (*counts)[r].assign(cnt.begin() + uoff_[r], cnt.begin() + uoff_[r + 1]);
         }
+        return res;
+    }
+    // ImuStream::running for every run in ONE call (cpi_preintegrate_streams_running_host): result[r][j][i] = window j of run r
+    // after interval i.  The default bound is the longest window of any run (found on the host from the stamps); a window longer
+    // than max_intervals is an error.
+    std::vector<std::vector<std::vector<CpiResult>>> running(const Context &ctx, const cpi_params &prm,
+                                                             std::vector<std::vector<int32_t>> *counts = nullptr,
+                                                             int32_t max_intervals = 0) const {
+        const int64_t R = (int64_t)runs_.size(), K = (int64_t)(knots_.size() / 7), U = (int64_t)ut_.size();
+        std::vector<std::vector<std::vector<CpiResult>>> res((size_t)R);
+        for (int64_t r = 0; r < R; r++) res[r].resize(runs_[r]);
+        if (counts) { counts->assign((size_t)R, std::vector<int32_t>()); for (int64_t r = 0; r < R; r++) (*counts)[r].assign(runs_[r], 0); }
+        if (U == 0) return res;
+        if (!qk_.empty() && qk_.size() != ut_.size() * 4) throw std::runtime_error("ImuStreamSet::running: q_k_lin given for some runs and not for others");
+        int32_t N = max_intervals;
+        if (N <= 0)
+            for (int64_t r = 0; r < R; r++)
+                N = std::max(N, longest_window(knots_.data() + soff_[r] * 7, (size_t)(soff_[r + 1] - soff_[r]), ut_.data() + uoff_[r], runs_[r]));
+        RunningRows rows;
+        cpi_outputs o = rows.bind(prm.model, U, N);
+        std::vector<int32_t> cnt((size_t)U, 0);
+        if (N > 0 || K == 0)
+            ctx.check(cpi_preintegrate_streams_running_host(ctx.get(), &prm, R, K, knots_.data(), soff_.data(), U, ut_.data(), uoff_.data(),
+                                                            std::max<int32_t>(N, 1), lin_.data(), qk_.empty() ? nullptr : qk_.data(), &o,
+                                                            cnt.data()));
+        for (int64_t r = 0; r < R; r++)
+            for (int64_t j = 0; j < (int64_t)runs_[r]; j++) {
+                const int64_t w = uoff_[r] + j;
+                if (cnt[w] > N) throw std::runtime_error("ImuStreamSet::running: window " + std::to_string(w) + " holds " + std::to_string(cnt[w]) +
+                                                         " intervals, more than max_intervals = " + std::to_string(N));
+                res[r][j] = rows.window(w, cnt[w]);
+                if (counts) (*counts)[r][j] = cnt[w];
+            }
         return res;
     }
 private:

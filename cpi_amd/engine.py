@@ -543,6 +543,143 @@ class Engine:
             raise ValueError("preintegrate_streams_host: a window has %d intervals, N = %d" % (int(cnt.max()), N))
         return (out, cnt) if return_counts else out
 
+    # ---- running rows from IMU stream(s), cut in place (cpi_preintegrate_stream_running / cpi_preintegrate_streams_running)
+    def _stream_running_out(self, U, N, want, params, packed, out):
+        if out is None:
+            out = self._running_views(self.alloc_outputs(U * N, self._running_want(tuple(want), params.model), params.model, packed), U, N)
+        return out, self._outputs_struct({k: v for k, v in out.items() if not k.startswith("_")})
+
+    def _stream_counts(self, ws, U, N, return_counts, check_counts, who):
+        counts = torch.empty((0,), dtype=torch.int32, device=self.device)
+        if U and (return_counts or check_counts):
+            off = (self.lib.cpi_stream_counts(_ptr(ws), U) - ws.data_ptr()) // 4
+            with torch.cuda.stream(self.stream) if (not self._follow and self.stream is not None) else _nullctx():
+                counts = ws.view(torch.int32)[off:off + U].clone()   # a copy: a re-used workspace is overwritten by the next call
+            if check_counts and int(counts.max().item()) > N:
+                raise ValueError("%s: a window has %d intervals, more than N = %d" % (who, int(counts.max().item()), N))
+        return counts
+
+    def preintegrate_stream_running(self, stream, update_times, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), N=None,
+                                    packed=False, out=None, return_counts=False, check_counts=True, workspace=None):
+        """The measurement after EVERY interval of every window of ONE IMU stream, cut in place
+        (cpi_preintegrate_stream_running): the inputs, N, return_counts, check_counts and workspace of preintegrate_stream, the
+        want / packed / out and the returned [U, N, ...] tensors of preintegrate_running -- entry [u, i] is window u after
+        interval i, skipped intervals and i >= count repeat the previous row, [u, N - 1] is what preintegrate_stream returns.
+        Bit for bit preintegrate_running on assemble_windows(stream, update_times) with the same N, params and lanes.
+        N=None: stream_bound() (the longest window with a tail assumed: exact when the longest window ends in a tail, one row
+        more -- a repeated final row per window -- when its update time falls on a stamp; the output is U * N rows; one host
+        synchronisation on first use of a pair); with check_counts=False an integer N is REQUIRED: the bound's cache is keyed by storage and version and can serve
+        a stale N, which only the count check catches.  Models 1 and 2; Jacobians for model 1 only."""
+        params = params or self.make_params()
+        K, U = stream.shape[0], update_times.shape[0]
+        for t in (stream, update_times, lin, q_k_lin):
+            assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64), "inputs must be contiguous CUDA float64 tensors"
+        if N is None:
+            if not check_counts:
+                raise ValueError("preintegrate_stream_running: check_counts=False needs an explicit N (the cached bound may be stale)")
+            N = self.stream_bound(stream, update_times)
+        N = int(N)
+        out, o = self._stream_running_out(U, N, want, params, packed, out)
+        ws = workspace if workspace is not None else self.stream_workspace(U)
+        self._sync_stream()
+        self._check(self.lib.cpi_preintegrate_stream_running(self.ctx, C.byref(params), K, _ptr(stream), U, _ptr(update_times), N,
+                                                             _ptr(lin), _ptr(q_k_lin), _ptr(ws), C.byref(o)))
+        if workspace is None and not self._follow and self.stream is not None:   # see preintegrate_stream
+            ws.record_stream(self.stream)
+        counts = self._stream_counts(ws, U, N, return_counts, check_counts, "preintegrate_stream_running")
+        return (out, counts) if return_counts else out
+
+    def preintegrate_streams_running(self, stream, stream_offsets, update_times, update_offsets, lin, q_k_lin=None, params=None,
+                                     want=("mean", "jac", "cov"), N=None, packed=False, out=None, return_counts=False,
+                                     check_counts=True, workspace=None):
+        """preintegrate_stream_running for MANY IMU streams in one call (cpi_preintegrate_streams_running): the inputs of
+        preintegrate_streams (the list-of-runs form included), the [U, N, ...] rows of preintegrate_running, U the windows of all
+        runs.  N=None: streams_bound() (tail assumed, as stream_bound(); one host synchronisation, not cached); check_counts=False
+        needs an integer N."""
+        params = params or self.make_params()
+        stream, soff = self._runs(stream, stream_offsets, "stream", self.device)
+        update_times, uoff = self._runs(update_times, update_offsets, "update_times", self.device)
+        if stream is None:
+            stream = torch.empty((0, 7), dtype=torch.float64, device=self.device)
+        if update_times is None:
+            update_times = torch.empty((0,), dtype=torch.float64, device=self.device)
+        R, K, U = soff.shape[0] - 1, stream.shape[0], update_times.shape[0]
+        assert uoff.shape[0] == R + 1, "stream_offsets and update_offsets must both hold R + 1 entries"
+        for t in (stream, update_times, lin, q_k_lin):
+            assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64), "inputs must be contiguous CUDA float64 tensors"
+        if N is None:
+            if not check_counts:
+                raise ValueError("preintegrate_streams_running: check_counts=False needs an explicit N")
+            N = self.streams_bound(stream, soff, update_times, uoff)
+        N = int(N)
+        out, o = self._stream_running_out(U, N, want, params, packed, out)
+        ws = workspace if workspace is not None else self.streams_workspace(R, U)
+        self._sync_stream()
+        self._check(self.lib.cpi_preintegrate_streams_running(self.ctx, C.byref(params), R, K, _ptr(stream), _ptr(soff), U,
+                                                              _ptr(update_times), _ptr(uoff), N, _ptr(lin), _ptr(q_k_lin), _ptr(ws),
+                                                              C.byref(o)))
+        # the workspace and the offsets must outlive the kernels that read them (see preintegrate_stream)
+        if not self._follow and self.stream is not None:
+            for t in ((ws,) if workspace is None else ()) + (soff, uoff, stream, update_times):
+                t.record_stream(self.stream)
+        counts = self._stream_counts(ws, U, N, return_counts, check_counts, "preintegrate_streams_running")
+        return (out, counts) if return_counts else out
+
+    def _stream_running_host_out(self, U, N, want, params, pinned):
+        out = {}
+        groups = self._running_want(tuple(want), params.model)
+        for name, n in OUT_FIELDS:
+            if _group_of(name) in groups and (params.model == 2 or name not in ("O_a", "O_b")):
+                out[name] = torch.empty((U, N) if n == 1 else (U, N, n), dtype=torch.float64, pin_memory=pinned)
+        return out
+
+    def preintegrate_stream_running_host(self, stream, update_times, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"),
+                                         N=None, pinned=False, return_counts=False, check_counts=True):
+        """preintegrate_stream_running from HOST memory (cpi_preintegrate_stream_running_host): CPU float64 tensors in, CPU
+        tensors [U, N, ...] out; synchronous.  N defaults to the longest window the stamps allow; with check_counts a window longer
+        than N raises (check_counts=False needs an integer N and returns the truncated rows)."""
+        params = params or self.make_params()
+        K, U = stream.shape[0], update_times.shape[0]
+        for t in (stream, update_times, lin, q_k_lin):
+            assert t is None or (not t.is_cuda and t.is_contiguous() and t.dtype == torch.float64), "inputs must be contiguous CPU float64 tensors"
+        if N is None and not check_counts:
+            raise ValueError("preintegrate_stream_running_host: check_counts=False needs an explicit N")
+        N = int(N) if N is not None else self._stream_bound(stream, update_times)
+        out = self._stream_running_host_out(U, N, want, params, pinned)
+        cnt = torch.empty((U,), dtype=torch.int32)
+        o = self._outputs_struct(out)
+        self._sync_stream()
+        self._check(self.lib.cpi_preintegrate_stream_running_host(self.ctx, C.byref(params), K, _ptr(stream), U, _ptr(update_times), N,
+                                                                  _ptr(lin), _ptr(q_k_lin), C.byref(o), _ptr(cnt)))
+        if check_counts and U and int(cnt.max()) > N:
+            raise ValueError("preintegrate_stream_running_host: a window has %d intervals, N = %d" % (int(cnt.max()), N))
+        return (out, cnt) if return_counts else out
+
+    def preintegrate_streams_running_host(self, stream, stream_offsets, update_times, update_offsets, lin, q_k_lin=None, params=None,
+                                          want=("mean", "jac", "cov"), N=None, pinned=False, return_counts=False, check_counts=True):
+        """preintegrate_streams_running from HOST memory (cpi_preintegrate_streams_running_host, which validates the offsets): CPU
+        float64 tensors and int64 offsets in, CPU tensors [U, N, ...] out; synchronous.  N, check_counts as in
+        preintegrate_stream_running_host (the default N is streams_bound())."""
+        params = params or self.make_params()
+        soff = torch.as_tensor(np.asarray(stream_offsets, dtype=np.int64))
+        uoff = torch.as_tensor(np.asarray(update_offsets, dtype=np.int64))
+        R, K, U = soff.shape[0] - 1, stream.shape[0], update_times.shape[0]
+        for t in (stream, update_times, lin, q_k_lin):
+            assert t is None or (not t.is_cuda and t.is_contiguous() and t.dtype == torch.float64), "inputs must be contiguous CPU float64 tensors"
+        if N is None and not check_counts:
+            raise ValueError("preintegrate_streams_running_host: check_counts=False needs an explicit N")
+        N = int(N) if N is not None else self.streams_bound(stream, soff, update_times, uoff)
+        out = self._stream_running_host_out(U, N, want, params, pinned)
+        cnt = torch.empty((U,), dtype=torch.int32)
+        o = self._outputs_struct(out)
+        self._sync_stream()
+        self._check(self.lib.cpi_preintegrate_streams_running_host(self.ctx, C.byref(params), R, K, _ptr(stream), _ptr(soff), U,
+                                                                   _ptr(update_times), _ptr(uoff), N, _ptr(lin), _ptr(q_k_lin),
+                                                                   C.byref(o), _ptr(cnt)))
+        if check_counts and U and int(cnt.max()) > N:
+            raise ValueError("preintegrate_streams_running_host: a window has %d intervals, N = %d" % (int(cnt.max()), N))
+        return (out, cnt) if return_counts else out
+
     def preintegrate_tiled_host(self, tiles, W, lin, q_k_lin=None, params=None, count=None, pinned=True, out=None):
         """Mean outputs from tiles held in HOST memory (cpi_preintegrate_tiled_batch_host: chunked upload / kernel /
         download pipeline).  CPU float64 tensors; returns CPU tensors; synchronous."""

@@ -50,7 +50,10 @@ extern "C" {
                                additions within 3 (new symbols only): cpi_carry_doubles, cpi_preintegrate_resume,
                                cpi_preintegrate_resume_host (resumable preintegration); cpi_streams_workspace_bytes,
                                cpi_preintegrate_streams, cpi_preintegrate_streams_host (many IMU streams in one call);
-                               cpi_preintegrate_running, cpi_preintegrate_running_host (the measurement after every interval) */
+                               cpi_preintegrate_running, cpi_preintegrate_running_host (the measurement after every interval);
+                               cpi_preintegrate_stream_running, cpi_preintegrate_streams_running,
+                               cpi_preintegrate_stream_running_host, cpi_preintegrate_streams_running_host (the running rows
+                               from IMU stream(s), windows cut in place) */
 
 enum { CPI_OK = 0, CPI_ERR_INVALID = 1, CPI_ERR_HIP = 2, CPI_ERR_NO_DEVICE = 3, CPI_ERR_RCCL = 4 };
 enum {
@@ -205,7 +208,8 @@ int cpi_preintegrate_resume(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int3
  * matrix at the end of the recursion).  W == 0 or N == 0 is a no-op; N <= 65535 and the 32-bit grid limit on W as in
  * cpi_preintegrate_batch.  No host synchronisation and a single stream: the call can be captured into a graph.
  * Composition: with F = W * N and idx_i[row] = row / N, cpi_predict_batch turns the rows into IMU-rate predicted states.
- * Not provided: running rows from the stream entries (cpi_preintegrate_stream[s]) and from a carry record. */
+ * Running rows from IMU stream(s), windows cut in place: cpi_preintegrate_stream_running / cpi_preintegrate_streams_running below.
+ * Not provided: running rows from a carry record. */
 int cpi_preintegrate_running(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                              const double *knots, const int64_t *first, const int32_t *count,
                              const double *lin, const double *q_k_lin, const cpi_outputs *rows);
@@ -268,6 +272,39 @@ size_t cpi_streams_workspace_bytes(int64_t R, int64_t U);
 int cpi_preintegrate_streams(cpi_ctx *ctx, const cpi_params *prm, int64_t R, int64_t K, const double *stream,
                              const int64_t *stream_offsets, int64_t U, const double *update_times, const int64_t *update_offsets,
                              int32_t N, const double *lin, const double *q_k_lin, void *workspace, const cpi_outputs *out);
+
+/* Running preintegration from IMU stream(s), cut in place: the rows of cpi_preintegrate_running for the windows of
+ * cpi_preintegrate_stream / cpi_preintegrate_streams, with ZERO copies of the IMU data and no host assembly.
+ *   - inputs, the window semantics, N as a truncating bound, the clamped offsets of the multi-stream form and the workspace
+ *     are exactly those of cpi_preintegrate_stream / cpi_preintegrate_streams (cpi_stream_workspace_bytes(U) /
+ *     cpi_streams_workspace_bytes(R, U) bytes, 16-byte aligned; after the call cpi_stream_counts(workspace, U) holds the TRUE
+ *     counts, the rest of its contents is unspecified).  The cut kernel always runs (there is no fused-cut variant);
+ *   - rows as in cpi_preintegrate_running: U * N rows, row u * N + i = window u after interval i; a skipped interval (dt <= 0)
+ *     repeats the previous row bit for bit; rows i >= count[u] repeat the window's final state, so row u * N + N - 1 is the
+ *     measurement cpi_preintegrate_stream[s] returns; a window of 0 intervals (an update time before the first reading, two
+ *     equal update times, a run without readings) gives N zero-state rows; a window longer than N gives the rows of its first N
+ *     intervals, none of them a tail; a P_sym row is bit for bit the upper triangle of the P row; 64-bit row offsets.  Give a
+ *     TIGHT N: the output is U * N rows;
+ *   - bit-identity: the rows are bit for bit those of cpi_preintegrate_running on the knots / first / count that the host
+ *     assemblers (cpi_amd/stream.py, cpi_host::assemble_windows) cut from the same stream(s), with count clamped to N and the same
+ *     N, params and lanes_per_window (0 included: the automatic lane choice is the same function of U, N and the request in
+ *     both entries).  Window u of run r of the multi-stream call is bit for bit window u - update_offsets[r] of the
+ *     single-stream call on run r alone at a pinned lanes_per_window;
+ *   - models 1 and 2, imu_avg 0 / 1; means and covariance for both, the five analytic bias Jacobians for model 1.
+ *     CPI_ERR_INVALID: CPI_MODEL_FORSTER, any Jacobian field (J_q ... O_b) with model 2, model 2 without q_k_lin, N > 65535, an
+ *     unsupported lanes_per_window, a NULL workspace / stream / update_times / lin / rows (or offsets), K == 0 or R == 0 with
+ *     U > 0.  U == 0 or N == 0 is a no-op (nothing is written, the workspace included).
+ * The kernels (cut, means / Jacobians, covariance) run one after the other on the context's stream, without host
+ * synchronisation: the call can be captured into a graph without parallel branches.  No read leaves the K readings of the
+ * stream, whatever the offsets hold and wherever a window lies.
+ * Composition: with F = U * N and idx_i[row] = row / N, cpi_predict_batch turns the rows into IMU-rate predicted states. */
+int cpi_preintegrate_stream_running(cpi_ctx *ctx, const cpi_params *prm, int64_t K, const double *stream, int64_t U,
+                                    const double *update_times, int32_t N, const double *lin, const double *q_k_lin,
+                                    void *workspace, const cpi_outputs *rows);
+int cpi_preintegrate_streams_running(cpi_ctx *ctx, const cpi_params *prm, int64_t R, int64_t K, const double *stream,
+                                     const int64_t *stream_offsets, int64_t U, const double *update_times,
+                                     const int64_t *update_offsets, int32_t N, const double *lin, const double *q_k_lin,
+                                     void *workspace, const cpi_outputs *rows);
 
 /* The same loop for the mean outputs (DT, alpha, beta, q) on the TILED layout: the knots of 64 consecutive windows
  * interleaved per step,
@@ -494,6 +531,19 @@ int cpi_preintegrate_streams_host(cpi_ctx *ctx, const cpi_params *prm, int64_t R
                                   const int64_t *stream_offsets, int64_t U, const double *update_times,
                                   const int64_t *update_offsets, int32_t N, const double *lin, const double *q_k_lin,
                                   const cpi_outputs *out, int32_t *count);
+/* cpi_preintegrate_stream_running / cpi_preintegrate_streams_running with HOST pointers (pageable or pinned): the stream(s) are
+ * uploaded once, whole, and cut on the device; rows holds U * N rows in host memory and comes back in chunks of whole windows,
+ * never more than 2^18 rows each (N <= 65535: at least 4 windows), so that the device staging stays bounded whatever N is -- the
+ * rows do not depend on the chunking.  count (may be NULL)
+ * receives the TRUE interval count of every window.  The multi-stream form validates the offsets as
+ * cpi_preintegrate_streams_host does.  PCIe-inclusive, never the benchmarked path. */
+int cpi_preintegrate_stream_running_host(cpi_ctx *ctx, const cpi_params *prm, int64_t K, const double *stream, int64_t U,
+                                         const double *update_times, int32_t N, const double *lin, const double *q_k_lin,
+                                         const cpi_outputs *rows, int32_t *count);
+int cpi_preintegrate_streams_running_host(cpi_ctx *ctx, const cpi_params *prm, int64_t R, int64_t K, const double *stream,
+                                          const int64_t *stream_offsets, int64_t U, const double *update_times,
+                                          const int64_t *update_offsets, int32_t N, const double *lin, const double *q_k_lin,
+                                          const cpi_outputs *rows, int32_t *count);
 void *cpi_host_alloc(size_t bytes);
 void cpi_host_free(void *p);
 int cpi_factor_eval_batch_host(cpi_ctx *ctx, int32_t model, const double grav[3], int64_t F,

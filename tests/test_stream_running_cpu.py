@@ -1,4 +1,20 @@
-kernel                                                                    SGPR  VGPR  AGPR scratch  occ    LDS
+"""CPU-only checks of running preintegration from IMU stream(s) (cpi_preintegrate_stream_running / _streams_running and their
+_host forms): the symbols are declared, listed under "additions within 3" and exported, the Python layer knows them, a NULL
+context is refused, the new kernels stand in the build report without scratch, and every row the report held before this
+feature -- registers, LDS, scratch, occupancy of every kernel -- is still there unchanged."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SYMBOLS = ("cpi_preintegrate_stream_running", "cpi_preintegrate_streams_running", "cpi_preintegrate_stream_running_host",
+           "cpi_preintegrate_streams_running_host")
+
+# cpi_amd/csrc/resource_usage.txt as it stood before cpi_mean_stream_running_kernel existed (header line left out)
+PARENT_ROWS = """\
 cpi_tile_knots_kernel                                                       51    22     0       0    8      0
 cpi_cut_windows_kernel                                                      48    26     0       0    8      0
 cpi_cut_runs_kernel                                                         44    36     0       0    8      0
@@ -339,18 +355,6 @@ cpi_mean_running_kernel<1, false, true, true>                              104  
 cpi_mean_running_kernel<1, false, true, false>                             102   206     0       0    1  36864
 cpi_mean_running_kernel<1, false, false, true>                             104   216     0       0    1  36864
 cpi_mean_running_kernel<1, false, false, false>                            102   206     0       0    1  36864
-cpi_mean_stream_running_kernel<2, false, true, true>                       106   242     0       0    1  36864
-cpi_mean_stream_running_kernel<2, false, true, false>                      105   228     0       0    1  36864
-cpi_mean_stream_running_kernel<2, false, false, true>                      106   242     0       0    1  36864
-cpi_mean_stream_running_kernel<2, false, false, false>                     105   228     0       0    1  36864
-cpi_mean_stream_running_kernel<1, true, true, true>                        106   256   112       0    1  36864
-cpi_mean_stream_running_kernel<1, true, true, false>                       106   256   100       0    1  36864
-cpi_mean_stream_running_kernel<1, true, false, true>                       106   256   116       0    1  36864
-cpi_mean_stream_running_kernel<1, true, false, false>                      106   256   100       0    1  36864
-cpi_mean_stream_running_kernel<1, false, true, true>                       106   222     0       0    1  36864
-cpi_mean_stream_running_kernel<1, false, true, false>                      105   212     0       0    1  36864
-cpi_mean_stream_running_kernel<1, false, false, true>                      106   222     0       0    1  36864
-cpi_mean_stream_running_kernel<1, false, false, false>                     105   212     0       0    1  36864
 cpi_forster_kernel                                                          97   248     0       0    2  19200
 cpi_cov_kernel<2, true>                                                    106   255     0       0    2  20096
 cpi_cov_kernel<2, false>                                                   106   255     0       0    2  20096
@@ -401,3 +405,69 @@ cpi_sqrt_info_kernel<true>                                                  43  
 cpi_sqrt_info_kernel<false>                                                 26    70     0       0    6   7200
 cpi_predict_kernel<1>                                                       43    94     0       0    3  13824
 cpi_predict_kernel<2>                                                       36    94     0       0    3  13824
+"""
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from cpi_amd import _lib
+    return _lib.load()
+
+
+def test_stream_running_symbols_are_declared_and_exported(lib):
+    header = open(os.path.join(ROOT, "include", "cpi_amd.h")).read()
+    from cpi_amd import build
+    dyn = subprocess.run(["nm", "-D", "--defined-only", build.LIB], stdout=subprocess.PIPE, text=True, check=True).stdout
+    additions = header.split("typedef struct cpi_ctx")[0].split("additions within 3")[1]
+    for s in SYMBOLS:
+        assert re.search(r"\bint %s\(" % s, header), s
+        assert re.search(r" T %s$" % s, dyn, re.M), s
+        assert getattr(lib, s).restype is C.c_int
+        assert re.search(r"\b%s\b" % s, additions), s
+    assert lib.cpi_abi_version() == 3
+    # the "Not provided" sentences name the carry record only
+    for path in (os.path.join(ROOT, "include", "cpi_amd.h"), os.path.join(ROOT, "INTEGRATION.md")):
+        for sentence in re.findall(r"Not provided:[^\n]*(?:\n[^\n]*)?", open(path).read()):
+            assert "stream entries" not in sentence, (path, sentence)
+
+
+def test_stream_running_rejects_a_null_context(lib):
+    from cpi_amd._lib import CpiOutputs, CpiParams
+    prm, out = CpiParams(), CpiOutputs()
+    assert lib.cpi_preintegrate_stream_running(None, C.byref(prm), 1, None, 1, None, 1, None, None, None, C.byref(out)) == 1
+    assert lib.cpi_preintegrate_streams_running(None, C.byref(prm), 1, 1, None, None, 1, None, None, 1, None, None, None, C.byref(out)) == 1
+    assert lib.cpi_preintegrate_stream_running_host(None, C.byref(prm), 1, None, 1, None, 1, None, None, C.byref(out), None) == 1
+    assert lib.cpi_preintegrate_streams_running_host(None, C.byref(prm), 1, 1, None, None, 1, None, None, 1, None, None, C.byref(out), None) == 1
+
+
+def test_engine_has_the_stream_running_entries():
+    import inspect
+    import cpi_amd
+    for name in ("preintegrate_stream_running", "preintegrate_streams_running", "preintegrate_stream_running_host",
+                 "preintegrate_streams_running_host"):
+        fn = getattr(cpi_amd.Engine, name)
+        assert callable(fn)
+        par = inspect.signature(fn).parameters
+        assert {"want", "N", "return_counts", "check_counts"} <= set(par), name
+    for name in ("preintegrate_stream_running", "preintegrate_streams_running"):
+        assert {"packed", "out", "workspace"} <= set(inspect.signature(getattr(cpi_amd.Engine, name)).parameters), name
+
+
+def test_stream_running_kernels_are_in_the_resource_report_and_nothing_else_moved():
+    from cpi_amd import build
+    lines = open(build.REPORT).read().splitlines()
+    new = [ln.split() for ln in lines if ln.startswith("cpi_mean_stream_running_kernel<")]
+    names = " ".join(lines)
+    for m in ("cpi_mean_stream_running_kernel<1, false, false, false>", "cpi_mean_stream_running_kernel<1, true, true, true>",
+              "cpi_mean_stream_running_kernel<2, false, true, true>", "cpi_mean_stream_running_kernel<2, false, false, false>"):
+        assert m in names, m
+    assert "cpi_mean_stream_running_kernel<2, true" not in names   # model 2 has no running Jacobian kernel
+    assert len(new) == 12 and all(r[-3] == "0" for r in new)       # scratch column
+    norm = lambda ln: " ".join(ln.split())
+    have = {norm(ln) for ln in lines}
+    parent = [ln for ln in PARENT_ROWS.splitlines() if ln.strip()]
+    assert len(parent) == 390
+    missing = [ln for ln in parent if norm(ln) not in have]
+    assert not missing, "rows of existing kernels changed: %s" % missing[:5]
+    # and nothing but the new kernels was added
+    assert len(lines) - 1 == len(parent) + len(new)
