@@ -507,6 +507,73 @@ extern "C" int cpi_preintegrate_running(cpi_ctx *ctx, const cpi_params *prm, int
     return CPI_OK;
 }
 
+// Running preintegration from and to carry records (include/cpi_amd.h): the argument rules of cpi_preintegrate_running and the
+// record / tag rules of cpi_preintegrate_resume.  cpi_mean_running_carry_kernel ALWAYS runs -- it owns the tag, the means and
+// the model-1 Jacobian block of carry_out, whatever rows asks for --, cpi_cov_running_carry_kernel adds the P / P_sym rows and
+// the covariance block.  Both read carry_in and write disjoint parts of carry_out, one after the other on the context's
+// stream: no side stream (a capture of the call is a chain), and still no in-place records.
+extern "C" int cpi_preintegrate_running_resume(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                               const double *knots, const int64_t *first, const int32_t *count,
+                                               const double *lin, const double *q_k_lin, const double *carry_in, double *carry_out,
+                                               const cpi_outputs *rows) {
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (!prm || !rows) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume: prm/rows is NULL");
+    if (prm->model == CPI_MODEL_FORSTER)
+        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume: model must be 1 or 2 (the Forster comparator has no running form and cannot be resumed)");
+    if (prm->model != CPI_MODEL_V1 && prm->model != CPI_MODEL_V2)
+        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume: model must be 1 or 2");
+    const bool want_mean = rows->DT || rows->alpha || rows->beta || rows->q;
+    const bool want_jac = rows->J_q || rows->J_a || rows->J_b || rows->H_a || rows->H_b || rows->O_a || rows->O_b;
+    const bool want_cov = rows->P != nullptr || rows->P_sym != nullptr;
+    if (prm->model == CPI_MODEL_V2 && want_jac)
+        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume: the Jacobian fields (J_q ... O_b) are not available for model 2 "
+                                          "(they are read out of the state transition matrix at the end of the recursion: finish the "
+                                          "chain with cpi_preintegrate_resume)");
+    if (!carry_out) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume: carry_out is NULL");
+    if (W < 0 || N < 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume: negative size");
+    const int CD = carry::doubles(prm->model);
+    if (carry_in && carry_in < carry_out + W * CD && carry_out < carry_in + W * CD)
+        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume: carry_in and carry_out overlap");
+    if (W == 0) return CPI_OK;
+    if (!knots || !lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume: knots/lin is NULL");
+    if (prm->model == CPI_MODEL_V2 && !q_k_lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume: model 2 needs q_k_lin");
+    if (!grid_ok(W)) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume: W exceeds 2^31 - 1 windows per call (32-bit grid)");
+    if (N > 65535) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume: N (intervals per window) must be <= 65535");
+    const int Lp = prm->lanes_per_window;
+    if (Lp != 0 && !launch::mean_lanes_supported(Lp)) return fail(ctx, CPI_ERR_INVALID, "lanes_per_window must be 0 or one of 1,2,3,4,5,6,8,12,16,32,64");
+    const bool avg = prm->imu_avg != 0;
+    const bool stj = prm->model == CPI_MODEL_V2 && prm->state_transition_jacobians != 0;
+    CarryArgs c;
+    const int hdr = 1 | (avg ? 8 : 0) | (stj ? 16 : 0) | (32 * prm->model);   // as cpi_preintegrate_resume: the records are interchangeable
+    c.in = carry_in;
+    c.out = carry_out;
+    c.need = hdr | (want_cov ? carry::TAG_P : 0) | (want_jac ? carry::TAG_J : 0);
+    c.tag_out = c.need;
+    c.own_means = 0;
+
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    PreArgs a;
+    memset(&a, 0, sizeof a);
+    a.W = W; a.N = N; a.knots = knots; a.first = (const long long *)first; a.count = count;
+    a.lin = lin; a.qk = q_k_lin;
+    for (int i = 0; i < 3; i++) a.grav[i] = prm->grav[i];
+    a.q4[0] = prm->sigma_w * prm->sigma_w; a.q4[1] = prm->sigma_wb * prm->sigma_wb;
+    a.q4[2] = prm->sigma_a * prm->sigma_a; a.q4[3] = prm->sigma_ab * prm->sigma_ab;
+    a.out = *rows;
+    {
+        PreArgs m = a;
+        m.write_means = want_mean ? 1 : 0;
+        m.write_jac = want_jac ? 1 : 0;
+        CarryArgs cm = c;
+        cm.own_means = 1;
+        launch::mean_running_carry(prm->model, want_jac, avg, pick_lanes(prm, W, N, want_jac), m, cm, ctx->stream);
+    }
+    if (want_cov) launch::cov_running_carry(prm->model, avg, a, c, ctx->stream);
+    CPI_HIP(ctx, hipGetLastError());
+    return CPI_OK;
+}
+
 // Replaces the caller-side loop of GraphSolver::createimufactor_cpi_v1 / _v2 (GraphSolver_IMU.cpp:43-75, 97-130) for ALL the
 // windows of a trajectory at once, with ZERO copies of the IMU data: cpi_cut_windows_kernel finds, per update time, where the
 // reference's deque would stand (28 bytes per window into the caller's workspace), and the preintegration kernels read the
@@ -1369,12 +1436,16 @@ struct HostPipe {
     size_t in_cap[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
     void *out[2][kOutFields] = {};
     size_t out_cap[2][kOutFields] = {};
+    void *cin[2] = {nullptr, nullptr}, *cout[2] = {nullptr, nullptr};   // carry records (cpi_preintegrate_running_resume_host)
+    size_t cin_cap[2] = {0, 0}, cout_cap[2] = {0, 0};
 };
 static void host_pipe_destroy(HostPipe *hp) {
     if (!hp) return;
     for (int s = 0; s < 2; s++) {
         for (int k = 0; k < 4; k++) if (hp->in[s][k]) (void)hipFree(hp->in[s][k]);
         for (int k = 0; k < kOutFields; k++) if (hp->out[s][k]) (void)hipFree(hp->out[s][k]);
+        if (hp->cin[s]) (void)hipFree(hp->cin[s]);
+        if (hp->cout[s]) (void)hipFree(hp->cout[s]);
         if (hp->ev_in[s]) (void)hipEventDestroy(hp->ev_in[s]);
         if (hp->ev_done[s]) (void)hipEventDestroy(hp->ev_done[s]);
         if (hp->ev_out[s]) (void)hipEventDestroy(hp->ev_out[s]);
@@ -1410,10 +1481,11 @@ extern "C" void *cpi_host_alloc(size_t bytes) {
 extern "C" void cpi_host_free(void *p) { if (p) (void)hipHostFree(p); }
 
 // tiled == false: knots[W][N+1][7];  tiled == true: tiles[ceil(W/64)][N+1][7][64] (chunks are whole tiles)
-// running: cpi_preintegrate_running -- N output rows per window instead of one, chunks of <= 65536 ROWS
+// running: cpi_preintegrate_running -- N output rows per window instead of one, chunks of <= 65536 ROWS (N >= 1)
+// carry_out: cpi_preintegrate_running_resume -- the records of a chunk go up and come down with it
 static int preintegrate_host_pipeline(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N, const double *knots, bool tiled,
                                       const int32_t *count, const double *lin, const double *q_k_lin, const cpi_outputs *out,
-                                      bool running = false) {
+                                      bool running = false, const double *carry_in = nullptr, double *carry_out = nullptr) {
     int rc = host_pipe_get(ctx);
     if (rc != CPI_OK) return rc;
     HostPipe *hp = ctx->pipe;
@@ -1425,7 +1497,10 @@ static int preintegrate_host_pipeline(cpi_ctx *ctx, const cpi_params *prm, int64
     const size_t knot_bytes = (size_t)(N + 1) * 7 * sizeof(double);
     auto in_bytes = [&](int64_t wn) { return tiled ? (size_t)((wn + 63) / 64) * 64 * knot_bytes : (size_t)wn * knot_bytes; };
     cpi_outputs h = *out;
+    const size_t cd_bytes = carry_out ? (size_t)carry::doubles(prm->model) * sizeof(double) : 0;
     for (int s = 0; s < nslots; s++) {
+        if (carry_in && (rc = host_pipe_reserve(ctx, hp->cin[s], hp->cin_cap[s], (size_t)Wc * cd_bytes)) != CPI_OK) return rc;
+        if (carry_out && (rc = host_pipe_reserve(ctx, hp->cout[s], hp->cout_cap[s], (size_t)Wc * cd_bytes)) != CPI_OK) return rc;
         const size_t need[4] = { in_bytes(Wc), count ? (size_t)Wc * sizeof(int32_t) : 0, (size_t)Wc * 6 * sizeof(double),
                                  q_k_lin ? (size_t)Wc * 4 * sizeof(double) : 0 };
         for (int k = 0; k < 4; k++)
@@ -1444,13 +1519,18 @@ static int preintegrate_host_pipeline(cpi_ctx *ctx, const cpi_params *prm, int64
         if (count && !hip_ok(hipMemcpyAsync(hp->in[s][1], count + w0, (size_t)wn * sizeof(int32_t), hipMemcpyHostToDevice, hp->up), "upload count")) break;
         if (!hip_ok(hipMemcpyAsync(hp->in[s][2], lin + (size_t)w0 * 6, (size_t)wn * 6 * sizeof(double), hipMemcpyHostToDevice, hp->up), "upload lin")) break;
         if (q_k_lin && !hip_ok(hipMemcpyAsync(hp->in[s][3], q_k_lin + (size_t)w0 * 4, (size_t)wn * 4 * sizeof(double), hipMemcpyHostToDevice, hp->up), "upload q_k_lin")) break;
+        if (carry_in && !hip_ok(hipMemcpyAsync(hp->cin[s], (const char *)carry_in + (size_t)w0 * cd_bytes, (size_t)wn * cd_bytes, hipMemcpyHostToDevice, hp->up), "upload carry_in")) break;
         if (!hip_ok(hipEventRecord(hp->ev_in[s], hp->up), "hipEventRecord")) break;
         if (!hip_ok(hipStreamWaitEvent(ctx->stream, hp->ev_in[s], 0), "hipStreamWaitEvent")) break;
         if (i >= 2 && !hip_ok(hipStreamWaitEvent(ctx->stream, hp->ev_out[s], 0), "hipStreamWaitEvent")) break;   // slot's outputs downloaded
         cpi_outputs d;
         memset(&d, 0, sizeof d);
         for (int k = 0; k < kOutFields; k++) if (*out_field(&h, k)) *out_field(&d, k) = (double *)hp->out[s][k];
-        if (running)
+        if (running && carry_out)
+            rc = cpi_preintegrate_running_resume(ctx, prm, wn, N, (const double *)hp->in[s][0], nullptr, count ? (const int32_t *)hp->in[s][1] : nullptr,
+                                                 (const double *)hp->in[s][2], q_k_lin ? (const double *)hp->in[s][3] : nullptr,
+                                                 carry_in ? (const double *)hp->cin[s] : nullptr, (double *)hp->cout[s], &d);
+        else if (running)
             rc = cpi_preintegrate_running(ctx, prm, wn, N, (const double *)hp->in[s][0], nullptr, count ? (const int32_t *)hp->in[s][1] : nullptr,
                                           (const double *)hp->in[s][2], q_k_lin ? (const double *)hp->in[s][3] : nullptr, &d);
         else if (tiled)
@@ -1466,11 +1546,12 @@ static int preintegrate_host_pipeline(cpi_ctx *ctx, const cpi_params *prm, int64
             if (*out_field(&h, k) && !hip_ok(hipMemcpyAsync(*out_field(&h, k) + (size_t)w0 * R * OUT_N[k], hp->out[s][k], (size_t)wn * R * OUT_N[k] * sizeof(double),
                                                             hipMemcpyDeviceToHost, hp->down), "download")) break;
         if (!err.empty()) break;
+        if (carry_out && !hip_ok(hipMemcpyAsync((char *)carry_out + (size_t)w0 * cd_bytes, hp->cout[s], (size_t)wn * cd_bytes, hipMemcpyDeviceToHost, hp->down), "download carry_out")) break;
         if (!hip_ok(hipEventRecord(hp->ev_out[s], hp->down), "hipEventRecord")) break;
     }
     const hipError_t e1 = hipStreamSynchronize(hp->up), e2 = hipStreamSynchronize(ctx->stream), e3 = hipStreamSynchronize(hp->down);
     if (rc != CPI_OK) return rc;   // message already set by the device-pointer entry
-    const char *who = running ? "cpi_preintegrate_running_host: " : "cpi_preintegrate_batch_host: ";
+    const char *who = running ? (carry_out ? "cpi_preintegrate_running_resume_host: " : "cpi_preintegrate_running_host: ") : "cpi_preintegrate_batch_host: ";
     if (!err.empty()) return fail(ctx, CPI_ERR_HIP, who + err);
     hip_ok(e1, "hipStreamSynchronize(upload)"); hip_ok(e2, "hipStreamSynchronize"); hip_ok(e3, "hipStreamSynchronize(download)");
     if (!err.empty()) return fail(ctx, CPI_ERR_HIP, who + err);
@@ -1602,6 +1683,55 @@ extern "C" int cpi_preintegrate_resume_host(cpi_ctx *ctx, const cpi_params *prm,
     for (int k = 0; k < kOutFields; k++)
         if (*out_field(&h, k))
             CPI_HIP(ctx, hipMemcpyAsync(*out_field(&h, k), dout[k].p, (size_t)W * OUT_N[k] * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    CPI_HIP(ctx, hipMemcpyAsync(carry_out, dco.p, (size_t)W * cd * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    CPI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CPI_OK;
+}
+
+// cpi_preintegrate_running_resume from host memory: dense batches through the chunked pipeline (the records of a chunk travel with
+// it), ragged ones -- and N = 0, which has no rows to chunk by -- staged whole as in cpi_preintegrate_resume_host.
+extern "C" int cpi_preintegrate_running_resume_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                                    const double *knots, const int64_t *first, const int32_t *count,
+                                                    int64_t n_knots, const double *lin, const double *q_k_lin,
+                                                    const double *carry_in, double *carry_out, const cpi_outputs *rows) {
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (!prm || !rows || !knots || !lin || !carry_out) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume_host: NULL argument");
+    if (W < 0 || N < 0) return fail(ctx, CPI_ERR_INVALID, "negative size");
+    if (prm->model != CPI_MODEL_V1 && prm->model != CPI_MODEL_V2)
+        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume_host: model must be 1 or 2 (the Forster comparator has no running form and cannot be resumed)");
+    if (prm->model == CPI_MODEL_V2 && (rows->J_q || rows->J_a || rows->J_b || rows->H_a || rows->H_b || rows->O_a || rows->O_b))
+        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume_host: the Jacobian fields (J_q ... O_b) are not available for model 2");
+    const size_t cd = (size_t)carry::doubles(prm->model);
+    if (carry_in && carry_in < carry_out + W * cd && carry_out < carry_in + W * cd)
+        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume_host: carry_in and carry_out overlap");
+    if (W == 0) return CPI_OK;
+    if (N > 65535) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume_host: N (intervals per window) must be <= 65535");
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    if (!first && N > 0) return preintegrate_host_pipeline(ctx, prm, W, N, knots, false, count, lin, q_k_lin, rows, true, carry_in, carry_out);
+    if (!first) n_knots = W * (int64_t)(N + 1);
+    if (n_knots <= 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume_host: n_knots must be > 0");
+    DevBuf dk, df, dc, dl, dq, dci, dco, dout[kOutFields];
+    CPI_UP(dk, knots, (size_t)n_knots * 7 * sizeof(double));
+    CPI_UP(df, first, (size_t)W * sizeof(int64_t));
+    CPI_UP(dc, count, (size_t)W * sizeof(int32_t));
+    CPI_UP(dl, lin, (size_t)W * 6 * sizeof(double));
+    CPI_UP(dq, q_k_lin, (size_t)W * 4 * sizeof(double));
+    CPI_UP(dci, carry_in, (size_t)W * cd * sizeof(double));
+    CPI_HIP(ctx, hipMalloc(&dco.p, (size_t)W * cd * sizeof(double)));
+    const size_t nrows = (size_t)W * (size_t)N;
+    cpi_outputs d = *rows, h = *rows;
+    for (int k = 0; k < kOutFields; k++)
+        if (*out_field(&h, k) && nrows) {
+            CPI_HIP(ctx, hipMalloc(&dout[k].p, nrows * OUT_N[k] * sizeof(double)));
+            *out_field(&d, k) = (double *)dout[k].p;
+        }
+    int rc = cpi_preintegrate_running_resume(ctx, prm, W, N, (const double *)dk.p, (const int64_t *)df.p, (const int32_t *)dc.p,
+                                             (const double *)dl.p, (const double *)dq.p, (const double *)dci.p, (double *)dco.p, &d);
+    if (rc != CPI_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    for (int k = 0; k < kOutFields; k++)
+        if (*out_field(&h, k) && nrows)
+            CPI_HIP(ctx, hipMemcpyAsync(*out_field(&h, k), dout[k].p, nrows * OUT_N[k] * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     CPI_HIP(ctx, hipMemcpyAsync(carry_out, dco.p, (size_t)W * cd * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     CPI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CPI_OK;

@@ -29,6 +29,10 @@ namespace {
 // LDS for a flat copy with consecutive lanes on consecutive doubles was measured and is SLOWER -- its 11 / 5.5 KB cost the kernel
 // 3 / 2 of its 8 wavefronts per CU: 100 k x 20 model 1 1.63 -> 1.47 ms, model 2 2.21 -> 1.60 ms, 549 x 50 166 -> 84 us.)  The means
 // of the rows belong to cpi_mean_running_kernel.
+// CARRY and RUNNING (cpi_cov_running_carry_kernel, cpi_preintegrate_running_resume): the rows of a window that continues from a
+// record.  The covariance block of carry_out is written after the last interval (the columns as row N - 1 has just read them
+// out), a window whose record does not fit gets NaN in EVERY row, and the tag / means of carry_out are left to
+// cpi_mean_running_carry_kernel (own_means = 0).
 template <int MODEL, bool AVG, bool CARRY, bool RUNNING = false>
 __device__ __forceinline__ void cov_body(const PreArgs &A, const CarryArgs &CA) {
     typedef CovDims<MODEL> D;
@@ -244,17 +248,24 @@ __device__ __forceinline__ void cov_body(const PreArgs &A, const CarryArgs &CA) 
                     if (A.out.P) {
                         double *p = A.out.P + r * 225 + jj * 15;
 #pragma unroll
-                        for (int i = 0; i < 15; i++) p[i] = Ln.P0[i];
+                        for (int i = 0; i < 15; i++) p[i] = (CARRY && cbad) ? __builtin_nan("") : Ln.P0[i];
                     }
                     if (A.out.P_sym) {
                         double *p = A.out.P_sym + r * CPI_TRI_DOUBLES + jj * (jj + 1) / 2;
 #pragma unroll
-                        for (int i = 0; i < 15; i++) if (i <= jj) p[i] = Ln.P0[i];
+                        for (int i = 0; i < 15; i++) if (i <= jj) p[i] = (CARRY && cbad) ? __builtin_nan("") : Ln.P0[i];
                     }
                 }
             }
         }
         wave_lds_fence();
+    }
+    if constexpr (RUNNING && CARRY) {   // the covariance state behind row N - 1 (N = 0: the carried one, passed through)
+        if (valid && jj < D::NCOL) {
+            double *co = CA.out + w * CD + CO + jj * D::NR;
+#pragma unroll
+            for (int i = 0; i < D::NR; i++) co[i] = cbad ? __builtin_nan("") : Ln.P0[i];
+        }
     }
     if constexpr (RUNNING) return;   // row N - 1 is the window's measurement
 
@@ -338,6 +349,13 @@ __global__ __launch_bounds__(64, CPI_COV_WPS) void cpi_cov_running_kernel(PreArg
     cov_body<MODEL, AVG, false, true>(A, CarryArgs());
 }
 
+// cpi_preintegrate_running_resume: cpi_cov_running_kernel from and to carry records
+template <int MODEL, bool AVG>
+__global__ __launch_bounds__(64, CPI_COV_WPS) void cpi_cov_running_carry_kernel(PreArgs A, CarryArgs C) {
+    cov_body<MODEL, AVG, true, true>(A, C);
+}
+
+#ifndef CPI_COV_TEMPLATES_ONLY   // (cpi_running_resume.hip takes the templates above only)
 // ============================================================================================
 // Forster / GTSAM discrete-preintegration comparator kernel (fsd:: in cpi_math.hpp)
 // ============================================================================================
@@ -501,5 +519,6 @@ __global__ __launch_bounds__(64, 2) void cpi_forster_kernel(PreArgs A) {
     }
 }
 
+#endif   // CPI_COV_TEMPLATES_ONLY
 
 }  // namespace

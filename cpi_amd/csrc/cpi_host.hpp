@@ -134,7 +134,7 @@ public:
         imu_avg = o.imu_avg; state_transition_jacobians = o.state_transition_jacobians;
         b_w_lin = o.b_w_lin; b_a_lin = o.b_a_lin; q_k_lin = o.q_k_lin; grav = o.grav;
         knots_ = o.knots_; model_ = o.model_; ctx_ = o.ctx_; dirty_ = o.dirty_; means_only_ = o.means_only_;
-        incremental_ = o.incremental_; carry_ = o.carry_;
+        incremental_ = o.incremental_; carry_ = o.carry_; fed_ = o.fed_;
         for (int i = 0; i < 4; i++) sig_[i] = o.sig_[i];
         put(o.peek());
         return *this;
@@ -186,6 +186,7 @@ public:
             push(t_0, w_m_0, a_m_0);
         }
         push(t_1, w_m_1, a_m_1);
+        if (incremental_) fed_.push_back((int32_t)(knots_.size() / 7 - 1));   // read_rows: this interval's closing knot
     }
     // Incremental mode (cpi_preintegrate_resume): a read runs only the intervals fed since the previous read, continuing
     // from the carried state, and keeps only the last knot -- O(1) per read instead of re-running the window.  Switch it on
@@ -197,6 +198,53 @@ public:
         incremental_ = on;
     }
     bool incremental() const { return incremental_; }
+    // Incremental preintegrators only: the members as they stood after EVERY feed_IMU since the previous read
+    // (cpi_preintegrate_running_resume_host) -- one CpiResult per fed interval, in order; a skipped interval (dt <= 0) repeats the
+    // entry before it, and the NaN separator knots feed_IMU places between intervals that do not chain produce no entry.  The
+    // carry and the tail knot advance exactly as in a member read, and the result members then equal the last entry.  Model 2: the
+    // entries hold no bias Jacobians (there is no running form of them); the members' Jacobians are read out of the carried
+    // state-transition columns by the next member read.
+    std::vector<CpiResult> read_rows(const Context &ctx) {
+        if (!incremental_) throw std::logic_error("read_rows: set_incremental(true) first (the rows continue from the carried state)");
+        if (model_ == CPI_MODEL_V2 && !state_transition_jacobians)
+            throw std::logic_error("read_rows: model 2's analytic Jacobians (state_transition_jacobians = false) have no running form");
+        std::vector<CpiResult> res;
+        if (fed_.empty()) return res;
+        cpi_params p = params();
+        const double lin[6] = { b_w_lin[0], b_w_lin[1], b_w_lin[2], b_a_lin[0], b_a_lin[1], b_a_lin[2] };
+        const int32_t n = (int32_t)(knots_.size() / 7 - 1);
+        const bool jac = model_ == CPI_MODEL_V1;
+        const size_t M = (size_t)n;
+        std::vector<double> DT_(M), al(M * 3), be(M * 3), q(M * 4), Jq(jac ? M * 9 : 0), Ja(jac ? M * 9 : 0), Jb(jac ? M * 9 : 0),
+            Ha(jac ? M * 9 : 0), Hb(jac ? M * 9 : 0), P(M * 225);
+        cpi_outputs o{};   // every running field, so that the carry holds every part a later read needs
+        o.DT = DT_.data(); o.alpha = al.data(); o.beta = be.data(); o.q = q.data(); o.P = P.data();
+        if (jac) { o.J_q = Jq.data(); o.J_a = Ja.data(); o.J_b = Jb.data(); o.H_a = Ha.data(); o.H_b = Hb.data(); }
+        std::vector<double> next(cpi_carry_doubles(model_));
+        ctx.check(cpi_preintegrate_running_resume_host(ctx.get(), &p, 1, n, knots_.data(), nullptr, nullptr, n + 1, lin, q_k_lin.data(),
+                                                       carry_.empty() ? nullptr : carry_.data(), next.data(), &o));
+        carry_.swap(next);
+        res.resize(fed_.size());
+        for (size_t e = 0; e < fed_.size(); e++) {
+            const size_t r = (size_t)fed_[e] - 1;
+            CpiResult &x = res[e];
+            x.DT = DT_[r];
+            for (int k = 0; k < 3; k++) { x.alpha_tau[k] = al[r * 3 + k]; x.beta_tau[k] = be[r * 3 + k]; }
+            for (int k = 0; k < 4; k++) x.q_k2tau[k] = q[r * 4 + k];
+            if (jac)
+                for (int k = 0; k < 9; k++) {
+                    x.J_q[k] = Jq[r * 9 + k]; x.J_a[k] = Ja[r * 9 + k]; x.J_b[k] = Jb[r * 9 + k];
+                    x.H_a[k] = Ha[r * 9 + k]; x.H_b[k] = Hb[r * 9 + k];
+                }
+            for (int k = 0; k < 225; k++) x.P_meas[k] = P[r * 225 + k];
+        }
+        knots_.erase(knots_.begin(), knots_.end() - 7);   // the next segment starts on this one's last knot
+        fed_.clear();
+        set_result(res.back());
+        if (!jac) dirty_ = true;                          // model 2: the next member read is a zero-interval resume (its Jacobians)
+        return res;
+    }
+    std::vector<CpiResult> read_rows() { return read_rows(ctx_ ? *ctx_ : default_context()); }
     // Runs this single window on the GPU and fills the result members (what a first read of any member does by itself).
     void finalize(const Context &ctx) {
         if (incremental_) { finalize_incremental(ctx); return; }
@@ -275,6 +323,7 @@ private:
                                                n + 1, lin, q_k_lin.data(), carry_.empty() ? nullptr : carry_.data(), next.data(), &o));
         carry_.swap(next);
         if (n > 0) knots_.erase(knots_.begin(), knots_.end() - 7);   // the next segment starts on this one's last knot
+        fed_.clear();
         set_result(r);
     }
     template <class T> friend class Lazy;
@@ -298,6 +347,7 @@ private:
     bool dirty_ = false;                         // intervals recorded since the result members were last computed
     bool means_only_ = false;                    // the last computation (CpiBatch::flush_means) filled the four means only
     bool incremental_ = false;                   // set_incremental
+    std::vector<int32_t> fed_;                   // incremental: per interval fed since the last read, the index of its closing knot
     std::vector<double> carry_;                  // incremental: the carry record of the intervals integrated so far
 };
 template <class T> inline void Lazy<T>::sync() const { owner_->ensure(!mean_); }

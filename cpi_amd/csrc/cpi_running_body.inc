@@ -1,7 +1,8 @@
 // cpi_running_body.inc -- the body of cpi_mean_running_kernel and cpi_mean_stream_running_kernel (cpi_running_kernels.hpp),
 // included inside both.  Shared as text rather than through a device function, as cpi_mean_body.inc is: the plain-knot kernel
 // compiles to exactly the code it had before the stream form existed.  In scope where it is included: MODEL, JAC, AVG, MULTI,
-// CUT (the windows are cut out of a stream in flight), the kernel arguments A (PreArgs) and L_arg.
+// CUT (the windows are cut out of a stream in flight), CARRY (cpi_mean_running_carry_kernel: the window continues from / is left
+// in a carry record), the kernel arguments A (PreArgs), CA (CarryArgs; read when CARRY only) and L_arg.
     static_assert(!(JAC && MODEL == 2), "model 2's Jacobians are read out of the state transition matrix");
     constexpr int T = CPI_RUN_T;
     constexpr int P1 = T | 1, P3 = (3 * T) | 1, P4 = (4 * T) | 1;   // odd pitches: a lane's slots start in distinct banks
@@ -57,6 +58,20 @@
 
     MeanState<JAC> st;
     mean_init(st);
+    // CARRY: lane 0 of the window -- the earliest rows -- starts from the record, in pass 1 (so that the scan hands every later
+    // lane carried o everything before it) and in the walk.  The record is read straight from memory where it is needed and
+    // never kept in a second set of registers: the Jacobian variant has 61 doubles of live state already.
+    constexpr int CD = carry::doubles(MODEL);
+    bool cbad = false;    // the record does not hold what this call continues: every row and the record left behind become NaN
+    bool chead = false;   // the window continues from a record
+    int owner = lane;     // the lane whose walked state is the window's final state (the state of row N - 1)
+    if constexpr (CARRY) {
+        if (CA.in) {
+            cbad = !carry_tag_ok(CA.in[w * CD + carry::TAG], CA.need);
+            chead = !cbad;
+            if (chead && l == 0) carry_load_mean<MODEL, JAC>(st, CA.in + w * CD, A.write_jac != 0);
+        }
+    }
     int lead = 0;        // leading rows of this lane before its first integrated interval (held back for the fix-up)
     int src = -1;        // the wavefront lane whose last row those rows repeat (-1: none -- the scanned state is exact)
     if constexpr (MULTI) {
@@ -118,7 +133,19 @@
         const unsigned long long below = moved & ((1ull << lane) - 1ull) & ~((1ull << (grp * L)) - 1ull);
         src = below ? 63 - __builtin_clzll(below) : -1;
         if (src < 0) lead = 0;
+        if constexpr (CARRY) {
+            // No earlier lane integrated anything: the state at this lane's first knot IS the carried one, and its leading no-op
+            // rows must show it bit for bit -- not `carried o identity o ...` as the scan composed it (mm() with the identity
+            // and x + 0 y are not exact copies for every input).  Lane 0 is always such a lane.
+            if (chead && src < 0) carry_load_mean<MODEL, JAC>(st, CA.in + w * CD, A.write_jac != 0);
+            // Row N - 1 repeats the last row of the window's last lane that integrated anything, so that lane's walked state is
+            // what carry_out must hold (the scanned total differs from it in the last bits); none: lane 0 holds the carried /
+            // zero state untouched.  With per = ceil(N / L) trailing lanes may own no row at all: they never count as moved.
+            const unsigned long long mine = moved & ((L >= 64 ? ~0ull : ((1ull << L) - 1ull)) << (grp * L));
+            owner = mine ? 63 - __builtin_clzll(mine) : grp * L;
+        }
     }
+    if constexpr (CARRY) { if (cbad) mean_poison(st); }
 
     s_rowbase[lane] = w * (long long)A.N + r0;
     s_lo[lane] = lead;
@@ -177,6 +204,9 @@
 #pragma unroll
                 for (int i = 0; i < 7; i++) pk[i] = q[i];
                 last.DT = st.DT; last.alpha = st.alpha; last.beta = st.beta; last.q = rot_2_quat(st.R);
+                if constexpr (CARRY) {   // (rot_2_quat of a NaN matrix is not all NaN)
+                    if (cbad) last.q.x = last.q.y = last.q.z = last.q.w = __builtin_nan("");
+                }
                 if (wm) stage(tt, last);
                 if constexpr (JAC) {
                     if (A.write_jac && t >= lead && t < nrows) store_jac(row0 + t, st);
@@ -184,6 +214,12 @@
             }
             if (wm) flush(tb);
         }
+    }
+
+    // ---- the record the window is left in: the walked state of the lane that owns the state of row N - 1
+    if constexpr (CARRY) {
+        if (valid && lane == owner)
+            carry_store_mean<MODEL, JAC>(CA.out + w * CD, st, true, cbad ? __builtin_nan("") : (double)CA.tag_out);
     }
 
     // ---- the fix-up: held-back rows repeat the last row of lane `src`

@@ -107,6 +107,8 @@ struct RunRow {
 template <int MODEL, bool JAC, bool AVG, bool MULTI>
 __global__ __launch_bounds__(64) void cpi_mean_running_kernel(PreArgs A, int L_arg) {
     constexpr bool CUT = false;
+    constexpr bool CARRY = false;
+    const CarryArgs CA = CarryArgs();
 #include "cpi_running_body.inc"
 }
 
@@ -116,6 +118,19 @@ __global__ __launch_bounds__(64) void cpi_mean_running_kernel(PreArgs A, int L_a
 template <int MODEL, bool JAC, bool AVG, bool MULTI>
 __global__ __launch_bounds__(64) void cpi_mean_stream_running_kernel(PreArgs A, int L_arg) {
     constexpr bool CUT = true;
+    constexpr bool CARRY = false;
+    const CarryArgs CA = CarryArgs();
+#include "cpi_running_body.inc"
+}
+
+// cpi_preintegrate_running_resume: cpi_mean_running_kernel from and to carry records (cpi_args.hpp: CarryArgs; this kernel always
+// owns the tag, the means and -- JAC -- the Jacobian block of carry_out).  Lane 0 starts from the record instead of the zero state;
+// a lane before which nothing was integrated shows the carried state itself; the record is stored from the walked state of the
+// lane whose last row is row N - 1.  Again a kernel of its own name over the shared body.
+template <int MODEL, bool JAC, bool AVG, bool MULTI>
+__global__ __launch_bounds__(64) void cpi_mean_running_carry_kernel(PreArgs A, CarryArgs CA, int L_arg) {
+    constexpr bool CUT = false;
+    constexpr bool CARRY = true;
 #include "cpi_running_body.inc"
 }
 

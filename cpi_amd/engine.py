@@ -282,6 +282,64 @@ class Engine:
                                                            _ptr(lin), _ptr(q_k_lin), C.byref(o)))
         return out
 
+    def preintegrate_running_resume(self, knots, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), first=None,
+                                    count=None, N=None, carry_in=None, carry_out=None, packed=False, out=None):
+        """cpi_preintegrate_running_resume: the rows of preintegrate_running for windows that continue from carry_in
+        ([W, carry_doubles] float64 CUDA tensor, None = the zero state) over these knots.  Returns (rows, carry_out): rows as
+        preintegrate_running returns them ([W, N, ...] views; entry [w, i] is the measurement of everything the record stands
+        for plus intervals 0 .. i of this segment), carry_out (allocated when not given, never carry_in itself) as
+        preintegrate_resume returns it -- the state of row N - 1.  The records of the two resume entries are interchangeable.
+        Models 1 and 2; Jacobians for model 1 only (the default want drops them for model 2).  Asynchronous."""
+        params = params or self.make_params()
+        if first is None:
+            W, n1, seven = knots.shape
+            N = n1 - 1
+        else:
+            W = first.shape[0]
+            assert N is not None, "ragged layout needs N = max intervals per window"
+        for t in (knots, lin, q_k_lin, first, count, carry_in, carry_out):
+            assert t is None or (t.is_cuda and t.is_contiguous()), "inputs must be contiguous CUDA tensors"
+        assert knots.dtype == torch.float64 and lin.dtype == torch.float64
+        cd = self.carry_doubles(params.model)
+        if carry_out is None and cd > 0:
+            carry_out = torch.empty((W, cd), dtype=torch.float64, device=self.device)
+        for t in (carry_in, carry_out):
+            assert t is None or (t.dtype == torch.float64 and t.numel() >= W * cd), "carry records are [W, carry_doubles] float64"
+        if out is None:
+            out = self._running_views(self.alloc_outputs(W * N, self._running_want(tuple(want), params.model), params.model, packed), W, N)
+        o = self._outputs_struct({k: v for k, v in out.items() if not k.startswith("_")})
+        self._sync_stream()
+        self._check(self.lib.cpi_preintegrate_running_resume(self.ctx, C.byref(params), W, N, _ptr(knots), _ptr(first), _ptr(count),
+                                                             _ptr(lin), _ptr(q_k_lin), _ptr(carry_in), _ptr(carry_out), C.byref(o)))
+        return out, carry_out
+
+    def preintegrate_running_resume_host(self, knots, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), count=None,
+                                         carry_in=None, carry_out=None, pinned=True, out=None):
+        """preintegrate_running_resume for a dense batch held in HOST memory (CPU float64 tensors, the records included):
+        cpi_preintegrate_running_resume_host.  Returns (rows, carry_out) as CPU tensors; synchronous."""
+        params = params or self.make_params()
+        W, n1, _ = knots.shape
+        N = n1 - 1
+        for t in (knots, lin, q_k_lin, count, carry_in, carry_out):
+            assert t is None or (not t.is_cuda and t.is_contiguous()), "inputs must be contiguous CPU tensors"
+        assert knots.dtype == torch.float64 and lin.dtype == torch.float64 and (count is None or count.dtype == torch.int32)
+        cd = self.carry_doubles(params.model)
+        if carry_out is None and cd > 0:
+            carry_out = torch.empty((W, cd), dtype=torch.float64, pin_memory=pinned)
+        for t in (carry_in, carry_out):
+            assert t is None or (t.dtype == torch.float64 and t.numel() >= W * cd), "carry records are [W, carry_doubles] float64"
+        if out is None:
+            out = {}
+            groups = self._running_want(tuple(want), params.model)
+            for name, n in OUT_FIELDS:
+                if _group_of(name) in groups and (params.model == 2 or name not in ("O_a", "O_b")):
+                    out[name] = torch.empty((W, N) if n == 1 else (W, N, n), dtype=torch.float64, pin_memory=pinned)
+        o = self._outputs_struct(out)
+        self._sync_stream()
+        self._check(self.lib.cpi_preintegrate_running_resume_host(self.ctx, C.byref(params), W, N, _ptr(knots), None, _ptr(count), 0,
+                                                                  _ptr(lin), _ptr(q_k_lin), _ptr(carry_in), _ptr(carry_out), C.byref(o)))
+        return out, carry_out
+
     def preintegrate_host(self, knots, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), count=None, pinned=True, out=None):
         """Dense batch held in HOST memory (CPU float64 tensors; pinned ones overlap upload / kernels / download):
         cpi_preintegrate_batch_host.  Returns a dict of CPU tensors (page-locked when pinned=True; out= re-uses the
@@ -910,8 +968,8 @@ class _CpiBase:
                          z if a_m_1 is None else np.asarray(a_m_1, float).reshape(3)))
         self._res = None
 
-    def _knots(self):
-        """Intervals -> knot records.  Consecutive intervals that chain (t1 == next t0 and the next
+    def _knots(self, closing=None):
+        """Intervals -> knot records (closing: a list that receives, per fed interval, the index of its closing knot).  Consecutive intervals that chain (t1 == next t0 and the next
         reading equals this interval's w1/a1) share a knot.  The reference's feed_IMU only ever uses
         t1 - t0, so intervals need not chain: a knot whose time is NaN acts as a separator (both
         intervals touching it have a NaN dt and are skipped by the kernels)."""
@@ -927,6 +985,8 @@ class _CpiBase:
                     rows.append(np.concatenate([[np.nan], np.zeros(6)]))
                 rows.append(np.concatenate([[t0], w0, a0]))
             rows.append(np.concatenate([[t1], w1, a1]))
+            if closing is not None:
+                closing.append(len(rows) - 1)
         return np.stack(rows) if rows else np.zeros((1, 7))
 
     def _run(self):
@@ -951,6 +1011,38 @@ class _CpiBase:
         eng.synchronize()
         self._res = {k: v.cpu().numpy()[0] for k, v in out.items()}
         return self._res
+
+    def read_rows(self):
+        """Incremental preintegrators only: run the intervals fed since the previous read through
+        Engine.preintegrate_running_resume and return one result dict per interval fed since then -- the members as they
+        stand after that feed_IMU (a skipped interval repeats the entry before it; the separator knots _knots() inserts
+        produce no entry).  The carry and the tail knot advance as in a member read, and the ordinary members (alpha_tau,
+        P_meas, ...) then equal the last entry.  Model 2: no Jacobians in the entries (read J_q ... from the members)."""
+        if not self._incremental:
+            raise RuntimeError("read_rows: set_incremental(True) first (the rows continue from the carried state)")
+        if self._model == 3:
+            raise ValueError("read_rows: the Forster comparator has no running form")
+        if self._model == 2 and not self.state_transition_jacobians:
+            raise ValueError("read_rows: model 2's analytic Jacobians (state_transition_jacobians = False) have no running form")
+        if not self._iv:
+            return []
+        eng = self._engine or default_engine()
+        closing = []
+        kn = self._knots(closing)
+        dev = eng.device
+        knots = torch.from_numpy(kn[None]).to(dev)
+        lin = torch.from_numpy(np.concatenate([self.b_w_lin, self.b_a_lin])[None]).to(dev)
+        q = torch.from_numpy(self.q_k_lin[None]).to(dev)
+        prm = eng.make_params(self._model, self.imu_avg, self.state_transition_jacobians, self._sig, tuple(self.grav))
+        # every running field, so that the carry holds every part a later read (of rows or of members) needs
+        rows, self._carry = eng.preintegrate_running_resume(knots, lin, q, prm, carry_in=self._carry)
+        eng.synchronize()
+        self._tail, self._iv = kn[-1], []
+        host = {k: v.cpu().numpy()[0] for k, v in rows.items()}
+        res = [{k: v[c - 1] for k, v in host.items()} for c in closing]
+        # model 2: the members' Jacobians are read out of the carried state-transition columns by a zero-interval resume
+        self._res = res[-1] if self._model == 1 else None
+        return res
 
     def _m3(self, name):
         return self._run()[name].reshape(3, 3).T  # column-major -> [row][col]

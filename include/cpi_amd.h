@@ -53,7 +53,9 @@ extern "C" {
                                cpi_preintegrate_running, cpi_preintegrate_running_host (the measurement after every interval);
                                cpi_preintegrate_stream_running, cpi_preintegrate_streams_running,
                                cpi_preintegrate_stream_running_host, cpi_preintegrate_streams_running_host (the running rows
-                               from IMU stream(s), windows cut in place) */
+                               from IMU stream(s), windows cut in place); cpi_preintegrate_running_resume,
+                               cpi_preintegrate_running_resume_host (the running rows of a window that continues from a
+                               carry record) */
 
 enum { CPI_OK = 0, CPI_ERR_INVALID = 1, CPI_ERR_HIP = 2, CPI_ERR_NO_DEVICE = 3, CPI_ERR_RCCL = 4 };
 enum {
@@ -209,10 +211,53 @@ int cpi_preintegrate_resume(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int3
  * cpi_preintegrate_batch.  No host synchronisation and a single stream: the call can be captured into a graph.
  * Composition: with F = W * N and idx_i[row] = row / N, cpi_predict_batch turns the rows into IMU-rate predicted states.
  * Running rows from IMU stream(s), windows cut in place: cpi_preintegrate_stream_running / cpi_preintegrate_streams_running below.
- * Not provided: running rows from a carry record. */
+ * Running rows of a window that is still open (from and to a carry record): cpi_preintegrate_running_resume below. */
 int cpi_preintegrate_running(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                              const double *knots, const int64_t *first, const int32_t *count,
                              const double *lin, const double *q_k_lin, const cpi_outputs *rows);
+
+/* Running preintegration from a carry record -- IMU-rate rows for windows that are still open: the IMU readings arrive in
+ * chunks, every call integrates the new intervals only, writes one row per new interval and hands the state back.  The union of
+ * the two contracts above, nothing else:
+ *   - knots / first / count / N / lin / q_k_lin, dense and ragged layouts, dt <= 0, NaN-stamp separators, clamping of count into
+ *     [0, N], models 1 and 2, imu_avg 0 / 1, lanes_per_window (0 = the choice cpi_preintegrate_running makes), N <= 65535 and
+ *     the 32-bit grid limit on W: as cpi_preintegrate_running;
+ *   - carry_in (NULL = the zero state), carry_out (required, must not overlap carry_in: both kernels read carry_in and write
+ *     disjoint parts of carry_out), the record layout, the tag rules and what must stay the same along a chain: as
+ *     cpi_preintegrate_resume.  Consecutive segments share their boundary knot.
+ *   - rows holds W * N rows, 64-bit offsets.  Row w * N + i is the measurement of ALL intervals integrated so far: those the
+ *     record stands for plus intervals 0 .. i of this segment.
+ *   - a skipped interval repeats the previous row bit for bit.  The "previous row" of row 0 is the CARRIED state read out as a
+ *     row: DT, alpha, beta of the record, q = rot_2_quat(R) of the record's rotation, the record's five Jacobians (model 1), P /
+ *     P_sym read out of the record's covariance state as the running kernel reads out a row.  With carry_in == NULL that is the
+ *     zero-state row of cpi_preintegrate_running.  Rows i >= count[w] repeat the final state, so row w * N + N - 1 is always the
+ *     state carry_out holds; count = 0 gives N copies of the carried row and passes the state through.
+ *   - carry_out describes exactly the state of row N - 1: its DT / alpha / beta are bit for bit that row's, rot_2_quat of its R
+ *     is bit for bit that row's q, its Jacobians (model 1, when computed) are that row's, and the P read out of its covariance
+ *     state is that row's P.  An all-skipped segment fed with this record therefore reproduces the last row of the call that
+ *     wrote it: "repeats the previous row" holds across calls.
+ *   - requests: means for both models, the five analytic bias Jacobians for model 1, P and / or P_sym for both models.  Any
+ *     Jacobian field with model 2, and CPI_MODEL_FORSTER, return CPI_ERR_INVALID.  Every pointer of rows may be NULL: nothing is
+ *     written to rows, carry_out still receives the means.
+ *   - tags: the call needs, and leaves, header | covariance state (P or P_sym wanted) | analytic Jacobians (model-1 Jacobian
+ *     rows wanted) -- the rule of cpi_preintegrate_resume.  The records of the two resume entries are interchangeable in both
+ *     directions, so a chain may mix them: running rows while the window is open, and one final cpi_preintegrate_resume on a
+ *     segment of 0 intervals to read model 2's Jacobians out of the carried state-transition columns (the chain must then have
+ *     asked for P or P_sym throughout, and state_transition_jacobians must be set).
+ *   - a window whose carry_in tag lacks a needed part or differs in model / imu_avg / state_transition_jacobians gets NaN in ALL
+ *     N rows of every requested field (all four components of q) and a NaN tag in carry_out; the other windows are unaffected.
+ *   - W == 0 is a no-op.  N == 0 writes no rows and passes every window's state through to carry_out (the zero state for a
+ *     NULL carry_in): a caller never holds an undefined record.
+ *   - the kernels run one after the other on the context's stream: no side stream, no host synchronisation; a capture of the
+ *     call is a chain without parallel branches.
+ *   - with carry_in == NULL the rows are bit for bit those of cpi_preintegrate_running on the same arguments, for every model,
+ *     request and lanes_per_window.
+ * Not provided: running Jacobian rows for model 2; running rows from a carry record for the STREAM entries
+ * (cpi_preintegrate_stream[s]_running); the Forster comparator. */
+int cpi_preintegrate_running_resume(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                    const double *knots, const int64_t *first, const int32_t *count,
+                                    const double *lin, const double *q_k_lin,
+                                    const double *carry_in, double *carry_out, const cpi_outputs *rows);
 
 /* Replaces: the whole caller side of GraphSolver::createimufactor_cpi_v1 / _v2 (GraphSolver_IMU.cpp:43-75, 97-130) for every
  * window of a trajectory at once, reading ONE IMU stream IN PLACE: no knot is copied, for any model and any output.
@@ -505,6 +550,13 @@ int cpi_preintegrate_running_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W
                                   const double *knots, const int64_t *first, const int32_t *count,
                                   int64_t n_knots, const double *lin, const double *q_k_lin,
                                   const cpi_outputs *rows);
+/* cpi_preintegrate_running_resume from host memory: every pointer a host pointer, n_knots as in cpi_preintegrate_batch_host.  Dense
+ * batches run through the chunked pipeline of cpi_preintegrate_running_host (the records of a chunk go up and come down with
+ * it; the rows and records do not depend on the chunking), ragged ones are staged whole. */
+int cpi_preintegrate_running_resume_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                         const double *knots, const int64_t *first, const int32_t *count,
+                                         int64_t n_knots, const double *lin, const double *q_k_lin,
+                                         const double *carry_in, double *carry_out, const cpi_outputs *rows);
 /* cpi_preintegrate_resume from host memory: every pointer a host pointer, n_knots as in cpi_preintegrate_batch_host. */
 int cpi_preintegrate_resume_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                                  const double *knots, const int64_t *first, const int32_t *count,
