@@ -38,6 +38,12 @@ using namespace cpi;
 
 constexpr int kOutFields = 13;   // fields of cpi_outputs (ABI 3: P_sym is the 13th)
 static_assert(sizeof(cpi_outputs) == kOutFields * sizeof(double *), "cpi_outputs is a plain table of kOutFields pointers");
+static const int OUT_N[kOutFields] = { 1, 3, 3, 4, 9, 9, 9, 9, 9, 9, 9, 225, CPI_TRI_DOUBLES };
+static double **out_field(cpi_outputs *o, int k) {
+    double **f[kOutFields] = { &o->DT, &o->alpha, &o->beta, &o->q, &o->J_q, &o->J_a, &o->J_b, &o->H_a, &o->H_b, &o->O_a, &o->O_b, &o->P, &o->P_sym };
+    return f[k];
+}
+static double *out_field_c(const cpi_outputs *o, int k) { cpi_outputs t = *o; return *out_field(&t, k); }
 
 // ============================================================================================
 // contexts
@@ -211,13 +217,112 @@ static PreArgs shift_windows(const PreArgs &a, long long w0) {
     if (a.count) t.count = a.count + w0;
     t.lin = a.lin + w0 * 6;
     if (a.qk) t.qk = a.qk + w0 * 4;
-    static const int n[kOutFields] = { 1, 3, 3, 4, 9, 9, 9, 9, 9, 9, 9, 225, 120 };
-    double **f[kOutFields] = { &t.out.DT, &t.out.alpha, &t.out.beta, &t.out.q, &t.out.J_q, &t.out.J_a, &t.out.J_b, &t.out.H_a,
-                               &t.out.H_b, &t.out.O_a, &t.out.O_b, &t.out.P, &t.out.P_sym };
-    for (int k = 0; k < kOutFields; k++) if (*f[k]) *f[k] += w0 * n[k];
+    for (int k = 0; k < kOutFields; k++) { double **f = out_field(&t.out, k); if (*f) *f += w0 * OUT_N[k]; }
     return t;
 }
 #endif
+
+// ---- what the preintegration entries share: the request, the kernel argument block, the refusals ---------------------------
+// Which groups of fields a cpi_outputs asks for (O_a / O_b count as Jacobians for every model).
+struct Request {
+    bool mean, jac, cov;
+    bool any() const { return mean || jac || cov; }
+};
+static Request request_of(const cpi_outputs *o) {
+    return { o->DT || o->alpha || o->beta || o->q,
+             o->J_q || o->J_a || o->J_b || o->H_a || o->H_b || o->O_a || o->O_b,
+             o->P != nullptr || o->P_sym != nullptr };
+}
+static PreArgs pre_args(const cpi_params *prm, int64_t W, int32_t N, const double *knots, const int64_t *first, const int32_t *count,
+                        const double *lin, const double *q_k_lin, const cpi_outputs *out) {
+    PreArgs a;
+    memset(&a, 0, sizeof a);
+    a.W = W; a.N = N; a.knots = knots; a.first = (const long long *)first; a.count = count;
+    a.lin = lin; a.qk = q_k_lin;
+    for (int i = 0; i < 3; i++) a.grav[i] = prm->grav[i];
+    a.q4[0] = prm->sigma_w * prm->sigma_w; a.q4[1] = prm->sigma_wb * prm->sigma_wb;
+    a.q4[2] = prm->sigma_a * prm->sigma_a; a.q4[3] = prm->sigma_ab * prm->sigma_ab;
+    a.out = *out;
+    return a;
+}
+
+// A refusal is "<entry>: <what>".  The text is put together on the failing path only: a call that succeeds builds no string.
+static int refuse(cpi_ctx *ctx, const char *who, const char *what, const char *more = "") {
+    return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": " + what + more);
+}
+#define CPI_TRY(call)                          \
+    do {                                       \
+        const int rc_ = (call);                \
+        if (rc_ != CPI_OK) return rc_;         \
+    } while (0)
+
+static bool model_is_cpi(const cpi_params *prm) { return prm->model == CPI_MODEL_V1 || prm->model == CPI_MODEL_V2; }
+// what the Forster comparator lacks for an entry that serves models 1 and 2 only
+enum { NO_RUNNING_FORM = 1, NOT_RESUMABLE = 2 };
+static int refuse_forster(cpi_ctx *ctx, const char *who, int lacks) {
+    const std::string why = std::string(lacks & NO_RUNNING_FORM ? "has no running form" : "") + (lacks == (NO_RUNNING_FORM | NOT_RESUMABLE) ? " and " : "") +
+                            (lacks & NOT_RESUMABLE ? "cannot be resumed" : "");
+    return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": model must be 1 or 2 (the Forster comparator " + why + ")");
+}
+// model 2 has no running Jacobian rows.  advice: what follows the reason inside its parentheses; NULL: no reason given
+static int refuse_v2_jac(cpi_ctx *ctx, const char *who, const char *advice) {
+    std::string msg = std::string(who) + ": the Jacobian fields (J_q ... O_b) are not available for model 2";
+    if (advice) msg = msg + " (they are read out of the state transition matrix at the end of the recursion" + advice + ")";
+    return fail(ctx, CPI_ERR_INVALID, msg);
+}
+static int check_qk(cpi_ctx *ctx, const char *who, const cpi_params *prm, const void *q_k_lin) {
+    return (prm->model == CPI_MODEL_V2 && !q_k_lin) ? refuse(ctx, who, "model 2 needs q_k_lin") : CPI_OK;
+}
+static int check_N(cpi_ctx *ctx, const char *who, int32_t N) {
+    return N > 65535 ? refuse(ctx, who, "N (intervals per window) must be <= 65535") : CPI_OK;
+}
+// dim: "W" or "U", the entry's name for its number of windows
+static int check_grid(cpi_ctx *ctx, const char *who, const char *dim, int64_t n, const char *note = "") {
+    return grid_ok(n) ? CPI_OK : fail(ctx, CPI_ERR_INVALID, std::string(who) + ": " + dim + " exceeds 2^31 - 1 windows per call" + note);
+}
+static int check_lanes(cpi_ctx *ctx, const cpi_params *prm) {
+    const int L = prm->lanes_per_window;
+    return (L != 0 && !launch::mean_lanes_supported(L)) ? fail(ctx, CPI_ERR_INVALID, "lanes_per_window must be 0 or one of 1,2,3,4,5,6,8,12,16,32,64") : CPI_OK;
+}
+// what the entries over W windows of <= N intervals refuse alike once their no-op returns are behind them
+static int check_windows(cpi_ctx *ctx, const char *who, const cpi_params *prm, int64_t W, int32_t N, const double *knots,
+                         const double *lin, const double *q_k_lin) {
+    if (!knots || !lin) return refuse(ctx, who, "knots/lin is NULL");
+    CPI_TRY(check_qk(ctx, who, prm, q_k_lin));
+    CPI_TRY(check_grid(ctx, who, "W", W, " (32-bit grid)"));
+    CPI_TRY(check_N(ctx, who, N));
+    return check_lanes(ctx, prm);
+}
+// Carry records.  The kernels of a resume call all read carry_in while they write their parts of carry_out, so the two may
+// not overlap; the header of a record's tag names what it was computed with (the records of the two resume entries are
+// interchangeable).
+static int check_carry_overlap(cpi_ctx *ctx, const char *who, const cpi_params *prm, int64_t W, const double *carry_in, const double *carry_out) {
+    const int64_t n = W * (int64_t)carry::doubles(prm->model);
+    return (carry_in && carry_in < carry_out + n && carry_out < carry_in + n) ? refuse(ctx, who, "carry_in and carry_out overlap") : CPI_OK;
+}
+static int carry_header(const cpi_params *prm) {
+    const bool stj = prm->model == CPI_MODEL_V2 && prm->state_transition_jacobians != 0;
+    return 1 | (prm->imu_avg != 0 ? 8 : 0) | (stj ? 16 : 0) | (32 * prm->model);
+}
+
+// Two INDEPENDENT kernels over the same knots (disjoint outputs) share the SIMDs when the second is issued on the context's side
+// stream: fork / join by events, so everything later on the context's stream still waits for both, and a stream capture sees an
+// ordinary fork.  side_fork returns with ctx->side ordered behind the context's stream; side_join orders the stream behind it.
+static int side_fork(cpi_ctx *ctx) {
+    if (!ctx->side) {
+        CPI_HIP(ctx, hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
+        CPI_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
+        CPI_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
+    }
+    CPI_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
+    CPI_HIP(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
+    return CPI_OK;
+}
+static int side_join(cpi_ctx *ctx) {
+    CPI_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->side));
+    CPI_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+    return CPI_OK;
+}
 
 // cpi_preintegrate_stream: knots = ONE stream of K readings cut at update[W]; the workspace arrays are filled by
 // cpi_cut_windows_kernel when a kernel that reads them runs (covariance / Forster / analytic-Jacobian kernels), and stay
@@ -230,34 +335,25 @@ struct StreamCut {
     double *tstart, *tend;
     const RunArgs *runs;   // cpi_preintegrate_streams: the windows of many runs (NULL: one stream)
 };
-static int preintegrate_impl(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N, const double *knots, const int64_t *first,
-                             const int32_t *count, const StreamCut *sc, const double *lin,
-                             const double *q_k_lin, const cpi_outputs *out);
-extern "C" int cpi_preintegrate_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
-                                      const double *knots, const int64_t *first, const int32_t *count,
-                                      const double *lin, const double *q_k_lin, const cpi_outputs *out) {
-    return preintegrate_impl(ctx, prm, W, N, knots, first, count, nullptr, lin, q_k_lin, out);
+static int cut_launch(cpi_ctx *ctx, const StreamCut &sc, const double *stream, int64_t U, int32_t N) {
+    if (sc.runs) launch::cut_runs(sc.K, stream, (long long)U, sc.update, *sc.runs, sc.first, sc.count, sc.tstart, sc.tend, ctx->stream);
+    else launch::cut_windows(sc.K, stream, (long long)U, sc.update, (int)N, sc.first, sc.count, sc.tstart, sc.tend, ctx->stream);
+    CPI_HIP(ctx, hipGetLastError());
+    return CPI_OK;
 }
-static int preintegrate_impl(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N, const double *knots, const int64_t *first,
-                             const int32_t *count, const StreamCut *sc, const double *lin,
+// who: the entry that is called (the batch entry, or a stream entry whose own checks are behind it).  Everything is refused
+// before the cut kernel is enqueued: an invalid call must not leave a launch behind that writes the caller's workspace.
+static int preintegrate_impl(cpi_ctx *ctx, const char *who, const cpi_params *prm, int64_t W, int32_t N, const double *knots,
+                             const int64_t *first, const int32_t *count, const StreamCut *sc, const double *lin,
                              const double *q_k_lin, const cpi_outputs *out) {
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
-    if (!prm || !out) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_batch: prm/out is NULL");
-    if (prm->model != CPI_MODEL_V1 && prm->model != CPI_MODEL_V2 && prm->model != CPI_MODEL_FORSTER)
-        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_batch: model must be 1, 2 or 3 (CPI_MODEL_FORSTER)");
-    if (W < 0 || N < 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_batch: negative size");
+    if (!prm || !out) return refuse(ctx, who, "prm/out is NULL");
+    if (!model_is_cpi(prm) && prm->model != CPI_MODEL_FORSTER) return refuse(ctx, who, "model must be 1, 2 or 3 (CPI_MODEL_FORSTER)");
+    if (W < 0 || N < 0) return refuse(ctx, who, "negative size");
     if (W == 0) return CPI_OK;
-    if (!knots || !lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_batch: knots/lin is NULL");
-    if (prm->model == CPI_MODEL_V2 && !q_k_lin)
-        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_batch: model 2 needs q_k_lin");
-    if (!grid_ok(W)) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_batch: W exceeds 2^31 - 1 windows per call (32-bit grid)");
-    if (N > 65535) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_batch: N (intervals per window) must be <= 65535");
-    int L = prm->lanes_per_window;
-    if (L != 0 && !launch::mean_lanes_supported(L)) return fail(ctx, CPI_ERR_INVALID, "lanes_per_window must be 0 or one of 1,2,3,4,5,6,8,12,16,32,64");
+    CPI_TRY(check_windows(ctx, who, prm, W, N, knots, lin, q_k_lin));
 
-    const bool want_mean = out->DT || out->alpha || out->beta || out->q;
-    const bool want_jac = out->J_q || out->J_a || out->J_b || out->H_a || out->H_b || out->O_a || out->O_b;
-    const bool want_cov = out->P != nullptr || out->P_sym != nullptr;
+    const Request rq = request_of(out);
     const bool forster = prm->model == CPI_MODEL_FORSTER;
     const bool avg = prm->imu_avg != 0;
     const bool v2 = prm->model == CPI_MODEL_V2;
@@ -267,14 +363,13 @@ static int preintegrate_impl(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int
     //                       Discrete_J_b; it also carries the means, so it writes them when it runs.
     //   mean kernel       : means when no covariance kernel runs; the ANALYTIC Jacobians (model 1 always,
     //                       model 2 when state_transition_jacobians == 0).
-    const bool anything = want_mean || want_jac || want_cov;
-    const bool run_cov = !forster && (want_cov || (stj && want_jac));
-    const bool mean_jac = !forster && want_jac && !stj;
-    const bool run_mean = !forster && (mean_jac || (want_mean && !run_cov));
+    const bool run_cov = !forster && (rq.cov || (stj && rq.jac));
+    const bool mean_jac = !forster && rq.jac && !stj;
+    const bool run_mean = !forster && (mean_jac || (rq.mean && !run_cov));
     // A stream: the mean-only kernel cuts its own windows (fused; it still leaves the TRUE counts in the workspace); every
     // other kernel reads the cut that cpi_cut_windows_kernel leaves there.  Nothing asked for: the counts are still owed.
     // (many runs: the kernel handles runs of any length itself -- the host cannot see them)
-    bool fused_cut = sc && anything && run_mean && !mean_jac && !run_cov && (sc->runs != nullptr || sc->K >= 4);
+    bool fused_cut = sc && rq.any() && run_mean && !mean_jac && !run_cov && (sc->runs != nullptr || sc->K >= 4);
 #ifdef CPI_EXPERIMENTS
     if (expsw::no_fused_cut()) fused_cut = false;
 #endif
@@ -282,57 +377,36 @@ static int preintegrate_impl(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int
     DeviceGuard guard_;
     CPI_HIP(ctx, guard_.enter(ctx->device));
     if (sc && !fused_cut) {
-        if (sc->runs) launch::cut_runs(sc->K, knots, (long long)W, sc->update, *sc->runs, sc->first, sc->count, sc->tstart, sc->tend, ctx->stream);
-        else launch::cut_windows(sc->K, knots, (long long)W, sc->update, (int)N, sc->first, sc->count, sc->tstart, sc->tend, ctx->stream);
-        CPI_HIP(ctx, hipGetLastError());
+        CPI_TRY(cut_launch(ctx, *sc, knots, W, N));
         first = reinterpret_cast<const int64_t *>(sc->first); count = sc->count;
     }
-    if (!anything) return CPI_OK;
-    PreArgs a;
-    memset(&a, 0, sizeof a);
-    a.W = W; a.N = N; a.knots = knots; a.first = (const long long *)first; a.count = count;
-    a.lin = lin; a.qk = q_k_lin;
+    if (!rq.any()) return CPI_OK;
+    PreArgs a = pre_args(prm, W, N, knots, first, count, lin, q_k_lin, out);
     if (sc) { a.K = sc->K; if (!fused_cut) { a.tstart = sc->tstart; a.tend = sc->tend; } }
-    for (int i = 0; i < 3; i++) a.grav[i] = prm->grav[i];
-    a.q4[0] = prm->sigma_w * prm->sigma_w; a.q4[1] = prm->sigma_wb * prm->sigma_wb;
-    a.q4[2] = prm->sigma_a * prm->sigma_a; a.q4[3] = prm->sigma_ab * prm->sigma_ab;
-    a.out = *out;
     if (forster) {   // one kernel owns everything; imu_avg, q_k_lin, grav play no part
         launch::forster(a, ctx->stream);
         CPI_HIP(ctx, hipGetLastError());
         return CPI_OK;
     }
 
-    // Model 1 with Jacobians AND covariance is two independent kernels over the same knots (disjoint outputs).  The
-    // covariance kernel waits on the LDS pipe about as much as it issues VALU work and uses no more than two wavefronts per
-    // SIMD; the Jacobian kernel is pure FP64 VALU with no LDS: issued on a side stream (fork / join by events, so everything
-    // later on the context's stream still waits for both, and a stream capture sees an ordinary fork) they share the SIMDs.
-    bool overlap_on = true;
+    // Model 1 with Jacobians AND covariance is two independent kernels (side_fork).  The covariance kernel waits on the LDS pipe
+    // about as much as it issues VALU work and uses no more than two wavefronts per SIMD; the Jacobian kernel is pure FP64 VALU
+    // with no LDS.
+    bool forked = run_cov && run_mean && mean_jac;
 #ifdef CPI_EXPERIMENTS
-    overlap_on = !expsw::no_overlap();
+    forked = forked && !expsw::no_overlap();
 #endif
-    hipStream_t mean_stream = ctx->stream;
-    bool forked = false;
-    if (run_cov && run_mean && mean_jac && overlap_on) {
-        if (!ctx->side) {
-            CPI_HIP(ctx, hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
-            CPI_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-            CPI_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-        }
-        CPI_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-        CPI_HIP(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
-        mean_stream = ctx->side;
-        forked = true;
-    }
+    if (forked) CPI_TRY(side_fork(ctx));
+    const hipStream_t mean_stream = forked ? ctx->side : ctx->stream;
     if (run_cov) {
         PreArgs c = a;
-        c.write_means = want_mean ? 1 : 0;
-        c.write_jac = (stj && want_jac) ? 1 : 0;
+        c.write_means = rq.mean ? 1 : 0;
+        c.write_jac = (stj && rq.jac) ? 1 : 0;
         launch::cov(prm->model, avg, c, ctx->stream);
     }
     if (run_mean) {
         PreArgs m = a;
-        m.write_means = (want_mean && !run_cov) ? 1 : 0;
+        m.write_means = (rq.mean && !run_cov) ? 1 : 0;
         m.write_jac = mean_jac ? 1 : 0;
         if (fused_cut) { m.update = sc->update; m.count_out = sc->count; m.first = nullptr; m.count = nullptr; }
         const int LL = pick_lanes(prm, W, N, mean_jac);
@@ -356,12 +430,14 @@ static int preintegrate_impl(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int
             else launch::mean(prm->model, mean_jac, avg, LL, m, mean_stream);
         }
     }
-    if (forked) {
-        CPI_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->side));
-        CPI_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-    }
+    if (forked) CPI_TRY(side_join(ctx));
     CPI_HIP(ctx, hipGetLastError());
     return CPI_OK;
+}
+extern "C" int cpi_preintegrate_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                      const double *knots, const int64_t *first, const int32_t *count,
+                                      const double *lin, const double *q_k_lin, const cpi_outputs *out) {
+    return preintegrate_impl(ctx, "cpi_preintegrate_batch", prm, W, N, knots, first, count, nullptr, lin, q_k_lin, out);
 }
 
 // Resumable preintegration: cpi_preintegrate_batch from and to carry records (include/cpi_amd.h).  The same ownership rules
@@ -373,84 +449,53 @@ extern "C" int cpi_preintegrate_resume(cpi_ctx *ctx, const cpi_params *prm, int6
                                        const double *knots, const int64_t *first, const int32_t *count,
                                        const double *lin, const double *q_k_lin, const double *carry_in, double *carry_out,
                                        const cpi_outputs *out) {
+    static const char who[] = "cpi_preintegrate_resume";
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
-    if (!prm || !out) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_resume: prm/out is NULL");
-    if (prm->model != CPI_MODEL_V1 && prm->model != CPI_MODEL_V2)
-        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_resume: model must be 1 or 2 (the Forster comparator cannot be resumed)");
-    if (!carry_out) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_resume: carry_out is NULL");
-    if (W < 0 || N < 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_resume: negative size");
-    const int CD = carry::doubles(prm->model);
-    if (carry_in && carry_in < carry_out + W * CD && carry_out < carry_in + W * CD)
-        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_resume: carry_in and carry_out overlap");
+    if (!prm || !out) return refuse(ctx, who, "prm/out is NULL");
+    if (!model_is_cpi(prm)) return refuse_forster(ctx, who, NOT_RESUMABLE);
+    if (!carry_out) return refuse(ctx, who, "carry_out is NULL");
+    if (W < 0 || N < 0) return refuse(ctx, who, "negative size");
+    CPI_TRY(check_carry_overlap(ctx, who, prm, W, carry_in, carry_out));
     if (W == 0) return CPI_OK;
-    if (!knots || !lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_resume: knots/lin is NULL");
-    if (prm->model == CPI_MODEL_V2 && !q_k_lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_resume: model 2 needs q_k_lin");
-    if (!grid_ok(W)) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_resume: W exceeds 2^31 - 1 windows per call (32-bit grid)");
-    if (N > 65535) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_resume: N (intervals per window) must be <= 65535");
-    const int L = prm->lanes_per_window;
-    if (L != 0 && !launch::mean_lanes_supported(L)) return fail(ctx, CPI_ERR_INVALID, "lanes_per_window must be 0 or one of 1,2,3,4,5,6,8,12,16,32,64");
+    CPI_TRY(check_windows(ctx, who, prm, W, N, knots, lin, q_k_lin));
 
-    const bool want_mean = out->DT || out->alpha || out->beta || out->q;
-    const bool want_jac = out->J_q || out->J_a || out->J_b || out->H_a || out->H_b || out->O_a || out->O_b;
-    const bool want_cov = out->P != nullptr || out->P_sym != nullptr;
+    const Request rq = request_of(out);
     const bool avg = prm->imu_avg != 0;
-    const bool v2 = prm->model == CPI_MODEL_V2;
-    const bool stj = v2 && prm->state_transition_jacobians != 0;
+    const bool stj = prm->model == CPI_MODEL_V2 && prm->state_transition_jacobians != 0;
     // ownership as in preintegrate_impl; the means always run (carry_out holds them even when out asks for none)
-    const bool run_cov = want_cov || (stj && want_jac);
-    const bool mean_jac = want_jac && !stj;
+    const bool run_cov = rq.cov || (stj && rq.jac);
+    const bool mean_jac = rq.jac && !stj;
     const bool run_mean = mean_jac || !run_cov;
     CarryArgs c;
-    const int hdr = 1 | (avg ? 8 : 0) | (stj ? 16 : 0) | (32 * prm->model);
     c.in = carry_in;
     c.out = carry_out;
-    c.need = hdr | (run_cov ? carry::TAG_P : 0) | (mean_jac ? carry::TAG_J : 0);
+    c.need = carry_header(prm) | (run_cov ? carry::TAG_P : 0) | (mean_jac ? carry::TAG_J : 0);
     c.tag_out = c.need;
 
     DeviceGuard guard_;
     CPI_HIP(ctx, guard_.enter(ctx->device));
-    PreArgs a;
-    memset(&a, 0, sizeof a);
-    a.W = W; a.N = N; a.knots = knots; a.first = (const long long *)first; a.count = count;
-    a.lin = lin; a.qk = q_k_lin;
-    for (int i = 0; i < 3; i++) a.grav[i] = prm->grav[i];
-    a.q4[0] = prm->sigma_w * prm->sigma_w; a.q4[1] = prm->sigma_wb * prm->sigma_wb;
-    a.q4[2] = prm->sigma_a * prm->sigma_a; a.q4[3] = prm->sigma_ab * prm->sigma_ab;
-    a.out = *out;
+    const PreArgs a = pre_args(prm, W, N, knots, first, count, lin, q_k_lin, out);
     // model 1 with Jacobians and covariance: the two kernels overlap on the side stream as in the batch entry.  They write
     // disjoint parts of carry_out and both only read carry_in (which is why the two may not overlap).
-    hipStream_t mean_stream = ctx->stream;
     const bool forked = run_cov && run_mean;
-    if (forked) {
-        if (!ctx->side) {
-            CPI_HIP(ctx, hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
-            CPI_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-            CPI_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-        }
-        CPI_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-        CPI_HIP(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
-        mean_stream = ctx->side;
-    }
+    if (forked) CPI_TRY(side_fork(ctx));
     if (run_cov) {
         PreArgs p = a;
-        p.write_means = want_mean ? 1 : 0;
-        p.write_jac = (stj && want_jac) ? 1 : 0;
+        p.write_means = rq.mean ? 1 : 0;
+        p.write_jac = (stj && rq.jac) ? 1 : 0;
         CarryArgs cc = c;
         cc.own_means = 1;
         launch::cov_carry(prm->model, avg, p, cc, ctx->stream);
     }
     if (run_mean) {
         PreArgs m = a;
-        m.write_means = (want_mean && !run_cov) ? 1 : 0;
+        m.write_means = (rq.mean && !run_cov) ? 1 : 0;
         m.write_jac = mean_jac ? 1 : 0;
         CarryArgs cm = c;
         cm.own_means = run_cov ? 0 : 1;
-        launch::mean_carry(prm->model, mean_jac, avg, pick_lanes(prm, W, N, mean_jac), m, cm, mean_stream);
+        launch::mean_carry(prm->model, mean_jac, avg, pick_lanes(prm, W, N, mean_jac), m, cm, forked ? ctx->side : ctx->stream);
     }
-    if (forked) {
-        CPI_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->side));
-        CPI_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-    }
+    if (forked) CPI_TRY(side_join(ctx));
     CPI_HIP(ctx, hipGetLastError());
     return CPI_OK;
 }
@@ -463,46 +508,29 @@ extern "C" int cpi_preintegrate_resume(cpi_ctx *ctx, const cpi_params *prm, int6
 extern "C" int cpi_preintegrate_running(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                                         const double *knots, const int64_t *first, const int32_t *count,
                                         const double *lin, const double *q_k_lin, const cpi_outputs *rows) {
+    static const char who[] = "cpi_preintegrate_running";
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
-    if (!prm || !rows) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running: prm/rows is NULL");
-    if (prm->model == CPI_MODEL_FORSTER)
-        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running: model must be 1 or 2 (the Forster comparator has no running form)");
-    if (prm->model != CPI_MODEL_V1 && prm->model != CPI_MODEL_V2)
-        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running: model must be 1 or 2");
-    const bool want_mean = rows->DT || rows->alpha || rows->beta || rows->q;
-    const bool want_jac = rows->J_q || rows->J_a || rows->J_b || rows->H_a || rows->H_b || rows->O_a || rows->O_b;
-    const bool want_cov = rows->P != nullptr || rows->P_sym != nullptr;
-    if (prm->model == CPI_MODEL_V2 && want_jac)
-        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running: the Jacobian fields (J_q ... O_b) are not available for model 2 "
-                                          "(they are read out of the state transition matrix at the end of the recursion)");
-    if (W < 0 || N < 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running: negative size");
+    if (!prm || !rows) return refuse(ctx, who, "prm/rows is NULL");
+    if (prm->model == CPI_MODEL_FORSTER) return refuse_forster(ctx, who, NO_RUNNING_FORM);
+    if (!model_is_cpi(prm)) return refuse(ctx, who, "model must be 1 or 2");
+    const Request rq = request_of(rows);
+    if (prm->model == CPI_MODEL_V2 && rq.jac) return refuse_v2_jac(ctx, who, "");
+    if (W < 0 || N < 0) return refuse(ctx, who, "negative size");
     if (W == 0 || N == 0) return CPI_OK;
-    if (!knots || !lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running: knots/lin is NULL");
-    if (prm->model == CPI_MODEL_V2 && !q_k_lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running: model 2 needs q_k_lin");
-    if (!grid_ok(W)) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running: W exceeds 2^31 - 1 windows per call (32-bit grid)");
-    if (N > 65535) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running: N (intervals per window) must be <= 65535");
-    const int Lp = prm->lanes_per_window;
-    if (Lp != 0 && !launch::mean_lanes_supported(Lp)) return fail(ctx, CPI_ERR_INVALID, "lanes_per_window must be 0 or one of 1,2,3,4,5,6,8,12,16,32,64");
-    if (!want_mean && !want_jac && !want_cov) return CPI_OK;
+    CPI_TRY(check_windows(ctx, who, prm, W, N, knots, lin, q_k_lin));
+    if (!rq.any()) return CPI_OK;
     const bool avg = prm->imu_avg != 0;
 
     DeviceGuard guard_;
     CPI_HIP(ctx, guard_.enter(ctx->device));
-    PreArgs a;
-    memset(&a, 0, sizeof a);
-    a.W = W; a.N = N; a.knots = knots; a.first = (const long long *)first; a.count = count;
-    a.lin = lin; a.qk = q_k_lin;
-    for (int i = 0; i < 3; i++) a.grav[i] = prm->grav[i];
-    a.q4[0] = prm->sigma_w * prm->sigma_w; a.q4[1] = prm->sigma_wb * prm->sigma_wb;
-    a.q4[2] = prm->sigma_a * prm->sigma_a; a.q4[3] = prm->sigma_ab * prm->sigma_ab;
-    a.out = *rows;
-    if (want_mean || want_jac) {
+    const PreArgs a = pre_args(prm, W, N, knots, first, count, lin, q_k_lin, rows);
+    if (rq.mean || rq.jac) {
         PreArgs m = a;
-        m.write_means = want_mean ? 1 : 0;
-        m.write_jac = want_jac ? 1 : 0;
-        launch::mean_running(prm->model, want_jac, avg, pick_lanes(prm, W, N, want_jac), m, ctx->stream);
+        m.write_means = rq.mean ? 1 : 0;
+        m.write_jac = rq.jac ? 1 : 0;
+        launch::mean_running(prm->model, rq.jac, avg, pick_lanes(prm, W, N, rq.jac), m, ctx->stream);
     }
-    if (want_cov) launch::cov_running(prm->model, avg, a, ctx->stream);
+    if (rq.cov) launch::cov_running(prm->model, avg, a, ctx->stream);
     CPI_HIP(ctx, hipGetLastError());
     return CPI_OK;
 }
@@ -516,60 +544,38 @@ extern "C" int cpi_preintegrate_running_resume(cpi_ctx *ctx, const cpi_params *p
                                                const double *knots, const int64_t *first, const int32_t *count,
                                                const double *lin, const double *q_k_lin, const double *carry_in, double *carry_out,
                                                const cpi_outputs *rows) {
+    static const char who[] = "cpi_preintegrate_running_resume";
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
-    if (!prm || !rows) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume: prm/rows is NULL");
-    if (prm->model == CPI_MODEL_FORSTER)
-        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume: model must be 1 or 2 (the Forster comparator has no running form and cannot be resumed)");
-    if (prm->model != CPI_MODEL_V1 && prm->model != CPI_MODEL_V2)
-        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume: model must be 1 or 2");
-    const bool want_mean = rows->DT || rows->alpha || rows->beta || rows->q;
-    const bool want_jac = rows->J_q || rows->J_a || rows->J_b || rows->H_a || rows->H_b || rows->O_a || rows->O_b;
-    const bool want_cov = rows->P != nullptr || rows->P_sym != nullptr;
-    if (prm->model == CPI_MODEL_V2 && want_jac)
-        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume: the Jacobian fields (J_q ... O_b) are not available for model 2 "
-                                          "(they are read out of the state transition matrix at the end of the recursion: finish the "
-                                          "chain with cpi_preintegrate_resume)");
-    if (!carry_out) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume: carry_out is NULL");
-    if (W < 0 || N < 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume: negative size");
-    const int CD = carry::doubles(prm->model);
-    if (carry_in && carry_in < carry_out + W * CD && carry_out < carry_in + W * CD)
-        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume: carry_in and carry_out overlap");
+    if (!prm || !rows) return refuse(ctx, who, "prm/rows is NULL");
+    if (prm->model == CPI_MODEL_FORSTER) return refuse_forster(ctx, who, NO_RUNNING_FORM | NOT_RESUMABLE);
+    if (!model_is_cpi(prm)) return refuse(ctx, who, "model must be 1 or 2");
+    const Request rq = request_of(rows);
+    if (prm->model == CPI_MODEL_V2 && rq.jac) return refuse_v2_jac(ctx, who, ": finish the chain with cpi_preintegrate_resume");
+    if (!carry_out) return refuse(ctx, who, "carry_out is NULL");
+    if (W < 0 || N < 0) return refuse(ctx, who, "negative size");
+    CPI_TRY(check_carry_overlap(ctx, who, prm, W, carry_in, carry_out));
     if (W == 0) return CPI_OK;
-    if (!knots || !lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume: knots/lin is NULL");
-    if (prm->model == CPI_MODEL_V2 && !q_k_lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume: model 2 needs q_k_lin");
-    if (!grid_ok(W)) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume: W exceeds 2^31 - 1 windows per call (32-bit grid)");
-    if (N > 65535) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume: N (intervals per window) must be <= 65535");
-    const int Lp = prm->lanes_per_window;
-    if (Lp != 0 && !launch::mean_lanes_supported(Lp)) return fail(ctx, CPI_ERR_INVALID, "lanes_per_window must be 0 or one of 1,2,3,4,5,6,8,12,16,32,64");
+    CPI_TRY(check_windows(ctx, who, prm, W, N, knots, lin, q_k_lin));
     const bool avg = prm->imu_avg != 0;
-    const bool stj = prm->model == CPI_MODEL_V2 && prm->state_transition_jacobians != 0;
     CarryArgs c;
-    const int hdr = 1 | (avg ? 8 : 0) | (stj ? 16 : 0) | (32 * prm->model);   // as cpi_preintegrate_resume: the records are interchangeable
     c.in = carry_in;
     c.out = carry_out;
-    c.need = hdr | (want_cov ? carry::TAG_P : 0) | (want_jac ? carry::TAG_J : 0);
+    c.need = carry_header(prm) | (rq.cov ? carry::TAG_P : 0) | (rq.jac ? carry::TAG_J : 0);
     c.tag_out = c.need;
     c.own_means = 0;
 
     DeviceGuard guard_;
     CPI_HIP(ctx, guard_.enter(ctx->device));
-    PreArgs a;
-    memset(&a, 0, sizeof a);
-    a.W = W; a.N = N; a.knots = knots; a.first = (const long long *)first; a.count = count;
-    a.lin = lin; a.qk = q_k_lin;
-    for (int i = 0; i < 3; i++) a.grav[i] = prm->grav[i];
-    a.q4[0] = prm->sigma_w * prm->sigma_w; a.q4[1] = prm->sigma_wb * prm->sigma_wb;
-    a.q4[2] = prm->sigma_a * prm->sigma_a; a.q4[3] = prm->sigma_ab * prm->sigma_ab;
-    a.out = *rows;
+    const PreArgs a = pre_args(prm, W, N, knots, first, count, lin, q_k_lin, rows);
     {
         PreArgs m = a;
-        m.write_means = want_mean ? 1 : 0;
-        m.write_jac = want_jac ? 1 : 0;
+        m.write_means = rq.mean ? 1 : 0;
+        m.write_jac = rq.jac ? 1 : 0;
         CarryArgs cm = c;
         cm.own_means = 1;
-        launch::mean_running_carry(prm->model, want_jac, avg, pick_lanes(prm, W, N, want_jac), m, cm, ctx->stream);
+        launch::mean_running_carry(prm->model, rq.jac, avg, pick_lanes(prm, W, N, rq.jac), m, cm, ctx->stream);
     }
-    if (want_cov) launch::cov_running_carry(prm->model, avg, a, c, ctx->stream);
+    if (rq.cov) launch::cov_running_carry(prm->model, avg, a, c, ctx->stream);
     CPI_HIP(ctx, hipGetLastError());
     return CPI_OK;
 }
@@ -599,27 +605,23 @@ static StreamCut stream_cut(int64_t K, const double *update_times, void *workspa
     sc.runs = runs;
     return sc;
 }
+static int check_workspace(cpi_ctx *ctx, const char *who, const void *workspace) {
+    return ((uintptr_t)workspace & 15) != 0 ? refuse(ctx, who, "the workspace must be 16-byte aligned") : CPI_OK;
+}
 extern "C" int cpi_preintegrate_stream(cpi_ctx *ctx, const cpi_params *prm, int64_t K, const double *stream, int64_t U,
                                        const double *update_times, int32_t N, const double *lin, const double *q_k_lin,
                                        void *workspace, const cpi_outputs *out) {
+    static const char who[] = "cpi_preintegrate_stream";
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
-    if (K < 0 || U < 0 || N < 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_stream: negative size");
+    if (K < 0 || U < 0 || N < 0) return refuse(ctx, who, "negative size");
     if (U == 0) return CPI_OK;
-    if (K == 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_stream: the stream is empty");
-    if (!stream || !update_times || !workspace) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_stream: NULL argument");
-    if (((uintptr_t)workspace & 15) != 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_stream: the workspace must be 16-byte aligned");
-    if (!grid_ok(U)) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_stream: U exceeds 2^31 - 1 windows per call");
-    // everything preintegrate_impl would refuse is refused HERE, before the cut kernel is enqueued: an invalid call must not
-    // leave a launch behind that writes the caller's workspace
-    if (!prm || !out || !lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_stream: prm/out/lin is NULL");
-    if (prm->model != CPI_MODEL_V1 && prm->model != CPI_MODEL_V2 && prm->model != CPI_MODEL_FORSTER)
-        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_stream: model must be 1, 2 or 3 (CPI_MODEL_FORSTER)");
-    if (prm->model == CPI_MODEL_V2 && !q_k_lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_stream: model 2 needs q_k_lin");
-    if (N > 65535) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_stream: N (intervals per window) must be <= 65535");
-    if (prm->lanes_per_window != 0 && !launch::mean_lanes_supported(prm->lanes_per_window))
-        return fail(ctx, CPI_ERR_INVALID, "lanes_per_window must be 0 or one of 1,2,3,4,5,6,8,12,16,32,64");
+    if (K == 0) return refuse(ctx, who, "the stream is empty");
+    if (!stream || !update_times || !workspace) return refuse(ctx, who, "NULL argument");
+    CPI_TRY(check_workspace(ctx, who, workspace));
+    CPI_TRY(check_grid(ctx, who, "U", U));
+    if (!prm || !out || !lin) return refuse(ctx, who, "prm/out/lin is NULL");
     const StreamCut sc = stream_cut(K, update_times, workspace, U, nullptr);
-    return preintegrate_impl(ctx, prm, U, N, stream, nullptr, nullptr, &sc, lin, q_k_lin, out);
+    return preintegrate_impl(ctx, who, prm, U, N, stream, nullptr, nullptr, &sc, lin, q_k_lin, out);
 }
 
 // Many IMU streams in one call: run r owns the knots [stream_offsets[r], stream_offsets[r + 1]) and the windows
@@ -634,30 +636,23 @@ extern "C" int cpi_preintegrate_streams(cpi_ctx *ctx, const cpi_params *prm, int
                                         const int64_t *stream_offsets, int64_t U, const double *update_times,
                                         const int64_t *update_offsets, int32_t N, const double *lin, const double *q_k_lin,
                                         void *workspace, const cpi_outputs *out) {
+    static const char who[] = "cpi_preintegrate_streams";
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
-    if (R < 0 || K < 0 || U < 0 || N < 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams: negative size");
+    if (R < 0 || K < 0 || U < 0 || N < 0) return refuse(ctx, who, "negative size");
     if (U == 0) return CPI_OK;
-    if (R == 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams: U > 0 windows and no run");
-    if (R > 0x7ffffffeLL) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams: R exceeds 2^31 - 2 runs");
-    if (K == 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams: the streams hold no reading");
-    if (!stream || !stream_offsets || !update_times || !update_offsets || !workspace)
-        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams: NULL argument");
-    if (((uintptr_t)workspace & 15) != 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams: the workspace must be 16-byte aligned");
-    if (!grid_ok(U)) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams: U exceeds 2^31 - 1 windows per call");
-    // as in cpi_preintegrate_stream: everything preintegrate_impl would refuse is refused before the cut kernel is enqueued
-    if (!prm || !out || !lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams: prm/out/lin is NULL");
-    if (prm->model != CPI_MODEL_V1 && prm->model != CPI_MODEL_V2 && prm->model != CPI_MODEL_FORSTER)
-        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams: model must be 1, 2 or 3 (CPI_MODEL_FORSTER)");
-    if (prm->model == CPI_MODEL_V2 && !q_k_lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams: model 2 needs q_k_lin");
-    if (N > 65535) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams: N (intervals per window) must be <= 65535");
-    if (prm->lanes_per_window != 0 && !launch::mean_lanes_supported(prm->lanes_per_window))
-        return fail(ctx, CPI_ERR_INVALID, "lanes_per_window must be 0 or one of 1,2,3,4,5,6,8,12,16,32,64");
+    if (R == 0) return refuse(ctx, who, "U > 0 windows and no run");
+    if (R > 0x7ffffffeLL) return refuse(ctx, who, "R exceeds 2^31 - 2 runs");
+    if (K == 0) return refuse(ctx, who, "the streams hold no reading");
+    if (!stream || !stream_offsets || !update_times || !update_offsets || !workspace) return refuse(ctx, who, "NULL argument");
+    CPI_TRY(check_workspace(ctx, who, workspace));
+    CPI_TRY(check_grid(ctx, who, "U", U));
+    if (!prm || !out || !lin) return refuse(ctx, who, "prm/out/lin is NULL");
     RunArgs ra;
     ra.soff = reinterpret_cast<const long long *>(stream_offsets);
     ra.uoff = reinterpret_cast<const long long *>(update_offsets);
     ra.R = (int)R;
     const StreamCut sc = stream_cut(K, update_times, workspace, U, &ra);
-    return preintegrate_impl(ctx, prm, U, N, stream, nullptr, nullptr, &sc, lin, q_k_lin, out);
+    return preintegrate_impl(ctx, who, prm, U, N, stream, nullptr, nullptr, &sc, lin, q_k_lin, out);
 }
 
 // Running rows from the stream entries (include/cpi_amd.h: cpi_preintegrate_stream_running / cpi_preintegrate_streams_running): the
@@ -665,71 +660,48 @@ extern "C" int cpi_preintegrate_streams(cpi_ctx *ctx, const cpi_params *prm, int
 // cpi_cov_running_kernel (whose phase A reads cut windows when PreArgs::tstart is set) read the stream in place -- one after the
 // other on the context's stream, as in cpi_preintegrate_running.  The lane choice is pick_lanes(U, N, request), the function
 // cpi_preintegrate_running uses: the rows are bit for bit those of that entry on the host-assembled windows.
-// the request asks for Jacobian rows: the predicate of cpi_preintegrate_running (O_a / O_b included), shared by the checks, the
-// kernel choice and the lane choice of these entries
-static bool rows_want_jac(const cpi_outputs *rows) {
-    return rows->J_q || rows->J_a || rows->J_b || rows->H_a || rows->H_b || rows->O_a || rows->O_b;
-}
-static int stream_running_check(cpi_ctx *ctx, const std::string &who, const cpi_params *prm, bool many, int64_t R, int64_t K, int64_t U,
+static int stream_running_check(cpi_ctx *ctx, const char *who, const cpi_params *prm, bool many, int64_t R, int64_t K, int64_t U,
                                 int32_t N, const void *stream, const void *soff, const void *update_times, const void *uoff,
                                 const void *lin, const void *q_k_lin, const cpi_outputs *rows, bool &noop) {
     noop = false;
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
-    if (!prm || !rows) return fail(ctx, CPI_ERR_INVALID, who + ": prm/rows is NULL");
-    if (prm->model == CPI_MODEL_FORSTER)
-        return fail(ctx, CPI_ERR_INVALID, who + ": model must be 1 or 2 (the Forster comparator has no running form)");
-    if (prm->model != CPI_MODEL_V1 && prm->model != CPI_MODEL_V2) return fail(ctx, CPI_ERR_INVALID, who + ": model must be 1 or 2");
-    if (prm->model == CPI_MODEL_V2 && rows_want_jac(rows))
-        return fail(ctx, CPI_ERR_INVALID, who + ": the Jacobian fields (J_q ... O_b) are not available for model 2 "
-                                                "(they are read out of the state transition matrix at the end of the recursion)");
-    if (R < 0 || K < 0 || U < 0 || N < 0) return fail(ctx, CPI_ERR_INVALID, who + ": negative size");
+    if (!prm || !rows) return refuse(ctx, who, "prm/rows is NULL");
+    if (prm->model == CPI_MODEL_FORSTER) return refuse_forster(ctx, who, NO_RUNNING_FORM);
+    if (!model_is_cpi(prm)) return refuse(ctx, who, "model must be 1 or 2");
+    if (prm->model == CPI_MODEL_V2 && request_of(rows).jac) return refuse_v2_jac(ctx, who, "");
+    if (R < 0 || K < 0 || U < 0 || N < 0) return refuse(ctx, who, "negative size");
     if (U == 0 || N == 0) { noop = true; return CPI_OK; }
-    if (many && R == 0) return fail(ctx, CPI_ERR_INVALID, who + ": U > 0 windows and no run");
-    if (many && R > 0x7ffffffeLL) return fail(ctx, CPI_ERR_INVALID, who + ": R exceeds 2^31 - 2 runs");
-    if (K == 0) return fail(ctx, CPI_ERR_INVALID, who + (many ? ": the streams hold no reading" : ": the stream is empty"));
-    if (!stream || !update_times || !lin || (many && (!soff || !uoff))) return fail(ctx, CPI_ERR_INVALID, who + ": NULL argument");
-    if (!grid_ok(U)) return fail(ctx, CPI_ERR_INVALID, who + ": U exceeds 2^31 - 1 windows per call");
-    if (prm->model == CPI_MODEL_V2 && !q_k_lin) return fail(ctx, CPI_ERR_INVALID, who + ": model 2 needs q_k_lin");
-    if (N > 65535) return fail(ctx, CPI_ERR_INVALID, who + ": N (intervals per window) must be <= 65535");
-    if (prm->lanes_per_window != 0 && !launch::mean_lanes_supported(prm->lanes_per_window))
-        return fail(ctx, CPI_ERR_INVALID, "lanes_per_window must be 0 or one of 1,2,3,4,5,6,8,12,16,32,64");
-    return CPI_OK;
+    if (many && R == 0) return refuse(ctx, who, "U > 0 windows and no run");
+    if (many && R > 0x7ffffffeLL) return refuse(ctx, who, "R exceeds 2^31 - 2 runs");
+    if (K == 0) return refuse(ctx, who, many ? "the streams hold no reading" : "the stream is empty");
+    if (!stream || !update_times || !lin || (many && (!soff || !uoff))) return refuse(ctx, who, "NULL argument");
+    CPI_TRY(check_grid(ctx, who, "U", U));
+    CPI_TRY(check_qk(ctx, who, prm, q_k_lin));
+    CPI_TRY(check_N(ctx, who, N));
+    return check_lanes(ctx, prm);
 }
 // the running kernels on the windows [w0, w0 + wn) of a cut that is already in the workspace; rows: row 0 = window w0, interval 0.
 // L: the lane choice of the WHOLE call (a chunked download must not change it)
 static int stream_running_launch(cpi_ctx *ctx, const cpi_params *prm, const StreamCut &sc, const double *stream, int32_t N, int L,
                                  const double *lin, const double *q_k_lin, const cpi_outputs *rows, int64_t w0, int64_t wn) {
-    const bool want_mean = rows->DT || rows->alpha || rows->beta || rows->q;
-    const bool want_jac = rows_want_jac(rows);
-    const bool want_cov = rows->P != nullptr || rows->P_sym != nullptr;
+    const Request rq = request_of(rows);
     const bool avg = prm->imu_avg != 0;
-    PreArgs a;
-    memset(&a, 0, sizeof a);
-    a.W = wn; a.N = N; a.knots = stream; a.K = sc.K;
-    a.first = sc.first + w0; a.count = sc.count + w0; a.tstart = sc.tstart + w0; a.tend = sc.tend + w0;
-    a.lin = lin + w0 * 6; a.qk = q_k_lin ? q_k_lin + w0 * 4 : nullptr;
-    for (int i = 0; i < 3; i++) a.grav[i] = prm->grav[i];
-    a.q4[0] = prm->sigma_w * prm->sigma_w; a.q4[1] = prm->sigma_wb * prm->sigma_wb;
-    a.q4[2] = prm->sigma_a * prm->sigma_a; a.q4[3] = prm->sigma_ab * prm->sigma_ab;
-    a.out = *rows;
-    if (want_mean || want_jac) {
+    PreArgs a = pre_args(prm, wn, N, stream, reinterpret_cast<const int64_t *>(sc.first), sc.count, lin, q_k_lin, rows);
+    a.K = sc.K; a.tstart = sc.tstart + w0; a.tend = sc.tend + w0;
+    a.first += w0; a.count += w0; a.lin += w0 * 6;
+    if (a.qk) a.qk += w0 * 4;
+    if (rq.mean || rq.jac) {
         PreArgs m = a;
-        m.write_means = want_mean ? 1 : 0;
-        m.write_jac = want_jac ? 1 : 0;
-        launch::mean_stream_running(prm->model, want_jac, avg, L, m, ctx->stream);
+        m.write_means = rq.mean ? 1 : 0;
+        m.write_jac = rq.jac ? 1 : 0;
+        launch::mean_stream_running(prm->model, rq.jac, avg, L, m, ctx->stream);
     }
-    if (want_cov) launch::cov_running(prm->model, avg, a, ctx->stream);
-    CPI_HIP(ctx, hipGetLastError());
-    return CPI_OK;
-}
-static int stream_running_cut(cpi_ctx *ctx, const StreamCut &sc, const double *stream, int64_t U, int32_t N) {
-    if (sc.runs) launch::cut_runs(sc.K, stream, (long long)U, sc.update, *sc.runs, sc.first, sc.count, sc.tstart, sc.tend, ctx->stream);
-    else launch::cut_windows(sc.K, stream, (long long)U, sc.update, (int)N, sc.first, sc.count, sc.tstart, sc.tend, ctx->stream);
+    if (rq.cov) launch::cov_running(prm->model, avg, a, ctx->stream);
     CPI_HIP(ctx, hipGetLastError());
     return CPI_OK;
 }
 static int stream_running_lanes(const cpi_params *prm, int64_t U, int32_t N, const cpi_outputs *rows) {
-    return pick_lanes(prm, U, N, rows_want_jac(rows));
+    return pick_lanes(prm, U, N, request_of(rows).jac);
 }
 static int stream_running_impl(cpi_ctx *ctx, const char *who, const cpi_params *prm, const RunArgs *runs, int64_t R, int64_t K,
                                const double *stream, int64_t U, const double *update_times, int32_t N, const double *lin,
@@ -738,15 +710,14 @@ static int stream_running_impl(cpi_ctx *ctx, const char *who, const cpi_params *
     const int rc = stream_running_check(ctx, who, prm, runs != nullptr, R, K, U, N, stream, runs ? runs->soff : nullptr, update_times,
                                         runs ? runs->uoff : nullptr, lin, q_k_lin, rows, noop);
     if (rc != CPI_OK || noop) return rc;
-    if (!workspace) return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": NULL argument");
-    if (((uintptr_t)workspace & 15) != 0) return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": the workspace must be 16-byte aligned");
+    if (!workspace) return refuse(ctx, who, "NULL argument");
+    CPI_TRY(check_workspace(ctx, who, workspace));
     DeviceGuard guard_;
     CPI_HIP(ctx, guard_.enter(ctx->device));
     RunArgs ra;
     if (runs) { ra = *runs; ra.R = (int)R; }
     const StreamCut sc = stream_cut(K, update_times, workspace, U, runs ? &ra : nullptr);
-    const int rcc = stream_running_cut(ctx, sc, stream, U, N);
-    if (rcc != CPI_OK) return rcc;
+    CPI_TRY(cut_launch(ctx, sc, stream, U, N));
     return stream_running_launch(ctx, prm, sc, stream, N, stream_running_lanes(prm, U, N, rows), lin, q_k_lin, rows, 0, U);
 }
 extern "C" int cpi_preintegrate_stream_running(cpi_ctx *ctx, const cpi_params *prm, int64_t K, const double *stream, int64_t U,
@@ -943,12 +914,6 @@ extern "C" int cpi_predict_batch(cpi_ctx *ctx, int32_t model, const double grav[
     return CPI_OK;
 }
 
-static const int OUT_N[kOutFields] = { 1, 3, 3, 4, 9, 9, 9, 9, 9, 9, 9, 225, CPI_TRI_DOUBLES };
-static double **out_field(cpi_outputs *o, int k) {
-    double **f[kOutFields] = { &o->DT, &o->alpha, &o->beta, &o->q, &o->J_q, &o->J_a, &o->J_b, &o->H_a, &o->H_b, &o->O_a, &o->O_b, &o->P, &o->P_sym };
-    return f[k];
-}
-static double *out_field_c(const cpi_outputs *o, int k) { cpi_outputs t = *o; return *out_field(&t, k); }
 
 extern "C" size_t cpi_outputs_slab_doubles(const cpi_outputs *mask, int64_t Wb) {
     if (!mask || Wb <= 0) return 0;
@@ -1004,22 +969,23 @@ extern "C" int cpi_assemble_tiles(cpi_ctx *ctx, int64_t K, const double *stream,
     CPI_HIP(ctx, hipGetLastError());
     return CPI_OK;
 }
+static const char kTiledMeansOnly[] = "the tiled layout serves the mean outputs (DT, alpha, beta, q) only";
 extern "C" int cpi_preintegrate_tiled_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N, const double *tiles,
                                             const int32_t *count, const double *lin, const double *q_k_lin, const cpi_outputs *out) {
+    static const char who[] = "cpi_preintegrate_tiled_batch";
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
-    if (!prm || !out) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_tiled_batch: prm/out is NULL");
-    if (prm->model != CPI_MODEL_V1 && prm->model != CPI_MODEL_V2) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_tiled_batch: model must be 1 or 2");
-    if (W < 0 || N < 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_tiled_batch: negative size");
+    if (!prm || !out) return refuse(ctx, who, "prm/out is NULL");
+    if (!model_is_cpi(prm)) return refuse(ctx, who, "model must be 1 or 2");
+    if (W < 0 || N < 0) return refuse(ctx, who, "negative size");
     if (W == 0) return CPI_OK;
-    if (!tiles || !lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_tiled_batch: tiles/lin is NULL");
-    if (prm->model == CPI_MODEL_V2 && !q_k_lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_tiled_batch: model 2 needs q_k_lin");
-    if (!grid_ok(W)) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_tiled_batch: W exceeds 2^31 - 1 windows per call");
-    if (out->J_q || out->J_a || out->J_b || out->H_a || out->H_b || out->O_a || out->O_b || out->P || out->P_sym)
-        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_tiled_batch: the tiled layout serves the mean outputs (DT, alpha, beta, q) only; "
-                                          "Jacobians and covariance are FP64-bound, not HBM-bound: use cpi_preintegrate_batch");
+    if (!tiles || !lin) return refuse(ctx, who, "tiles/lin is NULL");
+    CPI_TRY(check_qk(ctx, who, prm, q_k_lin));
+    CPI_TRY(check_grid(ctx, who, "W", W));
+    const Request rq = request_of(out);
+    if (rq.jac || rq.cov) return refuse(ctx, who, kTiledMeansOnly, "; Jacobians and covariance are FP64-bound, not HBM-bound: use cpi_preintegrate_batch");
     if (prm->lanes_per_window < 0 || prm->lanes_per_window > 8)
-        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_tiled_batch: lanes_per_window (here: wavefronts per tile) must be 0 (auto) or 1..8");
-    if (!(out->DT || out->alpha || out->beta || out->q)) return CPI_OK;
+        return refuse(ctx, who, "lanes_per_window (here: wavefronts per tile) must be 0 (auto) or 1..8");
+    if (!rq.mean) return CPI_OK;
     DeviceGuard guard_;
     CPI_HIP(ctx, guard_.enter(ctx->device));
     TiledArgs a;
@@ -1405,19 +1371,87 @@ extern "C" int cpi_test_quat_ops(cpi_ctx *ctx, int32_t op, int64_t n, const doub
 // ============================================================================================
 // host-pointer variants
 // ============================================================================================
+// Whole-batch staging, shared by every host-pointer entry that stages its arrays whole (one-off calls): device copies of the
+// caller's arrays and a device mirror of its cpi_outputs, all on the context's stream, all released when the entry returns.
+// Nothing returns while a copy is in flight: every way out of an entry -- a failed allocation, a refused device call, a
+// failed copy -- runs the destructor, which drains the stream before the buffers go and the caller sees its memory again.
 namespace {
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
+class Staging {
+public:
+    explicit Staging(cpi_ctx *c) : ctx(c) {}
+    Staging(const Staging &) = delete;
+    Staging &operator=(const Staging &) = delete;
+    ~Staging() {
+        if (in_flight) (void)hipStreamSynchronize(ctx->stream);
+        for (int i = 0; i < n; i++) (void)hipFree(buf[i]);
+    }
+    int alloc(size_t bytes, void **dev) {
+        if (n == kMax) return fail(ctx, CPI_ERR_INVALID, "host staging: too many arrays");
+        CPI_HIP(ctx, hipMalloc(dev, bytes));
+        buf[n++] = *dev;
+        return CPI_OK;
+    }
+    template <class T> int alloc(size_t count, T **dev) { return alloc(count * sizeof(T), reinterpret_cast<void **>(dev)); }
+    // device copy of host[count]; a NULL host array stays NULL
+    template <class T> int upload(const T *host, size_t count, const T **dev) {
+        *dev = nullptr;
+        if (!host) return CPI_OK;
+        T *d;
+        CPI_TRY(alloc(count, &d));
+        in_flight = true;
+        CPI_HIP(ctx, hipMemcpyAsync(d, host, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+        *dev = d;
+        return CPI_OK;
+    }
+    // dev: the fields of mask, each with room for `rows` rows.  rows == 0: the mask itself -- the device entry classifies the
+    // request by which fields are set and dereferences none of them
+    int mirror(const cpi_outputs *mask, size_t rows, cpi_outputs *dev) {
+        *dev = *mask;
+        for (int k = 0; k < kOutFields && rows; k++)
+            if (*out_field(dev, k)) CPI_TRY(alloc(rows * OUT_N[k], out_field(dev, k)));
+        return CPI_OK;
+    }
+    template <class T> int download(T *host, const T *dev, size_t count) {
+        in_flight = true;
+        CPI_HIP(ctx, hipMemcpyAsync(host, dev, count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+        return CPI_OK;
+    }
+    // rows [row0, row0 + rows) of the caller's fields from the first `rows` rows of the mirror
+    int download(const cpi_outputs *host, const cpi_outputs &dev, size_t rows, size_t row0 = 0) {
+        for (int k = 0; k < kOutFields && rows; k++)
+            if (double *h = out_field_c(host, k)) CPI_TRY(download(h + row0 * OUT_N[k], (const double *)out_field_c(&dev, k), rows * OUT_N[k]));
+        return CPI_OK;
+    }
+    // the end of a call that succeeded so far: the caller's memory holds the results when this returns CPI_OK
+    int finish() {
+        in_flight = false;
+        CPI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return CPI_OK;
+    }
+
+private:
+    static constexpr int kMax = 32;   // an entry stages at most 7 inputs, a workspace and kOutFields outputs
+    cpi_ctx *ctx;
+    void *buf[kMax];
+    int n = 0;
+    bool in_flight = false;
 };
+
+// the window arrays of a batch, staged whole
+struct WindowsDev {
+    const double *knots, *lin, *qk;
+    const int64_t *first;
+    const int32_t *count;
+};
+int stage_windows(Staging &st, int64_t W, int64_t n_knots, const double *knots, const int64_t *first, const int32_t *count,
+                  const double *lin, const double *q_k_lin, WindowsDev *d) {
+    CPI_TRY(st.upload(knots, (size_t)n_knots * 7, &d->knots));
+    CPI_TRY(st.upload(first, (size_t)W, &d->first));
+    CPI_TRY(st.upload(count, (size_t)W, &d->count));
+    CPI_TRY(st.upload(lin, (size_t)W * 6, &d->lin));
+    return st.upload(q_k_lin, (size_t)W * 4, &d->qk);
+}
 }  // namespace
-#define CPI_UP(buf, host, bytes)                                                          \
-    do {                                                                                  \
-        if (host) {                                                                       \
-            CPI_HIP(ctx, hipMalloc(&buf.p, (bytes)));                                     \
-            CPI_HIP(ctx, hipMemcpyAsync(buf.p, host, (bytes), hipMemcpyHostToDevice, ctx->stream)); \
-        }                                                                                 \
-    } while (0)
 
 // Dense (and tiled) batches from host memory run as a three-stage pipeline over chunks of <= 65536 windows: upload of
 // chunk i + 1 (copy stream), kernels of chunk i (the context's stream), download of chunk i - 1 (second copy stream) -- PCIe
@@ -1429,23 +1463,39 @@ struct DevBuf {
 // 52 / 56 ms.  Page-locked bounce buffers + copy threads for pageable destinations were built and measured: no faster
 // than the runtime's own path (112 ms) -- what costs is FRESH pageable output memory (first-touch page faults: 375-450 ms
 // for the same call), so callers should re-use their output buffers.
+constexpr int kPipeArrays = 6;   // per-window arrays of a chunk: knots, count, lin, q_k_lin and two of the caller's (the carry records)
+// One per-window array that travels with a chunk: `stride` bytes per window, uploaded from `up` before the chunk's kernels or
+// downloaded to `down` after them (both NULL: absent); whole groups of `group` windows are copied (64: tiles).
+struct PipeArray {
+    const char *name;
+    const void *up;
+    void *down;
+    size_t stride;
+    int group;
+};
+struct PipeArrays { PipeArray a[kPipeArrays]; };
+// knots[W][N+1][7] (group 1) or tiles[ceil(W/64)][N+1][7][64] (group 64: chunks are whole tiles) with count, lin and q_k_lin
+static PipeArrays pipe_windows(const double *knots, int32_t N, int group, const int32_t *count, const double *lin, const double *q_k_lin) {
+    PipeArrays p = {};
+    p.a[0] = {"knots", knots, nullptr, (size_t)(N + 1) * 7 * sizeof(double), group};
+    p.a[1] = {"count", count, nullptr, sizeof(int32_t), 1};
+    p.a[2] = {"lin", lin, nullptr, 6 * sizeof(double), 1};
+    p.a[3] = {"q_k_lin", q_k_lin, nullptr, 4 * sizeof(double), 1};
+    return p;
+}
 struct HostPipe {
     hipStream_t up = nullptr, down = nullptr;
     hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
-    void *in[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};   // knots, count, lin, q_k_lin
-    size_t in_cap[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+    void *arr[2][kPipeArrays] = {};
+    size_t arr_cap[2][kPipeArrays] = {};
     void *out[2][kOutFields] = {};
     size_t out_cap[2][kOutFields] = {};
-    void *cin[2] = {nullptr, nullptr}, *cout[2] = {nullptr, nullptr};   // carry records (cpi_preintegrate_running_resume_host)
-    size_t cin_cap[2] = {0, 0}, cout_cap[2] = {0, 0};
 };
 static void host_pipe_destroy(HostPipe *hp) {
     if (!hp) return;
     for (int s = 0; s < 2; s++) {
-        for (int k = 0; k < 4; k++) if (hp->in[s][k]) (void)hipFree(hp->in[s][k]);
+        for (int k = 0; k < kPipeArrays; k++) if (hp->arr[s][k]) (void)hipFree(hp->arr[s][k]);
         for (int k = 0; k < kOutFields; k++) if (hp->out[s][k]) (void)hipFree(hp->out[s][k]);
-        if (hp->cin[s]) (void)hipFree(hp->cin[s]);
-        if (hp->cout[s]) (void)hipFree(hp->cout[s]);
         if (hp->ev_in[s]) (void)hipEventDestroy(hp->ev_in[s]);
         if (hp->ev_done[s]) (void)hipEventDestroy(hp->ev_done[s]);
         if (hp->ev_out[s]) (void)hipEventDestroy(hp->ev_out[s]);
@@ -1480,212 +1530,180 @@ extern "C" void *cpi_host_alloc(size_t bytes) {
 }
 extern "C" void cpi_host_free(void *p) { if (p) (void)hipHostFree(p); }
 
-// tiled == false: knots[W][N+1][7];  tiled == true: tiles[ceil(W/64)][N+1][7][64] (chunks are whole tiles)
-// running: cpi_preintegrate_running -- N output rows per window instead of one, chunks of <= 65536 ROWS (N >= 1)
-// carry_out: cpi_preintegrate_running_resume -- the records of a chunk go up and come down with it
-static int preintegrate_host_pipeline(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N, const double *knots, bool tiled,
-                                      const int32_t *count, const double *lin, const double *q_k_lin, const cpi_outputs *out,
-                                      bool running = false, const double *carry_in = nullptr, double *carry_out = nullptr) {
+// who: the _host entry that is called.  rows: output rows per window (the running entries: N >= 1 rows, chunks of <= 65536 ROWS).
+// launch(wn, dev, d): the device-pointer entry on the wn windows of one chunk -- dev[k] the device copy of arr.a[k] (NULL:
+// absent), d the device mirror of out -- enqueued on the context's stream.
+template <class Launch>
+static int preintegrate_host_pipeline(cpi_ctx *ctx, const char *who, int64_t W, size_t rows, const PipeArrays &arr, const cpi_outputs *out,
+                                      Launch launch) {
     int rc = host_pipe_get(ctx);
     if (rc != CPI_OK) return rc;
     HostPipe *hp = ctx->pipe;
-    const size_t R = running ? (size_t)N : 1;            // output rows per window
-    const int64_t cw = running ? std::max<int64_t>(64, 65536 / (int64_t)R / 64 * 64) : 65536;
+    const int64_t cw = std::max<int64_t>(64, 65536 / (int64_t)rows / 64 * 64);
     const int64_t nch = (W + cw - 1) / cw;
     const int64_t Wc = std::min<int64_t>(W, (((W + nch - 1) / nch) + 63) / 64 * 64);   // balanced chunks, whole wavefronts / tiles
     const int nslots = nch > 1 ? 2 : 1;
-    const size_t knot_bytes = (size_t)(N + 1) * 7 * sizeof(double);
-    auto in_bytes = [&](int64_t wn) { return tiled ? (size_t)((wn + 63) / 64) * 64 * knot_bytes : (size_t)wn * knot_bytes; };
-    cpi_outputs h = *out;
-    const size_t cd_bytes = carry_out ? (size_t)carry::doubles(prm->model) * sizeof(double) : 0;
+    auto bytes_of = [](const PipeArray &p, int64_t wn) { return (size_t)((wn + p.group - 1) / p.group * p.group) * p.stride; };
     for (int s = 0; s < nslots; s++) {
-        if (carry_in && (rc = host_pipe_reserve(ctx, hp->cin[s], hp->cin_cap[s], (size_t)Wc * cd_bytes)) != CPI_OK) return rc;
-        if (carry_out && (rc = host_pipe_reserve(ctx, hp->cout[s], hp->cout_cap[s], (size_t)Wc * cd_bytes)) != CPI_OK) return rc;
-        const size_t need[4] = { in_bytes(Wc), count ? (size_t)Wc * sizeof(int32_t) : 0, (size_t)Wc * 6 * sizeof(double),
-                                 q_k_lin ? (size_t)Wc * 4 * sizeof(double) : 0 };
-        for (int k = 0; k < 4; k++)
-            if ((rc = host_pipe_reserve(ctx, hp->in[s][k], hp->in_cap[s][k], need[k])) != CPI_OK) return rc;
+        for (int k = 0; k < kPipeArrays; k++)
+            if ((arr.a[k].up || arr.a[k].down) && (rc = host_pipe_reserve(ctx, hp->arr[s][k], hp->arr_cap[s][k], bytes_of(arr.a[k], Wc))) != CPI_OK) return rc;
         for (int k = 0; k < kOutFields; k++)
-            if (*out_field(&h, k) && (rc = host_pipe_reserve(ctx, hp->out[s][k], hp->out_cap[s][k], (size_t)Wc * R * OUT_N[k] * sizeof(double))) != CPI_OK) return rc;
+            if (out_field_c(out, k) && (rc = host_pipe_reserve(ctx, hp->out[s][k], hp->out_cap[s][k], (size_t)Wc * rows * OUT_N[k] * sizeof(double))) != CPI_OK) return rc;
     }
     // after the first enqueue nothing may return before the three streams are idle: copies into the caller's memory are in flight
     std::string err;
-    auto hip_ok = [&](hipError_t e, const char *what) { if (e != hipSuccess && err.empty()) err = std::string(what) + ": " + hipGetErrorString(e); return e == hipSuccess; };
+    auto hip_ok = [&](hipError_t e, const char *what, const char *name = "") { if (e != hipSuccess && err.empty()) err = std::string(what) + name + ": " + hipGetErrorString(e); return e == hipSuccess; };
     for (int64_t i = 0; i < nch && err.empty() && rc == CPI_OK; i++) {
         const int s = (int)(i & 1);
         const int64_t w0 = i * Wc, wn = std::min<int64_t>(Wc, W - w0);
         if (i >= 2 && !hip_ok(hipStreamWaitEvent(hp->up, hp->ev_done[s], 0), "hipStreamWaitEvent")) break;   // slot's inputs consumed
-        if (!hip_ok(hipMemcpyAsync(hp->in[s][0], knots + (size_t)w0 * (N + 1) * 7, in_bytes(wn), hipMemcpyHostToDevice, hp->up), "upload knots")) break;
-        if (count && !hip_ok(hipMemcpyAsync(hp->in[s][1], count + w0, (size_t)wn * sizeof(int32_t), hipMemcpyHostToDevice, hp->up), "upload count")) break;
-        if (!hip_ok(hipMemcpyAsync(hp->in[s][2], lin + (size_t)w0 * 6, (size_t)wn * 6 * sizeof(double), hipMemcpyHostToDevice, hp->up), "upload lin")) break;
-        if (q_k_lin && !hip_ok(hipMemcpyAsync(hp->in[s][3], q_k_lin + (size_t)w0 * 4, (size_t)wn * 4 * sizeof(double), hipMemcpyHostToDevice, hp->up), "upload q_k_lin")) break;
-        if (carry_in && !hip_ok(hipMemcpyAsync(hp->cin[s], (const char *)carry_in + (size_t)w0 * cd_bytes, (size_t)wn * cd_bytes, hipMemcpyHostToDevice, hp->up), "upload carry_in")) break;
+        void *dev[kPipeArrays];
+        for (int k = 0; k < kPipeArrays; k++) {
+            const PipeArray &p = arr.a[k];
+            dev[k] = (p.up || p.down) ? hp->arr[s][k] : nullptr;
+            if (p.up && !hip_ok(hipMemcpyAsync(dev[k], (const char *)p.up + (size_t)w0 * p.stride, bytes_of(p, wn), hipMemcpyHostToDevice, hp->up), "upload ", p.name)) break;
+        }
+        if (!err.empty()) break;
         if (!hip_ok(hipEventRecord(hp->ev_in[s], hp->up), "hipEventRecord")) break;
         if (!hip_ok(hipStreamWaitEvent(ctx->stream, hp->ev_in[s], 0), "hipStreamWaitEvent")) break;
         if (i >= 2 && !hip_ok(hipStreamWaitEvent(ctx->stream, hp->ev_out[s], 0), "hipStreamWaitEvent")) break;   // slot's outputs downloaded
         cpi_outputs d;
         memset(&d, 0, sizeof d);
-        for (int k = 0; k < kOutFields; k++) if (*out_field(&h, k)) *out_field(&d, k) = (double *)hp->out[s][k];
-        if (running && carry_out)
-            rc = cpi_preintegrate_running_resume(ctx, prm, wn, N, (const double *)hp->in[s][0], nullptr, count ? (const int32_t *)hp->in[s][1] : nullptr,
-                                                 (const double *)hp->in[s][2], q_k_lin ? (const double *)hp->in[s][3] : nullptr,
-                                                 carry_in ? (const double *)hp->cin[s] : nullptr, (double *)hp->cout[s], &d);
-        else if (running)
-            rc = cpi_preintegrate_running(ctx, prm, wn, N, (const double *)hp->in[s][0], nullptr, count ? (const int32_t *)hp->in[s][1] : nullptr,
-                                          (const double *)hp->in[s][2], q_k_lin ? (const double *)hp->in[s][3] : nullptr, &d);
-        else if (tiled)
-            rc = cpi_preintegrate_tiled_batch(ctx, prm, wn, N, (const double *)hp->in[s][0], count ? (const int32_t *)hp->in[s][1] : nullptr,
-                                              (const double *)hp->in[s][2], q_k_lin ? (const double *)hp->in[s][3] : nullptr, &d);
-        else
-            rc = cpi_preintegrate_batch(ctx, prm, wn, N, (const double *)hp->in[s][0], nullptr, count ? (const int32_t *)hp->in[s][1] : nullptr,
-                                        (const double *)hp->in[s][2], q_k_lin ? (const double *)hp->in[s][3] : nullptr, &d);
+        for (int k = 0; k < kOutFields; k++) if (out_field_c(out, k)) *out_field(&d, k) = (double *)hp->out[s][k];
+        rc = launch(wn, dev, &d);
         if (rc != CPI_OK) break;
         if (!hip_ok(hipEventRecord(hp->ev_done[s], ctx->stream), "hipEventRecord")) break;
         if (!hip_ok(hipStreamWaitEvent(hp->down, hp->ev_done[s], 0), "hipStreamWaitEvent")) break;
         for (int k = 0; k < kOutFields; k++)
-            if (*out_field(&h, k) && !hip_ok(hipMemcpyAsync(*out_field(&h, k) + (size_t)w0 * R * OUT_N[k], hp->out[s][k], (size_t)wn * R * OUT_N[k] * sizeof(double),
-                                                            hipMemcpyDeviceToHost, hp->down), "download")) break;
+            if (out_field_c(out, k) && !hip_ok(hipMemcpyAsync(out_field_c(out, k) + (size_t)w0 * rows * OUT_N[k], hp->out[s][k], (size_t)wn * rows * OUT_N[k] * sizeof(double),
+                                                              hipMemcpyDeviceToHost, hp->down), "download")) break;
+        for (int k = 0; k < kPipeArrays && err.empty(); k++)
+            if (arr.a[k].down) hip_ok(hipMemcpyAsync((char *)arr.a[k].down + (size_t)w0 * arr.a[k].stride, dev[k], bytes_of(arr.a[k], wn), hipMemcpyDeviceToHost, hp->down), "download ", arr.a[k].name);
         if (!err.empty()) break;
-        if (carry_out && !hip_ok(hipMemcpyAsync((char *)carry_out + (size_t)w0 * cd_bytes, hp->cout[s], (size_t)wn * cd_bytes, hipMemcpyDeviceToHost, hp->down), "download carry_out")) break;
         if (!hip_ok(hipEventRecord(hp->ev_out[s], hp->down), "hipEventRecord")) break;
     }
     const hipError_t e1 = hipStreamSynchronize(hp->up), e2 = hipStreamSynchronize(ctx->stream), e3 = hipStreamSynchronize(hp->down);
     if (rc != CPI_OK) return rc;   // message already set by the device-pointer entry
-    const char *who = running ? (carry_out ? "cpi_preintegrate_running_resume_host: " : "cpi_preintegrate_running_host: ") : "cpi_preintegrate_batch_host: ";
-    if (!err.empty()) return fail(ctx, CPI_ERR_HIP, who + err);
     hip_ok(e1, "hipStreamSynchronize(upload)"); hip_ok(e2, "hipStreamSynchronize"); hip_ok(e3, "hipStreamSynchronize(download)");
-    if (!err.empty()) return fail(ctx, CPI_ERR_HIP, who + err);
+    if (!err.empty()) return fail(ctx, CPI_ERR_HIP, std::string(who) + ": " + err);
     return CPI_OK;
 }
 
 extern "C" int cpi_preintegrate_tiled_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N, const double *tiles,
                                                  const int32_t *count, const double *lin, const double *q_k_lin, const cpi_outputs *out) {
+    static const char who[] = "cpi_preintegrate_tiled_batch_host";
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
-    if (!prm || !out || !tiles || !lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_tiled_batch_host: NULL argument");
+    if (!prm || !out || !tiles || !lin) return refuse(ctx, who, "NULL argument");
     if (W <= 0) return W == 0 ? CPI_OK : fail(ctx, CPI_ERR_INVALID, "negative size");
     if (N < 0) return fail(ctx, CPI_ERR_INVALID, "negative size");
-    if (out->J_q || out->J_a || out->J_b || out->H_a || out->H_b || out->O_a || out->O_b || out->P || out->P_sym)
-        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_tiled_batch_host: the tiled layout serves the mean outputs (DT, alpha, beta, q) only");
+    if (request_of(out).jac || request_of(out).cov) return refuse(ctx, who, kTiledMeansOnly);
     DeviceGuard guard_;
     CPI_HIP(ctx, guard_.enter(ctx->device));
-    return preintegrate_host_pipeline(ctx, prm, W, N, tiles, true, count, lin, q_k_lin, out);
+    return preintegrate_host_pipeline(ctx, who, W, 1, pipe_windows(tiles, N, 64, count, lin, q_k_lin), out,
+                                      [&](int64_t wn, void *const *dev, const cpi_outputs *d) {
+                                          return cpi_preintegrate_tiled_batch(ctx, prm, wn, N, (const double *)dev[0], (const int32_t *)dev[1],
+                                                                              (const double *)dev[2], (const double *)dev[3], d);
+                                      });
 }
 
 extern "C" int cpi_preintegrate_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                                            const double *knots, const int64_t *first, const int32_t *count,
                                            int64_t n_knots, const double *lin, const double *q_k_lin,
                                            const cpi_outputs *out) {
+    static const char who[] = "cpi_preintegrate_batch_host";
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
-    if (!prm || !out || !knots || !lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_batch_host: NULL argument");
+    if (!prm || !out || !knots || !lin) return refuse(ctx, who, "NULL argument");
     if (W <= 0) return W == 0 ? CPI_OK : fail(ctx, CPI_ERR_INVALID, "negative size");
     if (N < 0) return fail(ctx, CPI_ERR_INVALID, "negative size");
     DeviceGuard guard_;
     CPI_HIP(ctx, guard_.enter(ctx->device));
-    if (!first) return preintegrate_host_pipeline(ctx, prm, W, N, knots, false, count, lin, q_k_lin, out);
+    if (!first)
+        return preintegrate_host_pipeline(ctx, who, W, 1, pipe_windows(knots, N, 1, count, lin, q_k_lin), out,
+                                          [&](int64_t wn, void *const *dev, const cpi_outputs *d) {
+                                              return cpi_preintegrate_batch(ctx, prm, wn, N, (const double *)dev[0], nullptr, (const int32_t *)dev[1],
+                                                                            (const double *)dev[2], (const double *)dev[3], d);
+                                          });
     // ragged windows share one knot stream: staged whole (one-off calls; the stream is usually small)
-    DevBuf dk, df, dc, dl, dq, dout[kOutFields];
-    CPI_UP(dk, knots, (size_t)n_knots * 7 * sizeof(double));
-    CPI_UP(df, first, (size_t)W * sizeof(int64_t));
-    CPI_UP(dc, count, (size_t)W * sizeof(int32_t));
-    CPI_UP(dl, lin, (size_t)W * 6 * sizeof(double));
-    CPI_UP(dq, q_k_lin, (size_t)W * 4 * sizeof(double));
-    cpi_outputs d = *out, h = *out;
-    for (int k = 0; k < kOutFields; k++)
-        if (*out_field(&h, k)) {
-            CPI_HIP(ctx, hipMalloc(&dout[k].p, (size_t)W * OUT_N[k] * sizeof(double)));
-            *out_field(&d, k) = (double *)dout[k].p;
-        }
-    int rc = cpi_preintegrate_batch(ctx, prm, W, N, (const double *)dk.p, (const int64_t *)df.p, (const int32_t *)dc.p,
-                                    (const double *)dl.p, (const double *)dq.p, &d);
-    if (rc != CPI_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    for (int k = 0; k < kOutFields; k++)
-        if (*out_field(&h, k))
-            CPI_HIP(ctx, hipMemcpyAsync(*out_field(&h, k), dout[k].p, (size_t)W * OUT_N[k] * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    CPI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CPI_OK;
+    Staging st(ctx);
+    WindowsDev in;
+    cpi_outputs d;
+    CPI_TRY(stage_windows(st, W, n_knots, knots, first, count, lin, q_k_lin, &in));
+    CPI_TRY(st.mirror(out, (size_t)W, &d));
+    CPI_TRY(cpi_preintegrate_batch(ctx, prm, W, N, in.knots, in.first, in.count, in.lin, in.qk, &d));
+    CPI_TRY(st.download(out, d, (size_t)W));
+    return st.finish();
 }
 
 extern "C" int cpi_preintegrate_running_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                                              const double *knots, const int64_t *first, const int32_t *count,
                                              int64_t n_knots, const double *lin, const double *q_k_lin,
                                              const cpi_outputs *rows) {
+    static const char who[] = "cpi_preintegrate_running_host";
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
-    if (!prm || !rows || !knots || !lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_host: NULL argument");
+    if (!prm || !rows || !knots || !lin) return refuse(ctx, who, "NULL argument");
     if (W < 0 || N < 0) return fail(ctx, CPI_ERR_INVALID, "negative size");
-    if (prm->model != CPI_MODEL_V1 && prm->model != CPI_MODEL_V2)
-        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_host: model must be 1 or 2 (the Forster comparator has no running form)");
-    if (prm->model == CPI_MODEL_V2 && (rows->J_q || rows->J_a || rows->J_b || rows->H_a || rows->H_b || rows->O_a || rows->O_b))
-        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_host: the Jacobian fields (J_q ... O_b) are not available for model 2");
+    if (!model_is_cpi(prm)) return refuse_forster(ctx, who, NO_RUNNING_FORM);
+    if (prm->model == CPI_MODEL_V2 && request_of(rows).jac) return refuse_v2_jac(ctx, who, nullptr);
     if (W == 0 || N == 0) return CPI_OK;
-    if (N > 65535) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_host: N (intervals per window) must be <= 65535");
+    CPI_TRY(check_N(ctx, who, N));
     DeviceGuard guard_;
     CPI_HIP(ctx, guard_.enter(ctx->device));
-    if (!first) return preintegrate_host_pipeline(ctx, prm, W, N, knots, false, count, lin, q_k_lin, rows, true);
+    if (!first)
+        return preintegrate_host_pipeline(ctx, who, W, (size_t)N, pipe_windows(knots, N, 1, count, lin, q_k_lin), rows,
+                                          [&](int64_t wn, void *const *dev, const cpi_outputs *d) {
+                                              return cpi_preintegrate_running(ctx, prm, wn, N, (const double *)dev[0], nullptr, (const int32_t *)dev[1],
+                                                                              (const double *)dev[2], (const double *)dev[3], d);
+                                          });
     // ragged windows share one knot stream: staged whole, as in cpi_preintegrate_batch_host
-    if (n_knots <= 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_host: n_knots must be > 0");
-    DevBuf dk, df, dc, dl, dq, dout[kOutFields];
-    CPI_UP(dk, knots, (size_t)n_knots * 7 * sizeof(double));
-    CPI_UP(df, first, (size_t)W * sizeof(int64_t));
-    CPI_UP(dc, count, (size_t)W * sizeof(int32_t));
-    CPI_UP(dl, lin, (size_t)W * 6 * sizeof(double));
-    CPI_UP(dq, q_k_lin, (size_t)W * 4 * sizeof(double));
-    const size_t nrows = (size_t)W * (size_t)N;
-    cpi_outputs d = *rows, h = *rows;
-    for (int k = 0; k < kOutFields; k++)
-        if (*out_field(&h, k)) {
-            CPI_HIP(ctx, hipMalloc(&dout[k].p, nrows * OUT_N[k] * sizeof(double)));
-            *out_field(&d, k) = (double *)dout[k].p;
-        }
-    int rc = cpi_preintegrate_running(ctx, prm, W, N, (const double *)dk.p, (const int64_t *)df.p, (const int32_t *)dc.p,
-                                      (const double *)dl.p, (const double *)dq.p, &d);
-    if (rc != CPI_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    for (int k = 0; k < kOutFields; k++)
-        if (*out_field(&h, k))
-            CPI_HIP(ctx, hipMemcpyAsync(*out_field(&h, k), dout[k].p, nrows * OUT_N[k] * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    CPI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CPI_OK;
+    if (n_knots <= 0) return refuse(ctx, who, "n_knots must be > 0");
+    Staging st(ctx);
+    WindowsDev in;
+    cpi_outputs d;
+    CPI_TRY(stage_windows(st, W, n_knots, knots, first, count, lin, q_k_lin, &in));
+    CPI_TRY(st.mirror(rows, (size_t)W * (size_t)N, &d));
+    CPI_TRY(cpi_preintegrate_running(ctx, prm, W, N, in.knots, in.first, in.count, in.lin, in.qk, &d));
+    CPI_TRY(st.download(rows, d, (size_t)W * (size_t)N));
+    return st.finish();
+}
+
+// the staged-whole form of the two resume entries: the records go up and come down with the windows.  rows_per_window: 1
+// (cpi_preintegrate_resume), N (the running rows; 0 rows: only the record is computed)
+template <class Entry>
+static int resume_staged(cpi_ctx *ctx, Entry entry, const cpi_params *prm, int64_t W, int32_t N, size_t rows_per_window, const double *knots,
+                         const int64_t *first, const int32_t *count, int64_t n_knots, const double *lin, const double *q_k_lin,
+                         const double *carry_in, double *carry_out, const cpi_outputs *out) {
+    const size_t cd = (size_t)W * (size_t)carry::doubles(prm->model);
+    Staging st(ctx);
+    WindowsDev in;
+    const double *dci;
+    double *dco;
+    cpi_outputs d;
+    CPI_TRY(stage_windows(st, W, n_knots, knots, first, count, lin, q_k_lin, &in));
+    CPI_TRY(st.upload(carry_in, cd, &dci));
+    CPI_TRY(st.alloc(cd, &dco));
+    CPI_TRY(st.mirror(out, (size_t)W * rows_per_window, &d));
+    CPI_TRY(entry(ctx, prm, W, N, in.knots, in.first, in.count, in.lin, in.qk, dci, dco, &d));
+    CPI_TRY(st.download(out, d, (size_t)W * rows_per_window));
+    CPI_TRY(st.download(carry_out, (const double *)dco, cd));
+    return st.finish();
 }
 
 extern "C" int cpi_preintegrate_resume_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                                             const double *knots, const int64_t *first, const int32_t *count,
                                             int64_t n_knots, const double *lin, const double *q_k_lin,
                                             const double *carry_in, double *carry_out, const cpi_outputs *out) {
+    static const char who[] = "cpi_preintegrate_resume_host";
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
-    if (!prm || !out || !knots || !lin || !carry_out) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_resume_host: NULL argument");
+    if (!prm || !out || !knots || !lin || !carry_out) return refuse(ctx, who, "NULL argument");
     if (W <= 0) return W == 0 ? CPI_OK : fail(ctx, CPI_ERR_INVALID, "negative size");
     if (N < 0) return fail(ctx, CPI_ERR_INVALID, "negative size");
-    if (prm->model != CPI_MODEL_V1 && prm->model != CPI_MODEL_V2)
-        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_resume_host: model must be 1 or 2 (the Forster comparator cannot be resumed)");
-    const size_t cd = (size_t)carry::doubles(prm->model);
-    if (carry_in && carry_in < carry_out + W * cd && carry_out < carry_in + W * cd)
-        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_resume_host: carry_in and carry_out overlap");
+    if (!model_is_cpi(prm)) return refuse_forster(ctx, who, NOT_RESUMABLE);
+    CPI_TRY(check_carry_overlap(ctx, who, prm, W, carry_in, carry_out));
     if (!first) n_knots = W * (int64_t)(N + 1);
-    if (n_knots <= 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_resume_host: n_knots must be > 0");
+    if (n_knots <= 0) return refuse(ctx, who, "n_knots must be > 0");
     DeviceGuard guard_;
     CPI_HIP(ctx, guard_.enter(ctx->device));
-    DevBuf dk, df, dc, dl, dq, dci, dco, dout[kOutFields];
-    CPI_UP(dk, knots, (size_t)n_knots * 7 * sizeof(double));
-    CPI_UP(df, first, (size_t)W * sizeof(int64_t));
-    CPI_UP(dc, count, (size_t)W * sizeof(int32_t));
-    CPI_UP(dl, lin, (size_t)W * 6 * sizeof(double));
-    CPI_UP(dq, q_k_lin, (size_t)W * 4 * sizeof(double));
-    CPI_UP(dci, carry_in, (size_t)W * cd * sizeof(double));
-    CPI_HIP(ctx, hipMalloc(&dco.p, (size_t)W * cd * sizeof(double)));
-    cpi_outputs d = *out, h = *out;
-    for (int k = 0; k < kOutFields; k++)
-        if (*out_field(&h, k)) {
-            CPI_HIP(ctx, hipMalloc(&dout[k].p, (size_t)W * OUT_N[k] * sizeof(double)));
-            *out_field(&d, k) = (double *)dout[k].p;
-        }
-    int rc = cpi_preintegrate_resume(ctx, prm, W, N, (const double *)dk.p, (const int64_t *)df.p, (const int32_t *)dc.p,
-                                     (const double *)dl.p, (const double *)dq.p, (const double *)dci.p, (double *)dco.p, &d);
-    if (rc != CPI_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    for (int k = 0; k < kOutFields; k++)
-        if (*out_field(&h, k))
-            CPI_HIP(ctx, hipMemcpyAsync(*out_field(&h, k), dout[k].p, (size_t)W * OUT_N[k] * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    CPI_HIP(ctx, hipMemcpyAsync(carry_out, dco.p, (size_t)W * cd * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    CPI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CPI_OK;
+    return resume_staged(ctx, cpi_preintegrate_resume, prm, W, N, 1, knots, first, count, n_knots, lin, q_k_lin, carry_in, carry_out, out);
 }
 
 // cpi_preintegrate_running_resume from host memory: dense batches through the chunked pipeline (the records of a chunk travel with
@@ -1694,47 +1712,62 @@ extern "C" int cpi_preintegrate_running_resume_host(cpi_ctx *ctx, const cpi_para
                                                     const double *knots, const int64_t *first, const int32_t *count,
                                                     int64_t n_knots, const double *lin, const double *q_k_lin,
                                                     const double *carry_in, double *carry_out, const cpi_outputs *rows) {
+    static const char who[] = "cpi_preintegrate_running_resume_host";
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
-    if (!prm || !rows || !knots || !lin || !carry_out) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume_host: NULL argument");
+    if (!prm || !rows || !knots || !lin || !carry_out) return refuse(ctx, who, "NULL argument");
     if (W < 0 || N < 0) return fail(ctx, CPI_ERR_INVALID, "negative size");
-    if (prm->model != CPI_MODEL_V1 && prm->model != CPI_MODEL_V2)
-        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume_host: model must be 1 or 2 (the Forster comparator has no running form and cannot be resumed)");
-    if (prm->model == CPI_MODEL_V2 && (rows->J_q || rows->J_a || rows->J_b || rows->H_a || rows->H_b || rows->O_a || rows->O_b))
-        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume_host: the Jacobian fields (J_q ... O_b) are not available for model 2");
-    const size_t cd = (size_t)carry::doubles(prm->model);
-    if (carry_in && carry_in < carry_out + W * cd && carry_out < carry_in + W * cd)
-        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume_host: carry_in and carry_out overlap");
+    if (!model_is_cpi(prm)) return refuse_forster(ctx, who, NO_RUNNING_FORM | NOT_RESUMABLE);
+    if (prm->model == CPI_MODEL_V2 && request_of(rows).jac) return refuse_v2_jac(ctx, who, nullptr);
+    CPI_TRY(check_carry_overlap(ctx, who, prm, W, carry_in, carry_out));
     if (W == 0) return CPI_OK;
-    if (N > 65535) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume_host: N (intervals per window) must be <= 65535");
+    CPI_TRY(check_N(ctx, who, N));
     DeviceGuard guard_;
     CPI_HIP(ctx, guard_.enter(ctx->device));
-    if (!first && N > 0) return preintegrate_host_pipeline(ctx, prm, W, N, knots, false, count, lin, q_k_lin, rows, true, carry_in, carry_out);
+    if (!first && N > 0) {
+        const size_t cd_bytes = (size_t)carry::doubles(prm->model) * sizeof(double);
+        PipeArrays arr = pipe_windows(knots, N, 1, count, lin, q_k_lin);
+        arr.a[4] = {"carry_in", carry_in, nullptr, cd_bytes, 1};
+        arr.a[5] = {"carry_out", nullptr, carry_out, cd_bytes, 1};
+        return preintegrate_host_pipeline(ctx, who, W, (size_t)N, arr, rows, [&](int64_t wn, void *const *dev, const cpi_outputs *d) {
+            return cpi_preintegrate_running_resume(ctx, prm, wn, N, (const double *)dev[0], nullptr, (const int32_t *)dev[1], (const double *)dev[2],
+                                                   (const double *)dev[3], (const double *)dev[4], (double *)dev[5], d);
+        });
+    }
     if (!first) n_knots = W * (int64_t)(N + 1);
-    if (n_knots <= 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_running_resume_host: n_knots must be > 0");
-    DevBuf dk, df, dc, dl, dq, dci, dco, dout[kOutFields];
-    CPI_UP(dk, knots, (size_t)n_knots * 7 * sizeof(double));
-    CPI_UP(df, first, (size_t)W * sizeof(int64_t));
-    CPI_UP(dc, count, (size_t)W * sizeof(int32_t));
-    CPI_UP(dl, lin, (size_t)W * 6 * sizeof(double));
-    CPI_UP(dq, q_k_lin, (size_t)W * 4 * sizeof(double));
-    CPI_UP(dci, carry_in, (size_t)W * cd * sizeof(double));
-    CPI_HIP(ctx, hipMalloc(&dco.p, (size_t)W * cd * sizeof(double)));
-    const size_t nrows = (size_t)W * (size_t)N;
-    cpi_outputs d = *rows, h = *rows;
-    for (int k = 0; k < kOutFields; k++)
-        if (*out_field(&h, k) && nrows) {
-            CPI_HIP(ctx, hipMalloc(&dout[k].p, nrows * OUT_N[k] * sizeof(double)));
-            *out_field(&d, k) = (double *)dout[k].p;
-        }
-    int rc = cpi_preintegrate_running_resume(ctx, prm, W, N, (const double *)dk.p, (const int64_t *)df.p, (const int32_t *)dc.p,
-                                             (const double *)dl.p, (const double *)dq.p, (const double *)dci.p, (double *)dco.p, &d);
-    if (rc != CPI_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    for (int k = 0; k < kOutFields; k++)
-        if (*out_field(&h, k) && nrows)
-            CPI_HIP(ctx, hipMemcpyAsync(*out_field(&h, k), dout[k].p, nrows * OUT_N[k] * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    CPI_HIP(ctx, hipMemcpyAsync(carry_out, dco.p, (size_t)W * cd * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    CPI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (n_knots <= 0) return refuse(ctx, who, "n_knots must be > 0");
+    return resume_staged(ctx, cpi_preintegrate_running_resume, prm, W, N, (size_t)N, knots, first, count, n_knots, lin, q_k_lin, carry_in,
+                         carry_out, rows);
+}
+
+// The offsets of a multi-run call as the _host entries can (and do) validate them before anything is enqueued: each array
+// starts at 0, never decreases and ends at K (stream_offsets) / U (update_offsets).
+static int check_offsets(cpi_ctx *ctx, const char *who, int64_t R, const int64_t *stream_offsets, int64_t K, const int64_t *update_offsets, int64_t U) {
+    for (int pass = 0; pass < 2; pass++) {
+        const int64_t *o = pass ? update_offsets : stream_offsets;
+        const int64_t end = pass ? U : K;
+        const char *what = pass ? "update_offsets" : "stream_offsets";
+        if (o[0] != 0) return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": " + what + "[0] is not 0");
+        for (int64_t r = 0; r < R; r++)
+            if (o[r + 1] < o[r]) return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": " + what + " decrease at run " + std::to_string(r));
+        if (o[R] != end) return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": " + what + "[R] is not " + (pass ? "U" : "K"));
+    }
     return CPI_OK;
+}
+// the arrays of the stream entries, staged whole (stream_offsets == NULL: one stream), and a workspace for U windows
+struct StreamsDev {
+    const double *stream, *update, *lin, *qk;
+    const int64_t *soff, *uoff;
+    void *ws;
+};
+static int stage_streams(Staging &st, int64_t R, int64_t K, const double *stream, const int64_t *stream_offsets, int64_t U,
+                         const double *update_times, const int64_t *update_offsets, const double *lin, const double *q_k_lin, StreamsDev *d) {
+    CPI_TRY(st.upload(stream, (size_t)K * 7, &d->stream));
+    CPI_TRY(st.upload(stream_offsets, (size_t)(R + 1), &d->soff));
+    CPI_TRY(st.upload(update_times, (size_t)U, &d->update));
+    CPI_TRY(st.upload(update_offsets, (size_t)(R + 1), &d->uoff));
+    CPI_TRY(st.upload(lin, (size_t)U * 6, &d->lin));
+    CPI_TRY(st.upload(q_k_lin, (size_t)U * 4, &d->qk));
+    return st.alloc(cpi_streams_workspace_bytes(R, U), &d->ws);
 }
 
 // The stream entry from HOST memory: what a GraphSolver-shaped caller holds (its IMU deque as one array, the update times of the
@@ -1743,85 +1776,51 @@ extern "C" int cpi_preintegrate_running_resume_host(cpi_ctx *ctx, const cpi_para
 extern "C" int cpi_preintegrate_stream_host(cpi_ctx *ctx, const cpi_params *prm, int64_t K, const double *stream, int64_t U,
                                             const double *update_times, int32_t N, const double *lin, const double *q_k_lin,
                                             const cpi_outputs *out, int32_t *count) {
+    static const char who[] = "cpi_preintegrate_stream_host";
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
-    if (K < 0 || U < 0 || N < 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_stream_host: negative size");
+    if (K < 0 || U < 0 || N < 0) return refuse(ctx, who, "negative size");
     if (U == 0) return CPI_OK;
-    if (K == 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_stream_host: the stream is empty");
-    if (!prm || !out || !stream || !update_times || !lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_stream_host: NULL argument");
-    if (prm->model == CPI_MODEL_V2 && !q_k_lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_stream_host: model 2 needs q_k_lin");
+    if (K == 0) return refuse(ctx, who, "the stream is empty");
+    if (!prm || !out || !stream || !update_times || !lin) return refuse(ctx, who, "NULL argument");
+    CPI_TRY(check_qk(ctx, who, prm, q_k_lin));
     DeviceGuard guard_;
     CPI_HIP(ctx, guard_.enter(ctx->device));
-    DevBuf ds, du, dl, dq, dw, dout[kOutFields];
-    CPI_UP(ds, stream, (size_t)K * 7 * sizeof(double));
-    CPI_UP(du, update_times, (size_t)U * sizeof(double));
-    CPI_UP(dl, lin, (size_t)U * 6 * sizeof(double));
-    CPI_UP(dq, q_k_lin, (size_t)U * 4 * sizeof(double));
-    CPI_HIP(ctx, hipMalloc(&dw.p, cpi_stream_workspace_bytes(U)));
-    cpi_outputs d = *out, h = *out;
-    for (int k = 0; k < kOutFields; k++)
-        if (*out_field(&h, k)) {
-            CPI_HIP(ctx, hipMalloc(&dout[k].p, (size_t)U * OUT_N[k] * sizeof(double)));
-            *out_field(&d, k) = (double *)dout[k].p;
-        }
-    const int rc = cpi_preintegrate_stream(ctx, prm, K, (const double *)ds.p, U, (const double *)du.p, N, (const double *)dl.p,
-                                           (const double *)dq.p, dw.p, &d);
-    if (rc != CPI_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    for (int k = 0; k < kOutFields; k++)
-        if (*out_field(&h, k))
-            CPI_HIP(ctx, hipMemcpyAsync(*out_field(&h, k), dout[k].p, (size_t)U * OUT_N[k] * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (count) CPI_HIP(ctx, hipMemcpyAsync(count, cpi_stream_counts(dw.p, U), (size_t)U * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    CPI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CPI_OK;
+    Staging st(ctx);
+    StreamsDev in;
+    cpi_outputs d;
+    CPI_TRY(stage_streams(st, 0, K, stream, nullptr, U, update_times, nullptr, lin, q_k_lin, &in));
+    CPI_TRY(st.mirror(out, (size_t)U, &d));
+    CPI_TRY(cpi_preintegrate_stream(ctx, prm, K, in.stream, U, in.update, N, in.lin, in.qk, in.ws, &d));
+    CPI_TRY(st.download(out, d, (size_t)U));
+    if (count) CPI_TRY(st.download(count, cpi_stream_counts(in.ws, U), (size_t)U));
+    return st.finish();
 }
 
-// The multi-run entry from HOST memory.  Unlike the device entry it can read the offsets, and it validates them before anything is
-// enqueued: each array starts at 0, never decreases and ends at K (stream_offsets) / U (update_offsets).
+// The multi-run entry from HOST memory.  Unlike the device entry it can read the offsets (check_offsets).
 extern "C" int cpi_preintegrate_streams_host(cpi_ctx *ctx, const cpi_params *prm, int64_t R, int64_t K, const double *stream,
                                              const int64_t *stream_offsets, int64_t U, const double *update_times,
                                              const int64_t *update_offsets, int32_t N, const double *lin, const double *q_k_lin,
                                              const cpi_outputs *out, int32_t *count) {
+    static const char who[] = "cpi_preintegrate_streams_host";
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
-    if (R < 0 || K < 0 || U < 0 || N < 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams_host: negative size");
+    if (R < 0 || K < 0 || U < 0 || N < 0) return refuse(ctx, who, "negative size");
     if (U == 0) return CPI_OK;
-    if (R == 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams_host: U > 0 windows and no run");
-    if (K == 0) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams_host: the streams hold no reading");
-    if (!prm || !out || !stream || !stream_offsets || !update_times || !update_offsets || !lin)
-        return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams_host: NULL argument");
-    if (prm->model == CPI_MODEL_V2 && !q_k_lin) return fail(ctx, CPI_ERR_INVALID, "cpi_preintegrate_streams_host: model 2 needs q_k_lin");
-    for (int pass = 0; pass < 2; pass++) {
-        const int64_t *o = pass ? update_offsets : stream_offsets;
-        const int64_t end = pass ? U : K;
-        const char *what = pass ? "update_offsets" : "stream_offsets";
-        if (o[0] != 0) return fail(ctx, CPI_ERR_INVALID, std::string("cpi_preintegrate_streams_host: ") + what + "[0] is not 0");
-        for (int64_t r = 0; r < R; r++)
-            if (o[r + 1] < o[r]) return fail(ctx, CPI_ERR_INVALID, std::string("cpi_preintegrate_streams_host: ") + what + " decrease at run " + std::to_string(r));
-        if (o[R] != end) return fail(ctx, CPI_ERR_INVALID, std::string("cpi_preintegrate_streams_host: ") + what + "[R] is not " + (pass ? "U" : "K"));
-    }
+    if (R == 0) return refuse(ctx, who, "U > 0 windows and no run");
+    if (K == 0) return refuse(ctx, who, "the streams hold no reading");
+    if (!prm || !out || !stream || !stream_offsets || !update_times || !update_offsets || !lin) return refuse(ctx, who, "NULL argument");
+    CPI_TRY(check_qk(ctx, who, prm, q_k_lin));
+    CPI_TRY(check_offsets(ctx, who, R, stream_offsets, K, update_offsets, U));
     DeviceGuard guard_;
     CPI_HIP(ctx, guard_.enter(ctx->device));
-    DevBuf ds, dso, du, duo, dl, dq, dw, dout[kOutFields];
-    CPI_UP(ds, stream, (size_t)K * 7 * sizeof(double));
-    CPI_UP(dso, stream_offsets, (size_t)(R + 1) * sizeof(int64_t));
-    CPI_UP(du, update_times, (size_t)U * sizeof(double));
-    CPI_UP(duo, update_offsets, (size_t)(R + 1) * sizeof(int64_t));
-    CPI_UP(dl, lin, (size_t)U * 6 * sizeof(double));
-    CPI_UP(dq, q_k_lin, (size_t)U * 4 * sizeof(double));
-    CPI_HIP(ctx, hipMalloc(&dw.p, cpi_streams_workspace_bytes(R, U)));
-    cpi_outputs d = *out, h = *out;
-    for (int k = 0; k < kOutFields; k++)
-        if (*out_field(&h, k)) {
-            CPI_HIP(ctx, hipMalloc(&dout[k].p, (size_t)U * OUT_N[k] * sizeof(double)));
-            *out_field(&d, k) = (double *)dout[k].p;
-        }
-    const int rc = cpi_preintegrate_streams(ctx, prm, R, K, (const double *)ds.p, (const int64_t *)dso.p, U, (const double *)du.p,
-                                            (const int64_t *)duo.p, N, (const double *)dl.p, (const double *)dq.p, dw.p, &d);
-    if (rc != CPI_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    for (int k = 0; k < kOutFields; k++)
-        if (*out_field(&h, k))
-            CPI_HIP(ctx, hipMemcpyAsync(*out_field(&h, k), dout[k].p, (size_t)U * OUT_N[k] * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (count) CPI_HIP(ctx, hipMemcpyAsync(count, cpi_stream_counts(dw.p, U), (size_t)U * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    CPI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CPI_OK;
+    Staging st(ctx);
+    StreamsDev in;
+    cpi_outputs d;
+    CPI_TRY(stage_streams(st, R, K, stream, stream_offsets, U, update_times, update_offsets, lin, q_k_lin, &in));
+    CPI_TRY(st.mirror(out, (size_t)U, &d));
+    CPI_TRY(cpi_preintegrate_streams(ctx, prm, R, K, in.stream, in.soff, U, in.update, in.uoff, N, in.lin, in.qk, in.ws, &d));
+    CPI_TRY(st.download(out, d, (size_t)U));
+    if (count) CPI_TRY(st.download(count, cpi_stream_counts(in.ws, U), (size_t)U));
+    return st.finish();
 }
 
 // The running stream entries from HOST memory: the stream(s) are uploaded once, whole, and cut on the device; the U * N rows come
@@ -1833,61 +1832,33 @@ static int stream_running_host_impl(cpi_ctx *ctx, const char *who, const cpi_par
                                     const int64_t *update_offsets, int32_t N, const double *lin, const double *q_k_lin,
                                     const cpi_outputs *rows, int32_t *count) {
     bool noop;
-    int rc = stream_running_check(ctx, who, prm, many, R, K, U, N, stream, stream_offsets, update_times, update_offsets, lin, q_k_lin, rows, noop);
+    const int rc = stream_running_check(ctx, who, prm, many, R, K, U, N, stream, stream_offsets, update_times, update_offsets, lin, q_k_lin, rows, noop);
     if (rc != CPI_OK || noop) return rc;
-    if (many) {
-        for (int pass = 0; pass < 2; pass++) {
-            const int64_t *o = pass ? update_offsets : stream_offsets;
-            const int64_t end = pass ? U : K;
-            const char *what = pass ? "update_offsets" : "stream_offsets";
-            if (o[0] != 0) return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": " + what + "[0] is not 0");
-            for (int64_t r = 0; r < R; r++)
-                if (o[r + 1] < o[r]) return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": " + what + " decrease at run " + std::to_string(r));
-            if (o[R] != end) return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": " + what + "[R] is not " + (pass ? "U" : "K"));
-        }
-    }
+    if (many) CPI_TRY(check_offsets(ctx, who, R, stream_offsets, K, update_offsets, U));
     DeviceGuard guard_;
     CPI_HIP(ctx, guard_.enter(ctx->device));
-    DevBuf ds, dso, du, duo, dl, dq, dw, dout[kOutFields];
-    CPI_UP(ds, stream, (size_t)K * 7 * sizeof(double));
-    if (many) {
-        CPI_UP(dso, stream_offsets, (size_t)(R + 1) * sizeof(int64_t));
-        CPI_UP(duo, update_offsets, (size_t)(R + 1) * sizeof(int64_t));
-    }
-    CPI_UP(du, update_times, (size_t)U * sizeof(double));
-    CPI_UP(dl, lin, (size_t)U * 6 * sizeof(double));
-    CPI_UP(dq, q_k_lin, (size_t)U * 4 * sizeof(double));
-    CPI_HIP(ctx, hipMalloc(&dw.p, many ? cpi_streams_workspace_bytes(R, U) : cpi_stream_workspace_bytes(U)));
+    Staging st(ctx);
+    StreamsDev in;
+    cpi_outputs d;
+    CPI_TRY(stage_streams(st, many ? R : 0, K, stream, many ? stream_offsets : nullptr, U, update_times, many ? update_offsets : nullptr, lin, q_k_lin, &in));
     // windows per chunk: as many whole windows as 2^18 rows hold (whole wavefronts of one-lane windows when that is 64 or more;
     // N <= 65535, so at least 4), never more than 2^18 rows of staging per output array
     int64_t cw = std::max<int64_t>(1, ((int64_t)1 << 18) / N);
     if (cw >= 64) cw = cw / 64 * 64;
     cw = std::min<int64_t>(U, cw);
-    cpi_outputs d = *rows, h = *rows;
-    for (int k = 0; k < kOutFields; k++)
-        if (*out_field(&h, k)) {
-            CPI_HIP(ctx, hipMalloc(&dout[k].p, (size_t)cw * (size_t)N * OUT_N[k] * sizeof(double)));
-            *out_field(&d, k) = (double *)dout[k].p;
-        }
+    CPI_TRY(st.mirror(rows, (size_t)cw * (size_t)N, &d));
     RunArgs ra;
-    ra.soff = (const long long *)dso.p; ra.uoff = (const long long *)duo.p; ra.R = (int)R;
-    const StreamCut sc = stream_cut(K, (const double *)du.p, dw.p, U, many ? &ra : nullptr);
-    rc = stream_running_cut(ctx, sc, (const double *)ds.p, U, N);
+    ra.soff = (const long long *)in.soff; ra.uoff = (const long long *)in.uoff; ra.R = (int)R;
+    const StreamCut sc = stream_cut(K, in.update, in.ws, U, many ? &ra : nullptr);
+    CPI_TRY(cut_launch(ctx, sc, in.stream, U, N));
     const int L = stream_running_lanes(prm, U, N, rows);
-    for (int64_t w0 = 0; w0 < U && rc == CPI_OK; w0 += cw) {
+    for (int64_t w0 = 0; w0 < U; w0 += cw) {
         const int64_t wn = std::min<int64_t>(cw, U - w0);
-        rc = stream_running_launch(ctx, prm, sc, (const double *)ds.p, N, L, (const double *)dl.p, (const double *)dq.p, &d, w0, wn);
-        for (int k = 0; k < kOutFields && rc == CPI_OK; k++)
-            if (*out_field(&h, k)) {
-                const hipError_t e = hipMemcpyAsync(*out_field(&h, k) + (size_t)w0 * (size_t)N * OUT_N[k], dout[k].p,
-                                                    (size_t)wn * (size_t)N * OUT_N[k] * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-                if (e != hipSuccess) rc = fail(ctx, CPI_ERR_HIP, std::string(who) + ": download: " + hipGetErrorString(e));
-            }
+        CPI_TRY(stream_running_launch(ctx, prm, sc, in.stream, N, L, in.lin, in.qk, &d, w0, wn));
+        CPI_TRY(st.download(rows, d, (size_t)wn * (size_t)N, (size_t)w0 * (size_t)N));
     }
-    if (rc != CPI_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }   // nothing returns while a copy is in flight
-    if (count) CPI_HIP(ctx, hipMemcpyAsync(count, cpi_stream_counts(dw.p, U), (size_t)U * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    CPI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CPI_OK;
+    if (count) CPI_TRY(st.download(count, cpi_stream_counts(in.ws, U), (size_t)U));
+    return st.finish();
 }
 extern "C" int cpi_preintegrate_stream_running_host(cpi_ctx *ctx, const cpi_params *prm, int64_t K, const double *stream, int64_t U,
                                                     const double *update_times, int32_t N, const double *lin, const double *q_k_lin,
@@ -1917,28 +1888,28 @@ extern "C" int cpi_factor_eval_batch_host(cpi_ctx *ctx, int32_t model, const dou
             return fail(ctx, CPI_ERR_INVALID, "cpi_factor_eval_batch_host: state index out of range at factor " + std::to_string(f));
     DeviceGuard guard_;
     CPI_HIP(ctx, guard_.enter(ctx->device));
-    DevBuf dl, dq, ds, di, dj, de, dh1, dh2, dm[11];
-    cpi_outputs hm = *meas, d;
+    Staging st(ctx);
+    cpi_outputs d;
     memset(&d, 0, sizeof d);
-    for (int k = 0; k < 11; k++)
-        if (*out_field(&hm, k)) {
-            CPI_UP(dm[k], *out_field(&hm, k), (size_t)F * OUT_N[k] * sizeof(double));
-            *out_field(&d, k) = (double *)dm[k].p;
-        }
-    CPI_UP(dl, lin, (size_t)F * 6 * sizeof(double));
-    CPI_UP(dq, q_k_lin, (size_t)F * 4 * sizeof(double));
-    CPI_UP(ds, states, (size_t)S * 16 * sizeof(double));
-    CPI_UP(di, idx_i, (size_t)F * sizeof(int32_t));
-    CPI_UP(dj, idx_j, (size_t)F * sizeof(int32_t));
-    CPI_HIP(ctx, hipMalloc(&de.p, (size_t)F * 15 * sizeof(double)));
-    if (H1) CPI_HIP(ctx, hipMalloc(&dh1.p, (size_t)F * 225 * sizeof(double)));
-    if (H2) CPI_HIP(ctx, hipMalloc(&dh2.p, (size_t)F * 225 * sizeof(double)));
-    int rc = cpi_factor_eval_batch(ctx, model, grav, F, &d, (const double *)dl.p, (const double *)dq.p, (const double *)ds.p, S,
-                                   (const int32_t *)di.p, (const int32_t *)dj.p, (double *)de.p, (double *)dh1.p, (double *)dh2.p);
-    if (rc != CPI_OK) return rc;
-    CPI_HIP(ctx, hipMemcpyAsync(err, de.p, (size_t)F * 15 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (H1) CPI_HIP(ctx, hipMemcpyAsync(H1, dh1.p, (size_t)F * 225 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (H2) CPI_HIP(ctx, hipMemcpyAsync(H2, dh2.p, (size_t)F * 225 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    CPI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CPI_OK;
+    for (int k = 0; k < 11; k++) {   // the measurement: every field but P / P_sym
+        const double *dm;
+        CPI_TRY(st.upload((const double *)out_field_c(meas, k), (size_t)F * OUT_N[k], &dm));
+        *out_field(&d, k) = const_cast<double *>(dm);
+    }
+    const double *dl, *dq, *ds;
+    const int32_t *di, *dj;
+    double *de, *dh1 = nullptr, *dh2 = nullptr;
+    CPI_TRY(st.upload(lin, (size_t)F * 6, &dl));
+    CPI_TRY(st.upload(q_k_lin, (size_t)F * 4, &dq));
+    CPI_TRY(st.upload(states, (size_t)S * 16, &ds));
+    CPI_TRY(st.upload(idx_i, (size_t)F, &di));
+    CPI_TRY(st.upload(idx_j, (size_t)F, &dj));
+    CPI_TRY(st.alloc((size_t)F * 15, &de));
+    if (H1) CPI_TRY(st.alloc((size_t)F * 225, &dh1));
+    if (H2) CPI_TRY(st.alloc((size_t)F * 225, &dh2));
+    CPI_TRY(cpi_factor_eval_batch(ctx, model, grav, F, &d, dl, dq, ds, S, di, dj, de, dh1, dh2));
+    CPI_TRY(st.download(err, (const double *)de, (size_t)F * 15));
+    if (H1) CPI_TRY(st.download(H1, (const double *)dh1, (size_t)F * 225));
+    if (H2) CPI_TRY(st.download(H2, (const double *)dh2, (size_t)F * 225));
+    return st.finish();
 }

@@ -170,21 +170,43 @@ class Engine:
             setattr(o, name, t.data_ptr() if t is not None else None)
         return o
 
+    @staticmethod
+    def _window_shape(knots, lin, first=None, count=None, N=None, others=(), cuda=True):
+        """(W, N) of a batch -- dense knots [W, N + 1, 7], or ragged (first given: N = max intervals per window) -- after the
+        asserts every windowed entry makes of its inputs (others: the remaining tensors, None allowed)."""
+        if first is None:
+            W, n1, _ = knots.shape
+            N = n1 - 1
+        else:
+            W = first.shape[0]
+            assert N is not None, "ragged layout needs N = max intervals per window"
+        for t in (knots, lin, first, count) + tuple(others):
+            assert t is None or (t.is_cuda == cuda and t.is_contiguous()), "inputs must be contiguous %s tensors" % ("CUDA" if cuda else "CPU")
+        assert knots.dtype == torch.float64 and lin.dtype == torch.float64 and (count is None or count.dtype == torch.int32)
+        return W, N
+
+    def _carry_out(self, W, model, carry_in, carry_out, **where):
+        """carry_out, allocated ([W, carry_doubles] float64; where: device= or pin_memory=) when not given; both records checked."""
+        cd = self.carry_doubles(model)
+        if carry_out is None and cd > 0:
+            carry_out = torch.empty((W, cd), dtype=torch.float64, **where)
+        for t in (carry_in, carry_out):
+            assert t is None or (t.dtype == torch.float64 and t.numel() >= W * cd), "carry records are [W, carry_doubles] float64"
+        return carry_out
+
+    @staticmethod
+    def _host_outputs(lead, groups, model, pinned):
+        """CPU tensors of leading shape `lead` ((W,) or (W, N)) for the fields of these want-groups, page-locked when pinned."""
+        return {name: torch.empty(lead if n == 1 else lead + (n,), dtype=torch.float64, pin_memory=pinned)
+                for name, n in OUT_FIELDS if _group_of(name) in groups and (model == 2 or name not in ("O_a", "O_b"))}
+
     def preintegrate(self, knots, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), first=None,
                      count=None, N=None, out=None):
         """knots [W,N+1,7] (dense) or [K,7] with first[W] (int64) / count[W] (int32); lin [W,6];
         q_k_lin [W,4].  All CUDA float64 tensors.  Returns a dict of device tensors (matrices flat,
         column-major).  Asynchronous on the engine's stream."""
         params = params or self.make_params()
-        if first is None:
-            W, n1, seven = knots.shape
-            N = n1 - 1
-        else:
-            W = first.shape[0]
-            assert N is not None, "ragged layout needs N = max intervals per window"
-        for t in (knots, lin, q_k_lin, first, count):
-            assert t is None or (t.is_cuda and t.is_contiguous()), "inputs must be contiguous CUDA tensors"
-        assert knots.dtype == torch.float64 and lin.dtype == torch.float64
+        W, N = self._window_shape(knots, lin, first, count, N, (q_k_lin,))
         if out is None:
             out = self.alloc_outputs(W, want, params.model)
         o = self._outputs_struct(out)
@@ -203,19 +225,8 @@ class Engine:
         zero state) over these knots (layouts as in preintegrate).  Returns (out, carry_out); out holds the measurement of all
         the intervals so far, carry_out (allocated when not given) the state to continue from.  Asynchronous."""
         params = params or self.make_params()
-        if first is None:
-            W, n1, seven = knots.shape
-            N = n1 - 1
-        else:
-            W = first.shape[0]
-            assert N is not None, "ragged layout needs N = max intervals per window"
-        for t in (knots, lin, q_k_lin, first, count, carry_in, carry_out):
-            assert t is None or (t.is_cuda and t.is_contiguous()), "inputs must be contiguous CUDA tensors"
-        cd = self.carry_doubles(params.model)
-        if carry_out is None and cd > 0:
-            carry_out = torch.empty((W, cd), dtype=torch.float64, device=self.device)
-        for t in (carry_in, carry_out):
-            assert t is None or (t.dtype == torch.float64 and t.numel() >= W * cd), "carry records are [W, carry_doubles] float64"
+        W, N = self._window_shape(knots, lin, first, count, N, (q_k_lin, carry_in, carry_out))
+        carry_out = self._carry_out(W, params.model, carry_in, carry_out, device=self.device)
         if out is None:
             out = self.alloc_outputs(W, want, params.model)
         o = self._outputs_struct(out)
@@ -243,15 +254,7 @@ class Engine:
         (idx_i[row] = row // N).  Models 1 and 2; Jacobians for model 1 only (the default want drops them for model 2).
         packed / out: as alloc_outputs(W * N, ..., packed) / the dict of an earlier call.  Asynchronous."""
         params = params or self.make_params()
-        if first is None:
-            W, n1, seven = knots.shape
-            N = n1 - 1
-        else:
-            W = first.shape[0]
-            assert N is not None, "ragged layout needs N = max intervals per window"
-        for t in (knots, lin, q_k_lin, first, count):
-            assert t is None or (t.is_cuda and t.is_contiguous()), "inputs must be contiguous CUDA tensors"
-        assert knots.dtype == torch.float64 and lin.dtype == torch.float64
+        W, N = self._window_shape(knots, lin, first, count, N, (q_k_lin,))
         if out is None:
             out = self._running_views(self.alloc_outputs(W * N, self._running_want(tuple(want), params.model), params.model, packed), W, N)
         o = self._outputs_struct({k: v for k, v in out.items() if not k.startswith("_")})
@@ -265,17 +268,9 @@ class Engine:
         """preintegrate_running for a dense batch held in HOST memory (CPU float64 tensors): cpi_preintegrate_running_host.
         Returns a dict of CPU tensors with leading shape [W, N]; synchronous."""
         params = params or self.make_params()
-        W, n1, _ = knots.shape
-        N = n1 - 1
-        for t in (knots, lin, q_k_lin, count):
-            assert t is None or (not t.is_cuda and t.is_contiguous()), "inputs must be contiguous CPU tensors"
-        assert knots.dtype == torch.float64 and lin.dtype == torch.float64 and (count is None or count.dtype == torch.int32)
+        W, N = self._window_shape(knots, lin, count=count, others=(q_k_lin,), cuda=False)
         if out is None:
-            out = {}
-            groups = self._running_want(tuple(want), params.model)
-            for name, n in OUT_FIELDS:
-                if _group_of(name) in groups and (params.model == 2 or name not in ("O_a", "O_b")):
-                    out[name] = torch.empty((W, N) if n == 1 else (W, N, n), dtype=torch.float64, pin_memory=pinned)
+            out = self._host_outputs((W, N), self._running_want(tuple(want), params.model), params.model, pinned)
         o = self._outputs_struct(out)
         self._sync_stream()
         self._check(self.lib.cpi_preintegrate_running_host(self.ctx, C.byref(params), W, N, _ptr(knots), None, _ptr(count), 0,
@@ -291,20 +286,8 @@ class Engine:
         preintegrate_resume returns it -- the state of row N - 1.  The records of the two resume entries are interchangeable.
         Models 1 and 2; Jacobians for model 1 only (the default want drops them for model 2).  Asynchronous."""
         params = params or self.make_params()
-        if first is None:
-            W, n1, seven = knots.shape
-            N = n1 - 1
-        else:
-            W = first.shape[0]
-            assert N is not None, "ragged layout needs N = max intervals per window"
-        for t in (knots, lin, q_k_lin, first, count, carry_in, carry_out):
-            assert t is None or (t.is_cuda and t.is_contiguous()), "inputs must be contiguous CUDA tensors"
-        assert knots.dtype == torch.float64 and lin.dtype == torch.float64
-        cd = self.carry_doubles(params.model)
-        if carry_out is None and cd > 0:
-            carry_out = torch.empty((W, cd), dtype=torch.float64, device=self.device)
-        for t in (carry_in, carry_out):
-            assert t is None or (t.dtype == torch.float64 and t.numel() >= W * cd), "carry records are [W, carry_doubles] float64"
+        W, N = self._window_shape(knots, lin, first, count, N, (q_k_lin, carry_in, carry_out))
+        carry_out = self._carry_out(W, params.model, carry_in, carry_out, device=self.device)
         if out is None:
             out = self._running_views(self.alloc_outputs(W * N, self._running_want(tuple(want), params.model), params.model, packed), W, N)
         o = self._outputs_struct({k: v for k, v in out.items() if not k.startswith("_")})
@@ -318,22 +301,10 @@ class Engine:
         """preintegrate_running_resume for a dense batch held in HOST memory (CPU float64 tensors, the records included):
         cpi_preintegrate_running_resume_host.  Returns (rows, carry_out) as CPU tensors; synchronous."""
         params = params or self.make_params()
-        W, n1, _ = knots.shape
-        N = n1 - 1
-        for t in (knots, lin, q_k_lin, count, carry_in, carry_out):
-            assert t is None or (not t.is_cuda and t.is_contiguous()), "inputs must be contiguous CPU tensors"
-        assert knots.dtype == torch.float64 and lin.dtype == torch.float64 and (count is None or count.dtype == torch.int32)
-        cd = self.carry_doubles(params.model)
-        if carry_out is None and cd > 0:
-            carry_out = torch.empty((W, cd), dtype=torch.float64, pin_memory=pinned)
-        for t in (carry_in, carry_out):
-            assert t is None or (t.dtype == torch.float64 and t.numel() >= W * cd), "carry records are [W, carry_doubles] float64"
+        W, N = self._window_shape(knots, lin, count=count, others=(q_k_lin, carry_in, carry_out), cuda=False)
+        carry_out = self._carry_out(W, params.model, carry_in, carry_out, pin_memory=pinned)
         if out is None:
-            out = {}
-            groups = self._running_want(tuple(want), params.model)
-            for name, n in OUT_FIELDS:
-                if _group_of(name) in groups and (params.model == 2 or name not in ("O_a", "O_b")):
-                    out[name] = torch.empty((W, N) if n == 1 else (W, N, n), dtype=torch.float64, pin_memory=pinned)
+            out = self._host_outputs((W, N), self._running_want(tuple(want), params.model), params.model, pinned)
         o = self._outputs_struct(out)
         self._sync_stream()
         self._check(self.lib.cpi_preintegrate_running_resume_host(self.ctx, C.byref(params), W, N, _ptr(knots), None, _ptr(count), 0,
@@ -345,19 +316,12 @@ class Engine:
         cpi_preintegrate_batch_host.  Returns a dict of CPU tensors (page-locked when pinned=True; out= re-uses the
         dict of an earlier call); synchronous."""
         params = params or self.make_params()
-        W, n1, _ = knots.shape
-        for t in (knots, lin, q_k_lin, count):
-            assert t is None or (not t.is_cuda and t.is_contiguous()), "inputs must be contiguous CPU tensors"
-        assert knots.dtype == torch.float64 and lin.dtype == torch.float64 and (count is None or count.dtype == torch.int32)
+        W, N = self._window_shape(knots, lin, count=count, others=(q_k_lin,), cuda=False)
         if out is None:
-            out = {}
-            for name, n in OUT_FIELDS:
-                grp = _group_of(name)
-                if grp in want and (params.model == 2 or name not in ("O_a", "O_b")):
-                    out[name] = torch.empty((W,) if n == 1 else (W, n), dtype=torch.float64, pin_memory=pinned)
+            out = self._host_outputs((W,), want, params.model, pinned)
         o = self._outputs_struct(out)
         self._sync_stream()
-        self._check(self.lib.cpi_preintegrate_batch_host(self.ctx, C.byref(params), W, n1 - 1, _ptr(knots), None, _ptr(count), 0,
+        self._check(self.lib.cpi_preintegrate_batch_host(self.ctx, C.byref(params), W, N, _ptr(knots), None, _ptr(count), 0,
                                                          _ptr(lin), _ptr(q_k_lin), C.byref(o)))
         return out
 
@@ -426,13 +390,7 @@ class Engine:
         # says so to the allocator.  Nothing but output fields is stored in the returned dict.
         if workspace is None and not self._follow and self.stream is not None:
             ws.record_stream(self.stream)
-        counts = torch.empty((0,), dtype=torch.int32, device=self.device)
-        if U and (return_counts or check_counts):
-            off = (self.lib.cpi_stream_counts(_ptr(ws), U) - ws.data_ptr()) // 4
-            with torch.cuda.stream(self.stream) if (not self._follow and self.stream is not None) else _nullctx():
-                counts = ws.view(torch.int32)[off:off + U].clone()   # a copy: a re-used workspace is overwritten by the next call
-            if check_counts and int(counts.max().item()) > N:
-                raise ValueError("preintegrate_stream: a window has %d intervals, more than N = %d" % (int(counts.max().item()), N))
+        counts = self._stream_counts(ws, U, N, return_counts, check_counts, "preintegrate_stream")
         return (out, counts) if return_counts else out
 
     def stream_bound(self, stream, update_times):
@@ -475,11 +433,7 @@ class Engine:
         N = int(N) if N is not None else self._stream_bound(stream, update_times)     # the same default as the device entry: same lane split, same bits
         for t in (stream, update_times, lin, q_k_lin):
             assert t is None or (not t.is_cuda and t.is_contiguous() and t.dtype == torch.float64), "inputs must be contiguous CPU float64 tensors"
-        out = {}
-        for name, n in OUT_FIELDS:
-            grp = _group_of(name)
-            if grp in want and (params.model == 2 or name not in ("O_a", "O_b")):
-                out[name] = torch.empty((U,) if n == 1 else (U, n), dtype=torch.float64, pin_memory=pinned)
+        out = self._host_outputs((U,), want, params.model, pinned)
         cnt = torch.empty((U,), dtype=torch.int32)
         o = self._outputs_struct(out)
         self._sync_stream()
@@ -542,13 +496,7 @@ class Engine:
         if not self._follow and self.stream is not None:
             for t in ((ws,) if workspace is None else ()) + (soff, uoff, stream, update_times):
                 t.record_stream(self.stream)
-        counts = torch.empty((0,), dtype=torch.int32, device=self.device)
-        if U and (return_counts or check_counts):
-            off = (self.lib.cpi_stream_counts(_ptr(ws), U) - ws.data_ptr()) // 4
-            with torch.cuda.stream(self.stream) if (not self._follow and self.stream is not None) else _nullctx():
-                counts = ws.view(torch.int32)[off:off + U].clone()
-            if check_counts and int(counts.max().item()) > N:
-                raise ValueError("preintegrate_streams: a window has %d intervals, more than N = %d" % (int(counts.max().item()), N))
+        counts = self._stream_counts(ws, U, N, return_counts, check_counts, "preintegrate_streams")
         return (out, counts) if return_counts else out
 
     @staticmethod
@@ -588,10 +536,7 @@ class Engine:
         N = int(N) if N is not None else self.streams_bound(stream, soff, update_times, uoff)
         for t in (stream, update_times, lin, q_k_lin):
             assert t is None or (not t.is_cuda and t.is_contiguous() and t.dtype == torch.float64), "inputs must be contiguous CPU float64 tensors"
-        out = {}
-        for name, n in OUT_FIELDS:
-            if _group_of(name) in want and (params.model == 2 or name not in ("O_a", "O_b")):
-                out[name] = torch.empty((U,) if n == 1 else (U, n), dtype=torch.float64, pin_memory=pinned)
+        out = self._host_outputs((U,), want, params.model, pinned)
         cnt = torch.empty((U,), dtype=torch.int32)
         o = self._outputs_struct(out)
         self._sync_stream()
@@ -683,14 +628,6 @@ class Engine:
         counts = self._stream_counts(ws, U, N, return_counts, check_counts, "preintegrate_streams_running")
         return (out, counts) if return_counts else out
 
-    def _stream_running_host_out(self, U, N, want, params, pinned):
-        out = {}
-        groups = self._running_want(tuple(want), params.model)
-        for name, n in OUT_FIELDS:
-            if _group_of(name) in groups and (params.model == 2 or name not in ("O_a", "O_b")):
-                out[name] = torch.empty((U, N) if n == 1 else (U, N, n), dtype=torch.float64, pin_memory=pinned)
-        return out
-
     def preintegrate_stream_running_host(self, stream, update_times, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"),
                                          N=None, pinned=False, return_counts=False, check_counts=True):
         """preintegrate_stream_running from HOST memory (cpi_preintegrate_stream_running_host): CPU float64 tensors in, CPU
@@ -703,7 +640,7 @@ class Engine:
         if N is None and not check_counts:
             raise ValueError("preintegrate_stream_running_host: check_counts=False needs an explicit N")
         N = int(N) if N is not None else self._stream_bound(stream, update_times)
-        out = self._stream_running_host_out(U, N, want, params, pinned)
+        out = self._host_outputs((U, N), self._running_want(tuple(want), params.model), params.model, pinned)
         cnt = torch.empty((U,), dtype=torch.int32)
         o = self._outputs_struct(out)
         self._sync_stream()
@@ -727,7 +664,7 @@ class Engine:
         if N is None and not check_counts:
             raise ValueError("preintegrate_streams_running_host: check_counts=False needs an explicit N")
         N = int(N) if N is not None else self.streams_bound(stream, soff, update_times, uoff)
-        out = self._stream_running_host_out(U, N, want, params, pinned)
+        out = self._host_outputs((U, N), self._running_want(tuple(want), params.model), params.model, pinned)
         cnt = torch.empty((U,), dtype=torch.int32)
         o = self._outputs_struct(out)
         self._sync_stream()
@@ -747,8 +684,7 @@ class Engine:
             assert t is None or (not t.is_cuda and t.is_contiguous()), "inputs must be contiguous CPU tensors"
         assert tiles.shape[0] == (W + 63) // 64 and tiles.shape[2:] == (7, 64)
         if out is None:
-            out = {name: torch.empty((W,) if n == 1 else (W, n), dtype=torch.float64, pin_memory=pinned)
-                   for name, n in OUT_FIELDS if name in MEAN_FIELDS}
+            out = self._host_outputs((W,), ("mean",), params.model, pinned)
         o = self._outputs_struct(out)
         self._sync_stream()
         self._check(self.lib.cpi_preintegrate_tiled_batch_host(self.ctx, C.byref(params), W, N, _ptr(tiles), _ptr(count), _ptr(lin),
@@ -785,14 +721,7 @@ class Engine:
         re-run fixed buffers in a loop (bench.py; a C or C++ host has no such overhead to begin with).  Returns
         (call, out)."""
         params = params or self.make_params()
-        if first is None:
-            W, n1, _ = knots.shape
-            N = n1 - 1
-        else:
-            W = first.shape[0]
-            assert N is not None
-        for t in (knots, lin, q_k_lin, first, count):
-            assert t is None or (t.is_cuda and t.is_contiguous()), "inputs must be contiguous CUDA tensors"
+        W, N = self._window_shape(knots, lin, first, count, N, (q_k_lin,))
         if out is None:
             out = self.alloc_outputs(W, want, params.model)
         o = self._outputs_struct(out)
