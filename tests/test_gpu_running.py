@@ -115,6 +115,12 @@ def _ragged(W, N, seed, garbage=False):
     """A ragged batch over one knot array: window w starts at first[w] (windows in shuffled order, a gap of unused knots between
     them) and has count[w] intervals; returns the dense view [W, N + 1, 7] the reference reads as well."""
     kn, lin, q = (t.numpy() for t in synth.make_windows(W, N, seed=seed))
+    return (kn, lin, q) + _ragged_layout(kn, seed, garbage)
+
+
+def _ragged_layout(kn, seed, garbage=False):
+    """The layout of _ragged over the dense knots kn [W, N + 1, 7]: flat, first, count, given."""
+    W, N = kn.shape[0], kn.shape[1] - 1
     rng = np.random.default_rng(seed)
     count = rng.integers(0, N + 1, size=W).astype(np.int32)
     count[:4] = [0, N, 1, max(N - 1, 0)][:min(4, W)]
@@ -129,7 +135,7 @@ def _ragged(W, N, seed, garbage=False):
     if garbage:                                             # counts outside [0, N] are clamped into it
         given[1::5] = np.where(count[1::5] == N, N + 1 + np.arange(len(count[1::5])) * 1000, given[1::5])
         given[0::7] = np.where(count[0::7] == 0, -1 - np.arange(len(count[0::7])), given[0::7])
-    return kn, lin, q, flat, first, count, given
+    return flat, first, count, given
 
 
 @pytest.mark.parametrize("layout", ["dense", "ragged"])

@@ -56,8 +56,9 @@ def _segment_ref(ref, lo, hi, Ns):
     return out
 
 
-def _run_chain(eng, prm, kn, lin, q, cuts, want):
-    """Window w as a chain over the cut points cuts[w]: returns per segment (rows on the host, count, Ns) and the last record."""
+def _run_chain(eng, prm, kn, lin, q, cuts, want, nan_rows=False):
+    """Window w as a chain over the cut points cuts[w]: returns per segment (rows on the host, count, Ns) and the last record.
+    nan_rows: the row arrays are filled with NaN before every call (a row the call does not write fails every comparison)."""
     W, n1, _ = kn.shape
     flat, base = _dev(kn.reshape(W * n1, 7), eng), np.arange(W, dtype=np.int64) * n1
     dl, dq = _dev(lin, eng), _dev(q, eng)
@@ -65,8 +66,12 @@ def _run_chain(eng, prm, kn, lin, q, cuts, want):
     for c in range(cuts.shape[1] - 1):
         count = (cuts[:, c + 1] - cuts[:, c]).astype(np.int32)
         Ns = max(int(count.max()), 1)
+        out = None
+        if nan_rows:
+            out = {k: v.fill_(float("nan")).view((W, Ns) + tuple(v.shape[1:]))
+                   for k, v in eng.alloc_outputs(W * Ns, eng._running_want(tuple(want), prm.model), prm.model).items()}
         rows, carry = eng.preintegrate_running_resume(flat, dl, dq, prm, want=want, first=_dev(base + cuts[:, c], eng), count=_dev(count, eng), N=Ns,
-                                                      carry_in=carry)
+                                                      carry_in=carry, out=out)
         segs.append((_host(rows), count, Ns))
     return segs, carry
 

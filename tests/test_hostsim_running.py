@@ -14,7 +14,8 @@ import numpy as np
 import pytest
 
 from oracle import oracle_py as op
-from tests.tol import check_pre
+from tests.running_cases import EDGE_N, tumbling_windows
+from tests.tol import TOL_JAC, TOL_MEAN, check_pre
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = os.path.join(_HERE, "hostsim", "hostsim_running.cpp")
@@ -23,7 +24,7 @@ _HDR = os.path.join(os.path.dirname(_HERE), "cpi_amd", "csrc", "cpi_math.hpp")
 GRAV = np.array([0.0, 0.0, 9.8])
 SIG = np.array([0.005, 4e-6, 0.01, 2e-4])
 LANES = [1, 2, 3, 4, 5, 6, 8, 12, 16, 32, 64]          # the kernels' lane choices (cpi_mean.hip: kMeanLanes)
-NS = [1, 2, 10, 20, 50, 80]
+NS = sorted({1, 2, 10, 20, 50, 80} | set(EDGE_N))      # + the lengths on and beside the pass and row-group boundaries
 MODES = [(1, 0), (1, 1), (2, 0), (2, 1)]
 MEAN = ("DT", "alpha", "beta", "q")
 JAC = ("J_q", "J_a", "J_b", "H_a", "H_b")
@@ -117,6 +118,38 @@ def test_hostsim_running_matches_the_oracle_trace(lib, N):
             check_pre(got, ref, what=("cov",), label="m%d avg%d N%d w%d cov" % (model, avg, N, w))
             worst.add(got, ref, ("P",))
     worst.report("hostsim running vs oracle.trace, N = %d" % N)
+
+
+def test_hostsim_running_under_large_rotations(lib):
+    """The tumbling windows of tests/running_cases.py (|w| dt up to ~1.16: the wide polynomial and the reduced path of
+    sincos_fast, every branch of rot_2_quat, scans that compose rotations past 90 degrees): every lane count, the model-1
+    Jacobians and the covariance rows; the gates of tests/tol.py relative to the magnitude of the quantity, as the stress
+    tests of tests/test_gpu_parity.py apply them."""
+    kn, lin, q = tumbling_windows()
+    worst = _Worst()
+
+    def close(got, ref, keys, tol, label):
+        for k in keys:
+            e, scale = float(np.abs(got[k] - ref[k]).max()), max(1.0, float(np.abs(ref[k]).max()))
+            assert e <= tol * scale, "%s %s err %.3e (scale %.3g)" % (label, k, e, scale)
+        worst.add(got, ref, keys)
+
+    for model, avg in MODES:
+        prm = op.make_params(model, avg, 1)
+        for w in range(kn.shape[0]):
+            ref = op.oracle().trace(prm, kn[w], lin[w], q[w])
+            assert all(np.isfinite(ref[k]).all() for k in MEAN + JAC + ("P",))
+            for L in LANES:
+                label = "tumbling m%d avg%d w%d L%d" % (model, avg, w, L)
+                close(mean_rows(lib, model, False, avg, L, kn[w], lin[w], q[w]), ref, MEAN, TOL_MEAN, label)
+                if model == 1:
+                    got = mean_rows(lib, 1, True, avg, L, kn[w], lin[w], q[w])
+                    close(got, ref, MEAN, TOL_MEAN, label + " jac")
+                    close(got, ref, JAC, TOL_JAC, label + " jac")
+            got = cov_rows(lib, model, avg, kn[w], lin[w], q[w])
+            check_pre(got, ref, what=("cov",), label="tumbling m%d avg%d w%d cov" % (model, avg, w))
+            worst.add(got, ref, ("P",))
+    worst.report("hostsim running vs oracle.trace, tumbling windows")
 
 
 def _edge_window(N, kind, seed):
