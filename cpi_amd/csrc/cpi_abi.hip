@@ -24,6 +24,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <algorithm>
+#include <cmath>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -576,6 +577,61 @@ extern "C" int cpi_preintegrate_running_resume(cpi_ctx *ctx, const cpi_params *p
         launch::mean_running_carry(prm->model, rq.jac, avg, pick_lanes(prm, W, N, rq.jac), m, cm, ctx->stream);
     }
     if (rq.cov) launch::cov_running_carry(prm->model, avg, a, c, ctx->stream);
+    CPI_HIP(ctx, hipGetLastError());
+    return CPI_OK;
+}
+
+// The measurement at arbitrary times inside a window (include/cpi_amd.h): one kernel, one lane per query, over the rows
+// cpi_preintegrate_running wrote for the same windows.  Nothing here looks at device memory, so the call can be captured.
+static const char kQueryNoCov[] = "P / P_sym are not available at query times (they need the covariance kernel's lane-spread RK4 step)";
+static int query_check(cpi_ctx *ctx, const char *who, const cpi_params *prm, const Request &rq) {
+    if (prm->model == CPI_MODEL_FORSTER) return refuse(ctx, who, "model must be 1 or 2 (the Forster comparator has no running form)");
+    if (!model_is_cpi(prm)) return refuse(ctx, who, "model must be 1 or 2");
+    if (rq.cov) return refuse(ctx, who, kQueryNoCov);
+    if (prm->model == CPI_MODEL_V2 && rq.jac) return refuse_v2_jac(ctx, who, "");
+    return CPI_OK;
+}
+static int query_trips(int32_t N) {
+    int trips = 0;
+    while ((1ll << trips) < (long long)N + 1) trips++;
+    return trips;
+}
+extern "C" int cpi_query_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                               const double *knots, const int64_t *first, const int32_t *count,
+                               const double *lin, const double *q_k_lin, const cpi_outputs *rows,
+                               int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out) {
+    static const char who[] = "cpi_query_batch";
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (!prm || !rows || !out) return refuse(ctx, who, "prm/rows/out is NULL");
+    const Request rq = request_of(out);
+    CPI_TRY(query_check(ctx, who, prm, rq));
+    if (W < 0 || N < 0 || Q < 0) return refuse(ctx, who, "negative size");
+    if (Q == 0) return CPI_OK;
+    if (W == 0) return refuse(ctx, who, "W is 0: there is no window to query");
+    if (!qwin || !qtime) return refuse(ctx, who, "qwin/qtime is NULL");
+    CPI_TRY(check_windows(ctx, who, prm, W, N, knots, lin, q_k_lin));
+    if (!grid_ok(Q)) return refuse(ctx, who, "Q exceeds 2^31 - 1 queries per call (32-bit grid)");
+    if (N > 0) {   // N == 0: every query is the zero state and rows is not read
+        if (!rows->DT || !rows->alpha || !rows->beta || !rows->q) return refuse(ctx, who, "rows needs DT, alpha, beta and q");
+        if ((out->J_q && !rows->J_q) || (out->J_a && !rows->J_a) || (out->J_b && !rows->J_b) || (out->H_a && !rows->H_a) || (out->H_b && !rows->H_b))
+            return refuse(ctx, who, "a Jacobian field of out needs the same field of rows");
+    }
+    if (!rq.any()) return CPI_OK;
+
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    QueryArgs a;
+    memset(&a, 0, sizeof a);
+    a.W = W; a.N = N; a.knots = knots; a.first = (const long long *)first; a.count = count; a.lin = lin; a.qk = q_k_lin;
+    for (int i = 0; i < 3; i++) a.grav[i] = prm->grav[i];
+    a.rows = *rows; a.Q = Q; a.qwin = qwin; a.qtime = qtime; a.trips = query_trips(N); a.out = *out;
+    if (rq.jac) {
+        // the Jacobian instance carries all five matrices: the ones out does not ask for are read from a field that is there
+        const double *any = rows->J_q ? rows->J_q : rows->J_a ? rows->J_a : rows->J_b ? rows->J_b : rows->H_a ? rows->H_a : rows->H_b;
+        double **f[5] = { &a.rows.J_q, &a.rows.J_a, &a.rows.J_b, &a.rows.H_a, &a.rows.H_b };
+        for (double **x : f) if (!*x) *x = const_cast<double *>(any);
+    }
+    launch::query(prm->model, rq.jac, prm->imu_avg != 0, a, ctx->stream);
     CPI_HIP(ctx, hipGetLastError());
     return CPI_OK;
 }
@@ -1737,6 +1793,67 @@ extern "C" int cpi_preintegrate_running_resume_host(cpi_ctx *ctx, const cpi_para
     if (n_knots <= 0) return refuse(ctx, who, "n_knots must be > 0");
     return resume_staged(ctx, cpi_preintegrate_running_resume, prm, W, N, (size_t)N, knots, first, count, n_knots, lin, q_k_lin, carry_in,
                          carry_out, rows);
+}
+
+// cpi_query_batch from host memory.  The windows are staged whole, the running rows are computed into device staging and never
+// leave it: Q rows come down.  What the device form cannot check is checked here, before anything is enqueued: qwin in range, and
+// finite non-decreasing stamps (the bisection's precondition) in every window that is queried.
+extern "C" int cpi_query_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                    const double *knots, const int64_t *first, const int32_t *count, int64_t n_knots,
+                                    const double *lin, const double *q_k_lin,
+                                    int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out) {
+    static const char who[] = "cpi_query_batch_host";
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (!prm || !out) return refuse(ctx, who, "prm/out is NULL");
+    const Request rq = request_of(out);
+    CPI_TRY(query_check(ctx, who, prm, rq));
+    if (W < 0 || N < 0 || Q < 0) return refuse(ctx, who, "negative size");
+    if (Q == 0) return CPI_OK;
+    if (W == 0) return refuse(ctx, who, "W is 0: there is no window to query");
+    if (!qwin || !qtime) return refuse(ctx, who, "qwin/qtime is NULL");
+    CPI_TRY(check_windows(ctx, who, prm, W, N, knots, lin, q_k_lin));
+    if (!grid_ok(Q)) return refuse(ctx, who, "Q exceeds 2^31 - 1 queries per call (32-bit grid)");
+    if (!first) n_knots = W * (int64_t)(N + 1);
+    if (n_knots <= 0) return refuse(ctx, who, "n_knots must be > 0");
+    {
+        std::vector<char> seen((size_t)W, 0);
+        for (int64_t k = 0; k < Q; k++) {
+            const int64_t w = qwin[k];
+            if (w < 0 || w >= W) return refuse(ctx, who, ("qwin[" + std::to_string(k) + "] = " + std::to_string(w) + " is not a window of [0, W)").c_str());
+            if (seen[w]) continue;
+            seen[w] = 1;
+            const int64_t k0 = first ? first[w] : w * (int64_t)(N + 1);
+            const int64_t n = count ? std::min<int64_t>(std::max<int64_t>(count[w], 0), N) : N;
+            if (k0 < 0 || k0 + n >= n_knots) return refuse(ctx, who, ("window " + std::to_string(w) + " does not lie inside the knots").c_str());
+            for (int64_t i = 0; i <= n; i++) {
+                const double t = knots[(k0 + i) * 7];
+                if (!std::isfinite(t) || (i > 0 && t < knots[(k0 + i - 1) * 7]))
+                    return refuse(ctx, who, ("window " + std::to_string(w) + " has a NaN, infinite or decreasing stamp at knot " + std::to_string(i) +
+                                             " (a queried window needs finite non-decreasing stamps)").c_str());
+            }
+        }
+    }
+    if (!rq.any()) return CPI_OK;
+
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    Staging st(ctx);
+    WindowsDev in;
+    const int32_t *dqwin;
+    const double *dqtime;
+    cpi_outputs rmask = {}, drows, d;
+    double dummy;
+    rmask.DT = rmask.alpha = rmask.beta = rmask.q = &dummy;   // mirror() allocates the fields that are set
+    rmask.J_q = out->J_q; rmask.J_a = out->J_a; rmask.J_b = out->J_b; rmask.H_a = out->H_a; rmask.H_b = out->H_b;
+    CPI_TRY(stage_windows(st, W, n_knots, knots, first, count, lin, q_k_lin, &in));
+    CPI_TRY(st.upload(qwin, (size_t)Q, &dqwin));
+    CPI_TRY(st.upload(qtime, (size_t)Q, &dqtime));
+    CPI_TRY(st.mirror(&rmask, (size_t)W * (size_t)N, &drows));
+    CPI_TRY(st.mirror(out, (size_t)Q, &d));
+    if (N > 0) CPI_TRY(cpi_preintegrate_running(ctx, prm, W, N, in.knots, in.first, in.count, in.lin, in.qk, &drows));
+    CPI_TRY(cpi_query_batch(ctx, prm, W, N, in.knots, in.first, in.count, in.lin, in.qk, &drows, Q, dqwin, dqtime, &d));
+    CPI_TRY(st.download(out, d, (size_t)Q));
+    return st.finish();
 }
 
 // The offsets of a multi-run call as the _host entries can (and do) validate them before anything is enqueued: each array

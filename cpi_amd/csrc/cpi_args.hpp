@@ -1,12 +1,14 @@
 // cpi_args.hpp -- kernel argument blocks and the launcher interface between the translation units of libcpi_amd.so.
 //
-// The library is six translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
+// The library is seven translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
 //   cpi_mean.hip    cpi_mean_kernel / cpi_mean_tiled_kernel / cpi_tile_*_kernel       (cpi_mean_kernels.hpp)
 //   cpi_running.hip cpi_mean_running_kernel / cpi_mean_stream_running_kernel: a row after every interval, from plain knots /
 //                   from windows cut out of IMU stream(s) in place         (cpi_running_kernels.hpp, cpi_running_body.inc)
 //   cpi_cov.hip     cpi_cov_kernel<1|2> / cpi_forster_kernel / cpi_cov_running_kernel  (cpi_cov_kernels.hpp)
 //   cpi_running_resume.hip  cpi_mean_running_carry_kernel / cpi_cov_running_carry_kernel: the running rows from and to carry
 //                   records, over the bodies of the two units above (cpi_running_body.inc, cov_body)
+//   cpi_query.hip   cpi_query_kernel: the measurement at arbitrary times inside a window, one partial interval from a running row
+//                                                                                      (cpi_query_kernels.hpp)
 //   cpi_factor.hip  evaluateError sweeps, square-root information, Hessian blocks, state prediction
 //                                                                                      (cpi_factor_kernels.hpp)
 //   cpi_abi.hip     the C-ABI of include/cpi_amd.h: argument checks, launch heuristics, device sets (RCCL), the
@@ -93,6 +95,25 @@ struct TiledArgs {
     long long ts, ss;   // doubles between consecutive tiles / consecutive steps of a tile
 };
 
+// cpi_query_batch: query k asks for the measurement of window qwin[k] at time qtime[k]; rows = the W * N rows
+// cpi_preintegrate_running wrote for the same windows (include/cpi_amd.h).  qwin lives in device memory and is CLAMPED into [0, W).
+struct QueryArgs {
+    long long W;
+    int N;
+    const double *knots;
+    const long long *first;
+    const int *count;
+    const double *lin;
+    const double *qk;
+    double grav[3];
+    cpi_outputs rows;      // DT / alpha / beta / q always; J_q ... H_b when out asks for them
+    long long Q;
+    const int *qwin;       // [Q]
+    const double *qtime;   // [Q]
+    int trips;             // ceil(log2(N + 1)): steps of the interval search, the same for every lane
+    cpi_outputs out;       // arrays of Q rows
+};
+
 struct FactorArgs {
     long long F;
     double grav[3];
@@ -163,6 +184,8 @@ void forster(const PreArgs &a, hipStream_t st);
 // ---- cpi_running_resume.hip (cpi_preintegrate_running_resume: the running rows from c.in to c.out)
 void mean_running_carry(int model, bool jac, bool avg, int L, const PreArgs &a, const CarryArgs &c, hipStream_t st);   // always owns tag + means of c.out
 void cov_running_carry(int model, bool avg, const PreArgs &a, const CarryArgs &c, hipStream_t st);   // P / P_sym rows + the covariance block of c.out
+// ---- cpi_query.hip (cpi_query_batch; jac: model 1 only)
+void query(int model, bool jac, bool avg, const QueryArgs &a, hipStream_t st);
 // ---- cpi_factor.hip
 void factor(int model, bool whiten, int lpf, const FactorArgs &a, hipStream_t st);            // lpf 16 | 8 | 4
 void factor_packed(int model, int lpf, const FactorArgs &a, double *packed, hipStream_t st);  // lpf 2 | 3 | 4 | 6 | 8

@@ -26,6 +26,17 @@ __device__ __forceinline__ void stm3_cm(double *p, const M3 &A) {
 }
 __device__ __forceinline__ void stv3(double *p, V3 v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; }
 
+// 16 bytes at an 8-byte aligned address with the non-temporal hint: the sweeps' outputs are written once and read by a later
+// kernel (the solver), never by this one.  Round 4, same-box A/B per 1 M factors: square-root information 709-716 -> 674-680 us,
+// Hessian blocks 1414 -> 1388 us (v2 1490 -> 1470), dense H1 / H2 793-804 -> 771-775 us on one box and unchanged on another,
+// whitened 1271 -> 1250 us, packed sweep 292 -> 280 us (v2 327 -> 318); the same hint on the LOADS -- the records, R of the whitened /
+// Hessian sweeps, P of the square-root information -- is neutral (within +-1 %): not used.
+typedef double cpi_d2v __attribute__((ext_vector_type(2), aligned(8)));
+__device__ __forceinline__ void st16_nt(double *dst2, double a, double b) {
+    cpi_d2v v; v.x = a; v.y = b;
+    __builtin_nontemporal_store(v, reinterpret_cast<cpi_d2v *>(dst2));
+}
+
 __device__ __forceinline__ V3 shfl_down(V3 v, int d) {
     return mk(__shfl_down(v.x, d), __shfl_down(v.y, d), __shfl_down(v.z, d));
 }

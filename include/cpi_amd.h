@@ -55,7 +55,8 @@ extern "C" {
                                cpi_preintegrate_stream_running_host, cpi_preintegrate_streams_running_host (the running rows
                                from IMU stream(s), windows cut in place); cpi_preintegrate_running_resume,
                                cpi_preintegrate_running_resume_host (the running rows of a window that continues from a
-                               carry record) */
+                               carry record); cpi_query_batch, cpi_query_batch_host (the measurement at arbitrary times inside
+                               a window) */
 
 enum { CPI_OK = 0, CPI_ERR_INVALID = 1, CPI_ERR_HIP = 2, CPI_ERR_NO_DEVICE = 3, CPI_ERR_RCCL = 4 };
 enum {
@@ -258,6 +259,47 @@ int cpi_preintegrate_running_resume(cpi_ctx *ctx, const cpi_params *prm, int64_t
                                     const double *knots, const int64_t *first, const int32_t *count,
                                     const double *lin, const double *q_k_lin,
                                     const double *carry_in, double *carry_out, const cpi_outputs *rows);
+
+/* The measurement at ARBITRARY TIMES inside a window: a camera, a lidar point or a rolling-shutter row stamped between two IMU
+ * readings, a keyframe time chosen after the fact, the poses at the 100 k point times of one lidar sweep for deskewing.  The rows
+ * of cpi_preintegrate_running hold the state after every interval, so a query is one gather and at most one partial interval
+ * instead of a window of its own re-integrated from the start.  The semantics are the reference's own: GraphSolver_IMU.cpp:64-69
+ * closes a window at `updatetime` by holding the front reading over [t_front, updatetime]; a query is that tail interval applied
+ * to a running row.
+ *
+ *   prm, W, N, knots, first, count, lin, q_k_lin   the arguments of the cpi_preintegrate_running call that wrote rows
+ *   rows    W * N rows, the output of cpi_preintegrate_running on THOSE arguments: DT, alpha, beta, q always; J_q ... H_b where
+ *           out asks for the same field
+ *   Q, qwin [Q], qtime [Q]   query k asks for window qwin[k] at time qtime[k]; any order, repeats allowed
+ *   out     arrays of Q rows; any pointer may be NULL = "not wanted"
+ * Query k: let w = qwin[k], n = the window's count clamped into [0, N], t_0 .. t_n its knot stamps, t_q = qtime[k].
+ *   - PRECONDITION: the stamps t_0 .. t_n of a queried window are finite and non-decreasing (NaN-stamp separators are not
+ *     supported here).  Otherwise the result of that query is unspecified -- but even then no read leaves the window's knots
+ *     [k0, k0 + n] or its rows [w N, w N + N);
+ *   - i = the largest index in [0, n] with t_i <= t_q; t_q < t_0: i = 0 and nothing is integrated;
+ *   - base state = the zero-state row (DT = 0, alpha = beta = 0, q = [0 0 0 1], Jacobians 0) when i == 0, else row w N + i - 1;
+ *   - i < n and t_q > t_i: the base state advanced by feed_IMU(t_i, t_q, w_i, a_i, w_i, a_i) -- reading i held, as for the
+ *     reference's tail; the rotation is rebuilt from the row's quaternion (quat_2_Rot);
+ *   - otherwise (t_q == t_i, or t_q >= t_n: there is no extrapolation) the base state, COPIED BIT FOR BIT in every requested field;
+ *   - t_q NaN: NaN in every requested field of that query (all four components of q);
+ *   - out[k] equals cpi_preintegrate_batch on the window [knot 0 .. knot i, {t_q, w_i, a_i}] up to rounding.
+ * Requests: DT / alpha / beta / q for models 1 and 2, imu_avg 0 / 1; J_q J_a J_b H_a H_b for model 1.  CPI_ERR_INVALID: P / P_sym
+ * in out, any Jacobian field with model 2, CPI_MODEL_FORSTER, model 2 without q_k_lin, a NULL prm / rows / out / qwin / qtime / lin /
+ * knots, a rows without DT / alpha / beta / q or without a Jacobian field out asks for (N > 0), negative sizes, W == 0 with Q > 0,
+ * N > 65535, Q > 2^31 - 1, an unsupported lanes_per_window (validated as elsewhere, otherwise ignored).  Q == 0 is a no-op.
+ * N == 0: every query gets the zero state and rows is not read.
+ * qwin lives in device memory and cannot be validated by the call: the kernel CLAMPS it into [0, W) -- a wrong index gives a
+ * wrong row, never an out-of-bounds read.  cpi_query_batch_host validates it.
+ * One kernel on the context's stream, no host synchronisation: the call can be captured into a graph (after the
+ * cpi_preintegrate_running that feeds it: a chain without parallel branches).
+ * Composition: cpi_predict_batch(F = Q, meas = out, idx_i = qwin) gives the predicted states AT the query times.
+ * Not provided: P / P_sym at query times (they need the covariance kernel's lane-spread RK4 step); Jacobians for model 2; windows
+ * cut from IMU streams in place (cpi_preintegrate_stream[s]_running: assemble the windows, or query per update time); rows that
+ * continue from a carry record (cpi_preintegrate_running_resume); extrapolation past t_n. */
+int cpi_query_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                    const double *knots, const int64_t *first, const int32_t *count,
+                    const double *lin, const double *q_k_lin, const cpi_outputs *rows,
+                    int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out);
 
 /* Replaces: the whole caller side of GraphSolver::createimufactor_cpi_v1 / _v2 (GraphSolver_IMU.cpp:43-75, 97-130) for every
  * window of a trajectory at once, reading ONE IMU stream IN PLACE: no knot is copied, for any model and any output.
@@ -557,6 +599,15 @@ int cpi_preintegrate_running_resume_host(cpi_ctx *ctx, const cpi_params *prm, in
                                          const double *knots, const int64_t *first, const int32_t *count,
                                          int64_t n_knots, const double *lin, const double *q_k_lin,
                                          const double *carry_in, double *carry_out, const cpi_outputs *rows);
+/* cpi_query_batch from host memory: every pointer a host pointer, n_knots as in cpi_preintegrate_batch_host, and NO rows
+ * argument -- the windows are staged whole, the running means (and, for a Jacobian request, Jacobians) are computed into device
+ * memory and stay there, the query kernel reads them and Q rows come down: the W * N rows never cross PCIe.  Validates what the
+ * device form cannot, before anything is enqueued: every qwin[k] in [0, W), and finite non-decreasing stamps in every QUERIED
+ * window (CPI_ERR_INVALID, the message names the window).  Bit for bit the device form on the same arguments. */
+int cpi_query_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                         const double *knots, const int64_t *first, const int32_t *count, int64_t n_knots,
+                         const double *lin, const double *q_k_lin,
+                         int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out);
 /* cpi_preintegrate_resume from host memory: every pointer a host pointer, n_knots as in cpi_preintegrate_batch_host. */
 int cpi_preintegrate_resume_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                                  const double *knots, const int64_t *first, const int32_t *count,
