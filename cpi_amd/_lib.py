@@ -165,6 +165,9 @@ def load():
     lib.cpi_query_batch.argtypes = [vp, C.POINTER(CpiParams), i64, i32, dp, vp, vp, dp, dp, C.POINTER(CpiOutputs), i64, vp, dp, C.POINTER(CpiOutputs)]
     lib.cpi_query_batch_host.argtypes = [vp, C.POINTER(CpiParams), i64, i32, dp, vp, vp, i64, dp, dp, i64, vp, dp, C.POINTER(CpiOutputs)]
     lib.cpi_query_batch.restype = lib.cpi_query_batch_host.restype = C.c_int
+    lib.cpi_query_cov_batch.argtypes = lib.cpi_query_batch.argtypes
+    lib.cpi_query_cov_batch_host.argtypes = lib.cpi_query_batch_host.argtypes
+    lib.cpi_query_cov_batch.restype = lib.cpi_query_cov_batch_host.restype = C.c_int
     lib.cpi_preintegrate_stream_running.argtypes = lib.cpi_preintegrate_stream.argtypes
     lib.cpi_preintegrate_stream_running_host.argtypes = lib.cpi_preintegrate_stream_host.argtypes
     lib.cpi_preintegrate_streams_running.argtypes = lib.cpi_preintegrate_streams.argtypes

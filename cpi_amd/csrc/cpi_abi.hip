@@ -583,11 +583,13 @@ extern "C" int cpi_preintegrate_running_resume(cpi_ctx *ctx, const cpi_params *p
 
 // The measurement at arbitrary times inside a window (include/cpi_amd.h): one kernel, one lane per query, over the rows
 // cpi_preintegrate_running wrote for the same windows.  Nothing here looks at device memory, so the call can be captured.
+// cpi_query_batch and cpi_query_cov_batch are one body: the latter also accepts P / P_sym in out (with_cov) and then enqueues
+// cpi_query_cov_kernel behind the mean kernel, on the same stream.
 static const char kQueryNoCov[] = "P / P_sym are not available at query times (they need the covariance kernel's lane-spread RK4 step)";
-static int query_check(cpi_ctx *ctx, const char *who, const cpi_params *prm, const Request &rq) {
+static int query_check(cpi_ctx *ctx, const char *who, const cpi_params *prm, const Request &rq, bool with_cov) {
     if (prm->model == CPI_MODEL_FORSTER) return refuse(ctx, who, "model must be 1 or 2 (the Forster comparator has no running form)");
     if (!model_is_cpi(prm)) return refuse(ctx, who, "model must be 1 or 2");
-    if (rq.cov) return refuse(ctx, who, kQueryNoCov);
+    if (rq.cov && !with_cov) return refuse(ctx, who, kQueryNoCov);
     if (prm->model == CPI_MODEL_V2 && rq.jac) return refuse_v2_jac(ctx, who, "");
     return CPI_OK;
 }
@@ -596,25 +598,42 @@ static int query_trips(int32_t N) {
     while ((1ll << trips) < (long long)N + 1) trips++;
     return trips;
 }
-extern "C" int cpi_query_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
-                               const double *knots, const int64_t *first, const int32_t *count,
-                               const double *lin, const double *q_k_lin, const cpi_outputs *rows,
-                               int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out) {
-    static const char who[] = "cpi_query_batch";
-    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
-    if (!prm || !rows || !out) return refuse(ctx, who, "prm/rows/out is NULL");
-    const Request rq = request_of(out);
-    CPI_TRY(query_check(ctx, who, prm, rq));
+// the checks the device and the host form share, up to the ones on rows (the host form computes its own rows); *done: a no-op call
+static int query_check_args(cpi_ctx *ctx, const char *who, bool with_cov, const cpi_params *prm, int64_t W, int32_t N, const double *knots,
+                            const double *lin, const double *q_k_lin, int64_t Q, const int32_t *qwin, const double *qtime,
+                            const cpi_outputs *out, bool *done) {
+    *done = true;
+    CPI_TRY(query_check(ctx, who, prm, request_of(out), with_cov));
     if (W < 0 || N < 0 || Q < 0) return refuse(ctx, who, "negative size");
     if (Q == 0) return CPI_OK;
     if (W == 0) return refuse(ctx, who, "W is 0: there is no window to query");
     if (!qwin || !qtime) return refuse(ctx, who, "qwin/qtime is NULL");
     CPI_TRY(check_windows(ctx, who, prm, W, N, knots, lin, q_k_lin));
     if (!grid_ok(Q)) return refuse(ctx, who, "Q exceeds 2^31 - 1 queries per call (32-bit grid)");
+    *done = false;
+    return CPI_OK;
+}
+static int query_device(cpi_ctx *ctx, const char *who, bool with_cov, const cpi_params *prm, int64_t W, int32_t N,
+                        const double *knots, const int64_t *first, const int32_t *count,
+                        const double *lin, const double *q_k_lin, const cpi_outputs *rows,
+                        int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out) {
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (!prm || !rows || !out) return refuse(ctx, who, "prm/rows/out is NULL");
+    const Request rq = request_of(out);
+    bool done;
+    CPI_TRY(query_check_args(ctx, who, with_cov, prm, W, N, knots, lin, q_k_lin, Q, qwin, qtime, out, &done));
+    if (done) return CPI_OK;
+    const bool means = rq.mean || rq.jac;
     if (N > 0) {   // N == 0: every query is the zero state and rows is not read
-        if (!rows->DT || !rows->alpha || !rows->beta || !rows->q) return refuse(ctx, who, "rows needs DT, alpha, beta and q");
-        if ((out->J_q && !rows->J_q) || (out->J_a && !rows->J_a) || (out->J_b && !rows->J_b) || (out->H_a && !rows->H_a) || (out->H_b && !rows->H_b))
-            return refuse(ctx, who, "a Jacobian field of out needs the same field of rows");
+        if (means || !rq.cov) {
+            if (!rows->DT || !rows->alpha || !rows->beta || !rows->q) return refuse(ctx, who, "rows needs DT, alpha, beta and q");
+            if ((out->J_q && !rows->J_q) || (out->J_a && !rows->J_a) || (out->J_b && !rows->J_b) || (out->H_a && !rows->H_a) || (out->H_b && !rows->H_b))
+                return refuse(ctx, who, "a Jacobian field of out needs the same field of rows");
+        }
+        if (rq.cov) {
+            if (!rows->q) return refuse(ctx, who, "rows needs q (the rotation at the start of the partial interval)");
+            if (!rows->P && !rows->P_sym) return refuse(ctx, who, "rows needs P or P_sym when out asks for P / P_sym");
+        }
     }
     if (!rq.any()) return CPI_OK;
 
@@ -631,9 +650,25 @@ extern "C" int cpi_query_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, i
         double **f[5] = { &a.rows.J_q, &a.rows.J_a, &a.rows.J_b, &a.rows.H_a, &a.rows.H_b };
         for (double **x : f) if (!*x) *x = const_cast<double *>(any);
     }
-    launch::query(prm->model, rq.jac, prm->imu_avg != 0, a, ctx->stream);
+    if (means) launch::query(prm->model, rq.jac, prm->imu_avg != 0, a, ctx->stream);
+    if (rq.cov) {
+        const double q4[4] = { prm->sigma_w * prm->sigma_w, prm->sigma_wb * prm->sigma_wb, prm->sigma_a * prm->sigma_a, prm->sigma_ab * prm->sigma_ab };
+        launch::query_cov(prm->model, prm->imu_avg != 0, a, q4, ctx->stream);
+    }
     CPI_HIP(ctx, hipGetLastError());
     return CPI_OK;
+}
+extern "C" int cpi_query_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                               const double *knots, const int64_t *first, const int32_t *count,
+                               const double *lin, const double *q_k_lin, const cpi_outputs *rows,
+                               int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out) {
+    return query_device(ctx, "cpi_query_batch", false, prm, W, N, knots, first, count, lin, q_k_lin, rows, Q, qwin, qtime, out);
+}
+extern "C" int cpi_query_cov_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                   const double *knots, const int64_t *first, const int32_t *count,
+                                   const double *lin, const double *q_k_lin, const cpi_outputs *rows,
+                                   int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out) {
+    return query_device(ctx, "cpi_query_cov_batch", true, prm, W, N, knots, first, count, lin, q_k_lin, rows, Q, qwin, qtime, out);
 }
 
 // Replaces the caller-side loop of GraphSolver::createimufactor_cpi_v1 / _v2 (GraphSolver_IMU.cpp:43-75, 97-130) for ALL the
@@ -1795,24 +1830,20 @@ extern "C" int cpi_preintegrate_running_resume_host(cpi_ctx *ctx, const cpi_para
                          carry_out, rows);
 }
 
-// cpi_query_batch from host memory.  The windows are staged whole, the running rows are computed into device staging and never
-// leave it: Q rows come down.  What the device form cannot check is checked here, before anything is enqueued: qwin in range, and
-// finite non-decreasing stamps (the bisection's precondition) in every window that is queried.
-extern "C" int cpi_query_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
-                                    const double *knots, const int64_t *first, const int32_t *count, int64_t n_knots,
-                                    const double *lin, const double *q_k_lin,
-                                    int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out) {
-    static const char who[] = "cpi_query_batch_host";
+// cpi_query_batch / cpi_query_cov_batch from host memory.  The windows are staged whole, the running rows are computed into device
+// staging and never leave it (the covariance rows as P_sym: 960 B per row instead of 1 800): Q rows come down.  What the device form
+// cannot check is checked here, before anything is enqueued: qwin in range, and finite non-decreasing stamps (the bisection's
+// precondition) in every window that is queried.
+static int query_host(cpi_ctx *ctx, const char *who, bool with_cov, const cpi_params *prm, int64_t W, int32_t N,
+                      const double *knots, const int64_t *first, const int32_t *count, int64_t n_knots,
+                      const double *lin, const double *q_k_lin,
+                      int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out) {
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
     if (!prm || !out) return refuse(ctx, who, "prm/out is NULL");
     const Request rq = request_of(out);
-    CPI_TRY(query_check(ctx, who, prm, rq));
-    if (W < 0 || N < 0 || Q < 0) return refuse(ctx, who, "negative size");
-    if (Q == 0) return CPI_OK;
-    if (W == 0) return refuse(ctx, who, "W is 0: there is no window to query");
-    if (!qwin || !qtime) return refuse(ctx, who, "qwin/qtime is NULL");
-    CPI_TRY(check_windows(ctx, who, prm, W, N, knots, lin, q_k_lin));
-    if (!grid_ok(Q)) return refuse(ctx, who, "Q exceeds 2^31 - 1 queries per call (32-bit grid)");
+    bool done;
+    CPI_TRY(query_check_args(ctx, who, with_cov, prm, W, N, knots, lin, q_k_lin, Q, qwin, qtime, out, &done));
+    if (done) return CPI_OK;
     if (!first) n_knots = W * (int64_t)(N + 1);
     if (n_knots <= 0) return refuse(ctx, who, "n_knots must be > 0");
     {
@@ -1845,15 +1876,28 @@ extern "C" int cpi_query_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t
     double dummy;
     rmask.DT = rmask.alpha = rmask.beta = rmask.q = &dummy;   // mirror() allocates the fields that are set
     rmask.J_q = out->J_q; rmask.J_a = out->J_a; rmask.J_b = out->J_b; rmask.H_a = out->H_a; rmask.H_b = out->H_b;
+    if (rq.cov) rmask.P_sym = &dummy;
     CPI_TRY(stage_windows(st, W, n_knots, knots, first, count, lin, q_k_lin, &in));
     CPI_TRY(st.upload(qwin, (size_t)Q, &dqwin));
     CPI_TRY(st.upload(qtime, (size_t)Q, &dqtime));
     CPI_TRY(st.mirror(&rmask, (size_t)W * (size_t)N, &drows));
     CPI_TRY(st.mirror(out, (size_t)Q, &d));
     if (N > 0) CPI_TRY(cpi_preintegrate_running(ctx, prm, W, N, in.knots, in.first, in.count, in.lin, in.qk, &drows));
-    CPI_TRY(cpi_query_batch(ctx, prm, W, N, in.knots, in.first, in.count, in.lin, in.qk, &drows, Q, dqwin, dqtime, &d));
+    CPI_TRY((with_cov ? cpi_query_cov_batch : cpi_query_batch)(ctx, prm, W, N, in.knots, in.first, in.count, in.lin, in.qk, &drows, Q, dqwin, dqtime, &d));
     CPI_TRY(st.download(out, d, (size_t)Q));
     return st.finish();
+}
+extern "C" int cpi_query_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                    const double *knots, const int64_t *first, const int32_t *count, int64_t n_knots,
+                                    const double *lin, const double *q_k_lin,
+                                    int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out) {
+    return query_host(ctx, "cpi_query_batch_host", false, prm, W, N, knots, first, count, n_knots, lin, q_k_lin, Q, qwin, qtime, out);
+}
+extern "C" int cpi_query_cov_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                        const double *knots, const int64_t *first, const int32_t *count, int64_t n_knots,
+                                        const double *lin, const double *q_k_lin,
+                                        int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out) {
+    return query_host(ctx, "cpi_query_cov_batch_host", true, prm, W, N, knots, first, count, n_knots, lin, q_k_lin, Q, qwin, qtime, out);
 }
 
 // The offsets of a multi-run call as the _host entries can (and do) validate them before anything is enqueued: each array

@@ -1,6 +1,6 @@
 // cpi_args.hpp -- kernel argument blocks and the launcher interface between the translation units of libcpi_amd.so.
 //
-// The library is seven translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
+// The library is eight translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
 //   cpi_mean.hip    cpi_mean_kernel / cpi_mean_tiled_kernel / cpi_tile_*_kernel       (cpi_mean_kernels.hpp)
 //   cpi_running.hip cpi_mean_running_kernel / cpi_mean_stream_running_kernel: a row after every interval, from plain knots /
 //                   from windows cut out of IMU stream(s) in place         (cpi_running_kernels.hpp, cpi_running_body.inc)
@@ -9,6 +9,8 @@
 //                   records, over the bodies of the two units above (cpi_running_body.inc, cov_body)
 //   cpi_query.hip   cpi_query_kernel: the measurement at arbitrary times inside a window, one partial interval from a running row
 //                                                                                      (cpi_query_kernels.hpp)
+//   cpi_query_cov.hip  cpi_query_cov_kernel: the covariance at arbitrary times, one partial interval of the covariance recursion
+//                   from a running P / P_sym row                                       (cpi_query_cov_kernels.hpp)
 //   cpi_factor.hip  evaluateError sweeps, square-root information, Hessian blocks, state prediction
 //                                                                                      (cpi_factor_kernels.hpp)
 //   cpi_abi.hip     the C-ABI of include/cpi_amd.h: argument checks, launch heuristics, device sets (RCCL), the
@@ -186,6 +188,8 @@ void mean_running_carry(int model, bool jac, bool avg, int L, const PreArgs &a, 
 void cov_running_carry(int model, bool avg, const PreArgs &a, const CarryArgs &c, hipStream_t st);   // P / P_sym rows + the covariance block of c.out
 // ---- cpi_query.hip (cpi_query_batch; jac: model 1 only)
 void query(int model, bool jac, bool avg, const QueryArgs &a, hipStream_t st);
+// ---- cpi_query_cov.hip (cpi_query_cov_batch: a.out.P / P_sym from a.rows.q and a.rows.P or P_sym; q4 as PreArgs::q4)
+void query_cov(int model, bool avg, const QueryArgs &a, const double q4[4], hipStream_t st);
 // ---- cpi_factor.hip
 void factor(int model, bool whiten, int lpf, const FactorArgs &a, hipStream_t st);            // lpf 16 | 8 | 4
 void factor_packed(int model, int lpf, const FactorArgs &a, double *packed, hipStream_t st);  // lpf 2 | 3 | 4 | 6 | 8

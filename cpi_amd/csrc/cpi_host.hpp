@@ -479,50 +479,14 @@ public:
     // interval with the reading held (the reference's tail, GraphSolver_IMU.cpp:64-69), before the window's first stamp the zero
     // state, at or past its last stamp the window's measurement.  times holds one vector per added window, in any order.  A
     // window that holds a separator knot (feed_IMU calls that do not chain) has no time axis to query: std::logic_error.  Models
-    // 1 and 2; the bias Jacobians are filled for model 1 only, P_meas is not computed.  The windows stay added.
+    // 1 and 2; the bias Jacobians are filled for model 1 only, P_meas is not computed (at_cov computes it).  The windows stay added.
     std::vector<std::vector<CpiResult>> at(const Context &ctx, const std::vector<std::vector<double>> &times) const {
-        if (times.size() != win_.size()) throw std::logic_error("CpiBatch::at: one vector of times per added window");
-        std::vector<std::vector<CpiResult>> res(win_.size());
-        std::vector<int32_t> qwin;
-        std::vector<double> qtime;
-        for (size_t w = 0; w < win_.size(); w++) {
-            const std::vector<double> &k = win_[w]->knots();
-            for (size_t i = 0; i < k.size(); i += 7)
-                if (k[i] != k[i]) throw std::logic_error("CpiBatch::at: window " + std::to_string(w) + " holds a separator knot (its intervals do not chain)");
-            qwin.insert(qwin.end(), times[w].size(), (int32_t)w);
-            qtime.insert(qtime.end(), times[w].begin(), times[w].end());
-            res[w].resize(times[w].size());
-        }
-        const int64_t Q = (int64_t)qtime.size();
-        if (Q == 0) return res;
-        const int64_t W = (int64_t)win_.size();
-        std::vector<double> knots, lin, qk;
-        std::vector<int64_t> first;
-        std::vector<int32_t> count;
-        const int32_t N = ragged(knots, first, count, lin, qk);
-        cpi_params p = win_[0]->params();
-        const bool jac = p.model == CPI_MODEL_V1;
-        std::vector<double> DT(Q), al(Q * 3), be(Q * 3), q(Q * 4), Jq(jac ? Q * 9 : 0), Ja(jac ? Q * 9 : 0), Jb(jac ? Q * 9 : 0),
-            Ha(jac ? Q * 9 : 0), Hb(jac ? Q * 9 : 0);
-        cpi_outputs o{};
-        o.DT = DT.data(); o.alpha = al.data(); o.beta = be.data(); o.q = q.data();
-        if (jac) { o.J_q = Jq.data(); o.J_a = Ja.data(); o.J_b = Jb.data(); o.H_a = Ha.data(); o.H_b = Hb.data(); }
-        ctx.check(cpi_query_batch_host(ctx.get(), &p, W, N, knots.data(), first.data(), count.data(), (int64_t)(knots.size() / 7),
-                                       lin.data(), qk.data(), Q, qwin.data(), qtime.data(), &o));
-        size_t r = 0;
-        for (std::vector<CpiResult> &win : res)
-            for (CpiResult &x : win) {
-                x.DT = DT[r];
-                for (int k = 0; k < 3; k++) { x.alpha_tau[k] = al[r * 3 + k]; x.beta_tau[k] = be[r * 3 + k]; }
-                for (int k = 0; k < 4; k++) x.q_k2tau[k] = q[r * 4 + k];
-                if (jac)
-                    for (int k = 0; k < 9; k++) {
-                        x.J_q[k] = Jq[r * 9 + k]; x.J_a[k] = Ja[r * 9 + k]; x.J_b[k] = Jb[r * 9 + k];
-                        x.H_a[k] = Ha[r * 9 + k]; x.H_b[k] = Hb[r * 9 + k];
-                    }
-                r++;
-            }
-        return res;
+        return at_impl(ctx, times, false);
+    }
+    // at() with the covariance: P_meas is filled as well (cpi_query_cov_batch_host) -- the complete measurement of a factor at a
+    // query time.
+    std::vector<std::vector<CpiResult>> at_cov(const Context &ctx, const std::vector<std::vector<double>> &times) const {
+        return at_impl(ctx, times, true);
     }
     // Mean outputs only (DT, alpha_tau, beta_tau, q_k2tau): the HBM-bound request.  The recorded windows are written
     // straight into the TILED layout (include/cpi_amd.h: tiles[ceil(W/64)][N+1][7][64], knot s of window w at
@@ -559,6 +523,57 @@ public:
         win_.clear();
     }
 private:
+    // at / at_cov: the queries of all windows in one call; cov: P_meas as well
+    std::vector<std::vector<CpiResult>> at_impl(const Context &ctx, const std::vector<std::vector<double>> &times, bool cov) const {
+        if (times.size() != win_.size()) throw std::logic_error("CpiBatch::at: one vector of times per added window");
+        std::vector<std::vector<CpiResult>> res(win_.size());
+        std::vector<int32_t> qwin;
+        std::vector<double> qtime;
+        for (size_t w = 0; w < win_.size(); w++) {
+            const std::vector<double> &k = win_[w]->knots();
+            for (size_t i = 0; i < k.size(); i += 7)
+                if (k[i] != k[i]) throw std::logic_error("CpiBatch::at: window " + std::to_string(w) + " holds a separator knot (its intervals do not chain)");
+            qwin.insert(qwin.end(), times[w].size(), (int32_t)w);
+            qtime.insert(qtime.end(), times[w].begin(), times[w].end());
+            res[w].resize(times[w].size());
+        }
+        const int64_t Q = (int64_t)qtime.size();
+        if (Q == 0) return res;
+        const int64_t W = (int64_t)win_.size();
+        std::vector<double> knots, lin, qk;
+        std::vector<int64_t> first;
+        std::vector<int32_t> count;
+        const int32_t N = ragged(knots, first, count, lin, qk);
+        cpi_params p = win_[0]->params();
+        const bool jac = p.model == CPI_MODEL_V1;
+        std::vector<double> DT(Q), al(Q * 3), be(Q * 3), q(Q * 4), Jq(jac ? Q * 9 : 0), Ja(jac ? Q * 9 : 0), Jb(jac ? Q * 9 : 0),
+            Ha(jac ? Q * 9 : 0), Hb(jac ? Q * 9 : 0), P(cov ? Q * 225 : 0);
+        cpi_outputs o{};
+        o.DT = DT.data(); o.alpha = al.data(); o.beta = be.data(); o.q = q.data();
+        if (jac) { o.J_q = Jq.data(); o.J_a = Ja.data(); o.J_b = Jb.data(); o.H_a = Ha.data(); o.H_b = Hb.data(); }
+        if (cov) o.P = P.data();
+        const int64_t K = (int64_t)(knots.size() / 7);
+        ctx.check(cov ? cpi_query_cov_batch_host(ctx.get(), &p, W, N, knots.data(), first.data(), count.data(), K, lin.data(), qk.data(), Q,
+                                                 qwin.data(), qtime.data(), &o)
+                      : cpi_query_batch_host(ctx.get(), &p, W, N, knots.data(), first.data(), count.data(), K, lin.data(), qk.data(), Q,
+                                             qwin.data(), qtime.data(), &o));
+        size_t r = 0;
+        for (std::vector<CpiResult> &win : res)
+            for (CpiResult &x : win) {
+                x.DT = DT[r];
+                for (int k = 0; k < 3; k++) { x.alpha_tau[k] = al[r * 3 + k]; x.beta_tau[k] = be[r * 3 + k]; }
+                for (int k = 0; k < 4; k++) x.q_k2tau[k] = q[r * 4 + k];
+                if (jac)
+                    for (int k = 0; k < 9; k++) {
+                        x.J_q[k] = Jq[r * 9 + k]; x.J_a[k] = Ja[r * 9 + k]; x.J_b[k] = Jb[r * 9 + k];
+                        x.H_a[k] = Ha[r * 9 + k]; x.H_b[k] = Hb[r * 9 + k];
+                    }
+                if (cov)
+                    for (int k = 0; k < 225; k++) x.P_meas[k] = P[r * 225 + k];
+                r++;
+            }
+        return res;
+    }
     // the added windows in the ragged layout of include/cpi_amd.h (a window without knots: one zero knot, count 0); returns N
     int32_t ragged(std::vector<double> &knots, std::vector<int64_t> &first, std::vector<int32_t> &count, std::vector<double> &lin,
                    std::vector<double> &qk) const {

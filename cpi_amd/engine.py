@@ -311,16 +311,22 @@ class Engine:
                                                                   _ptr(lin), _ptr(q_k_lin), _ptr(carry_in), _ptr(carry_out), C.byref(o)))
         return out, carry_out
 
+    @staticmethod
+    def _wants_cov(want):
+        return "cov" in want or "cov_sym" in want
+
     def query(self, knots, lin, rows, qwin, qtime, q_k_lin=None, params=None, want=("mean",), first=None, count=None, N=None,
               out=None):
         """cpi_query_batch: the measurement at arbitrary times inside a window.  knots / lin / q_k_lin / params / first / count / N:
         the arguments of the preintegrate_running call that returned `rows` (its dict, [W, N, ...] tensors); qwin [Q] int32 and
         qtime [Q] float64 CUDA tensors: query k asks for window qwin[k] at time qtime[k] (any order, repeats allowed; the
         stamps of a queried window must be finite and non-decreasing).  want: ("mean",) or ("mean", "jac") -- the Jacobians for
-        model 1 only, and rows must hold them.  Returns a dict of [Q, ...] tensors: a time on a knot stamp (or at / past the
-        window's end) gives the running row bit for bit, a time inside an interval that row advanced over the partial interval
-        with the reading held, a time before the window the zero state, a NaN time NaN.  The result is an ordinary measurement
-        dict: predict(model, result, states, idx_i=qwin) gives the states AT the query times.  Asynchronous."""
+        model 1 only, and rows must hold them -- and / or "cov" (P, [Q, 225]) / "cov_sym" (P_sym, [Q, 120]): the covariance at
+        the query times (cpi_query_cov_batch; rows must hold q and P or P_sym, models 1 and 2).  Returns a dict of [Q, ...]
+        tensors: a time on a knot stamp (or at / past the window's end) gives the running row bit for bit, a time inside an
+        interval that row advanced over the partial interval with the reading held, a time before the window the zero state, a
+        NaN time NaN.  The result is an ordinary measurement dict: predict(model, result, states, idx_i=qwin) gives the states
+        AT the query times, sqrt_information(result["P_sym"]) the whitening of a factor there.  Asynchronous."""
         params = params or self.make_params()
         W, N = self._window_shape(knots, lin, first, count, N, (q_k_lin, qwin, qtime))
         Q = qtime.shape[0]
@@ -333,14 +339,17 @@ class Engine:
         o = self._outputs_struct(out)
         ro = self._outputs_struct(r)
         self._sync_stream()
-        self._check(self.lib.cpi_query_batch(self.ctx, C.byref(params), W, N, _ptr(knots), _ptr(first), _ptr(count), _ptr(lin),
-                                             _ptr(q_k_lin), C.byref(ro), Q, _ptr(qwin), _ptr(qtime), C.byref(o)))
+        entry = self.lib.cpi_query_cov_batch if self._wants_cov(want) else self.lib.cpi_query_batch
+        self._check(entry(self.ctx, C.byref(params), W, N, _ptr(knots), _ptr(first), _ptr(count), _ptr(lin),
+                          _ptr(q_k_lin), C.byref(ro), Q, _ptr(qwin), _ptr(qtime), C.byref(o)))
         return out
 
     def query_host(self, knots, lin, qwin, qtime, q_k_lin=None, params=None, want=("mean",), count=None, pinned=True, out=None):
         """query for a dense batch held in HOST memory (CPU tensors): cpi_query_batch_host.  There is no rows argument -- the
         running rows are computed on the device and stay there, Q rows come back.  qwin and the stamps of every queried window
-        are validated (CpiError names the window).  Returns a dict of CPU tensors [Q, ...]; synchronous."""
+        are validated (CpiError names the window).  want as in query: with "cov" / "cov_sym" the call is
+        cpi_query_cov_batch_host and the covariance rows stay on the device as well.  Returns a dict of CPU tensors [Q, ...];
+        synchronous."""
         params = params or self.make_params()
         W, N = self._window_shape(knots, lin, count=count, others=(q_k_lin, qwin, qtime), cuda=False)
         Q = qtime.shape[0]
@@ -349,8 +358,9 @@ class Engine:
             out = self._host_outputs((Q,), tuple(want), params.model, pinned)
         o = self._outputs_struct(out)
         self._sync_stream()
-        self._check(self.lib.cpi_query_batch_host(self.ctx, C.byref(params), W, N, _ptr(knots), None, _ptr(count), 0, _ptr(lin),
-                                                  _ptr(q_k_lin), Q, _ptr(qwin), _ptr(qtime), C.byref(o)))
+        entry = self.lib.cpi_query_cov_batch_host if self._wants_cov(want) else self.lib.cpi_query_batch_host
+        self._check(entry(self.ctx, C.byref(params), W, N, _ptr(knots), None, _ptr(count), 0, _ptr(lin),
+                          _ptr(q_k_lin), Q, _ptr(qwin), _ptr(qtime), C.byref(o)))
         return out
 
     def preintegrate_host(self, knots, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), count=None, pinned=True, out=None):

@@ -56,7 +56,8 @@ extern "C" {
                                from IMU stream(s), windows cut in place); cpi_preintegrate_running_resume,
                                cpi_preintegrate_running_resume_host (the running rows of a window that continues from a
                                carry record); cpi_query_batch, cpi_query_batch_host (the measurement at arbitrary times inside
-                               a window) */
+                               a window); cpi_query_cov_batch, cpi_query_cov_batch_host (the same with the covariance P / P_sym
+                               at the query times) */
 
 enum { CPI_OK = 0, CPI_ERR_INVALID = 1, CPI_ERR_HIP = 2, CPI_ERR_NO_DEVICE = 3, CPI_ERR_RCCL = 4 };
 enum {
@@ -295,11 +296,47 @@ int cpi_preintegrate_running_resume(cpi_ctx *ctx, const cpi_params *prm, int64_t
  * Composition: cpi_predict_batch(F = Q, meas = out, idx_i = qwin) gives the predicted states AT the query times.
  * Not provided: P / P_sym at query times (they need the covariance kernel's lane-spread RK4 step); Jacobians for model 2; windows
  * cut from IMU streams in place (cpi_preintegrate_stream[s]_running: assemble the windows, or query per update time); rows that
- * continue from a carry record (cpi_preintegrate_running_resume); extrapolation past t_n. */
+ * continue from a carry record (cpi_preintegrate_running_resume); extrapolation past t_n.  (The covariance at query times is a
+ * call of its own: cpi_query_cov_batch below.) */
 int cpi_query_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                     const double *knots, const int64_t *first, const int32_t *count,
                     const double *lin, const double *q_k_lin, const cpi_outputs *rows,
                     int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out);
+
+/* cpi_query_batch WITH THE COVARIANCE: the noise model of a keyframe stamped between two IMU readings, or chosen after the fact,
+ * so that the factor at a query time can be whitened (cpi_sqrt_information_*) and enter cpi_factor_hessian_* -- without
+ * preintegrating a cut copy of the window from its start.  A superset of cpi_query_batch: the arguments, the choice of i, the
+ * precondition on the stamps, the clamping of qwin on the device, "no read leaves the window's knots or rows", Q == 0, N == 0, a NaN
+ * t_q and every refusal of cpi_query_batch (with its text) are the same, except that out may also hold
+ *   out->P [Q][225] and / or out->P_sym [Q][120] (independent of each other), for models 1 and 2, imu_avg 0 / 1, dense and ragged
+ *   layouts.
+ * The mean and Jacobian fields of out are written by cpi_query_batch's own kernel under cpi_query_batch's requirements on rows and
+ * are bit for bit what cpi_query_batch writes; with neither P nor P_sym in out the call IS cpi_query_batch.
+ * With P or P_sym in out, rows must hold (N > 0) q and P or P_sym -- CPI_ERR_INVALID names what is missing -- and nothing else: the
+ * partial interval needs of the row only its rotation (DT / alpha / beta only when out asks for a mean field).  Query k, with i as
+ * in cpi_query_batch:
+ *   - base matrix S = zeros when i == 0, else row w N + i - 1 of rows->P; when only rows->P_sym is given, that row mirrored across
+ *     the diagonal (rows->P is preferred when both are given);
+ *   - no step (t_q on a stamp, before t_0, at or past t_n): out->P[k] = S and out->P_sym[k] = its upper triangle, BIT FOR BIT (i == 0:
+ *     all +0);
+ *   - step (i < n and t_q > t_i): S propagated by the reference's covariance step (RK4, four stages) over feed_IMU(t_i, t_q, w_i,
+ *     a_i, w_i, a_i); the rotation at the start of the interval is quat_2_Rot of the row's q ([0 0 0 1] for i == 0), and R(q_k_lin) g
+ *     enters for model 2 as it does elsewhere.  Model 2 carries 18 rows and columns (the theta clone): after every interval the
+ *     reference clones and marginalises, so at a row boundary they are determined by the 15 x 15 row -- rows 15..17 of every column
+ *     are its rows 0..2, columns 15..17 are columns 0..2 -- and are rebuilt from it.  out->P_sym[k] is bit for bit the upper triangle
+ *     of out->P[k], and out->P[k] equals the P of cpi_preintegrate_batch on [knot 0 .. knot i, {t_q, w_i, a_i}] up to rounding;
+ *   - t_q NaN: NaN in all 225 / 120 entries.
+ * The kernels (cpi_query_batch's for the means, one more for the covariance) run one after the other on the context's stream: no
+ * side stream, no host synchronisation; a capture of cpi_preintegrate_running followed by this call is a chain without parallel
+ * branches.
+ * Composition: out->P_sym -> cpi_sqrt_information_packed_batch -> cpi_factor_eval_whitened_tri_batch / cpi_factor_hessian_tri_batch
+ * with idx_i = qwin: the whitened keyframe factor AT the query time.
+ * Still not provided: model-2 Jacobians at query times; windows cut from IMU streams in place; rows from a carry record;
+ * extrapolation past t_n. */
+int cpi_query_cov_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                        const double *knots, const int64_t *first, const int32_t *count,
+                        const double *lin, const double *q_k_lin, const cpi_outputs *rows,
+                        int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out);
 
 /* Replaces: the whole caller side of GraphSolver::createimufactor_cpi_v1 / _v2 (GraphSolver_IMU.cpp:43-75, 97-130) for every
  * window of a trajectory at once, reading ONE IMU stream IN PLACE: no knot is copied, for any model and any output.
@@ -608,6 +645,14 @@ int cpi_query_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t
                          const double *knots, const int64_t *first, const int32_t *count, int64_t n_knots,
                          const double *lin, const double *q_k_lin,
                          int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out);
+/* cpi_query_cov_batch from host memory: the arguments, the staging and the validation of cpi_query_batch_host (its messages carry
+ * this entry's name), with P / P_sym accepted in out.  The running rows stay in device staging, the covariance rows as P_sym (960 B
+ * per row instead of 1 800): the staging need is W * N rows of 88 B (means) + 72 B per requested Jacobian field + 960 B when out
+ * asks for P or P_sym, next to the windows and the Q output rows.  Bit for bit the device form on rows that hold P_sym. */
+int cpi_query_cov_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                             const double *knots, const int64_t *first, const int32_t *count, int64_t n_knots,
+                             const double *lin, const double *q_k_lin,
+                             int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out);
 /* cpi_preintegrate_resume from host memory: every pointer a host pointer, n_knots as in cpi_preintegrate_batch_host. */
 int cpi_preintegrate_resume_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                                  const double *knots, const int64_t *first, const int32_t *count,
