@@ -168,6 +168,12 @@ def load():
     lib.cpi_query_cov_batch.argtypes = lib.cpi_query_batch.argtypes
     lib.cpi_query_cov_batch_host.argtypes = lib.cpi_query_batch_host.argtypes
     lib.cpi_query_cov_batch.restype = lib.cpi_query_cov_batch_host.restype = C.c_int
+    lib.cpi_query_stj_batch.argtypes = lib.cpi_query_cov_batch.argtypes
+    lib.cpi_query_stj_batch_host.argtypes = lib.cpi_query_cov_batch_host.argtypes
+    lib.cpi_running_stj_batch.argtypes = lib.cpi_preintegrate_running.argtypes
+    lib.cpi_running_stj_batch_host.argtypes = lib.cpi_preintegrate_running_host.argtypes
+    for f in (lib.cpi_query_stj_batch, lib.cpi_query_stj_batch_host, lib.cpi_running_stj_batch, lib.cpi_running_stj_batch_host):
+        f.restype = C.c_int
     lib.cpi_preintegrate_stream_running.argtypes = lib.cpi_preintegrate_stream.argtypes
     lib.cpi_preintegrate_stream_running_host.argtypes = lib.cpi_preintegrate_stream_host.argtypes
     lib.cpi_preintegrate_streams_running.argtypes = lib.cpi_preintegrate_streams.argtypes

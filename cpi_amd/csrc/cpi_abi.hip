@@ -506,34 +506,56 @@ extern "C" int cpi_preintegrate_resume(cpi_ctx *ctx, const cpi_params *prm, int6
 // from cpi_cov_running_kernel.  The kernels run one after the other on the context's stream (no side stream: a capture of the
 // call is a chain), and unlike the batch entry the covariance kernel leaves the means to the mean kernel -- its own means
 // advance once per staged pass, not per interval.
-extern "C" int cpi_preintegrate_running(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
-                                        const double *knots, const int64_t *first, const int32_t *count,
-                                        const double *lin, const double *q_k_lin, const cpi_outputs *rows) {
-    static const char who[] = "cpi_preintegrate_running";
+// cpi_preintegrate_running and cpi_running_stj_batch (with_stj) are one body.  The latter serves the Jacobian fields of model 2
+// with state_transition_jacobians != 0 as well: cpi_cov_running_stj_kernel takes the place of cpi_cov_running_kernel (it runs even when
+// P / P_sym are not asked for: the transition columns ride on the covariance recursion) and the mean kernel is launched exactly as
+// for the same request without the Jacobian fields, so the mean and P rows are bit for bit those of cpi_preintegrate_running.
+static const char kNoAnalyticRunning[] = "the Jacobian fields (J_q ... O_b) of model 2 need state_transition_jacobians != 0 here: the analytic O_a / O_b "
+                                         "recursion has no running form (the rows are read out of the state transition matrix)";
+static int refuse_v2_jac_here(cpi_ctx *ctx, const char *who, bool with_stj, const cpi_params *prm, const char *advice) {
+    if (with_stj) return prm->state_transition_jacobians != 0 ? CPI_OK : refuse(ctx, who, kNoAnalyticRunning);
+    return refuse_v2_jac(ctx, who, advice);
+}
+static int running_device(cpi_ctx *ctx, const char *who, bool with_stj, const cpi_params *prm, int64_t W, int32_t N,
+                          const double *knots, const int64_t *first, const int32_t *count,
+                          const double *lin, const double *q_k_lin, const cpi_outputs *rows) {
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
     if (!prm || !rows) return refuse(ctx, who, "prm/rows is NULL");
     if (prm->model == CPI_MODEL_FORSTER) return refuse_forster(ctx, who, NO_RUNNING_FORM);
     if (!model_is_cpi(prm)) return refuse(ctx, who, "model must be 1 or 2");
     const Request rq = request_of(rows);
-    if (prm->model == CPI_MODEL_V2 && rq.jac) return refuse_v2_jac(ctx, who, "");
+    const bool stj = prm->model == CPI_MODEL_V2 && rq.jac;   // (past the refusal below: the rows of the transition columns)
+    if (stj) CPI_TRY(refuse_v2_jac_here(ctx, who, with_stj, prm, ""));
     if (W < 0 || N < 0) return refuse(ctx, who, "negative size");
     if (W == 0 || N == 0) return CPI_OK;
     CPI_TRY(check_windows(ctx, who, prm, W, N, knots, lin, q_k_lin));
     if (!rq.any()) return CPI_OK;
     const bool avg = prm->imu_avg != 0;
+    const bool mean_jac = rq.jac && !stj;
 
     DeviceGuard guard_;
     CPI_HIP(ctx, guard_.enter(ctx->device));
     const PreArgs a = pre_args(prm, W, N, knots, first, count, lin, q_k_lin, rows);
-    if (rq.mean || rq.jac) {
+    if (rq.mean || mean_jac) {
         PreArgs m = a;
         m.write_means = rq.mean ? 1 : 0;
-        m.write_jac = rq.jac ? 1 : 0;
-        launch::mean_running(prm->model, rq.jac, avg, pick_lanes(prm, W, N, rq.jac), m, ctx->stream);
+        m.write_jac = mean_jac ? 1 : 0;
+        launch::mean_running(prm->model, mean_jac, avg, pick_lanes(prm, W, N, mean_jac), m, ctx->stream);
     }
-    if (rq.cov) launch::cov_running(prm->model, avg, a, ctx->stream);
+    if (stj) launch::cov_running_stj(avg, a, ctx->stream);
+    else if (rq.cov) launch::cov_running(prm->model, avg, a, ctx->stream);
     CPI_HIP(ctx, hipGetLastError());
     return CPI_OK;
+}
+extern "C" int cpi_preintegrate_running(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                        const double *knots, const int64_t *first, const int32_t *count,
+                                        const double *lin, const double *q_k_lin, const cpi_outputs *rows) {
+    return running_device(ctx, "cpi_preintegrate_running", false, prm, W, N, knots, first, count, lin, q_k_lin, rows);
+}
+extern "C" int cpi_running_stj_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                     const double *knots, const int64_t *first, const int32_t *count,
+                                     const double *lin, const double *q_k_lin, const cpi_outputs *rows) {
+    return running_device(ctx, "cpi_running_stj_batch", true, prm, W, N, knots, first, count, lin, q_k_lin, rows);
 }
 
 // Running preintegration from and to carry records (include/cpi_amd.h): the argument rules of cpi_preintegrate_running and the
@@ -586,11 +608,13 @@ extern "C" int cpi_preintegrate_running_resume(cpi_ctx *ctx, const cpi_params *p
 // cpi_query_batch and cpi_query_cov_batch are one body: the latter also accepts P / P_sym in out (with_cov) and then enqueues
 // cpi_query_cov_kernel behind the mean kernel, on the same stream.
 static const char kQueryNoCov[] = "P / P_sym are not available at query times (they need the covariance kernel's lane-spread RK4 step)";
-static int query_check(cpi_ctx *ctx, const char *who, const cpi_params *prm, const Request &rq, bool with_cov) {
+// what an entry of the query family serves beyond the means and the model-1 Jacobians
+enum { QUERY_COV = 1, QUERY_STJ = 2 };
+static int query_check(cpi_ctx *ctx, const char *who, const cpi_params *prm, const Request &rq, int with) {
     if (prm->model == CPI_MODEL_FORSTER) return refuse(ctx, who, "model must be 1 or 2 (the Forster comparator has no running form)");
     if (!model_is_cpi(prm)) return refuse(ctx, who, "model must be 1 or 2");
-    if (rq.cov && !with_cov) return refuse(ctx, who, kQueryNoCov);
-    if (prm->model == CPI_MODEL_V2 && rq.jac) return refuse_v2_jac(ctx, who, "");
+    if (rq.cov && !(with & QUERY_COV)) return refuse(ctx, who, kQueryNoCov);
+    if (prm->model == CPI_MODEL_V2 && rq.jac) return refuse_v2_jac_here(ctx, who, (with & QUERY_STJ) != 0, prm, "");
     return CPI_OK;
 }
 static int query_trips(int32_t N) {
@@ -599,11 +623,11 @@ static int query_trips(int32_t N) {
     return trips;
 }
 // the checks the device and the host form share, up to the ones on rows (the host form computes its own rows); *done: a no-op call
-static int query_check_args(cpi_ctx *ctx, const char *who, bool with_cov, const cpi_params *prm, int64_t W, int32_t N, const double *knots,
+static int query_check_args(cpi_ctx *ctx, const char *who, int with, const cpi_params *prm, int64_t W, int32_t N, const double *knots,
                             const double *lin, const double *q_k_lin, int64_t Q, const int32_t *qwin, const double *qtime,
                             const cpi_outputs *out, bool *done) {
     *done = true;
-    CPI_TRY(query_check(ctx, who, prm, request_of(out), with_cov));
+    CPI_TRY(query_check(ctx, who, prm, request_of(out), with));
     if (W < 0 || N < 0 || Q < 0) return refuse(ctx, who, "negative size");
     if (Q == 0) return CPI_OK;
     if (W == 0) return refuse(ctx, who, "W is 0: there is no window to query");
@@ -613,7 +637,7 @@ static int query_check_args(cpi_ctx *ctx, const char *who, bool with_cov, const 
     *done = false;
     return CPI_OK;
 }
-static int query_device(cpi_ctx *ctx, const char *who, bool with_cov, const cpi_params *prm, int64_t W, int32_t N,
+static int query_device(cpi_ctx *ctx, const char *who, int with, const cpi_params *prm, int64_t W, int32_t N,
                         const double *knots, const int64_t *first, const int32_t *count,
                         const double *lin, const double *q_k_lin, const cpi_outputs *rows,
                         int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out) {
@@ -621,13 +645,22 @@ static int query_device(cpi_ctx *ctx, const char *who, bool with_cov, const cpi_
     if (!prm || !rows || !out) return refuse(ctx, who, "prm/rows/out is NULL");
     const Request rq = request_of(out);
     bool done;
-    CPI_TRY(query_check_args(ctx, who, with_cov, prm, W, N, knots, lin, q_k_lin, Q, qwin, qtime, out, &done));
+    CPI_TRY(query_check_args(ctx, who, with, prm, W, N, knots, lin, q_k_lin, Q, qwin, qtime, out, &done));
     if (done) return CPI_OK;
-    const bool means = rq.mean || rq.jac;
+    const bool stj = prm->model == CPI_MODEL_V2 && rq.jac;   // (cpi_query_stj_batch: query_check has refused it for the others)
+    const bool mean_jac = rq.jac && !stj;
+    const bool means = rq.mean || mean_jac;
+    if (N > 0 && stj) {   // the transition columns are rebuilt from ALL seven fields of a row, whatever subset out asks for
+        std::string lacks;
+        const struct { const char *name; const double *p; } need[] = { {"q", rows->q}, {"J_q", rows->J_q}, {"J_a", rows->J_a}, {"J_b", rows->J_b},
+                                                                       {"H_a", rows->H_a}, {"H_b", rows->H_b}, {"O_a", rows->O_a}, {"O_b", rows->O_b} };
+        for (const auto &f : need) if (!f.p) lacks += std::string(lacks.empty() ? "" : ", ") + f.name;
+        if (!lacks.empty()) return refuse(ctx, who, "rows needs q and all seven Jacobian fields for the model-2 Jacobians; missing: ", lacks.c_str());
+    }
     if (N > 0) {   // N == 0: every query is the zero state and rows is not read
-        if (means || !rq.cov) {
+        if (means || !(rq.cov || stj)) {
             if (!rows->DT || !rows->alpha || !rows->beta || !rows->q) return refuse(ctx, who, "rows needs DT, alpha, beta and q");
-            if ((out->J_q && !rows->J_q) || (out->J_a && !rows->J_a) || (out->J_b && !rows->J_b) || (out->H_a && !rows->H_a) || (out->H_b && !rows->H_b))
+            if (!stj && ((out->J_q && !rows->J_q) || (out->J_a && !rows->J_a) || (out->J_b && !rows->J_b) || (out->H_a && !rows->H_a) || (out->H_b && !rows->H_b)))
                 return refuse(ctx, who, "a Jacobian field of out needs the same field of rows");
         }
         if (rq.cov) {
@@ -644,13 +677,14 @@ static int query_device(cpi_ctx *ctx, const char *who, bool with_cov, const cpi_
     a.W = W; a.N = N; a.knots = knots; a.first = (const long long *)first; a.count = count; a.lin = lin; a.qk = q_k_lin;
     for (int i = 0; i < 3; i++) a.grav[i] = prm->grav[i];
     a.rows = *rows; a.Q = Q; a.qwin = qwin; a.qtime = qtime; a.trips = query_trips(N); a.out = *out;
-    if (rq.jac) {
+    if (mean_jac) {
         // the Jacobian instance carries all five matrices: the ones out does not ask for are read from a field that is there
         const double *any = rows->J_q ? rows->J_q : rows->J_a ? rows->J_a : rows->J_b ? rows->J_b : rows->H_a ? rows->H_a : rows->H_b;
         double **f[5] = { &a.rows.J_q, &a.rows.J_a, &a.rows.J_b, &a.rows.H_a, &a.rows.H_b };
         for (double **x : f) if (!*x) *x = const_cast<double *>(any);
     }
-    if (means) launch::query(prm->model, rq.jac, prm->imu_avg != 0, a, ctx->stream);
+    if (means) launch::query(prm->model, mean_jac, prm->imu_avg != 0, a, ctx->stream);
+    if (stj) launch::query_stj(prm->imu_avg != 0, a, ctx->stream);
     if (rq.cov) {
         const double q4[4] = { prm->sigma_w * prm->sigma_w, prm->sigma_wb * prm->sigma_wb, prm->sigma_a * prm->sigma_a, prm->sigma_ab * prm->sigma_ab };
         launch::query_cov(prm->model, prm->imu_avg != 0, a, q4, ctx->stream);
@@ -662,13 +696,20 @@ extern "C" int cpi_query_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, i
                                const double *knots, const int64_t *first, const int32_t *count,
                                const double *lin, const double *q_k_lin, const cpi_outputs *rows,
                                int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out) {
-    return query_device(ctx, "cpi_query_batch", false, prm, W, N, knots, first, count, lin, q_k_lin, rows, Q, qwin, qtime, out);
+    return query_device(ctx, "cpi_query_batch", 0, prm, W, N, knots, first, count, lin, q_k_lin, rows, Q, qwin, qtime, out);
 }
 extern "C" int cpi_query_cov_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                                    const double *knots, const int64_t *first, const int32_t *count,
                                    const double *lin, const double *q_k_lin, const cpi_outputs *rows,
                                    int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out) {
-    return query_device(ctx, "cpi_query_cov_batch", true, prm, W, N, knots, first, count, lin, q_k_lin, rows, Q, qwin, qtime, out);
+    return query_device(ctx, "cpi_query_cov_batch", QUERY_COV, prm, W, N, knots, first, count, lin, q_k_lin, rows, Q, qwin, qtime, out);
+}
+// cpi_query_cov_batch + the Jacobians of model 2 (state_transition_jacobians != 0): cpi_query_stj_kernel, on the same stream
+extern "C" int cpi_query_stj_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                   const double *knots, const int64_t *first, const int32_t *count,
+                                   const double *lin, const double *q_k_lin, const cpi_outputs *rows,
+                                   int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out) {
+    return query_device(ctx, "cpi_query_stj_batch", QUERY_COV | QUERY_STJ, prm, W, N, knots, first, count, lin, q_k_lin, rows, Q, qwin, qtime, out);
 }
 
 // Replaces the caller-side loop of GraphSolver::createimufactor_cpi_v1 / _v2 (GraphSolver_IMU.cpp:43-75, 97-130) for ALL the
@@ -1725,16 +1766,19 @@ extern "C" int cpi_preintegrate_batch_host(cpi_ctx *ctx, const cpi_params *prm, 
     return st.finish();
 }
 
-extern "C" int cpi_preintegrate_running_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
-                                             const double *knots, const int64_t *first, const int32_t *count,
-                                             int64_t n_knots, const double *lin, const double *q_k_lin,
-                                             const cpi_outputs *rows) {
-    static const char who[] = "cpi_preintegrate_running_host";
+// cpi_preintegrate_running_host / cpi_running_stj_batch_host: one body over the device entry of the same family
+typedef int (*RunningEntry)(cpi_ctx *, const cpi_params *, int64_t, int32_t, const double *, const int64_t *, const int32_t *, const double *,
+                            const double *, const cpi_outputs *);
+static int running_host(cpi_ctx *ctx, const char *who, bool with_stj, const cpi_params *prm, int64_t W, int32_t N,
+                        const double *knots, const int64_t *first, const int32_t *count,
+                        int64_t n_knots, const double *lin, const double *q_k_lin,
+                        const cpi_outputs *rows) {
+    const RunningEntry entry = with_stj ? cpi_running_stj_batch : cpi_preintegrate_running;
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
     if (!prm || !rows || !knots || !lin) return refuse(ctx, who, "NULL argument");
     if (W < 0 || N < 0) return fail(ctx, CPI_ERR_INVALID, "negative size");
     if (!model_is_cpi(prm)) return refuse_forster(ctx, who, NO_RUNNING_FORM);
-    if (prm->model == CPI_MODEL_V2 && request_of(rows).jac) return refuse_v2_jac(ctx, who, nullptr);
+    if (prm->model == CPI_MODEL_V2 && request_of(rows).jac) CPI_TRY(refuse_v2_jac_here(ctx, who, with_stj, prm, nullptr));
     if (W == 0 || N == 0) return CPI_OK;
     CPI_TRY(check_N(ctx, who, N));
     DeviceGuard guard_;
@@ -1742,7 +1786,7 @@ extern "C" int cpi_preintegrate_running_host(cpi_ctx *ctx, const cpi_params *prm
     if (!first)
         return preintegrate_host_pipeline(ctx, who, W, (size_t)N, pipe_windows(knots, N, 1, count, lin, q_k_lin), rows,
                                           [&](int64_t wn, void *const *dev, const cpi_outputs *d) {
-                                              return cpi_preintegrate_running(ctx, prm, wn, N, (const double *)dev[0], nullptr, (const int32_t *)dev[1],
+                                              return entry(ctx, prm, wn, N, (const double *)dev[0], nullptr, (const int32_t *)dev[1],
                                                                               (const double *)dev[2], (const double *)dev[3], d);
                                           });
     // ragged windows share one knot stream: staged whole, as in cpi_preintegrate_batch_host
@@ -1752,9 +1796,21 @@ extern "C" int cpi_preintegrate_running_host(cpi_ctx *ctx, const cpi_params *prm
     cpi_outputs d;
     CPI_TRY(stage_windows(st, W, n_knots, knots, first, count, lin, q_k_lin, &in));
     CPI_TRY(st.mirror(rows, (size_t)W * (size_t)N, &d));
-    CPI_TRY(cpi_preintegrate_running(ctx, prm, W, N, in.knots, in.first, in.count, in.lin, in.qk, &d));
+    CPI_TRY(entry(ctx, prm, W, N, in.knots, in.first, in.count, in.lin, in.qk, &d));
     CPI_TRY(st.download(rows, d, (size_t)W * (size_t)N));
     return st.finish();
+}
+extern "C" int cpi_preintegrate_running_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                             const double *knots, const int64_t *first, const int32_t *count,
+                                             int64_t n_knots, const double *lin, const double *q_k_lin,
+                                             const cpi_outputs *rows) {
+    return running_host(ctx, "cpi_preintegrate_running_host", false, prm, W, N, knots, first, count, n_knots, lin, q_k_lin, rows);
+}
+extern "C" int cpi_running_stj_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                          const double *knots, const int64_t *first, const int32_t *count,
+                                          int64_t n_knots, const double *lin, const double *q_k_lin,
+                                          const cpi_outputs *rows) {
+    return running_host(ctx, "cpi_running_stj_batch_host", true, prm, W, N, knots, first, count, n_knots, lin, q_k_lin, rows);
 }
 
 // the staged-whole form of the two resume entries: the records go up and come down with the windows.  rows_per_window: 1
@@ -1834,7 +1890,7 @@ extern "C" int cpi_preintegrate_running_resume_host(cpi_ctx *ctx, const cpi_para
 // staging and never leave it (the covariance rows as P_sym: 960 B per row instead of 1 800): Q rows come down.  What the device form
 // cannot check is checked here, before anything is enqueued: qwin in range, and finite non-decreasing stamps (the bisection's
 // precondition) in every window that is queried.
-static int query_host(cpi_ctx *ctx, const char *who, bool with_cov, const cpi_params *prm, int64_t W, int32_t N,
+static int query_host(cpi_ctx *ctx, const char *who, int with, const cpi_params *prm, int64_t W, int32_t N,
                       const double *knots, const int64_t *first, const int32_t *count, int64_t n_knots,
                       const double *lin, const double *q_k_lin,
                       int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out) {
@@ -1842,8 +1898,9 @@ static int query_host(cpi_ctx *ctx, const char *who, bool with_cov, const cpi_pa
     if (!prm || !out) return refuse(ctx, who, "prm/out is NULL");
     const Request rq = request_of(out);
     bool done;
-    CPI_TRY(query_check_args(ctx, who, with_cov, prm, W, N, knots, lin, q_k_lin, Q, qwin, qtime, out, &done));
+    CPI_TRY(query_check_args(ctx, who, with, prm, W, N, knots, lin, q_k_lin, Q, qwin, qtime, out, &done));
     if (done) return CPI_OK;
+    const bool stj = prm->model == CPI_MODEL_V2 && rq.jac;   // (cpi_query_stj_batch_host only: all seven Jacobian rows are computed)
     if (!first) n_knots = W * (int64_t)(N + 1);
     if (n_knots <= 0) return refuse(ctx, who, "n_knots must be > 0");
     {
@@ -1876,14 +1933,15 @@ static int query_host(cpi_ctx *ctx, const char *who, bool with_cov, const cpi_pa
     double dummy;
     rmask.DT = rmask.alpha = rmask.beta = rmask.q = &dummy;   // mirror() allocates the fields that are set
     rmask.J_q = out->J_q; rmask.J_a = out->J_a; rmask.J_b = out->J_b; rmask.H_a = out->H_a; rmask.H_b = out->H_b;
+    if (stj) rmask.J_q = rmask.J_a = rmask.J_b = rmask.H_a = rmask.H_b = rmask.O_a = rmask.O_b = &dummy;
     if (rq.cov) rmask.P_sym = &dummy;
     CPI_TRY(stage_windows(st, W, n_knots, knots, first, count, lin, q_k_lin, &in));
     CPI_TRY(st.upload(qwin, (size_t)Q, &dqwin));
     CPI_TRY(st.upload(qtime, (size_t)Q, &dqtime));
     CPI_TRY(st.mirror(&rmask, (size_t)W * (size_t)N, &drows));
     CPI_TRY(st.mirror(out, (size_t)Q, &d));
-    if (N > 0) CPI_TRY(cpi_preintegrate_running(ctx, prm, W, N, in.knots, in.first, in.count, in.lin, in.qk, &drows));
-    CPI_TRY((with_cov ? cpi_query_cov_batch : cpi_query_batch)(ctx, prm, W, N, in.knots, in.first, in.count, in.lin, in.qk, &drows, Q, dqwin, dqtime, &d));
+    if (N > 0) CPI_TRY((stj ? cpi_running_stj_batch : cpi_preintegrate_running)(ctx, prm, W, N, in.knots, in.first, in.count, in.lin, in.qk, &drows));
+    CPI_TRY(((with & QUERY_STJ) ? cpi_query_stj_batch : (with & QUERY_COV) ? cpi_query_cov_batch : cpi_query_batch)(ctx, prm, W, N, in.knots, in.first, in.count, in.lin, in.qk, &drows, Q, dqwin, dqtime, &d));
     CPI_TRY(st.download(out, d, (size_t)Q));
     return st.finish();
 }
@@ -1891,13 +1949,19 @@ extern "C" int cpi_query_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t
                                     const double *knots, const int64_t *first, const int32_t *count, int64_t n_knots,
                                     const double *lin, const double *q_k_lin,
                                     int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out) {
-    return query_host(ctx, "cpi_query_batch_host", false, prm, W, N, knots, first, count, n_knots, lin, q_k_lin, Q, qwin, qtime, out);
+    return query_host(ctx, "cpi_query_batch_host", 0, prm, W, N, knots, first, count, n_knots, lin, q_k_lin, Q, qwin, qtime, out);
 }
 extern "C" int cpi_query_cov_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                                         const double *knots, const int64_t *first, const int32_t *count, int64_t n_knots,
                                         const double *lin, const double *q_k_lin,
                                         int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out) {
-    return query_host(ctx, "cpi_query_cov_batch_host", true, prm, W, N, knots, first, count, n_knots, lin, q_k_lin, Q, qwin, qtime, out);
+    return query_host(ctx, "cpi_query_cov_batch_host", QUERY_COV, prm, W, N, knots, first, count, n_knots, lin, q_k_lin, Q, qwin, qtime, out);
+}
+extern "C" int cpi_query_stj_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                        const double *knots, const int64_t *first, const int32_t *count, int64_t n_knots,
+                                        const double *lin, const double *q_k_lin,
+                                        int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out) {
+    return query_host(ctx, "cpi_query_stj_batch_host", QUERY_COV | QUERY_STJ, prm, W, N, knots, first, count, n_knots, lin, q_k_lin, Q, qwin, qtime, out);
 }
 
 // The offsets of a multi-run call as the _host entries can (and do) validate them before anything is enqueued: each array

@@ -1,6 +1,6 @@
 // cpi_args.hpp -- kernel argument blocks and the launcher interface between the translation units of libcpi_amd.so.
 //
-// The library is eight translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
+// The library is nine translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
 //   cpi_mean.hip    cpi_mean_kernel / cpi_mean_tiled_kernel / cpi_tile_*_kernel       (cpi_mean_kernels.hpp)
 //   cpi_running.hip cpi_mean_running_kernel / cpi_mean_stream_running_kernel: a row after every interval, from plain knots /
 //                   from windows cut out of IMU stream(s) in place         (cpi_running_kernels.hpp, cpi_running_body.inc)
@@ -11,6 +11,8 @@
 //                                                                                      (cpi_query_kernels.hpp)
 //   cpi_query_cov.hip  cpi_query_cov_kernel: the covariance at arbitrary times, one partial interval of the covariance recursion
 //                   from a running P / P_sym row                                       (cpi_query_cov_kernels.hpp)
+//   cpi_stj.hip     cpi_cov_running_stj_kernel / cpi_query_stj_kernel: model 2's bias Jacobians (the Discrete_J_b columns of cov_body)
+//                   after every interval and at arbitrary times                (cpi_cov_kernels.hpp, cpi_stj_kernels.hpp)
 //   cpi_factor.hip  evaluateError sweeps, square-root information, Hessian blocks, state prediction
 //                                                                                      (cpi_factor_kernels.hpp)
 //   cpi_abi.hip     the C-ABI of include/cpi_amd.h: argument checks, launch heuristics, device sets (RCCL), the
@@ -190,6 +192,10 @@ void cov_running_carry(int model, bool avg, const PreArgs &a, const CarryArgs &c
 void query(int model, bool jac, bool avg, const QueryArgs &a, hipStream_t st);
 // ---- cpi_query_cov.hip (cpi_query_cov_batch: a.out.P / P_sym from a.rows.q and a.rows.P or P_sym; q4 as PreArgs::q4)
 void query_cov(int model, bool avg, const QueryArgs &a, const double q4[4], hipStream_t st);
+// ---- cpi_stj.hip (model 2; cpi_running_stj_batch: cov_running + the rows of J_q ... O_b that a.out asks for;
+// cpi_query_stj_batch: a.out.J_q ... O_b from a.rows.q and all seven Jacobian fields of a.rows)
+void cov_running_stj(bool avg, const PreArgs &a, hipStream_t st);
+void query_stj(bool avg, const QueryArgs &a, hipStream_t st);
 // ---- cpi_factor.hip
 void factor(int model, bool whiten, int lpf, const FactorArgs &a, hipStream_t st);            // lpf 16 | 8 | 4
 void factor_packed(int model, int lpf, const FactorArgs &a, double *packed, hipStream_t st);  // lpf 2 | 3 | 4 | 6 | 8

@@ -33,8 +33,16 @@ namespace {
 // record.  The covariance block of carry_out is written after the last interval (the columns as row N - 1 has just read them
 // out), a window whose record does not fit gets NaN in EVERY row, and the tag / means of carry_out are left to
 // cpi_mean_running_carry_kernel (own_means = 0).
-template <int MODEL, bool AVG, bool CARRY, bool RUNNING = false>
+// RUNNING and STJ (cpi_cov_running_stj_kernel, cpi_running_stj_batch; model 2): the Jacobian read-out of the end (the nine
+// Discrete_J_b columns, lanes jj in [NPCOL, NCOL)) after EVERY interval too, into row w N + i of the fields of A.out that are set.
+// The stores go straight from the column registers, 24 bytes per lane and field: the three lanes of a block complete the 72 bytes
+// of a field's row within one instruction each, and a row of all seven fields is 504 bytes against the 1 800 of P that the other
+// lanes store at the same point.  Staging the rows in LDS for wider stores is not worth its price here for the reason measured
+// for P above: the kernel holds 2 wavefronts per SIMD with the LDS it has, and the staging area would have to come out of that.
+// Every other instantiation is compiled without the block (if constexpr) and is unchanged.
+template <int MODEL, bool AVG, bool CARRY, bool RUNNING = false, bool STJ = false>
 __device__ __forceinline__ void cov_body(const PreArgs &A, const CarryArgs &CA) {
+    static_assert(!STJ || (MODEL == 2 && RUNNING && !CARRY), "the running Jacobian read-out belongs to model 2 without carry records");
     typedef CovDims<MODEL> D;
     constexpr int GROUP = D::GROUP;   // lanes per window
     constexpr int G = 64 / GROUP;     // windows per wavefront
@@ -256,6 +264,27 @@ __device__ __forceinline__ void cov_body(const PreArgs &A, const CarryArgs &CA) 
                         for (int i = 0; i < 15; i++) if (i <= jj) p[i] = (CARRY && cbad) ? __builtin_nan("") : Ln.P0[i];
                     }
                 }
+                if constexpr (STJ) {
+                    // the read-out of Discrete_J_b below (CpiV2.h:450-458), of the state behind interval base + sl
+                    if (valid && jj >= D::NPCOL && jj < D::NCOL) {
+                        const int d = (jj - D::NPCOL) / 3, c = (jj - D::NPCOL) % 3;
+                        const long long o = r * 9 + c * 3;
+                        const V3 th = mk(Ln.P0[0], Ln.P0[1], Ln.P0[2]);
+                        const V3 vv = mk(Ln.P0[6], Ln.P0[7], Ln.P0[8]);
+                        const V3 pp = mk(Ln.P0[12], Ln.P0[13], Ln.P0[14]);
+                        if (d == 0) {
+                            if (A.out.J_q) stv3(A.out.J_q + o, -th);
+                            if (A.out.J_a) stv3(A.out.J_a + o, pp);
+                            if (A.out.J_b) stv3(A.out.J_b + o, vv);
+                        } else if (d == 1) {
+                            if (A.out.H_a) stv3(A.out.H_a + o, pp);
+                            if (A.out.H_b) stv3(A.out.H_b + o, vv);
+                        } else {
+                            if (A.out.O_a) stv3(A.out.O_a + o, pp);
+                            if (A.out.O_b) stv3(A.out.O_b + o, vv);
+                        }
+                    }
+                }
             }
         }
         wave_lds_fence();
@@ -355,7 +384,13 @@ __global__ __launch_bounds__(64, CPI_COV_WPS) void cpi_cov_running_carry_kernel(
     cov_body<MODEL, AVG, true, true>(A, C);
 }
 
-#ifndef CPI_COV_TEMPLATES_ONLY   // (cpi_running_resume.hip takes the templates above only)
+// cpi_running_stj_batch: cpi_cov_running_kernel<2> with the Jacobian read-out after every interval as well (cpi_stj.hip)
+template <bool AVG>
+__global__ __launch_bounds__(64, CPI_COV_WPS) void cpi_cov_running_stj_kernel(PreArgs A) {
+    cov_body<2, AVG, false, true, true>(A, CarryArgs());
+}
+
+#ifndef CPI_COV_TEMPLATES_ONLY   // (cpi_running_resume.hip and cpi_stj.hip take the templates above only)
 // ============================================================================================
 // Forster / GTSAM discrete-preintegration comparator kernel (fsd:: in cpi_math.hpp)
 // ============================================================================================

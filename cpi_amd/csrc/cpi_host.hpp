@@ -437,43 +437,11 @@ public:
     // feed_IMU places between intervals that do not chain -- repeats the previous one).  Models 1 and 2; the bias Jacobians
     // are filled for model 1 only.  The windows stay added and their own result members are not touched: flush() still
     // computes them.
-    std::vector<std::vector<CpiResult>> running(const Context &ctx) const {
-        std::vector<std::vector<CpiResult>> res(win_.size());
-        if (win_.empty()) return res;
-        const int64_t W = (int64_t)win_.size();
-        std::vector<double> knots, lin, qk;
-        std::vector<int64_t> first;
-        std::vector<int32_t> count;
-        const int32_t N = ragged(knots, first, count, lin, qk);
-        if (N == 0) return res;
-        cpi_params p = win_[0]->params();
-        const bool jac = p.model == CPI_MODEL_V1;
-        const size_t M = (size_t)W * (size_t)N;
-        std::vector<double> DT(M), al(M * 3), be(M * 3), q(M * 4), Jq(jac ? M * 9 : 0), Ja(jac ? M * 9 : 0), Jb(jac ? M * 9 : 0),
-            Ha(jac ? M * 9 : 0), Hb(jac ? M * 9 : 0), P(M * 225);
-        cpi_outputs o{};
-        o.DT = DT.data(); o.alpha = al.data(); o.beta = be.data(); o.q = q.data(); o.P = P.data();
-        if (jac) { o.J_q = Jq.data(); o.J_a = Ja.data(); o.J_b = Jb.data(); o.H_a = Ha.data(); o.H_b = Hb.data(); }
-        ctx.check(cpi_preintegrate_running_host(ctx.get(), &p, W, N, knots.data(), first.data(), count.data(),
-                                                (int64_t)(knots.size() / 7), lin.data(), qk.data(), &o));
-        for (int64_t w = 0; w < W; w++) {
-            res[w].resize(count[w]);
-            for (int32_t i = 0; i < count[w]; i++) {
-                const size_t r = (size_t)w * N + i;
-                CpiResult &x = res[w][i];
-                x.DT = DT[r];
-                for (int k = 0; k < 3; k++) { x.alpha_tau[k] = al[r * 3 + k]; x.beta_tau[k] = be[r * 3 + k]; }
-                for (int k = 0; k < 4; k++) x.q_k2tau[k] = q[r * 4 + k];
-                if (jac)
-                    for (int k = 0; k < 9; k++) {
-                        x.J_q[k] = Jq[r * 9 + k]; x.J_a[k] = Ja[r * 9 + k]; x.J_b[k] = Jb[r * 9 + k];
-                        x.H_a[k] = Ha[r * 9 + k]; x.H_b[k] = Hb[r * 9 + k];
-                    }
-                for (int k = 0; k < 225; k++) x.P_meas[k] = P[r * 225 + k];
-            }
-        }
-        return res;
-    }
+    std::vector<std::vector<CpiResult>> running(const Context &ctx) const { return running_impl(ctx, false); }
+    // running() with model 2's bias Jacobians (cpi_running_stj_batch_host): J_q ... O_b are filled for model 2 as well (all
+    // seven, read out of the state transition columns after every interval; the windows' params must have
+    // state_transition_jacobians set).  Model 1: running().
+    std::vector<std::vector<CpiResult>> running_stj(const Context &ctx) const { return running_impl(ctx, true); }
     // The members of every added window at ARBITRARY times (cpi_query_batch_host): result[w][k] = window w at times[w][k] -- on a
     // knot stamp what running() holds after that knot's interval, inside an interval that state advanced over the partial
     // interval with the reading held (the reference's tail, GraphSolver_IMU.cpp:64-69), before the window's first stamp the zero
@@ -487,6 +455,11 @@ public:
     // query time.
     std::vector<std::vector<CpiResult>> at_cov(const Context &ctx, const std::vector<std::vector<double>> &times) const {
         return at_impl(ctx, times, true);
+    }
+    // at_cov() with model 2's bias Jacobians (cpi_query_stj_batch_host): J_q ... O_b are filled for model 2 as well, all seven -- what
+    // a model-2 factor at a query time needs (the windows' params must have state_transition_jacobians set).  Model 1: at_cov().
+    std::vector<std::vector<CpiResult>> at_stj(const Context &ctx, const std::vector<std::vector<double>> &times) const {
+        return at_impl(ctx, times, true, true);
     }
     // Mean outputs only (DT, alpha_tau, beta_tau, q_k2tau): the HBM-bound request.  The recorded windows are written
     // straight into the TILED layout (include/cpi_amd.h: tiles[ceil(W/64)][N+1][7][64], knot s of window w at
@@ -523,8 +496,50 @@ public:
         win_.clear();
     }
 private:
-    // at / at_cov: the queries of all windows in one call; cov: P_meas as well
-    std::vector<std::vector<CpiResult>> at_impl(const Context &ctx, const std::vector<std::vector<double>> &times, bool cov) const {
+    // running / running_stj: the rows of all windows in one call; stj: model 2's seven Jacobians as well
+    std::vector<std::vector<CpiResult>> running_impl(const Context &ctx, bool stj) const {
+        std::vector<std::vector<CpiResult>> res(win_.size());
+        if (win_.empty()) return res;
+        const int64_t W = (int64_t)win_.size();
+        std::vector<double> knots, lin, qk;
+        std::vector<int64_t> first;
+        std::vector<int32_t> count;
+        const int32_t N = ragged(knots, first, count, lin, qk);
+        if (N == 0) return res;
+        cpi_params p = win_[0]->params();
+        const bool v2 = stj && p.model == CPI_MODEL_V2;    // all seven matrices from the transition columns
+        const bool jac = p.model == CPI_MODEL_V1 || v2;
+        const size_t M = (size_t)W * (size_t)N;
+        std::vector<double> DT(M), al(M * 3), be(M * 3), q(M * 4), Jq(jac ? M * 9 : 0), Ja(jac ? M * 9 : 0), Jb(jac ? M * 9 : 0),
+            Ha(jac ? M * 9 : 0), Hb(jac ? M * 9 : 0), Oa(v2 ? M * 9 : 0), Ob(v2 ? M * 9 : 0), P(M * 225);
+        cpi_outputs o{};
+        o.DT = DT.data(); o.alpha = al.data(); o.beta = be.data(); o.q = q.data(); o.P = P.data();
+        if (jac) { o.J_q = Jq.data(); o.J_a = Ja.data(); o.J_b = Jb.data(); o.H_a = Ha.data(); o.H_b = Hb.data(); }
+        if (v2) { o.O_a = Oa.data(); o.O_b = Ob.data(); }
+        const int64_t K = (int64_t)(knots.size() / 7);
+        ctx.check(stj ? cpi_running_stj_batch_host(ctx.get(), &p, W, N, knots.data(), first.data(), count.data(), K, lin.data(), qk.data(), &o)
+                      : cpi_preintegrate_running_host(ctx.get(), &p, W, N, knots.data(), first.data(), count.data(), K, lin.data(), qk.data(), &o));
+        for (int64_t w = 0; w < W; w++) {
+            res[w].resize(count[w]);
+            for (int32_t i = 0; i < count[w]; i++) {
+                const size_t r = (size_t)w * N + i;
+                CpiResult &x = res[w][i];
+                x.DT = DT[r];
+                for (int k = 0; k < 3; k++) { x.alpha_tau[k] = al[r * 3 + k]; x.beta_tau[k] = be[r * 3 + k]; }
+                for (int k = 0; k < 4; k++) x.q_k2tau[k] = q[r * 4 + k];
+                if (jac)
+                    for (int k = 0; k < 9; k++) {
+                        x.J_q[k] = Jq[r * 9 + k]; x.J_a[k] = Ja[r * 9 + k]; x.J_b[k] = Jb[r * 9 + k];
+                        x.H_a[k] = Ha[r * 9 + k]; x.H_b[k] = Hb[r * 9 + k];
+                        if (v2) { x.O_a[k] = Oa[r * 9 + k]; x.O_b[k] = Ob[r * 9 + k]; }
+                    }
+                for (int k = 0; k < 225; k++) x.P_meas[k] = P[r * 225 + k];
+            }
+        }
+        return res;
+    }
+    // at / at_cov / at_stj: the queries of all windows in one call; cov: P_meas as well; stj: model 2's seven Jacobians as well
+    std::vector<std::vector<CpiResult>> at_impl(const Context &ctx, const std::vector<std::vector<double>> &times, bool cov, bool stj = false) const {
         if (times.size() != win_.size()) throw std::logic_error("CpiBatch::at: one vector of times per added window");
         std::vector<std::vector<CpiResult>> res(win_.size());
         std::vector<int32_t> qwin;
@@ -545,15 +560,19 @@ private:
         std::vector<int32_t> count;
         const int32_t N = ragged(knots, first, count, lin, qk);
         cpi_params p = win_[0]->params();
-        const bool jac = p.model == CPI_MODEL_V1;
+        const bool v2 = stj && p.model == CPI_MODEL_V2;
+        const bool jac = p.model == CPI_MODEL_V1 || v2;
         std::vector<double> DT(Q), al(Q * 3), be(Q * 3), q(Q * 4), Jq(jac ? Q * 9 : 0), Ja(jac ? Q * 9 : 0), Jb(jac ? Q * 9 : 0),
-            Ha(jac ? Q * 9 : 0), Hb(jac ? Q * 9 : 0), P(cov ? Q * 225 : 0);
+            Ha(jac ? Q * 9 : 0), Hb(jac ? Q * 9 : 0), Oa(v2 ? Q * 9 : 0), Ob(v2 ? Q * 9 : 0), P(cov ? Q * 225 : 0);
         cpi_outputs o{};
         o.DT = DT.data(); o.alpha = al.data(); o.beta = be.data(); o.q = q.data();
         if (jac) { o.J_q = Jq.data(); o.J_a = Ja.data(); o.J_b = Jb.data(); o.H_a = Ha.data(); o.H_b = Hb.data(); }
+        if (v2) { o.O_a = Oa.data(); o.O_b = Ob.data(); }
         if (cov) o.P = P.data();
         const int64_t K = (int64_t)(knots.size() / 7);
-        ctx.check(cov ? cpi_query_cov_batch_host(ctx.get(), &p, W, N, knots.data(), first.data(), count.data(), K, lin.data(), qk.data(), Q,
+        ctx.check(stj ? cpi_query_stj_batch_host(ctx.get(), &p, W, N, knots.data(), first.data(), count.data(), K, lin.data(), qk.data(), Q,
+                                                 qwin.data(), qtime.data(), &o)
+                  : cov ? cpi_query_cov_batch_host(ctx.get(), &p, W, N, knots.data(), first.data(), count.data(), K, lin.data(), qk.data(), Q,
                                                  qwin.data(), qtime.data(), &o)
                       : cpi_query_batch_host(ctx.get(), &p, W, N, knots.data(), first.data(), count.data(), K, lin.data(), qk.data(), Q,
                                              qwin.data(), qtime.data(), &o));
@@ -567,6 +586,7 @@ private:
                     for (int k = 0; k < 9; k++) {
                         x.J_q[k] = Jq[r * 9 + k]; x.J_a[k] = Ja[r * 9 + k]; x.J_b[k] = Jb[r * 9 + k];
                         x.H_a[k] = Ha[r * 9 + k]; x.H_b[k] = Hb[r * 9 + k];
+                        if (v2) { x.O_a[k] = Oa[r * 9 + k]; x.O_b[k] = Ob[r * 9 + k]; }
                     }
                 if (cov)
                     for (int k = 0; k < 225; k++) x.P_meas[k] = P[r * 225 + k];

@@ -277,6 +277,37 @@ class Engine:
                                                            _ptr(lin), _ptr(q_k_lin), C.byref(o)))
         return out
 
+    def preintegrate_running_stj(self, knots, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), first=None,
+                                 count=None, N=None, packed=False, out=None):
+        """cpi_running_stj_batch: preintegrate_running with model 2's Jacobian rows.  Arguments and result as
+        preintegrate_running; for model 2 (state_transition_jacobians set) "jac" means all seven matrices J_q J_a J_b H_a H_b
+        O_a O_b after every interval, read out of the state transition columns of the covariance recursion.  The mean and P /
+        P_sym rows are bit for bit those of preintegrate_running; without "jac", or for model 1, the call is
+        preintegrate_running.  Asynchronous."""
+        params = params or self.make_params()
+        W, N = self._window_shape(knots, lin, first, count, N, (q_k_lin,))
+        if out is None:
+            out = self._running_views(self.alloc_outputs(W * N, tuple(want), params.model, packed), W, N)
+        o = self._outputs_struct({k: v for k, v in out.items() if not k.startswith("_")})
+        self._sync_stream()
+        self._check(self.lib.cpi_running_stj_batch(self.ctx, C.byref(params), W, N, _ptr(knots), _ptr(first), _ptr(count),
+                                                          _ptr(lin), _ptr(q_k_lin), C.byref(o)))
+        return out
+
+    def preintegrate_running_stj_host(self, knots, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), count=None,
+                                      pinned=True, out=None):
+        """preintegrate_running_stj for a dense batch held in HOST memory (CPU float64 tensors):
+        cpi_running_stj_batch_host.  Returns a dict of CPU tensors with leading shape [W, N]; synchronous."""
+        params = params or self.make_params()
+        W, N = self._window_shape(knots, lin, count=count, others=(q_k_lin,), cuda=False)
+        if out is None:
+            out = self._host_outputs((W, N), tuple(want), params.model, pinned)
+        o = self._outputs_struct(out)
+        self._sync_stream()
+        self._check(self.lib.cpi_running_stj_batch_host(self.ctx, C.byref(params), W, N, _ptr(knots), None, _ptr(count), 0,
+                                                               _ptr(lin), _ptr(q_k_lin), C.byref(o)))
+        return out
+
     def preintegrate_running_resume(self, knots, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), first=None,
                                     count=None, N=None, carry_in=None, carry_out=None, packed=False, out=None):
         """cpi_preintegrate_running_resume: the rows of preintegrate_running for windows that continue from carry_in
@@ -361,6 +392,45 @@ class Engine:
         entry = self.lib.cpi_query_cov_batch_host if self._wants_cov(want) else self.lib.cpi_query_batch_host
         self._check(entry(self.ctx, C.byref(params), W, N, _ptr(knots), None, _ptr(count), 0, _ptr(lin),
                           _ptr(q_k_lin), Q, _ptr(qwin), _ptr(qtime), C.byref(o)))
+        return out
+
+    def query_stj(self, knots, lin, rows, qwin, qtime, q_k_lin=None, params=None, want=("mean",), first=None, count=None, N=None,
+                  out=None):
+        """cpi_query_stj_batch: query with model 2's Jacobians.  Arguments and result as query; for model 2
+        (state_transition_jacobians set) "jac" in want means all seven matrices J_q J_a J_b H_a H_b O_a O_b at the query times,
+        and rows -- the dict of preintegrate_running_stj on the same arguments -- must then hold q and all seven.  The mean
+        fields and P / P_sym are bit for bit those of query; the result feeds sqrt_information / factor_eval for model 2 with
+        idx_i = qwin.  Asynchronous."""
+        params = params or self.make_params()
+        W, N = self._window_shape(knots, lin, first, count, N, (q_k_lin, qwin, qtime))
+        Q = qtime.shape[0]
+        assert qwin.dtype == torch.int32 and qtime.dtype == torch.float64 and qwin.shape == (Q,), "qwin [Q] int32, qtime [Q] float64"
+        r = {k: v for k, v in rows.items() if not k.startswith("_")}
+        for k, v in r.items():
+            assert v.is_cuda and v.is_contiguous() and v.shape[:2] == (W, N), "rows: the [W, N, ...] dict of preintegrate_running_stj"
+        if out is None:
+            out = self.alloc_outputs(Q, tuple(want), params.model)
+        o = self._outputs_struct(out)
+        ro = self._outputs_struct(r)
+        self._sync_stream()
+        self._check(self.lib.cpi_query_stj_batch(self.ctx, C.byref(params), W, N, _ptr(knots), _ptr(first), _ptr(count), _ptr(lin),
+                                                 _ptr(q_k_lin), C.byref(ro), Q, _ptr(qwin), _ptr(qtime), C.byref(o)))
+        return out
+
+    def query_stj_host(self, knots, lin, qwin, qtime, q_k_lin=None, params=None, want=("mean",), count=None, pinned=True, out=None):
+        """query_stj for a dense batch held in HOST memory (CPU tensors): cpi_query_stj_batch_host.  No rows argument: the running
+        rows (for a model-2 Jacobian request all seven Jacobian fields) are computed on the device and stay there.  Returns a
+        dict of CPU tensors [Q, ...]; synchronous."""
+        params = params or self.make_params()
+        W, N = self._window_shape(knots, lin, count=count, others=(q_k_lin, qwin, qtime), cuda=False)
+        Q = qtime.shape[0]
+        assert qwin.dtype == torch.int32 and qtime.dtype == torch.float64 and qwin.shape == (Q,), "qwin [Q] int32, qtime [Q] float64"
+        if out is None:
+            out = self._host_outputs((Q,), tuple(want), params.model, pinned)
+        o = self._outputs_struct(out)
+        self._sync_stream()
+        self._check(self.lib.cpi_query_stj_batch_host(self.ctx, C.byref(params), W, N, _ptr(knots), None, _ptr(count), 0, _ptr(lin),
+                                                      _ptr(q_k_lin), Q, _ptr(qwin), _ptr(qtime), C.byref(o)))
         return out
 
     def preintegrate_host(self, knots, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), count=None, pinned=True, out=None):

@@ -57,7 +57,9 @@ extern "C" {
                                cpi_preintegrate_running_resume_host (the running rows of a window that continues from a
                                carry record); cpi_query_batch, cpi_query_batch_host (the measurement at arbitrary times inside
                                a window); cpi_query_cov_batch, cpi_query_cov_batch_host (the same with the covariance P / P_sym
-                               at the query times) */
+                               at the query times); cpi_running_stj_batch, cpi_running_stj_batch_host,
+                               cpi_query_stj_batch, cpi_query_stj_batch_host (model 2's seven bias Jacobians after every
+                               interval and at the query times) */
 
 enum { CPI_OK = 0, CPI_ERR_INVALID = 1, CPI_ERR_HIP = 2, CPI_ERR_NO_DEVICE = 3, CPI_ERR_RCCL = 4 };
 enum {
@@ -213,7 +215,8 @@ int cpi_preintegrate_resume(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int3
  * cpi_preintegrate_batch.  No host synchronisation and a single stream: the call can be captured into a graph.
  * Composition: with F = W * N and idx_i[row] = row / N, cpi_predict_batch turns the rows into IMU-rate predicted states.
  * Running rows from IMU stream(s), windows cut in place: cpi_preintegrate_stream_running / cpi_preintegrate_streams_running below.
- * Running rows of a window that is still open (from and to a carry record): cpi_preintegrate_running_resume below. */
+ * Running rows of a window that is still open (from and to a carry record): cpi_preintegrate_running_resume below.
+ * Running Jacobian rows for model 2 (state_transition_jacobians): cpi_running_stj_batch below. */
 int cpi_preintegrate_running(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                              const double *knots, const int64_t *first, const int32_t *count,
                              const double *lin, const double *q_k_lin, const cpi_outputs *rows);
@@ -255,7 +258,8 @@ int cpi_preintegrate_running(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int
  *   - with carry_in == NULL the rows are bit for bit those of cpi_preintegrate_running on the same arguments, for every model,
  *     request and lanes_per_window.
  * Not provided: running Jacobian rows for model 2; running rows from a carry record for the STREAM entries
- * (cpi_preintegrate_stream[s]_running); the Forster comparator. */
+ * (cpi_preintegrate_stream[s]_running); the Forster comparator.  (Model 2's running Jacobian rows without a carry record:
+ * cpi_running_stj_batch below.) */
 int cpi_preintegrate_running_resume(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                                     const double *knots, const int64_t *first, const int32_t *count,
                                     const double *lin, const double *q_k_lin,
@@ -297,7 +301,7 @@ int cpi_preintegrate_running_resume(cpi_ctx *ctx, const cpi_params *prm, int64_t
  * Not provided: P / P_sym at query times (they need the covariance kernel's lane-spread RK4 step); Jacobians for model 2; windows
  * cut from IMU streams in place (cpi_preintegrate_stream[s]_running: assemble the windows, or query per update time); rows that
  * continue from a carry record (cpi_preintegrate_running_resume); extrapolation past t_n.  (The covariance at query times is a
- * call of its own: cpi_query_cov_batch below.) */
+ * call of its own: cpi_query_cov_batch below; the Jacobians of model 2 at query times: cpi_query_stj_batch below.) */
 int cpi_query_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                     const double *knots, const int64_t *first, const int32_t *count,
                     const double *lin, const double *q_k_lin, const cpi_outputs *rows,
@@ -332,8 +336,58 @@ int cpi_query_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
  * Composition: out->P_sym -> cpi_sqrt_information_packed_batch -> cpi_factor_eval_whitened_tri_batch / cpi_factor_hessian_tri_batch
  * with idx_i = qwin: the whitened keyframe factor AT the query time.
  * Still not provided: model-2 Jacobians at query times; windows cut from IMU streams in place; rows from a carry record;
- * extrapolation past t_n. */
+ * extrapolation past t_n.  (The model-2 Jacobians at query times are a call of their own: cpi_query_stj_batch below.) */
 int cpi_query_cov_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                        const double *knots, const int64_t *first, const int32_t *count,
+                        const double *lin, const double *q_k_lin, const cpi_outputs *rows,
+                        int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out);
+
+/* cpi_preintegrate_running WITH MODEL 2's JACOBIAN ROWS: J_q J_a J_b H_a H_b O_a O_b after every interval, so that a model-2 factor
+ * can be closed at any IMU reading (evaluateError of model 2 needs all seven).  A superset of cpi_preintegrate_running: the
+ * arguments and every rule of its contract are the same.  Without a Jacobian field in rows, or with model 1, the call IS
+ * cpi_preintegrate_running (the same kernels, bit for bit the same rows).
+ * With model 2, state_transition_jacobians != 0 and any of J_q ... O_b in rows: row w * N + i of each requested field is what
+ * cpi_preintegrate_batch (state_transition_jacobians = 1) returns for window w cut after interval i -- the read-out of the nine
+ * transition columns of Discrete_J_b (b_w, b_a, theta_klin) that the covariance kernel does at the end of a window, done after
+ * every interval, with its signs and blocks (J_q = -theta rows of the b_w columns, ...).  The running contract holds for these rows
+ * as it stands: a skipped interval repeats the previous row bit for bit, rows i >= count[w] repeat the final state, row 0 of a window
+ * that has integrated nothing is all zeros, count is clamped into [0, N], dense and ragged layouts, imu_avg 0 / 1, 64-bit row
+ * offsets.  The transition columns ride on the covariance recursion, so the covariance kernel runs whether or not P / P_sym are
+ * asked for; the mean rows and the P / P_sym rows of the call are bit for bit those of cpi_preintegrate_running on the same
+ * arguments.
+ * CPI_ERR_INVALID beyond cpi_preintegrate_running's: model 2 with state_transition_jacobians == 0 and a Jacobian field (the analytic
+ * O_a / O_b recursion has no running form).  CPI_MODEL_FORSTER is refused as there.
+ * No host synchronisation and a single stream: a capture of the call is a chain without parallel branches.
+ * Still not provided: these rows for the stream entries (cpi_preintegrate_stream[s]_running); for the carry-record entries
+ * (cpi_preintegrate_running_resume); model 2's analytic Jacobians (state_transition_jacobians == 0); extrapolation past t_n. */
+int cpi_running_stj_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                          const double *knots, const int64_t *first, const int32_t *count,
+                          const double *lin, const double *q_k_lin, const cpi_outputs *rows);
+
+/* cpi_query_cov_batch WITH MODEL 2's JACOBIANS: everything a model-2 keyframe factor at a query time needs, in one call.  A
+ * superset of cpi_query_cov_batch: the arguments, the choice of i, the precondition on the stamps, the clamping of qwin on the device,
+ * "no read leaves the window's knots or rows", Q == 0, N == 0, a NaN t_q are the same; the mean fields and P / P_sym are written by
+ * the kernels of cpi_query_batch / cpi_query_cov_batch and are bit for bit what those entries write; model-1 Jacobians are handled as
+ * there; with no model-2 Jacobian field in out the call IS cpi_query_cov_batch.
+ * With model 2, state_transition_jacobians != 0 and any of J_q ... O_b in out: rows -- written by cpi_running_stj_batch on the
+ * same arguments -- must hold (N > 0) q and ALL SEVEN Jacobian fields, whatever subset out asks for (CPI_ERR_INVALID names what is
+ * missing).  Query k, with i as in cpi_query_batch:
+ *   - no step (t_q on a stamp, before t_0, at or past t_n): the Jacobians of row w N + i - 1 copied BIT FOR BIT; zeros when i == 0;
+ *   - step (i < n and t_q > t_i): the nine transition columns are rebuilt from row w N + i - 1 -- at a row boundary they are
+ *     determined by the seven matrices: b_w column c = [-J_q[:,c] | e_c | J_b[:,c] | 0 | J_a[:,c] | -J_q[:,c]], b_a column c =
+ *     [0 | 0 | H_b[:,c] | e_c | H_a[:,c] | 0], theta_klin column c = [0 | 0 | O_b[:,c] | 0 | O_a[:,c] | 0] over the rows [theta | b_w |
+ *     v | b_a | p | theta clone]; i == 0: the initial state -- and advanced by the reference's RK4 step over feed_IMU(t_i, t_q, w_i,
+ *     a_i, w_i, a_i) with the start rotation quat_2_Rot of the row's q, then read out as at the end of a window.  The result equals
+ *     cpi_preintegrate_batch (state_transition_jacobians = 1) on [knot 0 .. knot i, {t_q, w_i, a_i}] up to rounding;
+ *   - t_q NaN: NaN in every requested field.
+ * CPI_ERR_INVALID beyond cpi_query_cov_batch's: model 2 with state_transition_jacobians == 0 and a Jacobian field in out.
+ * The kernels run one after the other on the context's stream: no side stream, no host synchronisation; a capture of
+ * cpi_running_stj_batch followed by this call is a chain without parallel branches.
+ * Composition: out (means, seven Jacobians, P_sym) -> cpi_sqrt_information_packed_batch -> cpi_factor_eval_whitened_tri_batch /
+ * cpi_factor_hessian_tri_batch with model 2 and idx_i = qwin.
+ * Still not provided: windows cut from IMU streams in place (the stream entries); rows that continue from a carry record
+ * (cpi_preintegrate_running_resume); model 2's analytic Jacobians (state_transition_jacobians == 0); extrapolation past t_n. */
+int cpi_query_stj_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                         const double *knots, const int64_t *first, const int32_t *count,
                         const double *lin, const double *q_k_lin, const cpi_outputs *rows,
                         int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out);
@@ -650,6 +704,19 @@ int cpi_query_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t
  * per row instead of 1 800): the staging need is W * N rows of 88 B (means) + 72 B per requested Jacobian field + 960 B when out
  * asks for P or P_sym, next to the windows and the Q output rows.  Bit for bit the device form on rows that hold P_sym. */
 int cpi_query_cov_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                             const double *knots, const int64_t *first, const int32_t *count, int64_t n_knots,
+                             const double *lin, const double *q_k_lin,
+                             int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out);
+/* cpi_running_stj_batch from host memory: the arguments and the pipeline of cpi_preintegrate_running_host (its messages carry
+ * this entry's name).  Bit for bit the device form on the same arguments and lanes_per_window. */
+int cpi_running_stj_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                               const double *knots, const int64_t *first, const int32_t *count,
+                               int64_t n_knots, const double *lin, const double *q_k_lin,
+                               const cpi_outputs *rows);
+/* cpi_query_stj_batch from host memory: the arguments, the staging and the validation of cpi_query_cov_batch_host (its messages carry
+ * this entry's name).  For a model-2 Jacobian request the W * N rows of all seven Jacobian fields (504 B per row) are computed by
+ * cpi_running_stj_batch into device staging and stay there.  Bit for bit the device form on rows that hold P_sym. */
+int cpi_query_stj_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                              const double *knots, const int64_t *first, const int32_t *count, int64_t n_knots,
                              const double *lin, const double *q_k_lin,
                              int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out);
