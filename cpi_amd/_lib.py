@@ -181,6 +181,15 @@ def load():
     for f in (lib.cpi_preintegrate_stream_running, lib.cpi_preintegrate_stream_running_host, lib.cpi_preintegrate_streams_running,
               lib.cpi_preintegrate_streams_running_host):
         f.restype = C.c_int
+    lib.cpi_stream_running_stj_batch.argtypes = lib.cpi_preintegrate_streams.argtypes
+    lib.cpi_stream_running_stj_batch_host.argtypes = lib.cpi_preintegrate_streams_host.argtypes
+    lib.cpi_query_stream_batch.argtypes = [vp, C.POINTER(CpiParams), i64, i64, dp, vp, i64, dp, vp, i32, dp, dp, vp, C.POINTER(CpiOutputs),
+                                           i64, vp, dp, vp, C.POINTER(CpiOutputs)]
+    lib.cpi_query_stream_batch_host.argtypes = [vp, C.POINTER(CpiParams), i64, i64, dp, vp, i64, dp, vp, i32, dp, dp,
+                                                i64, vp, dp, vp, C.POINTER(CpiOutputs)]
+    for f in (lib.cpi_stream_running_stj_batch, lib.cpi_stream_running_stj_batch_host, lib.cpi_query_stream_batch,
+              lib.cpi_query_stream_batch_host):
+        f.restype = C.c_int
     lib.cpi_host_alloc.argtypes = [C.c_size_t]
     lib.cpi_host_alloc.restype = C.c_void_p
     lib.cpi_host_free.argtypes = [vp]

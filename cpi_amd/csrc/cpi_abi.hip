@@ -637,6 +637,29 @@ static int query_check_args(cpi_ctx *ctx, const char *who, int with, const cpi_p
     *done = false;
     return CPI_OK;
 }
+// what rows must hold (N > 0) for the request of out: shared by the query entries
+static int query_rows_check(cpi_ctx *ctx, const char *who, const cpi_params *prm, const cpi_outputs *rows, const cpi_outputs *out) {
+    const Request rq = request_of(out);
+    const bool stj = prm->model == CPI_MODEL_V2 && rq.jac;
+    const bool means = rq.mean || (rq.jac && !stj);
+    if (stj) {   // the transition columns are rebuilt from ALL seven fields of a row, whatever subset out asks for
+        std::string lacks;
+        const struct { const char *name; const double *p; } need[] = { {"q", rows->q}, {"J_q", rows->J_q}, {"J_a", rows->J_a}, {"J_b", rows->J_b},
+                                                                       {"H_a", rows->H_a}, {"H_b", rows->H_b}, {"O_a", rows->O_a}, {"O_b", rows->O_b} };
+        for (const auto &f : need) if (!f.p) lacks += std::string(lacks.empty() ? "" : ", ") + f.name;
+        if (!lacks.empty()) return refuse(ctx, who, "rows needs q and all seven Jacobian fields for the model-2 Jacobians; missing: ", lacks.c_str());
+    }
+    if (means || !(rq.cov || stj)) {
+        if (!rows->DT || !rows->alpha || !rows->beta || !rows->q) return refuse(ctx, who, "rows needs DT, alpha, beta and q");
+        if (!stj && ((out->J_q && !rows->J_q) || (out->J_a && !rows->J_a) || (out->J_b && !rows->J_b) || (out->H_a && !rows->H_a) || (out->H_b && !rows->H_b)))
+            return refuse(ctx, who, "a Jacobian field of out needs the same field of rows");
+    }
+    if (rq.cov) {
+        if (!rows->q) return refuse(ctx, who, "rows needs q (the rotation at the start of the partial interval)");
+        if (!rows->P && !rows->P_sym) return refuse(ctx, who, "rows needs P or P_sym when out asks for P / P_sym");
+    }
+    return CPI_OK;
+}
 static int query_device(cpi_ctx *ctx, const char *who, int with, const cpi_params *prm, int64_t W, int32_t N,
                         const double *knots, const int64_t *first, const int32_t *count,
                         const double *lin, const double *q_k_lin, const cpi_outputs *rows,
@@ -650,24 +673,7 @@ static int query_device(cpi_ctx *ctx, const char *who, int with, const cpi_param
     const bool stj = prm->model == CPI_MODEL_V2 && rq.jac;   // (cpi_query_stj_batch: query_check has refused it for the others)
     const bool mean_jac = rq.jac && !stj;
     const bool means = rq.mean || mean_jac;
-    if (N > 0 && stj) {   // the transition columns are rebuilt from ALL seven fields of a row, whatever subset out asks for
-        std::string lacks;
-        const struct { const char *name; const double *p; } need[] = { {"q", rows->q}, {"J_q", rows->J_q}, {"J_a", rows->J_a}, {"J_b", rows->J_b},
-                                                                       {"H_a", rows->H_a}, {"H_b", rows->H_b}, {"O_a", rows->O_a}, {"O_b", rows->O_b} };
-        for (const auto &f : need) if (!f.p) lacks += std::string(lacks.empty() ? "" : ", ") + f.name;
-        if (!lacks.empty()) return refuse(ctx, who, "rows needs q and all seven Jacobian fields for the model-2 Jacobians; missing: ", lacks.c_str());
-    }
-    if (N > 0) {   // N == 0: every query is the zero state and rows is not read
-        if (means || !(rq.cov || stj)) {
-            if (!rows->DT || !rows->alpha || !rows->beta || !rows->q) return refuse(ctx, who, "rows needs DT, alpha, beta and q");
-            if (!stj && ((out->J_q && !rows->J_q) || (out->J_a && !rows->J_a) || (out->J_b && !rows->J_b) || (out->H_a && !rows->H_a) || (out->H_b && !rows->H_b)))
-                return refuse(ctx, who, "a Jacobian field of out needs the same field of rows");
-        }
-        if (rq.cov) {
-            if (!rows->q) return refuse(ctx, who, "rows needs q (the rotation at the start of the partial interval)");
-            if (!rows->P && !rows->P_sym) return refuse(ctx, who, "rows needs P or P_sym when out asks for P / P_sym");
-        }
-    }
+    if (N > 0) CPI_TRY(query_rows_check(ctx, who, prm, rows, out));   // N == 0: every query is the zero state and rows is not read
     if (!rq.any()) return CPI_OK;
 
     DeviceGuard guard_;
@@ -792,7 +798,9 @@ extern "C" int cpi_preintegrate_streams(cpi_ctx *ctx, const cpi_params *prm, int
 // cpi_cov_running_kernel (whose phase A reads cut windows when PreArgs::tstart is set) read the stream in place -- one after the
 // other on the context's stream, as in cpi_preintegrate_running.  The lane choice is pick_lanes(U, N, request), the function
 // cpi_preintegrate_running uses: the rows are bit for bit those of that entry on the host-assembled windows.
-static int stream_running_check(cpi_ctx *ctx, const char *who, const cpi_params *prm, bool many, int64_t R, int64_t K, int64_t U,
+// with_stj: cpi_stream_running_stj_batch, which serves model 2's Jacobian rows as cpi_running_stj_batch does (cpi_cov_running_stj_kernel
+// sits on cov_body, whose phase A reads cut windows: the same launch with tstart / tend set).
+static int stream_running_check(cpi_ctx *ctx, const char *who, bool with_stj, const cpi_params *prm, bool many, int64_t R, int64_t K, int64_t U,
                                 int32_t N, const void *stream, const void *soff, const void *update_times, const void *uoff,
                                 const void *lin, const void *q_k_lin, const cpi_outputs *rows, bool &noop) {
     noop = false;
@@ -800,7 +808,7 @@ static int stream_running_check(cpi_ctx *ctx, const char *who, const cpi_params 
     if (!prm || !rows) return refuse(ctx, who, "prm/rows is NULL");
     if (prm->model == CPI_MODEL_FORSTER) return refuse_forster(ctx, who, NO_RUNNING_FORM);
     if (!model_is_cpi(prm)) return refuse(ctx, who, "model must be 1 or 2");
-    if (prm->model == CPI_MODEL_V2 && request_of(rows).jac) return refuse_v2_jac(ctx, who, "");
+    if (prm->model == CPI_MODEL_V2 && request_of(rows).jac) CPI_TRY(refuse_v2_jac_here(ctx, who, with_stj, prm, ""));
     if (R < 0 || K < 0 || U < 0 || N < 0) return refuse(ctx, who, "negative size");
     if (U == 0 || N == 0) { noop = true; return CPI_OK; }
     if (many && R == 0) return refuse(ctx, who, "U > 0 windows and no run");
@@ -818,28 +826,31 @@ static int stream_running_launch(cpi_ctx *ctx, const cpi_params *prm, const Stre
                                  const double *lin, const double *q_k_lin, const cpi_outputs *rows, int64_t w0, int64_t wn) {
     const Request rq = request_of(rows);
     const bool avg = prm->imu_avg != 0;
+    const bool stj = prm->model == CPI_MODEL_V2 && rq.jac;   // (cpi_stream_running_stj_batch: the check has refused it for the others)
+    const bool mean_jac = rq.jac && !stj;
     PreArgs a = pre_args(prm, wn, N, stream, reinterpret_cast<const int64_t *>(sc.first), sc.count, lin, q_k_lin, rows);
     a.K = sc.K; a.tstart = sc.tstart + w0; a.tend = sc.tend + w0;
     a.first += w0; a.count += w0; a.lin += w0 * 6;
     if (a.qk) a.qk += w0 * 4;
-    if (rq.mean || rq.jac) {
+    if (rq.mean || mean_jac) {
         PreArgs m = a;
         m.write_means = rq.mean ? 1 : 0;
-        m.write_jac = rq.jac ? 1 : 0;
-        launch::mean_stream_running(prm->model, rq.jac, avg, L, m, ctx->stream);
+        m.write_jac = mean_jac ? 1 : 0;
+        launch::mean_stream_running(prm->model, mean_jac, avg, L, m, ctx->stream);
     }
-    if (rq.cov) launch::cov_running(prm->model, avg, a, ctx->stream);
+    if (stj) launch::cov_running_stj(avg, a, ctx->stream);
+    else if (rq.cov) launch::cov_running(prm->model, avg, a, ctx->stream);
     CPI_HIP(ctx, hipGetLastError());
     return CPI_OK;
 }
 static int stream_running_lanes(const cpi_params *prm, int64_t U, int32_t N, const cpi_outputs *rows) {
-    return pick_lanes(prm, U, N, request_of(rows).jac);
+    return pick_lanes(prm, U, N, request_of(rows).jac && prm->model != CPI_MODEL_V2);   // as running_device: model 2's rows are not the mean kernel's
 }
-static int stream_running_impl(cpi_ctx *ctx, const char *who, const cpi_params *prm, const RunArgs *runs, int64_t R, int64_t K,
+static int stream_running_impl(cpi_ctx *ctx, const char *who, bool with_stj, const cpi_params *prm, const RunArgs *runs, int64_t R, int64_t K,
                                const double *stream, int64_t U, const double *update_times, int32_t N, const double *lin,
                                const double *q_k_lin, void *workspace, const cpi_outputs *rows) {
     bool noop;
-    const int rc = stream_running_check(ctx, who, prm, runs != nullptr, R, K, U, N, stream, runs ? runs->soff : nullptr, update_times,
+    const int rc = stream_running_check(ctx, who, with_stj, prm, runs != nullptr, R, K, U, N, stream, runs ? runs->soff : nullptr, update_times,
                                         runs ? runs->uoff : nullptr, lin, q_k_lin, rows, noop);
     if (rc != CPI_OK || noop) return rc;
     if (!workspace) return refuse(ctx, who, "NULL argument");
@@ -855,7 +866,7 @@ static int stream_running_impl(cpi_ctx *ctx, const char *who, const cpi_params *
 extern "C" int cpi_preintegrate_stream_running(cpi_ctx *ctx, const cpi_params *prm, int64_t K, const double *stream, int64_t U,
                                                const double *update_times, int32_t N, const double *lin, const double *q_k_lin,
                                                void *workspace, const cpi_outputs *rows) {
-    return stream_running_impl(ctx, "cpi_preintegrate_stream_running", prm, nullptr, 0, K, stream, U, update_times, N, lin, q_k_lin,
+    return stream_running_impl(ctx, "cpi_preintegrate_stream_running", false, prm, nullptr, 0, K, stream, U, update_times, N, lin, q_k_lin,
                                workspace, rows);
 }
 extern "C" int cpi_preintegrate_streams_running(cpi_ctx *ctx, const cpi_params *prm, int64_t R, int64_t K, const double *stream,
@@ -866,8 +877,103 @@ extern "C" int cpi_preintegrate_streams_running(cpi_ctx *ctx, const cpi_params *
     ra.soff = reinterpret_cast<const long long *>(stream_offsets);
     ra.uoff = reinterpret_cast<const long long *>(update_offsets);
     ra.R = 0;
-    return stream_running_impl(ctx, "cpi_preintegrate_streams_running", prm, &ra, R, K, stream, U, update_times, N, lin, q_k_lin,
+    return stream_running_impl(ctx, "cpi_preintegrate_streams_running", false, prm, &ra, R, K, stream, U, update_times, N, lin, q_k_lin,
                                workspace, rows);
+}
+// One entry for one stream (R == 1, both offsets NULL: cpi_preintegrate_stream_running) or many (cpi_preintegrate_streams_running).
+static bool one_stream(int64_t R, const void *stream_offsets, const void *update_offsets) { return R == 1 && !stream_offsets && !update_offsets; }
+extern "C" int cpi_stream_running_stj_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t R, int64_t K, const double *stream,
+                                            const int64_t *stream_offsets, int64_t U, const double *update_times,
+                                            const int64_t *update_offsets, int32_t N, const double *lin, const double *q_k_lin,
+                                            void *workspace, const cpi_outputs *rows) {
+    static const char who[] = "cpi_stream_running_stj_batch";
+    RunArgs ra;
+    ra.soff = reinterpret_cast<const long long *>(stream_offsets);
+    ra.uoff = reinterpret_cast<const long long *>(update_offsets);
+    ra.R = 0;
+    const bool one = one_stream(R, stream_offsets, update_offsets);
+    return stream_running_impl(ctx, who, true, prm, one ? nullptr : &ra, one ? 0 : R, K, stream, U, update_times, N, lin, q_k_lin, workspace, rows);
+}
+
+// The query family by ABSOLUTE time over IMU stream(s) (include/cpi_amd.h: cpi_query_stream_batch): the cut kernel into the workspace,
+// then the kernels of cpi_query_stream.hip, which find the window among the run's update times and the interval among the patched
+// stamps before they do what cpi_query_kernel / cpi_query_cov_kernel / cpi_query_stj_kernel do -- one after the other on the context's
+// stream.  The first kernel that runs writes qwin_out (the mean kernel alone when out asks for nothing).
+// *done: a no-op call.  The checks the device and the host form share, up to the ones on rows and the workspace.
+static int query_stream_check(cpi_ctx *ctx, const char *who, const cpi_params *prm, bool one, int64_t R, int64_t K, int64_t U, int32_t N,
+                              const void *stream, const void *soff, const void *update_times, const void *uoff, const void *lin,
+                              const void *q_k_lin, int64_t Q, const void *qtime, const cpi_outputs *out, bool *done) {
+    *done = true;
+    CPI_TRY(query_check(ctx, who, prm, request_of(out), QUERY_COV | QUERY_STJ));
+    if (R < 0 || K < 0 || U < 0 || N < 0 || Q < 0) return refuse(ctx, who, "negative size");
+    if (Q == 0) return CPI_OK;
+    if (U == 0) return refuse(ctx, who, "U is 0: there is no window to query");
+    if (R == 0) return refuse(ctx, who, "U > 0 windows and no run");
+    if (R > 0x7ffffffeLL) return refuse(ctx, who, "R exceeds 2^31 - 2 runs");
+    if (K == 0) return refuse(ctx, who, one ? "the stream is empty" : "the streams hold no reading");
+    if (!stream || !update_times || !lin || !qtime || (!one && (!soff || !uoff))) return refuse(ctx, who, "NULL argument");
+    CPI_TRY(check_grid(ctx, who, "U", U));
+    CPI_TRY(check_qk(ctx, who, prm, q_k_lin));
+    CPI_TRY(check_N(ctx, who, N));
+    CPI_TRY(check_lanes(ctx, prm));
+    if (!grid_ok(Q)) return refuse(ctx, who, "Q exceeds 2^31 - 1 queries per call (32-bit grid)");
+    *done = false;
+    return CPI_OK;
+}
+extern "C" int cpi_query_stream_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t R, int64_t K, const double *stream,
+                                      const int64_t *stream_offsets, int64_t U, const double *update_times,
+                                      const int64_t *update_offsets, int32_t N, const double *lin, const double *q_k_lin,
+                                      void *workspace, const cpi_outputs *rows, int64_t Q, const int32_t *qrun, const double *qtime,
+                                      int32_t *qwin_out, const cpi_outputs *out) {
+    static const char who[] = "cpi_query_stream_batch";
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (!prm || !rows || !out) return refuse(ctx, who, "prm/rows/out is NULL");
+    const bool one = one_stream(R, stream_offsets, update_offsets);
+    bool done;
+    CPI_TRY(query_stream_check(ctx, who, prm, one, R, K, U, N, stream, stream_offsets, update_times, update_offsets, lin, q_k_lin, Q, qtime, out, &done));
+    if (done) return CPI_OK;
+    if (!workspace) return refuse(ctx, who, "NULL argument");
+    CPI_TRY(check_workspace(ctx, who, workspace));
+    const Request rq = request_of(out);
+    if (N > 0 && rq.any()) CPI_TRY(query_rows_check(ctx, who, prm, rows, out));   // N == 0: every query is the zero state and rows is not read
+    if (!rq.any() && !qwin_out) return CPI_OK;
+    const bool stj = prm->model == CPI_MODEL_V2 && rq.jac;
+    const bool mean_jac = rq.jac && !stj;
+    const bool means = rq.mean || mean_jac || !rq.any();
+    const bool avg = prm->imu_avg != 0;
+
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    RunArgs ra;
+    ra.soff = reinterpret_cast<const long long *>(stream_offsets);
+    ra.uoff = reinterpret_cast<const long long *>(update_offsets);
+    ra.R = (int)R;
+    const StreamCut sc = stream_cut(K, update_times, workspace, U, one ? nullptr : &ra);
+    CPI_TRY(cut_launch(ctx, sc, stream, U, N));
+    StreamQueryArgs a;
+    memset(&a, 0, sizeof a);
+    a.U = U; a.N = N; a.stream = stream; a.K = K; a.update = update_times; a.uoff = one ? nullptr : ra.uoff; a.R = (int)R;
+    a.first = sc.first; a.count = sc.count; a.tstart = sc.tstart; a.tend = sc.tend; a.lin = lin; a.qk = q_k_lin;
+    for (int i = 0; i < 3; i++) a.grav[i] = prm->grav[i];
+    if (rq.any()) a.rows = *rows;   // (a call for qwin_out alone reads no row)
+    a.Q = Q; a.qrun = qrun; a.qtime = qtime; a.qwin_out = qwin_out;
+    a.wtrips = 0;
+    while ((1ll << a.wtrips) < (long long)U + 1) a.wtrips++;
+    a.trips = query_trips(N); a.out = *out;
+    if (mean_jac) {
+        // the Jacobian instance carries all five matrices: the ones out does not ask for are read from a field that is there
+        const double *any = rows->J_q ? rows->J_q : rows->J_a ? rows->J_a : rows->J_b ? rows->J_b : rows->H_a ? rows->H_a : rows->H_b;
+        double **f[5] = { &a.rows.J_q, &a.rows.J_a, &a.rows.J_b, &a.rows.H_a, &a.rows.H_b };
+        for (double **x : f) if (!*x) *x = const_cast<double *>(any);
+    }
+    if (means) { launch::squery_mean(prm->model, mean_jac, avg, a, ctx->stream); a.qwin_out = nullptr; }
+    if (stj) { launch::squery_jac2(avg, a, ctx->stream); a.qwin_out = nullptr; }
+    if (rq.cov) {
+        const double q4[4] = { prm->sigma_w * prm->sigma_w, prm->sigma_wb * prm->sigma_wb, prm->sigma_a * prm->sigma_a, prm->sigma_ab * prm->sigma_ab };
+        launch::squery_cov(prm->model, avg, a, q4, ctx->stream);
+    }
+    CPI_HIP(ctx, hipGetLastError());
+    return CPI_OK;
 }
 
 // ============================================================================================
@@ -1562,7 +1668,9 @@ public:
     }
 
 private:
-    static constexpr int kMax = 32;   // an entry stages at most 7 inputs, a workspace and kOutFields outputs
+    // the most any entry stages is cpi_query_stream_batch_host's: 6 stream inputs and the workspace, qrun, qtime and qwin_out,
+    // a mirror of the running rows and a mirror of the outputs, each of at most kOutFields arrays
+    static constexpr int kMax = 10 + 2 * kOutFields;
     cpi_ctx *ctx;
     void *buf[kMax];
     int n = 0;
@@ -2052,12 +2160,12 @@ extern "C" int cpi_preintegrate_streams_host(cpi_ctx *ctx, const cpi_params *prm
 // back in chunks of whole windows, never more than 2^18 rows per chunk (N <= 65535: at least 4 windows), the
 // kernels of a chunk and its download following each other on the context's stream.  The lane choice is that of the whole call,
 // so the rows do not depend on the chunking.
-static int stream_running_host_impl(cpi_ctx *ctx, const char *who, const cpi_params *prm, bool many, int64_t R, int64_t K,
+static int stream_running_host_impl(cpi_ctx *ctx, const char *who, bool with_stj, const cpi_params *prm, bool many, int64_t R, int64_t K,
                                     const double *stream, const int64_t *stream_offsets, int64_t U, const double *update_times,
                                     const int64_t *update_offsets, int32_t N, const double *lin, const double *q_k_lin,
                                     const cpi_outputs *rows, int32_t *count) {
     bool noop;
-    const int rc = stream_running_check(ctx, who, prm, many, R, K, U, N, stream, stream_offsets, update_times, update_offsets, lin, q_k_lin, rows, noop);
+    const int rc = stream_running_check(ctx, who, with_stj, prm, many, R, K, U, N, stream, stream_offsets, update_times, update_offsets, lin, q_k_lin, rows, noop);
     if (rc != CPI_OK || noop) return rc;
     if (many) CPI_TRY(check_offsets(ctx, who, R, stream_offsets, K, update_offsets, U));
     DeviceGuard guard_;
@@ -2088,15 +2196,73 @@ static int stream_running_host_impl(cpi_ctx *ctx, const char *who, const cpi_par
 extern "C" int cpi_preintegrate_stream_running_host(cpi_ctx *ctx, const cpi_params *prm, int64_t K, const double *stream, int64_t U,
                                                     const double *update_times, int32_t N, const double *lin, const double *q_k_lin,
                                                     const cpi_outputs *rows, int32_t *count) {
-    return stream_running_host_impl(ctx, "cpi_preintegrate_stream_running_host", prm, false, 0, K, stream, nullptr, U, update_times,
+    return stream_running_host_impl(ctx, "cpi_preintegrate_stream_running_host", false, prm, false, 0, K, stream, nullptr, U, update_times,
                                     nullptr, N, lin, q_k_lin, rows, count);
 }
 extern "C" int cpi_preintegrate_streams_running_host(cpi_ctx *ctx, const cpi_params *prm, int64_t R, int64_t K, const double *stream,
                                                      const int64_t *stream_offsets, int64_t U, const double *update_times,
                                                      const int64_t *update_offsets, int32_t N, const double *lin, const double *q_k_lin,
                                                      const cpi_outputs *rows, int32_t *count) {
-    return stream_running_host_impl(ctx, "cpi_preintegrate_streams_running_host", prm, true, R, K, stream, stream_offsets, U,
+    return stream_running_host_impl(ctx, "cpi_preintegrate_streams_running_host", false, prm, true, R, K, stream, stream_offsets, U,
                                     update_times, update_offsets, N, lin, q_k_lin, rows, count);
+}
+extern "C" int cpi_stream_running_stj_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t R, int64_t K, const double *stream,
+                                                 const int64_t *stream_offsets, int64_t U, const double *update_times,
+                                                 const int64_t *update_offsets, int32_t N, const double *lin, const double *q_k_lin,
+                                                 const cpi_outputs *rows, int32_t *count) {
+    const bool one = one_stream(R, stream_offsets, update_offsets);
+    return stream_running_host_impl(ctx, "cpi_stream_running_stj_batch_host", true, prm, !one, one ? 0 : R, K, stream, stream_offsets, U,
+                                    update_times, update_offsets, N, lin, q_k_lin, rows, count);
+}
+
+// cpi_query_stream_batch from host memory.  The stream(s) are staged whole, the running rows are computed into device staging by
+// cpi_stream_running_stj_batch and never leave it (the covariance rows as P_sym), Q rows and qwin_out come down.  What the device form
+// cannot check is checked here, before anything is enqueued: the offsets and qrun in range.
+extern "C" int cpi_query_stream_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t R, int64_t K, const double *stream,
+                                           const int64_t *stream_offsets, int64_t U, const double *update_times,
+                                           const int64_t *update_offsets, int32_t N, const double *lin, const double *q_k_lin,
+                                           int64_t Q, const int32_t *qrun, const double *qtime, int32_t *qwin_out,
+                                           const cpi_outputs *out) {
+    static const char who[] = "cpi_query_stream_batch_host";
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (!prm || !out) return refuse(ctx, who, "prm/out is NULL");
+    const bool one = one_stream(R, stream_offsets, update_offsets);
+    bool done;
+    CPI_TRY(query_stream_check(ctx, who, prm, one, R, K, U, N, stream, stream_offsets, update_times, update_offsets, lin, q_k_lin, Q, qtime, out, &done));
+    if (done) return CPI_OK;
+    if (!one) CPI_TRY(check_offsets(ctx, who, R, stream_offsets, K, update_offsets, U));
+    if (qrun)
+        for (int64_t k = 0; k < Q; k++)
+            if (qrun[k] < 0 || qrun[k] >= R) return refuse(ctx, who, ("qrun[" + std::to_string(k) + "] = " + std::to_string(qrun[k]) + " is not a run of [0, R)").c_str());
+    const Request rq = request_of(out);
+    if (!rq.any() && !qwin_out) return CPI_OK;
+    const bool stj = prm->model == CPI_MODEL_V2 && rq.jac;
+
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    Staging st(ctx);
+    StreamsDev in;
+    const int32_t *dqrun;
+    const double *dqtime;
+    int32_t *dqwin = nullptr;
+    cpi_outputs rmask = {}, drows, d;
+    double dummy;
+    if (rq.any()) rmask.DT = rmask.alpha = rmask.beta = rmask.q = &dummy;   // mirror() allocates the fields that are set
+    rmask.J_q = out->J_q; rmask.J_a = out->J_a; rmask.J_b = out->J_b; rmask.H_a = out->H_a; rmask.H_b = out->H_b;
+    if (stj) rmask.J_q = rmask.J_a = rmask.J_b = rmask.H_a = rmask.H_b = rmask.O_a = rmask.O_b = &dummy;
+    if (rq.cov) rmask.P_sym = &dummy;
+    CPI_TRY(stage_streams(st, one ? 0 : R, K, stream, one ? nullptr : stream_offsets, U, update_times, one ? nullptr : update_offsets, lin, q_k_lin, &in));
+    CPI_TRY(st.upload(qrun, (size_t)Q, &dqrun));
+    CPI_TRY(st.upload(qtime, (size_t)Q, &dqtime));
+    if (qwin_out) CPI_TRY(st.alloc((size_t)Q, &dqwin));
+    CPI_TRY(st.mirror(&rmask, (size_t)U * (size_t)N, &drows));
+    CPI_TRY(st.mirror(out, (size_t)Q, &d));
+    if (N > 0 && rq.any())
+        CPI_TRY(cpi_stream_running_stj_batch(ctx, prm, R, K, in.stream, in.soff, U, in.update, in.uoff, N, in.lin, in.qk, in.ws, &drows));
+    CPI_TRY(cpi_query_stream_batch(ctx, prm, R, K, in.stream, in.soff, U, in.update, in.uoff, N, in.lin, in.qk, in.ws, &drows, Q, dqrun, dqtime, dqwin, &d));
+    CPI_TRY(st.download(out, d, (size_t)Q));
+    if (qwin_out) CPI_TRY(st.download(qwin_out, (const int32_t *)dqwin, (size_t)Q));
+    return st.finish();
 }
 
 extern "C" int cpi_factor_eval_batch_host(cpi_ctx *ctx, int32_t model, const double grav[3], int64_t F,

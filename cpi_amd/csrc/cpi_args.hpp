@@ -1,6 +1,6 @@
 // cpi_args.hpp -- kernel argument blocks and the launcher interface between the translation units of libcpi_amd.so.
 //
-// The library is nine translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
+// The library is ten translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
 //   cpi_mean.hip    cpi_mean_kernel / cpi_mean_tiled_kernel / cpi_tile_*_kernel       (cpi_mean_kernels.hpp)
 //   cpi_running.hip cpi_mean_running_kernel / cpi_mean_stream_running_kernel: a row after every interval, from plain knots /
 //                   from windows cut out of IMU stream(s) in place         (cpi_running_kernels.hpp, cpi_running_body.inc)
@@ -13,6 +13,9 @@
 //                   from a running P / P_sym row                                       (cpi_query_cov_kernels.hpp)
 //   cpi_stj.hip     cpi_cov_running_stj_kernel / cpi_query_stj_kernel: model 2's bias Jacobians (the Discrete_J_b columns of cov_body)
 //                   after every interval and at arbitrary times                (cpi_cov_kernels.hpp, cpi_stj_kernels.hpp)
+//   cpi_query_stream.hip  cpi_squery_mean_kernel / cpi_squery_cov_kernel / cpi_squery_jac2_kernel: the three query kernels by
+//                   ABSOLUTE time over IMU stream(s) read in place -- window lookup over the update times, search over the
+//                   patched stamps of the cut, then the same arithmetic                 (cpi_query_stream_kernels.hpp)
 //   cpi_factor.hip  evaluateError sweeps, square-root information, Hessian blocks, state prediction
 //                                                                                      (cpi_factor_kernels.hpp)
 //   cpi_abi.hip     the C-ABI of include/cpi_amd.h: argument checks, launch heuristics, device sets (RCCL), the
@@ -118,6 +121,36 @@ struct QueryArgs {
     cpi_outputs out;       // arrays of Q rows
 };
 
+// cpi_query_stream_batch: query k asks for the measurement of run qrun[k] at the ABSOLUTE time qtime[k]; the kernels find the
+// window among the run's update times and the interval among the patched stamps of the cut (first / count / tstart / tend: the
+// workspace of the stream entries, filled by the cut kernel in front of them); rows = the U * N rows of the running stream entries.
+// qrun and uoff live in device memory and are CLAMPED where they are read.  A struct of its own, so that QueryArgs and PreArgs --
+// and with them the code of every existing kernel -- stay as they were.
+struct StreamQueryArgs {
+    long long U;
+    int N;
+    const double *stream;    // [K][7], read in place
+    long long K;
+    const double *update;    // [U]
+    const long long *uoff;   // [R + 1], or NULL: one run owning [0, U)
+    int R;
+    const long long *first;
+    const int *count;
+    const double *tstart;
+    const double *tend;
+    const double *lin;
+    const double *qk;
+    double grav[3];
+    cpi_outputs rows;        // as QueryArgs::rows
+    long long Q;
+    const int *qrun;         // [Q] or NULL (run 0)
+    const double *qtime;     // [Q]
+    int *qwin_out;           // [Q] or NULL: the GLOBAL window found, -1 for a run without update times
+    int wtrips;              // ceil(log2(U + 1)): steps of the window lookup, the same for every lane
+    int trips;               // ceil(log2(N + 1)): steps of the interval search
+    cpi_outputs out;         // arrays of Q rows
+};
+
 struct FactorArgs {
     long long F;
     double grav[3];
@@ -196,6 +229,10 @@ void query_cov(int model, bool avg, const QueryArgs &a, const double q4[4], hipS
 // cpi_query_stj_batch: a.out.J_q ... O_b from a.rows.q and all seven Jacobian fields of a.rows)
 void cov_running_stj(bool avg, const PreArgs &a, hipStream_t st);
 void query_stj(bool avg, const QueryArgs &a, hipStream_t st);
+// ---- cpi_query_stream.hip (cpi_query_stream_batch: the three launchers above over StreamQueryArgs; each writes a.qwin_out when set)
+void squery_mean(int model, bool jac, bool avg, const StreamQueryArgs &a, hipStream_t st);
+void squery_cov(int model, bool avg, const StreamQueryArgs &a, const double q4[4], hipStream_t st);
+void squery_jac2(bool avg, const StreamQueryArgs &a, hipStream_t st);
 // ---- cpi_factor.hip
 void factor(int model, bool whiten, int lpf, const FactorArgs &a, hipStream_t st);            // lpf 16 | 8 | 4
 void factor_packed(int model, int lpf, const FactorArgs &a, double *packed, hipStream_t st);  // lpf 2 | 3 | 4 | 6 | 8

@@ -772,6 +772,48 @@ struct RunningRows {
     }
 };
 
+// The members at ABSOLUTE query times over IMU stream(s) read in place (cpi_query_stream_batch_host), one CpiResult per time: what
+// ImuStream::at* / ImuStreamSet::at* share.  soff / uoff / qrun NULL: one stream.  cov: P_meas as well; stj: model 2's seven bias
+// Jacobians as well (model 1's five are always filled).  windows (optional) receives the GLOBAL window index of every time (-1: a
+// run without update times, whose members are NaN).
+inline std::vector<CpiResult> query_stream_results(const Context &ctx, const cpi_params &prm, int64_t R, const std::vector<double> &knots,
+                                                   const int64_t *soff, const std::vector<double> &ut, const int64_t *uoff, int32_t N,
+                                                   const std::vector<double> &lin, const std::vector<double> &qk, const int32_t *qrun,
+                                                   const std::vector<double> &times, bool cov, bool stj, std::vector<int32_t> *windows) {
+    const int64_t Q = (int64_t)times.size(), K = (int64_t)(knots.size() / 7), U = (int64_t)ut.size();
+    std::vector<CpiResult> res((size_t)Q);
+    if (windows) windows->assign((size_t)Q, -1);
+    if (Q == 0) return res;
+    const bool v2 = stj && prm.model == CPI_MODEL_V2;
+    const bool jac = prm.model == CPI_MODEL_V1 || v2;
+    std::vector<double> DT(Q), al(Q * 3), be(Q * 3), q(Q * 4), Jq(jac ? Q * 9 : 0), Ja(jac ? Q * 9 : 0), Jb(jac ? Q * 9 : 0),
+        Ha(jac ? Q * 9 : 0), Hb(jac ? Q * 9 : 0), Oa(v2 ? Q * 9 : 0), Ob(v2 ? Q * 9 : 0), P(cov ? Q * 225 : 0);
+    std::vector<int32_t> qwin((size_t)Q, -1);
+    cpi_outputs o{};
+    o.DT = DT.data(); o.alpha = al.data(); o.beta = be.data(); o.q = q.data();
+    if (jac) { o.J_q = Jq.data(); o.J_a = Ja.data(); o.J_b = Jb.data(); o.H_a = Ha.data(); o.H_b = Hb.data(); }
+    if (v2) { o.O_a = Oa.data(); o.O_b = Ob.data(); }
+    if (cov) o.P = P.data();
+    ctx.check(cpi_query_stream_batch_host(ctx.get(), &prm, R, K, knots.data(), soff, U, ut.data(), uoff, N, lin.data(),
+                                          qk.empty() ? nullptr : qk.data(), Q, qrun, times.data(), qwin.data(), &o));
+    for (size_t r = 0; r < (size_t)Q; r++) {
+        CpiResult &x = res[r];
+        x.DT = DT[r];
+        for (int k = 0; k < 3; k++) { x.alpha_tau[k] = al[r * 3 + k]; x.beta_tau[k] = be[r * 3 + k]; }
+        for (int k = 0; k < 4; k++) x.q_k2tau[k] = q[r * 4 + k];
+        if (jac)
+            for (int k = 0; k < 9; k++) {
+                x.J_q[k] = Jq[r * 9 + k]; x.J_a[k] = Ja[r * 9 + k]; x.J_b[k] = Jb[r * 9 + k];
+                x.H_a[k] = Ha[r * 9 + k]; x.H_b[k] = Hb[r * 9 + k];
+                if (v2) { x.O_a[k] = Oa[r * 9 + k]; x.O_b[k] = Ob[r * 9 + k]; }
+            }
+        if (cov)
+            for (int k = 0; k < 225; k++) x.P_meas[k] = P[r * 225 + k];
+    }
+    if (windows) *windows = qwin;
+    return res;
+}
+
 // ---- the caller's loop for MANY windows at once --------------------------------------------------------------------
 // What GraphSolver keeps between two states is a deque of IMU readings (GraphSolver.h: imu_times / imu_linaccs /
 // imu_angvel, filled by addmeasurement_imu); createimufactor_cpi_v1 / _v2 (GraphSolver_IMU.cpp:34-134) walk it up to the
@@ -855,7 +897,38 @@ public:
         if (counts) *counts = cnt;
         return res;
     }
+    // The members at ABSOLUTE times (cpi_query_stream_batch_host; the lidar points of a sweep, keyframes chosen after the fact):
+    // result[k] = the window that holds times[k] -- the first whose update time is not before it, the last one for a later time --
+    // at that time, as CpiBatch::at returns it for a window it was given: on a stamp what running() holds there, inside an interval
+    // that state advanced with the reading held, at or past the window's end its measurement.  Nothing is assembled on the host.
+    // windows (optional) receives the window of every time.  A window longer than max_intervals (default: the longest window, found
+    // on the host from the stamps) is queried as truncated to it.  Models 1 and 2; the bias Jacobians are filled for model 1 only,
+    // P_meas by at_cov / at_stj, model 2's seven Jacobians by at_stj (prm.state_transition_jacobians set).
+    std::vector<CpiResult> at(const Context &ctx, const cpi_params &prm, const std::vector<double> &update_times, const std::vector<double> &lin,
+                              const std::vector<double> &times, const std::vector<double> &q_k_lin = std::vector<double>(),
+                              std::vector<int32_t> *windows = nullptr, int32_t max_intervals = 0) const {
+        return at_impl(ctx, prm, update_times, lin, times, q_k_lin, windows, max_intervals, false, false);
+    }
+    std::vector<CpiResult> at_cov(const Context &ctx, const cpi_params &prm, const std::vector<double> &update_times, const std::vector<double> &lin,
+                                  const std::vector<double> &times, const std::vector<double> &q_k_lin = std::vector<double>(),
+                                  std::vector<int32_t> *windows = nullptr, int32_t max_intervals = 0) const {
+        return at_impl(ctx, prm, update_times, lin, times, q_k_lin, windows, max_intervals, true, false);
+    }
+    std::vector<CpiResult> at_stj(const Context &ctx, const cpi_params &prm, const std::vector<double> &update_times, const std::vector<double> &lin,
+                                  const std::vector<double> &times, const std::vector<double> &q_k_lin = std::vector<double>(),
+                                  std::vector<int32_t> *windows = nullptr, int32_t max_intervals = 0) const {
+        return at_impl(ctx, prm, update_times, lin, times, q_k_lin, windows, max_intervals, true, true);
+    }
 private:
+    std::vector<CpiResult> at_impl(const Context &ctx, const cpi_params &prm, const std::vector<double> &update_times, const std::vector<double> &lin,
+                                   const std::vector<double> &times, const std::vector<double> &q_k_lin, std::vector<int32_t> *windows,
+                                   int32_t max_intervals, bool cov, bool stj) const {
+        const size_t U = update_times.size();
+        if (lin.size() != U * 6) throw std::runtime_error("ImuStream::at: lin must hold 6 doubles per update time");
+        if (!q_k_lin.empty() && q_k_lin.size() != U * 4) throw std::runtime_error("ImuStream::at: q_k_lin must hold 4 doubles per update time");
+        const int32_t N = max_intervals > 0 ? max_intervals : longest_window(knots_.data(), size(), update_times.data(), U);
+        return query_stream_results(ctx, prm, 1, knots_, nullptr, update_times, nullptr, N, lin, q_k_lin, nullptr, times, cov, stj, windows);
+    }
     std::vector<double> knots_;
 };
 
@@ -952,7 +1025,33 @@ public:
             }
         return res;
     }
+    // ImuStream::at / at_cov / at_stj for the runs of the set in ONE call: result[k] = run runs[k] at the absolute time times[k] (of
+    // that run's clock).  windows (optional) receives the GLOBAL window index of every time, -1 (and NaN members) for a run without
+    // update times; a run index outside the set is an error.
+    std::vector<CpiResult> at(const Context &ctx, const cpi_params &prm, const std::vector<int32_t> &runs, const std::vector<double> &times,
+                              std::vector<int32_t> *windows = nullptr, int32_t max_intervals = 0) const {
+        return at_impl(ctx, prm, runs, times, windows, max_intervals, false, false);
+    }
+    std::vector<CpiResult> at_cov(const Context &ctx, const cpi_params &prm, const std::vector<int32_t> &runs, const std::vector<double> &times,
+                                  std::vector<int32_t> *windows = nullptr, int32_t max_intervals = 0) const {
+        return at_impl(ctx, prm, runs, times, windows, max_intervals, true, false);
+    }
+    std::vector<CpiResult> at_stj(const Context &ctx, const cpi_params &prm, const std::vector<int32_t> &runs, const std::vector<double> &times,
+                                  std::vector<int32_t> *windows = nullptr, int32_t max_intervals = 0) const {
+        return at_impl(ctx, prm, runs, times, windows, max_intervals, true, true);
+    }
 private:
+    std::vector<CpiResult> at_impl(const Context &ctx, const cpi_params &prm, const std::vector<int32_t> &runs, const std::vector<double> &times,
+                                   std::vector<int32_t> *windows, int32_t max_intervals, bool cov, bool stj) const {
+        if (runs.size() != times.size()) throw std::runtime_error("ImuStreamSet::at: one run index per time");
+        if (!qk_.empty() && qk_.size() != ut_.size() * 4) throw std::runtime_error("ImuStreamSet::at: q_k_lin given for some runs and not for others");
+        const int64_t R = (int64_t)runs_.size();
+        int32_t N = max_intervals;
+        if (N <= 0)
+            for (int64_t r = 0; r < R; r++)
+                N = std::max(N, longest_window(knots_.data() + soff_[r] * 7, (size_t)(soff_[r + 1] - soff_[r]), ut_.data() + uoff_[r], runs_[r]));
+        return query_stream_results(ctx, prm, R, knots_, soff_.data(), ut_, uoff_.data(), N, lin_, qk_, runs.data(), times, cov, stj, windows);
+    }
     std::vector<double> knots_, ut_, lin_, qk_;
     std::vector<int64_t> soff_{0}, uoff_{0};   // [R + 1]
     std::vector<size_t> runs_;                 // update times per run

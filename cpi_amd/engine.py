@@ -669,9 +669,10 @@ class Engine:
         return (out, cnt) if return_counts else out
 
     # ---- running rows from IMU stream(s), cut in place (cpi_preintegrate_stream_running / cpi_preintegrate_streams_running)
-    def _stream_running_out(self, U, N, want, params, packed, out):
+    def _stream_running_out(self, U, N, want, params, packed, out, stj=False):
         if out is None:
-            out = self._running_views(self.alloc_outputs(U * N, self._running_want(tuple(want), params.model), params.model, packed), U, N)
+            want = tuple(want) if stj else self._running_want(tuple(want), params.model)
+            out = self._running_views(self.alloc_outputs(U * N, want, params.model, packed), U, N)
         return out, self._outputs_struct({k: v for k, v in out.items() if not k.startswith("_")})
 
     def _stream_counts(self, ws, U, N, return_counts, check_counts, who):
@@ -685,7 +686,7 @@ class Engine:
         return counts
 
     def preintegrate_stream_running(self, stream, update_times, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), N=None,
-                                    packed=False, out=None, return_counts=False, check_counts=True, workspace=None):
+                                    packed=False, out=None, return_counts=False, check_counts=True, workspace=None, _stj=False):
         """The measurement after EVERY interval of every window of ONE IMU stream, cut in place
         (cpi_preintegrate_stream_running): the inputs, N, return_counts, check_counts and workspace of preintegrate_stream, the
         want / packed / out and the returned [U, N, ...] tensors of preintegrate_running -- entry [u, i] is window u after
@@ -704,11 +705,15 @@ class Engine:
                 raise ValueError("preintegrate_stream_running: check_counts=False needs an explicit N (the cached bound may be stale)")
             N = self.stream_bound(stream, update_times)
         N = int(N)
-        out, o = self._stream_running_out(U, N, want, params, packed, out)
+        out, o = self._stream_running_out(U, N, want, params, packed, out, _stj)
         ws = workspace if workspace is not None else self.stream_workspace(U)
         self._sync_stream()
-        self._check(self.lib.cpi_preintegrate_stream_running(self.ctx, C.byref(params), K, _ptr(stream), U, _ptr(update_times), N,
-                                                             _ptr(lin), _ptr(q_k_lin), _ptr(ws), C.byref(o)))
+        if _stj:
+            self._check(self.lib.cpi_stream_running_stj_batch(self.ctx, C.byref(params), 1, K, _ptr(stream), None, U, _ptr(update_times),
+                                                              None, N, _ptr(lin), _ptr(q_k_lin), _ptr(ws), C.byref(o)))
+        else:
+            self._check(self.lib.cpi_preintegrate_stream_running(self.ctx, C.byref(params), K, _ptr(stream), U, _ptr(update_times), N,
+                                                                 _ptr(lin), _ptr(q_k_lin), _ptr(ws), C.byref(o)))
         if workspace is None and not self._follow and self.stream is not None:   # see preintegrate_stream
             ws.record_stream(self.stream)
         counts = self._stream_counts(ws, U, N, return_counts, check_counts, "preintegrate_stream_running")
@@ -716,7 +721,7 @@ class Engine:
 
     def preintegrate_streams_running(self, stream, stream_offsets, update_times, update_offsets, lin, q_k_lin=None, params=None,
                                      want=("mean", "jac", "cov"), N=None, packed=False, out=None, return_counts=False,
-                                     check_counts=True, workspace=None):
+                                     check_counts=True, workspace=None, _stj=False):
         """preintegrate_stream_running for MANY IMU streams in one call (cpi_preintegrate_streams_running): the inputs of
         preintegrate_streams (the list-of-runs form included), the [U, N, ...] rows of preintegrate_running, U the windows of all
         runs.  N=None: streams_bound() (tail assumed, as stream_bound(); one host synchronisation, not cached); check_counts=False
@@ -737,12 +742,12 @@ class Engine:
                 raise ValueError("preintegrate_streams_running: check_counts=False needs an explicit N")
             N = self.streams_bound(stream, soff, update_times, uoff)
         N = int(N)
-        out, o = self._stream_running_out(U, N, want, params, packed, out)
+        out, o = self._stream_running_out(U, N, want, params, packed, out, _stj)
         ws = workspace if workspace is not None else self.streams_workspace(R, U)
         self._sync_stream()
-        self._check(self.lib.cpi_preintegrate_streams_running(self.ctx, C.byref(params), R, K, _ptr(stream), _ptr(soff), U,
-                                                              _ptr(update_times), _ptr(uoff), N, _ptr(lin), _ptr(q_k_lin), _ptr(ws),
-                                                              C.byref(o)))
+        entry = self.lib.cpi_stream_running_stj_batch if _stj else self.lib.cpi_preintegrate_streams_running
+        self._check(entry(self.ctx, C.byref(params), R, K, _ptr(stream), _ptr(soff), U,
+                          _ptr(update_times), _ptr(uoff), N, _ptr(lin), _ptr(q_k_lin), _ptr(ws), C.byref(o)))
         # the workspace and the offsets must outlive the kernels that read them (see preintegrate_stream)
         if not self._follow and self.stream is not None:
             for t in ((ws,) if workspace is None else ()) + (soff, uoff, stream, update_times):
@@ -751,7 +756,7 @@ class Engine:
         return (out, counts) if return_counts else out
 
     def preintegrate_stream_running_host(self, stream, update_times, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"),
-                                         N=None, pinned=False, return_counts=False, check_counts=True):
+                                         N=None, pinned=False, return_counts=False, check_counts=True, _stj=False):
         """preintegrate_stream_running from HOST memory (cpi_preintegrate_stream_running_host): CPU float64 tensors in, CPU
         tensors [U, N, ...] out; synchronous.  N defaults to the longest window the stamps allow; with check_counts a window longer
         than N raises (check_counts=False needs an integer N and returns the truncated rows)."""
@@ -762,18 +767,23 @@ class Engine:
         if N is None and not check_counts:
             raise ValueError("preintegrate_stream_running_host: check_counts=False needs an explicit N")
         N = int(N) if N is not None else self._stream_bound(stream, update_times)
-        out = self._host_outputs((U, N), self._running_want(tuple(want), params.model), params.model, pinned)
+        out = self._host_outputs((U, N), tuple(want) if _stj else self._running_want(tuple(want), params.model), params.model, pinned)
         cnt = torch.empty((U,), dtype=torch.int32)
         o = self._outputs_struct(out)
         self._sync_stream()
-        self._check(self.lib.cpi_preintegrate_stream_running_host(self.ctx, C.byref(params), K, _ptr(stream), U, _ptr(update_times), N,
-                                                                  _ptr(lin), _ptr(q_k_lin), C.byref(o), _ptr(cnt)))
+        if _stj:
+            self._check(self.lib.cpi_stream_running_stj_batch_host(self.ctx, C.byref(params), 1, K, _ptr(stream), None, U, _ptr(update_times),
+                                                                   None, N, _ptr(lin), _ptr(q_k_lin), C.byref(o), _ptr(cnt)))
+        else:
+            self._check(self.lib.cpi_preintegrate_stream_running_host(self.ctx, C.byref(params), K, _ptr(stream), U, _ptr(update_times), N,
+                                                                      _ptr(lin), _ptr(q_k_lin), C.byref(o), _ptr(cnt)))
         if check_counts and U and int(cnt.max()) > N:
             raise ValueError("preintegrate_stream_running_host: a window has %d intervals, N = %d" % (int(cnt.max()), N))
         return (out, cnt) if return_counts else out
 
     def preintegrate_streams_running_host(self, stream, stream_offsets, update_times, update_offsets, lin, q_k_lin=None, params=None,
-                                          want=("mean", "jac", "cov"), N=None, pinned=False, return_counts=False, check_counts=True):
+                                          want=("mean", "jac", "cov"), N=None, pinned=False, return_counts=False, check_counts=True,
+                                          _stj=False):
         """preintegrate_streams_running from HOST memory (cpi_preintegrate_streams_running_host, which validates the offsets): CPU
         float64 tensors and int64 offsets in, CPU tensors [U, N, ...] out; synchronous.  N, check_counts as in
         preintegrate_stream_running_host (the default N is streams_bound())."""
@@ -786,16 +796,111 @@ class Engine:
         if N is None and not check_counts:
             raise ValueError("preintegrate_streams_running_host: check_counts=False needs an explicit N")
         N = int(N) if N is not None else self.streams_bound(stream, soff, update_times, uoff)
-        out = self._host_outputs((U, N), self._running_want(tuple(want), params.model), params.model, pinned)
+        out = self._host_outputs((U, N), tuple(want) if _stj else self._running_want(tuple(want), params.model), params.model, pinned)
         cnt = torch.empty((U,), dtype=torch.int32)
         o = self._outputs_struct(out)
         self._sync_stream()
-        self._check(self.lib.cpi_preintegrate_streams_running_host(self.ctx, C.byref(params), R, K, _ptr(stream), _ptr(soff), U,
-                                                                   _ptr(update_times), _ptr(uoff), N, _ptr(lin), _ptr(q_k_lin),
-                                                                   C.byref(o), _ptr(cnt)))
+        entry = self.lib.cpi_stream_running_stj_batch_host if _stj else self.lib.cpi_preintegrate_streams_running_host
+        self._check(entry(self.ctx, C.byref(params), R, K, _ptr(stream), _ptr(soff), U, _ptr(update_times), _ptr(uoff), N, _ptr(lin),
+                          _ptr(q_k_lin), C.byref(o), _ptr(cnt)))
         if check_counts and U and int(cnt.max()) > N:
             raise ValueError("preintegrate_streams_running_host: a window has %d intervals, N = %d" % (int(cnt.max()), N))
         return (out, cnt) if return_counts else out
+
+    # ---- model 2's Jacobian rows from IMU stream(s) (cpi_stream_running_stj_batch) and the query by absolute time (cpi_query_stream_batch)
+    def preintegrate_stream_running_stj(self, stream, update_times, lin, **kw):
+        """preintegrate_stream_running with model 2's Jacobian rows (cpi_stream_running_stj_batch, one stream): the arguments and
+        the result of preintegrate_stream_running; for model 2 (state_transition_jacobians set) "jac" means all seven matrices after
+        every interval, bit for bit preintegrate_running_stj on assemble_windows(stream, update_times).  Without "jac", or for model
+        1, the call is preintegrate_stream_running."""
+        return self.preintegrate_stream_running(stream, update_times, lin, _stj=True, **kw)
+
+    def preintegrate_streams_running_stj(self, stream, stream_offsets, update_times, update_offsets, lin, **kw):
+        """preintegrate_streams_running with model 2's Jacobian rows (cpi_stream_running_stj_batch, many streams)."""
+        return self.preintegrate_streams_running(stream, stream_offsets, update_times, update_offsets, lin, _stj=True, **kw)
+
+    def preintegrate_stream_running_stj_host(self, stream, update_times, lin, **kw):
+        """preintegrate_stream_running_stj from HOST memory (cpi_stream_running_stj_batch_host); arguments and result as
+        preintegrate_stream_running_host."""
+        return self.preintegrate_stream_running_host(stream, update_times, lin, _stj=True, **kw)
+
+    def preintegrate_streams_running_stj_host(self, stream, stream_offsets, update_times, update_offsets, lin, **kw):
+        """preintegrate_streams_running_stj from HOST memory (cpi_stream_running_stj_batch_host, which validates the offsets)."""
+        return self.preintegrate_streams_running_host(stream, stream_offsets, update_times, update_offsets, lin, _stj=True, **kw)
+
+    def query_stream(self, stream, update_times, lin, rows, qtime, q_k_lin=None, params=None, want=("mean",), N=None,
+                     stream_offsets=None, update_offsets=None, qrun=None, workspace=None, out=None):
+        """cpi_query_stream_batch: the query family by ABSOLUTE time over IMU stream(s) read in place.  stream / update_times / lin /
+        q_k_lin / params / N / the offsets: the arguments of the preintegrate_stream[s]_running[_stj] call that returned `rows` (its
+        dict of [U, N, ...] tensors; N defaults to their second dimension).  Both offsets None: one stream; otherwise int64 [R + 1]
+        CUDA tensors (or sequences) and qrun [Q] int32 names the run of every query.  qtime [Q] float64: absolute times, any order.
+        The window (the first of the run whose update time is not before the query time; the last one for a later time) and the
+        interval are found on the device.  want as in query_stj: "mean", "jac" (model 1: five matrices, model 2: seven), "cov",
+        "cov_sym".  Returns (out, qwin): out a dict of [Q, ...] tensors, bit for bit query_stj on the host-assembled windows with
+        qwin; qwin [Q] int32, the GLOBAL window of every query (-1 and NaN rows for a run without update times) -- the idx_i of
+        predict / factor_eval / factor_hessian.  Asynchronous; the call cuts the windows into the workspace itself."""
+        params = params or self.make_params()
+        r = {k: v for k, v in rows.items() if not k.startswith("_")}
+        K, U, Q = stream.shape[0], update_times.shape[0], qtime.shape[0]
+        if N is None:
+            N = next(iter(r.values())).shape[1]
+        N = int(N)
+        one = stream_offsets is None and update_offsets is None
+        soff = uoff = None
+        R = 1
+        if not one:
+            _, soff = self._runs(stream, stream_offsets, "stream", self.device)
+            _, uoff = self._runs(update_times, update_offsets, "update_times", self.device)
+            R = soff.shape[0] - 1
+            assert uoff.shape[0] == R + 1, "stream_offsets and update_offsets must both hold R + 1 entries"
+        for t in (stream, update_times, lin, q_k_lin, qtime):
+            assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64), "inputs must be contiguous CUDA float64 tensors"
+        assert qrun is None or (qrun.is_cuda and qrun.dtype == torch.int32 and qrun.shape == (Q,)), "qrun [Q] int32"
+        for k, v in r.items():
+            assert v.is_cuda and v.is_contiguous() and v.shape[:2] == (U, N), "rows: the [U, N, ...] dict of preintegrate_stream[s]_running[_stj]"
+        if out is None:
+            out = self.alloc_outputs(Q, tuple(want), params.model)
+        qwin = torch.empty((Q,), dtype=torch.int32, device=self.device)
+        ws = workspace if workspace is not None else self.streams_workspace(R, U)
+        o = self._outputs_struct(out)
+        ro = self._outputs_struct(r)
+        self._sync_stream()
+        self._check(self.lib.cpi_query_stream_batch(self.ctx, C.byref(params), R, K, _ptr(stream), _ptr(soff), U, _ptr(update_times),
+                                                    _ptr(uoff), N, _ptr(lin), _ptr(q_k_lin), _ptr(ws), C.byref(ro), Q, _ptr(qrun),
+                                                    _ptr(qtime), _ptr(qwin), C.byref(o)))
+        if not self._follow and self.stream is not None:   # see preintegrate_stream
+            for t in ((ws,) if workspace is None else ()) + (() if one else (soff, uoff)) + (qwin,):
+                t.record_stream(self.stream)
+        return out, qwin
+
+    def query_stream_host(self, stream, update_times, lin, qtime, q_k_lin=None, params=None, want=("mean",), N=None,
+                          stream_offsets=None, update_offsets=None, qrun=None, pinned=True, out=None):
+        """query_stream from HOST memory (cpi_query_stream_batch_host): CPU tensors in; there is no rows argument -- the running rows
+        are computed on the device and stay there.  The offsets and qrun are validated.  N defaults to stream_bound() /
+        streams_bound().  Returns (out, qwin) as CPU tensors; synchronous."""
+        params = params or self.make_params()
+        K, U, Q = stream.shape[0], update_times.shape[0], qtime.shape[0]
+        one = stream_offsets is None and update_offsets is None
+        soff = uoff = None
+        R = 1
+        if not one:
+            soff = torch.as_tensor(np.asarray(stream_offsets, dtype=np.int64))
+            uoff = torch.as_tensor(np.asarray(update_offsets, dtype=np.int64))
+            R = soff.shape[0] - 1
+        if N is None:
+            N = self._stream_bound(stream, update_times) if one else self.streams_bound(stream, soff, update_times, uoff)
+        for t in (stream, update_times, lin, q_k_lin, qtime):
+            assert t is None or (not t.is_cuda and t.is_contiguous() and t.dtype == torch.float64), "inputs must be contiguous CPU float64 tensors"
+        assert qrun is None or (qrun.dtype == torch.int32 and qrun.shape == (Q,)), "qrun [Q] int32"
+        if out is None:
+            out = self._host_outputs((Q,), tuple(want), params.model, pinned)
+        qwin = torch.empty((Q,), dtype=torch.int32)
+        o = self._outputs_struct(out)
+        self._sync_stream()
+        self._check(self.lib.cpi_query_stream_batch_host(self.ctx, C.byref(params), R, K, _ptr(stream), _ptr(soff), U, _ptr(update_times),
+                                                         _ptr(uoff), int(N), _ptr(lin), _ptr(q_k_lin), Q, _ptr(qrun), _ptr(qtime),
+                                                         _ptr(qwin), C.byref(o)))
+        return out, qwin
 
     def preintegrate_tiled_host(self, tiles, W, lin, q_k_lin=None, params=None, count=None, pinned=True, out=None):
         """Mean outputs from tiles held in HOST memory (cpi_preintegrate_tiled_batch_host: chunked upload / kernel /

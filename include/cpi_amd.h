@@ -59,7 +59,10 @@ extern "C" {
                                a window); cpi_query_cov_batch, cpi_query_cov_batch_host (the same with the covariance P / P_sym
                                at the query times); cpi_running_stj_batch, cpi_running_stj_batch_host,
                                cpi_query_stj_batch, cpi_query_stj_batch_host (model 2's seven bias Jacobians after every
-                               interval and at the query times) */
+                               interval and at the query times); cpi_stream_running_stj_batch,
+                               cpi_stream_running_stj_batch_host (those rows from IMU stream(s), cut in place);
+                               cpi_query_stream_batch, cpi_query_stream_batch_host (the query family by absolute time over IMU
+                               stream(s): the window and the interval are found on the device) */
 
 enum { CPI_OK = 0, CPI_ERR_INVALID = 1, CPI_ERR_HIP = 2, CPI_ERR_NO_DEVICE = 3, CPI_ERR_RCCL = 4 };
 enum {
@@ -301,7 +304,8 @@ int cpi_preintegrate_running_resume(cpi_ctx *ctx, const cpi_params *prm, int64_t
  * Not provided: P / P_sym at query times (they need the covariance kernel's lane-spread RK4 step); Jacobians for model 2; windows
  * cut from IMU streams in place (cpi_preintegrate_stream[s]_running: assemble the windows, or query per update time); rows that
  * continue from a carry record (cpi_preintegrate_running_resume); extrapolation past t_n.  (The covariance at query times is a
- * call of its own: cpi_query_cov_batch below; the Jacobians of model 2 at query times: cpi_query_stj_batch below.) */
+ * call of its own: cpi_query_cov_batch below; the Jacobians of model 2 at query times: cpi_query_stj_batch below; streams
+ * queried in place by absolute time: cpi_query_stream_batch below.) */
 int cpi_query_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                     const double *knots, const int64_t *first, const int32_t *count,
                     const double *lin, const double *q_k_lin, const cpi_outputs *rows,
@@ -336,7 +340,8 @@ int cpi_query_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
  * Composition: out->P_sym -> cpi_sqrt_information_packed_batch -> cpi_factor_eval_whitened_tri_batch / cpi_factor_hessian_tri_batch
  * with idx_i = qwin: the whitened keyframe factor AT the query time.
  * Still not provided: model-2 Jacobians at query times; windows cut from IMU streams in place; rows from a carry record;
- * extrapolation past t_n.  (The model-2 Jacobians at query times are a call of their own: cpi_query_stj_batch below.) */
+ * extrapolation past t_n.  (The model-2 Jacobians at query times are a call of their own: cpi_query_stj_batch below; streams queried in
+ * place by absolute time: cpi_query_stream_batch below.) */
 int cpi_query_cov_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                         const double *knots, const int64_t *first, const int32_t *count,
                         const double *lin, const double *q_k_lin, const cpi_outputs *rows,
@@ -359,7 +364,8 @@ int cpi_query_cov_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t 
  * O_a / O_b recursion has no running form).  CPI_MODEL_FORSTER is refused as there.
  * No host synchronisation and a single stream: a capture of the call is a chain without parallel branches.
  * Still not provided: these rows for the stream entries (cpi_preintegrate_stream[s]_running); for the carry-record entries
- * (cpi_preintegrate_running_resume); model 2's analytic Jacobians (state_transition_jacobians == 0); extrapolation past t_n. */
+ * (cpi_preintegrate_running_resume); model 2's analytic Jacobians (state_transition_jacobians == 0); extrapolation past t_n.
+ * (From IMU stream(s) cut in place: cpi_stream_running_stj_batch below.) */
 int cpi_running_stj_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                           const double *knots, const int64_t *first, const int32_t *count,
                           const double *lin, const double *q_k_lin, const cpi_outputs *rows);
@@ -386,7 +392,8 @@ int cpi_running_stj_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_
  * Composition: out (means, seven Jacobians, P_sym) -> cpi_sqrt_information_packed_batch -> cpi_factor_eval_whitened_tri_batch /
  * cpi_factor_hessian_tri_batch with model 2 and idx_i = qwin.
  * Still not provided: windows cut from IMU streams in place (the stream entries); rows that continue from a carry record
- * (cpi_preintegrate_running_resume); model 2's analytic Jacobians (state_transition_jacobians == 0); extrapolation past t_n. */
+ * (cpi_preintegrate_running_resume); model 2's analytic Jacobians (state_transition_jacobians == 0); extrapolation past t_n.
+ * (Streams queried in place by absolute time: cpi_query_stream_batch below.) */
 int cpi_query_stj_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                         const double *knots, const int64_t *first, const int32_t *count,
                         const double *lin, const double *q_k_lin, const cpi_outputs *rows,
@@ -483,6 +490,62 @@ int cpi_preintegrate_streams_running(cpi_ctx *ctx, const cpi_params *prm, int64_
                                      const int64_t *stream_offsets, int64_t U, const double *update_times,
                                      const int64_t *update_offsets, int32_t N, const double *lin, const double *q_k_lin,
                                      void *workspace, const cpi_outputs *rows);
+
+/* cpi_preintegrate_stream_running / cpi_preintegrate_streams_running WITH MODEL 2's JACOBIAN ROWS: to them what cpi_running_stj_batch
+ * is to cpi_preintegrate_running.  One entry serves one stream or many: the single-stream form is R == 1 with stream_offsets ==
+ * update_offsets == NULL (cpi_preintegrate_stream_running); otherwise the arguments and every rule are those of
+ * cpi_preintegrate_streams_running.  Without a model-2 Jacobian field in rows the call IS the older entry: the same kernels, rows
+ * bit for bit.  With model 2, state_transition_jacobians != 0 and any of J_q ... O_b in rows, the Jacobian rows are bit for bit the
+ * rows of cpi_running_stj_batch on the knots / first / count that the host assemblers cut from the same stream(s), with count
+ * clamped to N and the same N, params and lanes_per_window; the mean and P / P_sym rows are those of the older entry.  The cut kernel,
+ * the stream mean kernel and cpi_running_stj_batch's covariance kernel (which reads the cut windows in place) run one after the other
+ * on the context's stream: a capture is a chain without parallel branches.
+ * CPI_ERR_INVALID beyond the older entries': model 2 with state_transition_jacobians == 0 and a Jacobian field, with
+ * cpi_running_stj_batch's text.
+ * Still not provided: rows from a carry record; model 2's analytic Jacobians; the device-set (cpi_group_*) path. */
+int cpi_stream_running_stj_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t R, int64_t K, const double *stream,
+                                 const int64_t *stream_offsets, int64_t U, const double *update_times,
+                                 const int64_t *update_offsets, int32_t N, const double *lin, const double *q_k_lin,
+                                 void *workspace, const cpi_outputs *rows);
+
+/* The query family BY ABSOLUTE TIME over IMU stream(s) read in place: what cpi_query_batch / cpi_query_cov_batch /
+ * cpi_query_stj_batch return, for a caller that holds a resident stream, its update times and point stamps in absolute time (a lidar
+ * sweep to deskew, keyframes chosen after the fact) -- no host assembly, no copy of the IMU data, no window index computed by the
+ * caller.  The call finds the window and the interval on the device and returns the window index it found.
+ *   prm, R, K, stream, stream_offsets, U, update_times, update_offsets, N, lin, q_k_lin
+ *             the arguments of the cpi_preintegrate_stream[s]_running / cpi_stream_running_stj_batch call that wrote rows (R == 1
+ *             with both offsets NULL: one stream)
+ *   rows      the U * N rows that call wrote; what they must hold per request is what the three query entries say
+ *   workspace cpi_streams_workspace_bytes(R, U) bytes, 16-byte aligned.  The call runs the cut kernel into it ITSELF (deterministic,
+ *             U lanes): it depends on nothing an earlier call left there.  Afterwards cpi_stream_counts holds the true counts
+ *   Q, qrun [Q] (int32; may be NULL when R == 1: run 0), qtime [Q]   query k asks for run qrun[k] at the absolute time qtime[k]
+ *   qwin_out  [Q] int32, may be NULL: the GLOBAL window index of every query, -1 for a run without update times
+ *   out       arrays of Q rows; any pointer may be NULL = "not wanted"
+ * Window lookup, query k: r = qrun[k] CLAMPED into [0, R); [u0, u1) = the run's windows from the clamped update_offsets.  u1 <= u0:
+ * NaN in every requested field and qwin_out[k] = -1.  Otherwise u = u0 + #{v in [u0, u1) : update_times[v] < t_q}, clamped to
+ * u1 - 1: window u covers (update[u - 1], update[u]], so u is the first window of the run whose update time is not before t_q; of equal
+ * update times the first wins; a time past the last update gets the last window; a NaN t_q gives u0.  No read leaves
+ * update_times[0, U), whatever qrun or the offsets hold.
+ * Inside the window the semantics are exactly those of the three query entries on the window as the kernels see it: t_0 = the
+ * patched front stamp, t_1 .. t_{n-1} the stream's own stamps, t_n = the update time when the window has a tail, else the stream's
+ * stamp; n = the cut count clamped into [0, N].  i, the base row u N + i - 1, the held-reading step over [t_i, t_q], the bit-for-bit
+ * copy when there is no step, NaN for a NaN t_q, no extrapolation, model 2's clone rows and transition columns rebuilt from the row:
+ * all unchanged.
+ * DEFINING PROPERTY: with knots / first / count = what the host assemblers cut from the stream(s) (count clamped to N), out is bit for
+ * bit what cpi_query_stj_batch(..., rows, Q, qwin_out, qtime, out) writes, for every field, model and request.
+ * Requests and refusals: the union of the three query entries (means for models 1 and 2, model-1 Jacobians, P / P_sym, model 2's
+ * seven Jacobians with state_transition_jacobians != 0).  CPI_ERR_INVALID as the stream entries: CPI_MODEL_FORSTER, N > 65535,
+ * Q > 2^31 - 1, K == 0 or R == 0 with U > 0, U == 0 with Q > 0, a NULL argument.  Q == 0 is a no-op.
+ * The kernels (cut, then one per group of fields) run one after the other on the context's stream, with no side stream and no host
+ * synchronisation: a capture is a chain without parallel branches.
+ * Composition: cpi_predict_batch and the factor sweeps with idx_i = qwin_out, as with cpi_query_*_batch.
+ * Still not provided: rows from a carry record; model 2's analytic Jacobians (state_transition_jacobians == 0); extrapolation past
+ * t_n; the device-set (cpi_group_*) path. */
+int cpi_query_stream_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t R, int64_t K, const double *stream,
+                           const int64_t *stream_offsets, int64_t U, const double *update_times,
+                           const int64_t *update_offsets, int32_t N, const double *lin, const double *q_k_lin,
+                           void *workspace, const cpi_outputs *rows, int64_t Q, const int32_t *qrun, const double *qtime,
+                           int32_t *qwin_out, const cpi_outputs *out);
 
 /* The same loop for the mean outputs (DT, alpha, beta, q) on the TILED layout: the knots of 64 consecutive windows
  * interleaved per step,
@@ -759,6 +822,20 @@ int cpi_preintegrate_streams_running_host(cpi_ctx *ctx, const cpi_params *prm, i
                                           const int64_t *stream_offsets, int64_t U, const double *update_times,
                                           const int64_t *update_offsets, int32_t N, const double *lin, const double *q_k_lin,
                                           const cpi_outputs *rows, int32_t *count);
+/* cpi_stream_running_stj_batch with HOST pointers: the staging and chunking of cpi_preintegrate_stream[s]_running_host (its
+ * messages carry this entry's name).  Bit for bit the device form. */
+int cpi_stream_running_stj_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t R, int64_t K, const double *stream,
+                                      const int64_t *stream_offsets, int64_t U, const double *update_times,
+                                      const int64_t *update_offsets, int32_t N, const double *lin, const double *q_k_lin,
+                                      const cpi_outputs *rows, int32_t *count);
+/* cpi_query_stream_batch from host memory: stream, offsets, update times, lin, q_k_lin, qrun and qtime are host pointers, and there
+ * is no rows and no workspace argument -- the stream(s) are staged whole, cpi_stream_running_stj_batch computes the rows into device
+ * staging (the covariance rows as P_sym), Q rows and qwin_out (may be NULL) come down.  Validates what the device form cannot,
+ * before anything is enqueued: the offsets, and every qrun[k] in [0, R).  Bit for bit the device form on rows that hold P_sym. */
+int cpi_query_stream_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t R, int64_t K, const double *stream,
+                                const int64_t *stream_offsets, int64_t U, const double *update_times,
+                                const int64_t *update_offsets, int32_t N, const double *lin, const double *q_k_lin,
+                                int64_t Q, const int32_t *qrun, const double *qtime, int32_t *qwin_out, const cpi_outputs *out);
 void *cpi_host_alloc(size_t bytes);
 void cpi_host_free(void *p);
 int cpi_factor_eval_batch_host(cpi_ctx *ctx, int32_t model, const double grav[3], int64_t F,
