@@ -563,17 +563,22 @@ extern "C" int cpi_running_stj_batch(cpi_ctx *ctx, const cpi_params *prm, int64_
 // the model-1 Jacobian block of carry_out, whatever rows asks for --, cpi_cov_running_carry_kernel adds the P / P_sym rows and
 // the covariance block.  Both read carry_in and write disjoint parts of carry_out, one after the other on the context's
 // stream: no side stream (a capture of the call is a chain), and still no in-place records.
-extern "C" int cpi_preintegrate_running_resume(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
-                                               const double *knots, const int64_t *first, const int32_t *count,
-                                               const double *lin, const double *q_k_lin, const double *carry_in, double *carry_out,
-                                               const cpi_outputs *rows) {
-    static const char who[] = "cpi_preintegrate_running_resume";
+// cpi_preintegrate_running_resume and cpi_running_resume_stj_batch (with_stj) are one body, as running_device is.  The latter serves
+// the Jacobian fields of model 2 with state_transition_jacobians != 0: cpi_cov_running_stj_carry_kernel takes the place of
+// cpi_cov_running_carry_kernel (it runs even when P / P_sym are not asked for, and the call then needs and leaves the covariance
+// state), and the mean kernel is launched exactly as for the same request without the Jacobian fields.
+static int running_resume_device(cpi_ctx *ctx, const char *who, bool with_stj, const cpi_params *prm, int64_t W, int32_t N,
+                                 const double *knots, const int64_t *first, const int32_t *count,
+                                 const double *lin, const double *q_k_lin, const double *carry_in, double *carry_out,
+                                 const cpi_outputs *rows) {
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
     if (!prm || !rows) return refuse(ctx, who, "prm/rows is NULL");
     if (prm->model == CPI_MODEL_FORSTER) return refuse_forster(ctx, who, NO_RUNNING_FORM | NOT_RESUMABLE);
     if (!model_is_cpi(prm)) return refuse(ctx, who, "model must be 1 or 2");
     const Request rq = request_of(rows);
-    if (prm->model == CPI_MODEL_V2 && rq.jac) return refuse_v2_jac(ctx, who, ": finish the chain with cpi_preintegrate_resume");
+    const bool stj = prm->model == CPI_MODEL_V2 && rq.jac;   // (past the refusal below: the rows of the transition columns)
+    if (stj) CPI_TRY(refuse_v2_jac_here(ctx, who, with_stj, prm, ": finish the chain with cpi_preintegrate_resume"));
+    const bool mean_jac = rq.jac && !stj;
     if (!carry_out) return refuse(ctx, who, "carry_out is NULL");
     if (W < 0 || N < 0) return refuse(ctx, who, "negative size");
     CPI_TRY(check_carry_overlap(ctx, who, prm, W, carry_in, carry_out));
@@ -583,7 +588,7 @@ extern "C" int cpi_preintegrate_running_resume(cpi_ctx *ctx, const cpi_params *p
     CarryArgs c;
     c.in = carry_in;
     c.out = carry_out;
-    c.need = carry_header(prm) | (rq.cov ? carry::TAG_P : 0) | (rq.jac ? carry::TAG_J : 0);
+    c.need = carry_header(prm) | ((rq.cov || stj) ? carry::TAG_P : 0) | (mean_jac ? carry::TAG_J : 0);
     c.tag_out = c.need;
     c.own_means = 0;
 
@@ -593,14 +598,27 @@ extern "C" int cpi_preintegrate_running_resume(cpi_ctx *ctx, const cpi_params *p
     {
         PreArgs m = a;
         m.write_means = rq.mean ? 1 : 0;
-        m.write_jac = rq.jac ? 1 : 0;
+        m.write_jac = mean_jac ? 1 : 0;
         CarryArgs cm = c;
         cm.own_means = 1;
-        launch::mean_running_carry(prm->model, rq.jac, avg, pick_lanes(prm, W, N, rq.jac), m, cm, ctx->stream);
+        launch::mean_running_carry(prm->model, mean_jac, avg, pick_lanes(prm, W, N, mean_jac), m, cm, ctx->stream);
     }
-    if (rq.cov) launch::cov_running_carry(prm->model, avg, a, c, ctx->stream);
+    if (stj) launch::cov_running_carry_stj(avg, a, c, ctx->stream);
+    else if (rq.cov) launch::cov_running_carry(prm->model, avg, a, c, ctx->stream);
     CPI_HIP(ctx, hipGetLastError());
     return CPI_OK;
+}
+extern "C" int cpi_preintegrate_running_resume(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                               const double *knots, const int64_t *first, const int32_t *count,
+                                               const double *lin, const double *q_k_lin, const double *carry_in, double *carry_out,
+                                               const cpi_outputs *rows) {
+    return running_resume_device(ctx, "cpi_preintegrate_running_resume", false, prm, W, N, knots, first, count, lin, q_k_lin, carry_in, carry_out, rows);
+}
+extern "C" int cpi_running_resume_stj_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                            const double *knots, const int64_t *first, const int32_t *count,
+                                            const double *lin, const double *q_k_lin, const double *carry_in, double *carry_out,
+                                            const cpi_outputs *rows) {
+    return running_resume_device(ctx, "cpi_running_resume_stj_batch", true, prm, W, N, knots, first, count, lin, q_k_lin, carry_in, carry_out, rows);
 }
 
 // The measurement at arbitrary times inside a window (include/cpi_amd.h): one kernel, one lane per query, over the rows
@@ -638,7 +656,10 @@ static int query_check_args(cpi_ctx *ctx, const char *who, int with, const cpi_p
     return CPI_OK;
 }
 // what rows must hold (N > 0) for the request of out: shared by the query entries
-static int query_rows_check(cpi_ctx *ctx, const char *who, const cpi_params *prm, const cpi_outputs *rows, const cpi_outputs *out) {
+// (what: "rows", or "base" for the base row of cpi_query_open_batch, which must hold the same)
+static int query_rows_check(cpi_ctx *ctx, const char *who, const cpi_params *prm, const cpi_outputs *rows, const cpi_outputs *out,
+                            const char *what = "rows") {
+    const std::string R = what;
     const Request rq = request_of(out);
     const bool stj = prm->model == CPI_MODEL_V2 && rq.jac;
     const bool means = rq.mean || (rq.jac && !stj);
@@ -647,25 +668,27 @@ static int query_rows_check(cpi_ctx *ctx, const char *who, const cpi_params *prm
         const struct { const char *name; const double *p; } need[] = { {"q", rows->q}, {"J_q", rows->J_q}, {"J_a", rows->J_a}, {"J_b", rows->J_b},
                                                                        {"H_a", rows->H_a}, {"H_b", rows->H_b}, {"O_a", rows->O_a}, {"O_b", rows->O_b} };
         for (const auto &f : need) if (!f.p) lacks += std::string(lacks.empty() ? "" : ", ") + f.name;
-        if (!lacks.empty()) return refuse(ctx, who, "rows needs q and all seven Jacobian fields for the model-2 Jacobians; missing: ", lacks.c_str());
+        if (!lacks.empty()) return refuse(ctx, who, (R + " needs q and all seven Jacobian fields for the model-2 Jacobians; missing: ").c_str(), lacks.c_str());
     }
     if (means || !(rq.cov || stj)) {
-        if (!rows->DT || !rows->alpha || !rows->beta || !rows->q) return refuse(ctx, who, "rows needs DT, alpha, beta and q");
+        if (!rows->DT || !rows->alpha || !rows->beta || !rows->q) return refuse(ctx, who, (R + " needs DT, alpha, beta and q").c_str());
         if (!stj && ((out->J_q && !rows->J_q) || (out->J_a && !rows->J_a) || (out->J_b && !rows->J_b) || (out->H_a && !rows->H_a) || (out->H_b && !rows->H_b)))
-            return refuse(ctx, who, "a Jacobian field of out needs the same field of rows");
+            return refuse(ctx, who, ("a Jacobian field of out needs the same field of " + R).c_str());
     }
     if (rq.cov) {
-        if (!rows->q) return refuse(ctx, who, "rows needs q (the rotation at the start of the partial interval)");
-        if (!rows->P && !rows->P_sym) return refuse(ctx, who, "rows needs P or P_sym when out asks for P / P_sym");
+        if (!rows->q) return refuse(ctx, who, (R + " needs q (the rotation at the start of the partial interval)").c_str());
+        if (!rows->P && !rows->P_sym) return refuse(ctx, who, (R + " needs P or P_sym when out asks for P / P_sym").c_str());
     }
     return CPI_OK;
 }
 static int query_device(cpi_ctx *ctx, const char *who, int with, const cpi_params *prm, int64_t W, int32_t N,
                         const double *knots, const int64_t *first, const int32_t *count,
                         const double *lin, const double *q_k_lin, const cpi_outputs *rows,
-                        int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out) {
+                        int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out,
+                        const cpi_outputs *base = nullptr, int32_t base_N = 0) {
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
     if (!prm || !rows || !out) return refuse(ctx, who, "prm/rows/out is NULL");
+    if (base && base_N < 1) return refuse(ctx, who, "base_N must be >= 1 when base is given");
     const Request rq = request_of(out);
     bool done;
     CPI_TRY(query_check_args(ctx, who, with, prm, W, N, knots, lin, q_k_lin, Q, qwin, qtime, out, &done));
@@ -674,6 +697,7 @@ static int query_device(cpi_ctx *ctx, const char *who, int with, const cpi_param
     const bool mean_jac = rq.jac && !stj;
     const bool means = rq.mean || mean_jac;
     if (N > 0) CPI_TRY(query_rows_check(ctx, who, prm, rows, out));   // N == 0: every query is the zero state and rows is not read
+    if (base) CPI_TRY(query_rows_check(ctx, who, prm, base, out, "base"));
     if (!rq.any()) return CPI_OK;
 
     DeviceGuard guard_;
@@ -683,18 +707,28 @@ static int query_device(cpi_ctx *ctx, const char *who, int with, const cpi_param
     a.W = W; a.N = N; a.knots = knots; a.first = (const long long *)first; a.count = count; a.lin = lin; a.qk = q_k_lin;
     for (int i = 0; i < 3; i++) a.grav[i] = prm->grav[i];
     a.rows = *rows; a.Q = Q; a.qwin = qwin; a.qtime = qtime; a.trips = query_trips(N); a.out = *out;
-    if (mean_jac) {
-        // the Jacobian instance carries all five matrices: the ones out does not ask for are read from a field that is there
-        const double *any = rows->J_q ? rows->J_q : rows->J_a ? rows->J_a : rows->J_b ? rows->J_b : rows->H_a ? rows->H_a : rows->H_b;
-        double **f[5] = { &a.rows.J_q, &a.rows.J_a, &a.rows.J_b, &a.rows.H_a, &a.rows.H_b };
+    // the Jacobian instance carries all five matrices: the ones out does not ask for are read from a field that is there
+    auto fill_jac = [](cpi_outputs &r) {
+        const double *any = r.J_q ? r.J_q : r.J_a ? r.J_a : r.J_b ? r.J_b : r.H_a ? r.H_a : r.H_b;
+        double **f[5] = { &r.J_q, &r.J_a, &r.J_b, &r.H_a, &r.H_b };
         for (double **x : f) if (!*x) *x = const_cast<double *>(any);
+    };
+    if (mean_jac) fill_jac(a.rows);
+    const double q4[4] = { prm->sigma_w * prm->sigma_w, prm->sigma_wb * prm->sigma_wb, prm->sigma_a * prm->sigma_a, prm->sigma_ab * prm->sigma_ab };
+    if (base) {   // cpi_query_open_batch: the same three kernels with the base row where the zero state stood, on the same stream
+        QueryBase b;
+        b.rows = *base;
+        b.N = base_N;
+        if (mean_jac) fill_jac(b.rows);
+        if (means) launch::query_open(prm->model, mean_jac, prm->imu_avg != 0, a, b, ctx->stream);
+        if (stj) launch::query_stj_open(prm->imu_avg != 0, a, b, ctx->stream);
+        if (rq.cov) launch::query_cov_open(prm->model, prm->imu_avg != 0, a, q4, b, ctx->stream);
+        CPI_HIP(ctx, hipGetLastError());
+        return CPI_OK;
     }
     if (means) launch::query(prm->model, mean_jac, prm->imu_avg != 0, a, ctx->stream);
     if (stj) launch::query_stj(prm->imu_avg != 0, a, ctx->stream);
-    if (rq.cov) {
-        const double q4[4] = { prm->sigma_w * prm->sigma_w, prm->sigma_wb * prm->sigma_wb, prm->sigma_a * prm->sigma_a, prm->sigma_ab * prm->sigma_ab };
-        launch::query_cov(prm->model, prm->imu_avg != 0, a, q4, ctx->stream);
-    }
+    if (rq.cov) launch::query_cov(prm->model, prm->imu_avg != 0, a, q4, ctx->stream);
     CPI_HIP(ctx, hipGetLastError());
     return CPI_OK;
 }
@@ -716,6 +750,16 @@ extern "C" int cpi_query_stj_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t 
                                    const double *lin, const double *q_k_lin, const cpi_outputs *rows,
                                    int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out) {
     return query_device(ctx, "cpi_query_stj_batch", QUERY_COV | QUERY_STJ, prm, W, N, knots, first, count, lin, q_k_lin, rows, Q, qwin, qtime, out);
+}
+// cpi_query_stj_batch for windows that continue from a carried state: base (row w * base_N + base_N - 1) stands where the zero state
+// stood.  base == NULL: cpi_query_stj_batch itself.
+extern "C" int cpi_query_open_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                    const double *knots, const int64_t *first, const int32_t *count,
+                                    const double *lin, const double *q_k_lin, const cpi_outputs *rows,
+                                    int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out,
+                                    const cpi_outputs *base, int32_t base_N) {
+    return query_device(ctx, "cpi_query_open_batch", QUERY_COV | QUERY_STJ, prm, W, N, knots, first, count, lin, q_k_lin, rows, Q, qwin, qtime, out,
+                        base, base_N);
 }
 
 // Replaces the caller-side loop of GraphSolver::createimufactor_cpi_v1 / _v2 (GraphSolver_IMU.cpp:43-75, 97-130) for ALL the
@@ -1668,9 +1712,10 @@ public:
     }
 
 private:
-    // the most any entry stages is cpi_query_stream_batch_host's: 6 stream inputs and the workspace, qrun, qtime and qwin_out,
-    // a mirror of the running rows and a mirror of the outputs, each of at most kOutFields arrays
-    static constexpr int kMax = 10 + 2 * kOutFields;
+    // the most any entry stages is cpi_query_open_batch_host's: the 5 window arrays, qwin and qtime, carry_in, carry_out and the
+    // record the base-row call leaves, its all-zero counts, and mirrors of the running rows, of the base rows and of the outputs,
+    // each of at most kOutFields arrays (cpi_query_stream_batch_host: 10 arrays and two mirrors)
+    static constexpr int kMax = 11 + 3 * kOutFields;
     cpi_ctx *ctx;
     void *buf[kMax];
     int n = 0;
@@ -1963,16 +2008,19 @@ extern "C" int cpi_preintegrate_resume_host(cpi_ctx *ctx, const cpi_params *prm,
 
 // cpi_preintegrate_running_resume from host memory: dense batches through the chunked pipeline (the records of a chunk travel with
 // it), ragged ones -- and N = 0, which has no rows to chunk by -- staged whole as in cpi_preintegrate_resume_host.
-extern "C" int cpi_preintegrate_running_resume_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
-                                                    const double *knots, const int64_t *first, const int32_t *count,
-                                                    int64_t n_knots, const double *lin, const double *q_k_lin,
-                                                    const double *carry_in, double *carry_out, const cpi_outputs *rows) {
-    static const char who[] = "cpi_preintegrate_running_resume_host";
+// cpi_running_resume_stj_batch_host (with_stj) is the same body over its own device entry.
+typedef int (*RunningResumeEntry)(cpi_ctx *, const cpi_params *, int64_t, int32_t, const double *, const int64_t *, const int32_t *, const double *,
+                                  const double *, const double *, double *, const cpi_outputs *);
+static int running_resume_host(cpi_ctx *ctx, const char *who, bool with_stj, const cpi_params *prm, int64_t W, int32_t N,
+                               const double *knots, const int64_t *first, const int32_t *count,
+                               int64_t n_knots, const double *lin, const double *q_k_lin,
+                               const double *carry_in, double *carry_out, const cpi_outputs *rows) {
+    const RunningResumeEntry entry = with_stj ? cpi_running_resume_stj_batch : cpi_preintegrate_running_resume;
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
     if (!prm || !rows || !knots || !lin || !carry_out) return refuse(ctx, who, "NULL argument");
     if (W < 0 || N < 0) return fail(ctx, CPI_ERR_INVALID, "negative size");
     if (!model_is_cpi(prm)) return refuse_forster(ctx, who, NO_RUNNING_FORM | NOT_RESUMABLE);
-    if (prm->model == CPI_MODEL_V2 && request_of(rows).jac) return refuse_v2_jac(ctx, who, nullptr);
+    if (prm->model == CPI_MODEL_V2 && request_of(rows).jac) CPI_TRY(refuse_v2_jac_here(ctx, who, with_stj, prm, nullptr));
     CPI_TRY(check_carry_overlap(ctx, who, prm, W, carry_in, carry_out));
     if (W == 0) return CPI_OK;
     CPI_TRY(check_N(ctx, who, N));
@@ -1984,20 +2032,62 @@ extern "C" int cpi_preintegrate_running_resume_host(cpi_ctx *ctx, const cpi_para
         arr.a[4] = {"carry_in", carry_in, nullptr, cd_bytes, 1};
         arr.a[5] = {"carry_out", nullptr, carry_out, cd_bytes, 1};
         return preintegrate_host_pipeline(ctx, who, W, (size_t)N, arr, rows, [&](int64_t wn, void *const *dev, const cpi_outputs *d) {
-            return cpi_preintegrate_running_resume(ctx, prm, wn, N, (const double *)dev[0], nullptr, (const int32_t *)dev[1], (const double *)dev[2],
-                                                   (const double *)dev[3], (const double *)dev[4], (double *)dev[5], d);
+            return entry(ctx, prm, wn, N, (const double *)dev[0], nullptr, (const int32_t *)dev[1], (const double *)dev[2],
+                         (const double *)dev[3], (const double *)dev[4], (double *)dev[5], d);
         });
     }
     if (!first) n_knots = W * (int64_t)(N + 1);
     if (n_knots <= 0) return refuse(ctx, who, "n_knots must be > 0");
-    return resume_staged(ctx, cpi_preintegrate_running_resume, prm, W, N, (size_t)N, knots, first, count, n_knots, lin, q_k_lin, carry_in,
-                         carry_out, rows);
+    return resume_staged(ctx, entry, prm, W, N, (size_t)N, knots, first, count, n_knots, lin, q_k_lin, carry_in, carry_out, rows);
+}
+extern "C" int cpi_preintegrate_running_resume_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                                    const double *knots, const int64_t *first, const int32_t *count,
+                                                    int64_t n_knots, const double *lin, const double *q_k_lin,
+                                                    const double *carry_in, double *carry_out, const cpi_outputs *rows) {
+    return running_resume_host(ctx, "cpi_preintegrate_running_resume_host", false, prm, W, N, knots, first, count, n_knots, lin, q_k_lin,
+                               carry_in, carry_out, rows);
+}
+extern "C" int cpi_running_resume_stj_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                                 const double *knots, const int64_t *first, const int32_t *count,
+                                                 int64_t n_knots, const double *lin, const double *q_k_lin,
+                                                 const double *carry_in, double *carry_out, const cpi_outputs *rows) {
+    return running_resume_host(ctx, "cpi_running_resume_stj_batch_host", true, prm, W, N, knots, first, count, n_knots, lin, q_k_lin,
+                               carry_in, carry_out, rows);
 }
 
 // cpi_query_batch / cpi_query_cov_batch from host memory.  The windows are staged whole, the running rows are computed into device
 // staging and never leave it (the covariance rows as P_sym: 960 B per row instead of 1 800): Q rows come down.  What the device form
 // cannot check is checked here, before anything is enqueued: qwin in range, and finite non-decreasing stamps (the bisection's
 // precondition) in every window that is queried.
+static int query_host_check_windows(cpi_ctx *ctx, const char *who, int64_t W, int32_t N, const double *knots, const int64_t *first,
+                                    const int32_t *count, int64_t n_knots, int64_t Q, const int32_t *qwin) {
+    std::vector<char> seen((size_t)W, 0);
+    for (int64_t k = 0; k < Q; k++) {
+        const int64_t w = qwin[k];
+        if (w < 0 || w >= W) return refuse(ctx, who, ("qwin[" + std::to_string(k) + "] = " + std::to_string(w) + " is not a window of [0, W)").c_str());
+        if (seen[w]) continue;
+        seen[w] = 1;
+        const int64_t k0 = first ? first[w] : w * (int64_t)(N + 1);
+        const int64_t n = count ? std::min<int64_t>(std::max<int64_t>(count[w], 0), N) : N;
+        if (k0 < 0 || k0 + n >= n_knots) return refuse(ctx, who, ("window " + std::to_string(w) + " does not lie inside the knots").c_str());
+        for (int64_t i = 0; i <= n; i++) {
+            const double t = knots[(k0 + i) * 7];
+            if (!std::isfinite(t) || (i > 0 && t < knots[(k0 + i - 1) * 7]))
+                return refuse(ctx, who, ("window " + std::to_string(w) + " has a NaN, infinite or decreasing stamp at knot " + std::to_string(i) +
+                                         " (a queried window needs finite non-decreasing stamps)").c_str());
+        }
+    }
+    return CPI_OK;
+}
+// the rows a query entry's host form computes for the request of out (mirror() allocates the fields that are set)
+static cpi_outputs query_host_rows_mask(const cpi_outputs *out, bool stj, bool cov, double *dummy) {
+    cpi_outputs rmask = {};
+    rmask.DT = rmask.alpha = rmask.beta = rmask.q = dummy;
+    rmask.J_q = out->J_q; rmask.J_a = out->J_a; rmask.J_b = out->J_b; rmask.H_a = out->H_a; rmask.H_b = out->H_b;
+    if (stj) rmask.J_q = rmask.J_a = rmask.J_b = rmask.H_a = rmask.H_b = rmask.O_a = rmask.O_b = dummy;
+    if (cov) rmask.P_sym = dummy;
+    return rmask;
+}
 static int query_host(cpi_ctx *ctx, const char *who, int with, const cpi_params *prm, int64_t W, int32_t N,
                       const double *knots, const int64_t *first, const int32_t *count, int64_t n_knots,
                       const double *lin, const double *q_k_lin,
@@ -2011,24 +2101,7 @@ static int query_host(cpi_ctx *ctx, const char *who, int with, const cpi_params 
     const bool stj = prm->model == CPI_MODEL_V2 && rq.jac;   // (cpi_query_stj_batch_host only: all seven Jacobian rows are computed)
     if (!first) n_knots = W * (int64_t)(N + 1);
     if (n_knots <= 0) return refuse(ctx, who, "n_knots must be > 0");
-    {
-        std::vector<char> seen((size_t)W, 0);
-        for (int64_t k = 0; k < Q; k++) {
-            const int64_t w = qwin[k];
-            if (w < 0 || w >= W) return refuse(ctx, who, ("qwin[" + std::to_string(k) + "] = " + std::to_string(w) + " is not a window of [0, W)").c_str());
-            if (seen[w]) continue;
-            seen[w] = 1;
-            const int64_t k0 = first ? first[w] : w * (int64_t)(N + 1);
-            const int64_t n = count ? std::min<int64_t>(std::max<int64_t>(count[w], 0), N) : N;
-            if (k0 < 0 || k0 + n >= n_knots) return refuse(ctx, who, ("window " + std::to_string(w) + " does not lie inside the knots").c_str());
-            for (int64_t i = 0; i <= n; i++) {
-                const double t = knots[(k0 + i) * 7];
-                if (!std::isfinite(t) || (i > 0 && t < knots[(k0 + i - 1) * 7]))
-                    return refuse(ctx, who, ("window " + std::to_string(w) + " has a NaN, infinite or decreasing stamp at knot " + std::to_string(i) +
-                                             " (a queried window needs finite non-decreasing stamps)").c_str());
-            }
-        }
-    }
+    CPI_TRY(query_host_check_windows(ctx, who, W, N, knots, first, count, n_knots, Q, qwin));
     if (!rq.any()) return CPI_OK;
 
     DeviceGuard guard_;
@@ -2037,12 +2110,9 @@ static int query_host(cpi_ctx *ctx, const char *who, int with, const cpi_params 
     WindowsDev in;
     const int32_t *dqwin;
     const double *dqtime;
-    cpi_outputs rmask = {}, drows, d;
+    cpi_outputs drows, d;
     double dummy;
-    rmask.DT = rmask.alpha = rmask.beta = rmask.q = &dummy;   // mirror() allocates the fields that are set
-    rmask.J_q = out->J_q; rmask.J_a = out->J_a; rmask.J_b = out->J_b; rmask.H_a = out->H_a; rmask.H_b = out->H_b;
-    if (stj) rmask.J_q = rmask.J_a = rmask.J_b = rmask.H_a = rmask.H_b = rmask.O_a = rmask.O_b = &dummy;
-    if (rq.cov) rmask.P_sym = &dummy;
+    const cpi_outputs rmask = query_host_rows_mask(out, stj, rq.cov, &dummy);
     CPI_TRY(stage_windows(st, W, n_knots, knots, first, count, lin, q_k_lin, &in));
     CPI_TRY(st.upload(qwin, (size_t)Q, &dqwin));
     CPI_TRY(st.upload(qtime, (size_t)Q, &dqtime));
@@ -2070,6 +2140,67 @@ extern "C" int cpi_query_stj_batch_host(cpi_ctx *ctx, const cpi_params *prm, int
                                         const double *lin, const double *q_k_lin,
                                         int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out) {
     return query_host(ctx, "cpi_query_stj_batch_host", QUERY_COV | QUERY_STJ, prm, W, N, knots, first, count, n_knots, lin, q_k_lin, Q, qwin, qtime, out);
+}
+
+// cpi_query_open_batch from host memory: the chunk's windows are staged whole; the base rows (cpi_running_resume_stj_batch with N = 1
+// and every count 0: the carried state read out), the chunk's running rows and carry_out are computed in device staging, Q rows and
+// the records come down.  The checks on qwin and the stamps are cpi_query_batch_host's.
+extern "C" int cpi_query_open_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                         const double *knots, const int64_t *first, const int32_t *count, int64_t n_knots,
+                                         const double *lin, const double *q_k_lin, const double *carry_in, double *carry_out,
+                                         int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out) {
+    static const char who[] = "cpi_query_open_batch_host";
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (!prm || !out) return refuse(ctx, who, "prm/out is NULL");
+    if (!carry_out) return refuse(ctx, who, "carry_out is NULL");
+    const Request rq = request_of(out);
+    CPI_TRY(query_check(ctx, who, prm, rq, QUERY_COV | QUERY_STJ));
+    if (W < 0 || N < 0 || Q < 0) return refuse(ctx, who, "negative size");
+    CPI_TRY(check_carry_overlap(ctx, who, prm, W, carry_in, carry_out));
+    if (W == 0) return Q == 0 ? CPI_OK : refuse(ctx, who, "W is 0: there is no window to query");
+    if (Q > 0 && (!qwin || !qtime)) return refuse(ctx, who, "qwin/qtime is NULL");
+    CPI_TRY(check_windows(ctx, who, prm, W, N, knots, lin, q_k_lin));
+    if (Q > 0 && !grid_ok(Q)) return refuse(ctx, who, "Q exceeds 2^31 - 1 queries per call (32-bit grid)");
+    const bool stj = prm->model == CPI_MODEL_V2 && rq.jac;
+    if (!first) n_knots = W * (int64_t)(N + 1);
+    if (n_knots <= 0) return refuse(ctx, who, "n_knots must be > 0");
+    CPI_TRY(query_host_check_windows(ctx, who, W, N, knots, first, count, n_knots, Q, qwin));
+
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    const size_t cd = (size_t)W * (size_t)carry::doubles(prm->model);
+    // the base-row call is N = 1 with every count 0: it touches knot first[w] alone, so a dense chunk gets its own first (a dense
+    // N = 1 call would look for window w at knot 2 w)
+    std::vector<int64_t> first0;
+    if (!first) { first0.resize((size_t)W); for (int64_t w = 0; w < W; w++) first0[w] = w * (int64_t)(N + 1); }
+    Staging st(ctx);
+    WindowsDev in;
+    const int64_t *dfirst0 = nullptr;
+    const int32_t *dqwin;
+    const double *dqtime, *dci;
+    double *dco, *dcb;
+    int32_t *zero;
+    cpi_outputs dbase, drows, d;
+    double dummy;
+    const cpi_outputs rmask = query_host_rows_mask(out, stj, rq.cov, &dummy);
+    CPI_TRY(stage_windows(st, W, n_knots, knots, first, count, lin, q_k_lin, &in));
+    CPI_TRY(st.upload(qwin, (size_t)Q, &dqwin));
+    CPI_TRY(st.upload(qtime, (size_t)Q, &dqtime));
+    CPI_TRY(st.upload(carry_in, cd, &dci));
+    CPI_TRY(st.alloc(cd, &dco));
+    CPI_TRY(st.alloc(cd, &dcb));
+    CPI_TRY(st.alloc((size_t)W, &zero));
+    if (!first) CPI_TRY(st.upload(first0.data(), (size_t)W, &dfirst0));
+    CPI_HIP(ctx, hipMemsetAsync(zero, 0, (size_t)W * sizeof(int32_t), ctx->stream));
+    CPI_TRY(st.mirror(&rmask, (size_t)W, &dbase));
+    CPI_TRY(st.mirror(&rmask, (size_t)W * (size_t)N, &drows));
+    CPI_TRY(st.mirror(out, (size_t)Q, &d));
+    CPI_TRY(cpi_running_resume_stj_batch(ctx, prm, W, 1, in.knots, first ? in.first : dfirst0, zero, in.lin, in.qk, dci, dcb, &dbase));
+    CPI_TRY(cpi_running_resume_stj_batch(ctx, prm, W, N, in.knots, in.first, in.count, in.lin, in.qk, dci, dco, &drows));
+    if (Q > 0) CPI_TRY(cpi_query_open_batch(ctx, prm, W, N, in.knots, in.first, in.count, in.lin, in.qk, &drows, Q, dqwin, dqtime, &d, &dbase, 1));
+    CPI_TRY(st.download(out, d, (size_t)Q));
+    CPI_TRY(st.download(carry_out, (const double *)dco, cd));
+    return st.finish();
 }
 
 // The offsets of a multi-run call as the _host entries can (and do) validate them before anything is enqueued: each array

@@ -1,12 +1,14 @@
 // cpi_args.hpp -- kernel argument blocks and the launcher interface between the translation units of libcpi_amd.so.
 //
-// The library is ten translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
+// The library is twelve translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
 //   cpi_mean.hip    cpi_mean_kernel / cpi_mean_tiled_kernel / cpi_tile_*_kernel       (cpi_mean_kernels.hpp)
 //   cpi_running.hip cpi_mean_running_kernel / cpi_mean_stream_running_kernel: a row after every interval, from plain knots /
 //                   from windows cut out of IMU stream(s) in place         (cpi_running_kernels.hpp, cpi_running_body.inc)
 //   cpi_cov.hip     cpi_cov_kernel<1|2> / cpi_forster_kernel / cpi_cov_running_kernel  (cpi_cov_kernels.hpp)
 //   cpi_running_resume.hip  cpi_mean_running_carry_kernel / cpi_cov_running_carry_kernel: the running rows from and to carry
 //                   records, over the bodies of the two units above (cpi_running_body.inc, cov_body)
+//   cpi_running_resume_stj.hip  cpi_cov_running_stj_carry_kernel: cov_body with the read-out of model 2's Discrete_J_b columns after
+//                   every interval for windows that continue from carry records (cpi_running_resume_stj_batch)
 //   cpi_query.hip   cpi_query_kernel: the measurement at arbitrary times inside a window, one partial interval from a running row
 //                                                                                      (cpi_query_kernels.hpp)
 //   cpi_query_cov.hip  cpi_query_cov_kernel: the covariance at arbitrary times, one partial interval of the covariance recursion
@@ -16,6 +18,9 @@
 //   cpi_query_stream.hip  cpi_squery_mean_kernel / cpi_squery_cov_kernel / cpi_squery_jac2_kernel: the three query kernels by
 //                   ABSOLUTE time over IMU stream(s) read in place -- window lookup over the update times, search over the
 //                   patched stamps of the cut, then the same arithmetic                 (cpi_query_stream_kernels.hpp)
+//   cpi_query_open.hip  cpi_query_open_kernel / cpi_query_cov_open_kernel / cpi_query_stj_open_kernel: the three query kernels for
+//                   windows that continue from a carried state -- the same bodies, their i == 0 gather reading a base row
+//                                                    (cpi_query_open_kernels.hpp over the three query bodies)
 //   cpi_factor.hip  evaluateError sweeps, square-root information, Hessian blocks, state prediction
 //                                                                                      (cpi_factor_kernels.hpp)
 //   cpi_abi.hip     the C-ABI of include/cpi_amd.h: argument checks, launch heuristics, device sets (RCCL), the
@@ -121,6 +126,14 @@ struct QueryArgs {
     cpi_outputs out;       // arrays of Q rows
 };
 
+// cpi_query_open_batch: the state window w had BEFORE knot 0 of the queried segment = row w * N + N - 1 of every array of rows
+// (ordinary rows, e.g. the previous chunk's).  It stands where the zero state stands in the closed entries.  A kernel argument of
+// its own, so that QueryArgs -- and with it the code of every existing kernel -- stays as it was.
+struct QueryBase {
+    cpi_outputs rows;
+    int N;                 // >= 1
+};
+
 // cpi_query_stream_batch: query k asks for the measurement of run qrun[k] at the ABSOLUTE time qtime[k]; the kernels find the
 // window among the run's update times and the interval among the patched stamps of the cut (first / count / tstart / tend: the
 // workspace of the stream entries, filled by the cut kernel in front of them); rows = the U * N rows of the running stream entries.
@@ -221,6 +234,8 @@ void forster(const PreArgs &a, hipStream_t st);
 // ---- cpi_running_resume.hip (cpi_preintegrate_running_resume: the running rows from c.in to c.out)
 void mean_running_carry(int model, bool jac, bool avg, int L, const PreArgs &a, const CarryArgs &c, hipStream_t st);   // always owns tag + means of c.out
 void cov_running_carry(int model, bool avg, const PreArgs &a, const CarryArgs &c, hipStream_t st);   // P / P_sym rows + the covariance block of c.out
+// ---- cpi_running_resume_stj.hip (cpi_running_resume_stj_batch, model 2: cov_running_carry + the rows of J_q ... O_b that a.out asks for)
+void cov_running_carry_stj(bool avg, const PreArgs &a, const CarryArgs &c, hipStream_t st);
 // ---- cpi_query.hip (cpi_query_batch; jac: model 1 only)
 void query(int model, bool jac, bool avg, const QueryArgs &a, hipStream_t st);
 // ---- cpi_query_cov.hip (cpi_query_cov_batch: a.out.P / P_sym from a.rows.q and a.rows.P or P_sym; q4 as PreArgs::q4)
@@ -229,6 +244,10 @@ void query_cov(int model, bool avg, const QueryArgs &a, const double q4[4], hipS
 // cpi_query_stj_batch: a.out.J_q ... O_b from a.rows.q and all seven Jacobian fields of a.rows)
 void cov_running_stj(bool avg, const PreArgs &a, hipStream_t st);
 void query_stj(bool avg, const QueryArgs &a, hipStream_t st);
+// ---- cpi_query_open.hip (cpi_query_open_batch: query / query_cov / query_stj with b standing where the zero state stood)
+void query_open(int model, bool jac, bool avg, const QueryArgs &a, const QueryBase &b, hipStream_t st);
+void query_cov_open(int model, bool avg, const QueryArgs &a, const double q4[4], const QueryBase &b, hipStream_t st);
+void query_stj_open(bool avg, const QueryArgs &a, const QueryBase &b, hipStream_t st);
 // ---- cpi_query_stream.hip (cpi_query_stream_batch: the three launchers above over StreamQueryArgs; each writes a.qwin_out when set)
 void squery_mean(int model, bool jac, bool avg, const StreamQueryArgs &a, hipStream_t st);
 void squery_cov(int model, bool avg, const StreamQueryArgs &a, const double q4[4], hipStream_t st);

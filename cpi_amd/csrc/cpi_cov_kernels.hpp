@@ -40,9 +40,12 @@ namespace {
 // lanes store at the same point.  Staging the rows in LDS for wider stores is not worth its price here for the reason measured
 // for P above: the kernel holds 2 wavefronts per SIMD with the LDS it has, and the staging area would have to come out of that.
 // Every other instantiation is compiled without the block (if constexpr) and is unchanged.
+// CARRY, RUNNING and STJ (cpi_cov_running_stj_carry_kernel, cpi_running_resume_stj_batch; model 2): the same read-out for a window
+// that continues from a record.  The nine columns start from the record like every other column, so row 0 continues the carried
+// read-out, and a window whose record does not fit gets NaN in every row of the Jacobian fields too.
 template <int MODEL, bool AVG, bool CARRY, bool RUNNING = false, bool STJ = false>
 __device__ __forceinline__ void cov_body(const PreArgs &A, const CarryArgs &CA) {
-    static_assert(!STJ || (MODEL == 2 && RUNNING && !CARRY), "the running Jacobian read-out belongs to model 2 without carry records");
+    static_assert(!STJ || (MODEL == 2 && RUNNING), "the running Jacobian read-out belongs to model 2");
     typedef CovDims<MODEL> D;
     constexpr int GROUP = D::GROUP;   // lanes per window
     constexpr int G = 64 / GROUP;     // windows per wavefront
@@ -269,9 +272,10 @@ __device__ __forceinline__ void cov_body(const PreArgs &A, const CarryArgs &CA) 
                     if (valid && jj >= D::NPCOL && jj < D::NCOL) {
                         const int d = (jj - D::NPCOL) / 3, c = (jj - D::NPCOL) % 3;
                         const long long o = r * 9 + c * 3;
-                        const V3 th = mk(Ln.P0[0], Ln.P0[1], Ln.P0[2]);
-                        const V3 vv = mk(Ln.P0[6], Ln.P0[7], Ln.P0[8]);
-                        const V3 pp = mk(Ln.P0[12], Ln.P0[13], Ln.P0[14]);
+                        V3 th = mk(Ln.P0[0], Ln.P0[1], Ln.P0[2]);
+                        V3 vv = mk(Ln.P0[6], Ln.P0[7], Ln.P0[8]);
+                        V3 pp = mk(Ln.P0[12], Ln.P0[13], Ln.P0[14]);
+                        if constexpr (CARRY) { if (cbad) { th = mk(__builtin_nan(""), __builtin_nan(""), __builtin_nan("")); vv = th; pp = th; } }
                         if (d == 0) {
                             if (A.out.J_q) stv3(A.out.J_q + o, -th);
                             if (A.out.J_a) stv3(A.out.J_a + o, pp);
@@ -390,7 +394,13 @@ __global__ __launch_bounds__(64, CPI_COV_WPS) void cpi_cov_running_stj_kernel(Pr
     cov_body<2, AVG, false, true, true>(A, CarryArgs());
 }
 
-#ifndef CPI_COV_TEMPLATES_ONLY   // (cpi_running_resume.hip and cpi_stj.hip take the templates above only)
+// cpi_running_resume_stj_batch: cpi_cov_running_stj_kernel from and to carry records (cpi_running_resume_stj.hip)
+template <bool AVG>
+__global__ __launch_bounds__(64, CPI_COV_WPS) void cpi_cov_running_stj_carry_kernel(PreArgs A, CarryArgs C) {
+    cov_body<2, AVG, true, true, true>(A, C);
+}
+
+#ifndef CPI_COV_TEMPLATES_ONLY   // (cpi_running_resume.hip, cpi_stj.hip and cpi_running_resume_stj.hip take the templates above only)
 // ============================================================================================
 // Forster / GTSAM discrete-preintegration comparator kernel (fsd:: in cpi_math.hpp)
 // ============================================================================================

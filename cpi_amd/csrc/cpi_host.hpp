@@ -245,6 +245,55 @@ public:
         return res;
     }
     std::vector<CpiResult> read_rows() { return read_rows(ctx_ ? *ctx_ : default_context()); }
+    // Incremental preintegrators only: the measurement AT each of `times` -- a camera frame stamped inside the chunk that has just
+    // been fed (cpi_query_open_batch_host).  Runs the intervals fed since the previous read; the carry and the tail knot advance
+    // exactly as in read_rows().  One CpiResult per time: the means, P_meas, and model 1's five Jacobians or model 2's seven.  A
+    // time on a fed stamp gives the members as they stood there, a time inside an interval that state advanced with the interval's
+    // opening reading held, a time before the first pending interval the state at the previous read, a time at or past the last
+    // stamp the current state.  The pending intervals must chain (a separator knot is refused by the library).
+    std::vector<CpiResult> at(const Context &ctx, const std::vector<double> &times) {
+        if (!incremental_) throw std::logic_error("at: set_incremental(true) first (the queries continue from the carried state)");
+        if (model_ == CPI_MODEL_V2 && !state_transition_jacobians)
+            throw std::logic_error("at: model 2's analytic Jacobians (state_transition_jacobians = false) have no running form");
+        std::vector<CpiResult> res;
+        if (times.empty()) return res;
+        cpi_params p = params();
+        const double lin[6] = { b_w_lin[0], b_w_lin[1], b_w_lin[2], b_a_lin[0], b_a_lin[1], b_a_lin[2] };
+        const int32_t n = knots_.empty() ? 0 : (int32_t)(knots_.size() / 7 - 1);
+        static const double zero_knot[7] = { 0, 0, 0, 0, 0, 0, 0 };
+        const size_t Q = times.size();
+        const bool v2 = model_ == CPI_MODEL_V2;
+        std::vector<double> DT_(Q), al(Q * 3), be(Q * 3), q(Q * 4), Jq(Q * 9), Ja(Q * 9), Jb(Q * 9), Ha(Q * 9), Hb(Q * 9),
+            Oa(v2 ? Q * 9 : 0), Ob(v2 ? Q * 9 : 0), P(Q * 225);
+        const std::vector<int32_t> qwin(Q, 0);
+        cpi_outputs o{};   // every field, so that the carry holds every part a later read needs
+        o.DT = DT_.data(); o.alpha = al.data(); o.beta = be.data(); o.q = q.data(); o.P = P.data();
+        o.J_q = Jq.data(); o.J_a = Ja.data(); o.J_b = Jb.data(); o.H_a = Ha.data(); o.H_b = Hb.data();
+        if (v2) { o.O_a = Oa.data(); o.O_b = Ob.data(); }
+        std::vector<double> next(cpi_carry_doubles(model_));
+        ctx.check(cpi_query_open_batch_host(ctx.get(), &p, 1, n, knots_.empty() ? zero_knot : knots_.data(), nullptr, nullptr, n + 1, lin,
+                                            q_k_lin.data(), carry_.empty() ? nullptr : carry_.data(), next.data(), (int64_t)Q, qwin.data(),
+                                            times.data(), &o));
+        carry_.swap(next);
+        res.resize(Q);
+        for (size_t r = 0; r < Q; r++) {
+            CpiResult &x = res[r];
+            x.DT = DT_[r];
+            for (int k = 0; k < 3; k++) { x.alpha_tau[k] = al[r * 3 + k]; x.beta_tau[k] = be[r * 3 + k]; }
+            for (int k = 0; k < 4; k++) x.q_k2tau[k] = q[r * 4 + k];
+            for (int k = 0; k < 9; k++) {
+                x.J_q[k] = Jq[r * 9 + k]; x.J_a[k] = Ja[r * 9 + k]; x.J_b[k] = Jb[r * 9 + k];
+                x.H_a[k] = Ha[r * 9 + k]; x.H_b[k] = Hb[r * 9 + k];
+                if (v2) { x.O_a[k] = Oa[r * 9 + k]; x.O_b[k] = Ob[r * 9 + k]; }
+            }
+            for (int k = 0; k < 225; k++) x.P_meas[k] = P[r * 225 + k];
+        }
+        if (n > 0) knots_.erase(knots_.begin(), knots_.end() - 7);   // the next segment starts on this one's last knot
+        fed_.clear();
+        dirty_ = true;   // the next member read is a zero-interval resume from the carried state
+        return res;
+    }
+    std::vector<CpiResult> at(const std::vector<double> &times) { return at(ctx_ ? *ctx_ : default_context(), times); }
     // Runs this single window on the GPU and fills the result members (what a first read of any member does by itself).
     void finalize(const Context &ctx) {
         if (incremental_) { finalize_incremental(ctx); return; }

@@ -342,6 +342,40 @@ class Engine:
                                                                   _ptr(lin), _ptr(q_k_lin), _ptr(carry_in), _ptr(carry_out), C.byref(o)))
         return out, carry_out
 
+    def preintegrate_running_resume_stj(self, knots, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), first=None,
+                                        count=None, N=None, carry_in=None, carry_out=None, packed=False, out=None):
+        """cpi_running_resume_stj_batch: preintegrate_running_resume with model 2's Jacobian rows.  Arguments and result as
+        preintegrate_running_resume; for model 2 (state_transition_jacobians set) "jac" means all seven matrices after every
+        interval of this segment, continued from the transition columns carry_in holds (the call then needs and leaves the
+        covariance state whether or not "cov" is wanted).  The mean and P / P_sym rows and carry_out are bit for bit those of
+        preintegrate_running_resume; without "jac", or for model 1, the call is preintegrate_running_resume.  A dense call on
+        knots [W, 2, 7] with count = zeros reads the record out as one row per window: the base of query_open.  Asynchronous."""
+        params = params or self.make_params()
+        W, N = self._window_shape(knots, lin, first, count, N, (q_k_lin, carry_in, carry_out))
+        carry_out = self._carry_out(W, params.model, carry_in, carry_out, device=self.device)
+        if out is None:
+            out = self._running_views(self.alloc_outputs(W * N, tuple(want), params.model, packed), W, N)
+        o = self._outputs_struct({k: v for k, v in out.items() if not k.startswith("_")})
+        self._sync_stream()
+        self._check(self.lib.cpi_running_resume_stj_batch(self.ctx, C.byref(params), W, N, _ptr(knots), _ptr(first), _ptr(count),
+                                                          _ptr(lin), _ptr(q_k_lin), _ptr(carry_in), _ptr(carry_out), C.byref(o)))
+        return out, carry_out
+
+    def preintegrate_running_resume_stj_host(self, knots, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), count=None,
+                                             carry_in=None, carry_out=None, pinned=True, out=None):
+        """preintegrate_running_resume_stj for a dense batch held in HOST memory (CPU float64 tensors, the records included):
+        cpi_running_resume_stj_batch_host.  Returns (rows, carry_out) as CPU tensors; synchronous."""
+        params = params or self.make_params()
+        W, N = self._window_shape(knots, lin, count=count, others=(q_k_lin, carry_in, carry_out), cuda=False)
+        carry_out = self._carry_out(W, params.model, carry_in, carry_out, pin_memory=pinned)
+        if out is None:
+            out = self._host_outputs((W, N), tuple(want), params.model, pinned)
+        o = self._outputs_struct(out)
+        self._sync_stream()
+        self._check(self.lib.cpi_running_resume_stj_batch_host(self.ctx, C.byref(params), W, N, _ptr(knots), None, _ptr(count), 0,
+                                                               _ptr(lin), _ptr(q_k_lin), _ptr(carry_in), _ptr(carry_out), C.byref(o)))
+        return out, carry_out
+
     @staticmethod
     def _wants_cov(want):
         return "cov" in want or "cov_sym" in want
@@ -432,6 +466,59 @@ class Engine:
         self._check(self.lib.cpi_query_stj_batch_host(self.ctx, C.byref(params), W, N, _ptr(knots), None, _ptr(count), 0, _ptr(lin),
                                                       _ptr(q_k_lin), Q, _ptr(qwin), _ptr(qtime), C.byref(o)))
         return out
+
+    def query_open(self, knots, lin, rows, qwin, qtime, base, q_k_lin=None, params=None, want=("mean",), first=None, count=None,
+                   N=None, out=None):
+        """cpi_query_open_batch: query_stj for windows that are still open.  knots / lin / q_k_lin / params / first / count / N and
+        rows describe the SEGMENT (the chunk that has just arrived) as given to and returned by preintegrate_running_resume[_stj];
+        base: the state each window had before knot 0 of the segment, as a dict of [W, base_N, ...] (or [W, ...]) tensors whose row
+        [w, base_N - 1] is used -- the rows dict of the PREVIOUS chunk's call in place, or the one-row read-out of a record
+        (preintegrate_running_resume_stj).  It stands where the zero state stands in query: a time on or before the segment's
+        first stamp returns the base row bit for bit, a time inside interval 0 advances it.  base must hold what rows must hold
+        for the request.  base=None: query_stj.  Returns a dict of [Q, ...] tensors.  Asynchronous."""
+        params = params or self.make_params()
+        W, N = self._window_shape(knots, lin, first, count, N, (q_k_lin, qwin, qtime))
+        Q = qtime.shape[0]
+        assert qwin.dtype == torch.int32 and qtime.dtype == torch.float64 and qwin.shape == (Q,), "qwin [Q] int32, qtime [Q] float64"
+        r = {k: v for k, v in rows.items() if not k.startswith("_")}
+        for k, v in r.items():
+            assert v.is_cuda and v.is_contiguous() and v.shape[:2] == (W, N), "rows: the [W, N, ...] dict of preintegrate_running_resume[_stj]"
+        bo, base_N = None, 0
+        if base is not None:
+            b = {k: v for k, v in base.items() if not k.startswith("_")}
+            sizes = {v.numel() // (W * n) for k, v in b.items() for name, n in OUT_FIELDS if name == k}
+            assert len(sizes) == 1 and all(v.is_cuda and v.is_contiguous() and v.shape[0] == W for v in b.values()), \
+                "base: a dict of [W, base_N, ...] tensors with one base_N"
+            base_N = int(sizes.pop())
+            bo = self._outputs_struct(b)
+        if out is None:
+            out = self.alloc_outputs(Q, tuple(want), params.model)
+        o = self._outputs_struct(out)
+        ro = self._outputs_struct(r)
+        self._sync_stream()
+        self._check(self.lib.cpi_query_open_batch(self.ctx, C.byref(params), W, N, _ptr(knots), _ptr(first), _ptr(count), _ptr(lin),
+                                                  _ptr(q_k_lin), C.byref(ro), Q, _ptr(qwin), _ptr(qtime), C.byref(o),
+                                                  C.byref(bo) if bo is not None else None, base_N))
+        return out
+
+    def query_open_host(self, knots, lin, qwin, qtime, q_k_lin=None, params=None, want=("mean",), count=None, carry_in=None,
+                        carry_out=None, pinned=True, out=None):
+        """One chunk of a live loop from HOST memory (CPU tensors): cpi_query_open_batch_host.  The base rows are read out of
+        carry_in (None: the zero state), the chunk's rows and carry_out are computed on the device, the queries run against
+        them.  Returns (out, carry_out): a dict of CPU tensors [Q, ...] and the record to continue from; synchronous."""
+        params = params or self.make_params()
+        W, N = self._window_shape(knots, lin, count=count, others=(q_k_lin, qwin, qtime, carry_in, carry_out), cuda=False)
+        Q = qtime.shape[0]
+        assert qwin.dtype == torch.int32 and qtime.dtype == torch.float64 and qwin.shape == (Q,), "qwin [Q] int32, qtime [Q] float64"
+        carry_out = self._carry_out(W, params.model, carry_in, carry_out, pin_memory=pinned)
+        if out is None:
+            out = self._host_outputs((Q,), tuple(want), params.model, pinned)
+        o = self._outputs_struct(out)
+        self._sync_stream()
+        self._check(self.lib.cpi_query_open_batch_host(self.ctx, C.byref(params), W, N, _ptr(knots), None, _ptr(count), 0, _ptr(lin),
+                                                       _ptr(q_k_lin), _ptr(carry_in), _ptr(carry_out), Q, _ptr(qwin), _ptr(qtime),
+                                                       C.byref(o)))
+        return out, carry_out
 
     def preintegrate_host(self, knots, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), count=None, pinned=True, out=None):
         """Dense batch held in HOST memory (CPU float64 tensors; pinned ones overlap upload / kernels / download):
@@ -1199,6 +1286,48 @@ class _CpiBase:
         # model 2: the members' Jacobians are read out of the carried state-transition columns by a zero-interval resume
         self._res = res[-1] if self._model == 1 else None
         return res
+
+    def at(self, times):
+        """Incremental preintegrators only: the measurement AT each of `times` (a camera frame stamped inside the chunk that has
+        just been fed).  Runs the intervals fed since the previous read (Engine.preintegrate_running_resume_stj) -- the carry and
+        the tail knot advance exactly as in read_rows() -- and queries them with the state at the previous read as the base row
+        (Engine.query_open).  Returns one result dict per time: the means, P, and model 1's five Jacobians or model 2's seven.  A
+        time on a fed stamp gives the members as they stood there, a time inside an interval that state advanced with the
+        interval's opening reading held, a time before the first pending interval the state at the previous read, a time at or
+        past the last stamp the current state.  The pending intervals must chain (no separator knots)."""
+        if not self._incremental:
+            raise RuntimeError("at: set_incremental(True) first (the queries continue from the carried state)")
+        if self._model == 3:
+            raise ValueError("at: the Forster comparator has no running form")
+        if self._model == 2 and not self.state_transition_jacobians:
+            raise ValueError("at: model 2's analytic Jacobians (state_transition_jacobians = False) have no running form")
+        times = np.asarray(times, dtype=np.float64).reshape(-1)
+        if times.size == 0:
+            return []
+        kn = self._knots()
+        if np.isnan(kn[:, 0]).any():
+            raise ValueError("at: the intervals fed since the previous read do not chain (a query needs finite, non-decreasing stamps)")
+        eng = self._engine or default_engine()
+        dev = eng.device
+        knots = torch.from_numpy(kn[None]).to(dev)
+        lin = torch.from_numpy(np.concatenate([self.b_w_lin, self.b_a_lin])[None]).to(dev)
+        q = torch.from_numpy(self.q_k_lin[None]).to(dev)
+        prm = eng.make_params(self._model, self.imu_avg, self.state_transition_jacobians, self._sig, tuple(self.grav))
+        # the state at the previous read as one ordinary row: a segment of one interval that is not counted
+        base, _ = eng.preintegrate_running_resume_stj(knots[:, :1].repeat(1, 2, 1).contiguous(), lin, q, prm,
+                                                      count=torch.zeros(1, dtype=torch.int32, device=dev), carry_in=self._carry)
+        rows = {}
+        if self._iv:
+            # every running field, so that the carry holds every part a later read (of rows or of members) needs
+            rows, self._carry = eng.preintegrate_running_resume_stj(knots, lin, q, prm, carry_in=self._carry)
+        out = eng.query_open(knots, lin, rows, torch.zeros(times.size, dtype=torch.int32, device=dev), torch.from_numpy(times).to(dev),
+                             base, q, prm, want=("mean", "jac", "cov"))
+        eng.synchronize()
+        if self._iv:
+            self._tail, self._iv = kn[-1], []
+        self._res = None   # the members are read out of the carried state by the next member read
+        host = {k: v.cpu().numpy() for k, v in out.items()}
+        return [{k: v[i] for k, v in host.items()} for i in range(times.size)]
 
     def _m3(self, name):
         return self._run()[name].reshape(3, 3).T  # column-major -> [row][col]

@@ -62,7 +62,10 @@ extern "C" {
                                interval and at the query times); cpi_stream_running_stj_batch,
                                cpi_stream_running_stj_batch_host (those rows from IMU stream(s), cut in place);
                                cpi_query_stream_batch, cpi_query_stream_batch_host (the query family by absolute time over IMU
-                               stream(s): the window and the interval are found on the device) */
+                               stream(s): the window and the interval are found on the device);
+                               cpi_running_resume_stj_batch, cpi_running_resume_stj_batch_host (model 2's Jacobian rows from a
+                               carry record); cpi_query_open_batch, cpi_query_open_batch_host (the query family for a window
+                               that continues from a carried state, given as a base row) */
 
 enum { CPI_OK = 0, CPI_ERR_INVALID = 1, CPI_ERR_HIP = 2, CPI_ERR_NO_DEVICE = 3, CPI_ERR_RCCL = 4 };
 enum {
@@ -262,7 +265,7 @@ int cpi_preintegrate_running(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int
  *     request and lanes_per_window.
  * Not provided: running Jacobian rows for model 2; running rows from a carry record for the STREAM entries
  * (cpi_preintegrate_stream[s]_running); the Forster comparator.  (Model 2's running Jacobian rows without a carry record:
- * cpi_running_stj_batch below.) */
+ * cpi_running_stj_batch below; from a carry record: cpi_running_resume_stj_batch below.) */
 int cpi_preintegrate_running_resume(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                                     const double *knots, const int64_t *first, const int32_t *count,
                                     const double *lin, const double *q_k_lin,
@@ -305,7 +308,8 @@ int cpi_preintegrate_running_resume(cpi_ctx *ctx, const cpi_params *prm, int64_t
  * cut from IMU streams in place (cpi_preintegrate_stream[s]_running: assemble the windows, or query per update time); rows that
  * continue from a carry record (cpi_preintegrate_running_resume); extrapolation past t_n.  (The covariance at query times is a
  * call of its own: cpi_query_cov_batch below; the Jacobians of model 2 at query times: cpi_query_stj_batch below; streams
- * queried in place by absolute time: cpi_query_stream_batch below.) */
+ * queried in place by absolute time: cpi_query_stream_batch below; rows that continue from a carry record: cpi_query_open_batch
+ * below.) */
 int cpi_query_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                     const double *knots, const int64_t *first, const int32_t *count,
                     const double *lin, const double *q_k_lin, const cpi_outputs *rows,
@@ -341,7 +345,7 @@ int cpi_query_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
  * with idx_i = qwin: the whitened keyframe factor AT the query time.
  * Still not provided: model-2 Jacobians at query times; windows cut from IMU streams in place; rows from a carry record;
  * extrapolation past t_n.  (The model-2 Jacobians at query times are a call of their own: cpi_query_stj_batch below; streams queried in
- * place by absolute time: cpi_query_stream_batch below.) */
+ * place by absolute time: cpi_query_stream_batch below; rows from a carry record: cpi_query_open_batch below.) */
 int cpi_query_cov_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                         const double *knots, const int64_t *first, const int32_t *count,
                         const double *lin, const double *q_k_lin, const cpi_outputs *rows,
@@ -365,7 +369,7 @@ int cpi_query_cov_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t 
  * No host synchronisation and a single stream: a capture of the call is a chain without parallel branches.
  * Still not provided: these rows for the stream entries (cpi_preintegrate_stream[s]_running); for the carry-record entries
  * (cpi_preintegrate_running_resume); model 2's analytic Jacobians (state_transition_jacobians == 0); extrapolation past t_n.
- * (From IMU stream(s) cut in place: cpi_stream_running_stj_batch below.) */
+ * (From IMU stream(s) cut in place: cpi_stream_running_stj_batch below; from a carry record: cpi_running_resume_stj_batch below.) */
 int cpi_running_stj_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                           const double *knots, const int64_t *first, const int32_t *count,
                           const double *lin, const double *q_k_lin, const cpi_outputs *rows);
@@ -393,11 +397,73 @@ int cpi_running_stj_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_
  * cpi_factor_hessian_tri_batch with model 2 and idx_i = qwin.
  * Still not provided: windows cut from IMU streams in place (the stream entries); rows that continue from a carry record
  * (cpi_preintegrate_running_resume); model 2's analytic Jacobians (state_transition_jacobians == 0); extrapolation past t_n.
- * (Streams queried in place by absolute time: cpi_query_stream_batch below.) */
+ * (Streams queried in place by absolute time: cpi_query_stream_batch below; rows that continue from a carry record:
+ * cpi_query_open_batch below.) */
 int cpi_query_stj_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                         const double *knots, const int64_t *first, const int32_t *count,
                         const double *lin, const double *q_k_lin, const cpi_outputs *rows,
                         int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out);
+
+/* cpi_preintegrate_running_resume WITH MODEL 2's JACOBIAN ROWS: the seven matrices after every interval of a window that is still
+ * open, so that a live model-2 estimator gets them per IMU reading and not only at a chunk's end.  A superset of
+ * cpi_preintegrate_running_resume, as cpi_running_stj_batch is of cpi_preintegrate_running: the arguments and every rule of its
+ * contract are the same.  Without a Jacobian field in rows, or with model 1, the call IS cpi_preintegrate_running_resume (the same
+ * kernels, bit for bit the same rows and records).
+ * With model 2, state_transition_jacobians != 0 and any of J_q ... O_b in rows: row w * N + i of each requested field is the
+ * read-out of the nine Discrete_J_b transition columns behind interval i of this segment, continued from the columns carry_in
+ * holds -- exactly the read-out of cpi_running_stj_batch.  The covariance kernel runs whether or not P / P_sym are asked for.
+ *   - tags: the call needs, and leaves, header | covariance state (the transition columns are part of it).  The tag, NaN and
+ *     pass-through rules of cpi_preintegrate_running_resume hold unchanged.
+ *   - the running contract holds for the new rows: a skipped interval repeats the previous row bit for bit, the "previous row" of
+ *     row 0 is the carried columns read out, rows i >= count[w] repeat the final state, count = 0 gives N copies of the carried
+ *     read-out, and a window whose record does not fit gets NaN in all N rows of every requested field.  A call with N = 1 and
+ *     every count 0 therefore reads a record out as one ordinary row per window (it reads knot first[w] of each window and nothing
+ *     behind it): the base row of cpi_query_open_batch.
+ *   - carry_in == NULL gives bit for bit the rows of cpi_running_stj_batch.  The mean and P / P_sym rows and carry_out are bit
+ *     for bit those of cpi_preintegrate_running_resume on the same arguments (with P or P_sym in rows), so records stay
+ *     interchangeable with both older resume entries, and a zero-interval cpi_preintegrate_resume on carry_out returns the seven
+ *     matrices of row N - 1 bit for bit: both read the same columns the same way.
+ * CPI_ERR_INVALID beyond cpi_preintegrate_running_resume's: model 2 with state_transition_jacobians == 0 and a Jacobian field.
+ * CPI_MODEL_FORSTER is refused as there.
+ * One stream, no host synchronisation: a capture of the call is a chain without parallel branches.
+ * Still not provided: carry records for the stream entries; model 2's analytic Jacobians in running form
+ * (state_transition_jacobians == 0); extrapolation past t_n. */
+int cpi_running_resume_stj_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                 const double *knots, const int64_t *first, const int32_t *count,
+                                 const double *lin, const double *q_k_lin,
+                                 const double *carry_in, double *carry_out, const cpi_outputs *rows);
+
+/* cpi_query_stj_batch FOR A WINDOW THAT IS STILL OPEN: a camera frame stamped inside the IMU chunk that has just arrived, of a
+ * window that continues from a carried state.  The arguments of cpi_query_stj_batch -- knots, first, count, rows describe the
+ * SEGMENT (the chunk), rows being what a resume entry (cpi_preintegrate_running_resume, cpi_running_resume_stj_batch) wrote for
+ * it -- plus
+ *   base, base_N   the state each window had BEFORE knot 0 of the segment, as ordinary rows: the row of window w is row
+ *                  w * base_N + base_N - 1 of every array of base.  base_N = 1: W contiguous rows (what an N = 1, all-counts-0 call
+ *                  of cpi_running_resume_stj_batch writes from the record).  base_N = the previous chunk's N: the previous call's
+ *                  rows used in place, without a gather -- that row is the one its carry_out describes.
+ * No record is parsed here: the base row stands where the zero state stands in the closed entries.  The semantics are the
+ * family's with "the zero state when i == 0" read as "the base row of window w":
+ *   - a query on or before the segment's first stamp (t_q <= t_0) returns the base row BIT FOR BIT in every requested field;
+ *   - a query inside interval 0 advances the base row by feed_IMU(t_0, t_q, w_0, a_0, w_0, a_0): the means, model 1's Jacobians, P
+ *     (the clone rows and columns rebuilt as for any row) and model 2's nine columns (rebuilt from the base row's seven matrices as
+ *     for any row);
+ *   - i > 0 is unchanged, and so are the clamping of qwin, Q == 0, a NaN t_q, and "no read leaves the window's knots, its rows, or
+ *     row w * base_N + base_N - 1 of base".  N == 0: every query gets the base row and rows is not read;
+ *   - a gathered state (row or base) whose q[0] is NaN -- the rows a refused carry leaves -- gives NaN in every requested field of
+ *     that query (all four components of q).
+ * base must hold what rows must hold for the same request (for every N); CPI_ERR_INVALID names base and what is missing.
+ * base_N < 1 with a non-NULL base is refused.  base == NULL: the call IS cpi_query_stj_batch, bit for bit.
+ * On a view of a closed window -- first + m, count - m, rows m ..., base = row m - 1 -- the call returns bit for bit what
+ * cpi_query_stj_batch returns on the whole window for every t_q >= t_m: the arithmetic behind the gather is the same code.
+ * The kernels run one after the other on the context's stream; a capture of cpi_running_resume_stj_batch followed by this call
+ * is a chain without parallel branches.
+ * Composition: out -> cpi_sqrt_information_packed_batch -> cpi_factor_eval_whitened_tri_batch with idx_i = qwin.
+ * Still not provided: carry records for the stream entries; model 2's analytic Jacobians in running form; extrapolation past t_n. */
+int cpi_query_open_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                         const double *knots, const int64_t *first, const int32_t *count,
+                         const double *lin, const double *q_k_lin, const cpi_outputs *rows,
+                         int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out,
+                         const cpi_outputs *base, int32_t base_N);
 
 /* Replaces: the whole caller side of GraphSolver::createimufactor_cpi_v1 / _v2 (GraphSolver_IMU.cpp:43-75, 97-130) for every
  * window of a trajectory at once, reading ONE IMU stream IN PLACE: no knot is copied, for any model and any output.
@@ -783,6 +849,23 @@ int cpi_query_stj_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int
                              const double *knots, const int64_t *first, const int32_t *count, int64_t n_knots,
                              const double *lin, const double *q_k_lin,
                              int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out);
+/* cpi_running_resume_stj_batch from host memory: the arguments and the pipeline of cpi_preintegrate_running_resume_host (its
+ * messages carry this entry's name).  Bit for bit the device form on the same arguments and lanes_per_window. */
+int cpi_running_resume_stj_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                                      const double *knots, const int64_t *first, const int32_t *count,
+                                      int64_t n_knots, const double *lin, const double *q_k_lin,
+                                      const double *carry_in, double *carry_out, const cpi_outputs *rows);
+/* cpi_query_open_batch from host memory, one chunk of a live loop in one call: host knots of the chunk (n_knots as in
+ * cpi_preintegrate_batch_host), carry_in (NULL: the zero state) / carry_out in host memory, the queries and host outputs.  The base
+ * rows are read out of carry_in (cpi_running_resume_stj_batch, N = 1, every count 0), the chunk's rows and carry_out come from
+ * cpi_running_resume_stj_batch, then the device entry runs with base_N = 1; all rows stay in device staging, Q rows and the records
+ * come down.  carry_in must hold what the request of out needs (covariance state for P / P_sym or model-2 Jacobians, analytic
+ * Jacobians for model-1 Jacobians).  qwin and the stamps are validated as in cpi_query_batch_host.  Q == 0 still advances the
+ * record.  Bit for bit the device composition on rows that hold P_sym. */
+int cpi_query_open_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
+                              const double *knots, const int64_t *first, const int32_t *count, int64_t n_knots,
+                              const double *lin, const double *q_k_lin, const double *carry_in, double *carry_out,
+                              int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out);
 /* cpi_preintegrate_resume from host memory: every pointer a host pointer, n_knots as in cpi_preintegrate_batch_host. */
 int cpi_preintegrate_resume_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                                  const double *knots, const int64_t *first, const int32_t *count,
