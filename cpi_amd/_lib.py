@@ -180,6 +180,9 @@ def load():
     lib.cpi_query_open_batch_host.argtypes = [vp, C.POINTER(CpiParams), i64, i32, dp, vp, vp, i64, dp, dp, dp, dp, i64, vp, dp, C.POINTER(CpiOutputs)]
     for f in (lib.cpi_running_resume_stj_batch, lib.cpi_running_resume_stj_batch_host, lib.cpi_query_open_batch, lib.cpi_query_open_batch_host):
         f.restype = C.c_int
+    lib.cpi_merge_batch.argtypes = [vp, i32, i64, i32, i64, C.POINTER(CpiOutputs), vp, vp, C.POINTER(CpiOutputs)]
+    lib.cpi_merge_batch_host.argtypes = lib.cpi_merge_batch.argtypes
+    lib.cpi_merge_batch.restype = lib.cpi_merge_batch_host.restype = C.c_int
     lib.cpi_preintegrate_stream_running.argtypes = lib.cpi_preintegrate_stream.argtypes
     lib.cpi_preintegrate_stream_running_host.argtypes = lib.cpi_preintegrate_stream_host.argtypes
     lib.cpi_preintegrate_streams_running.argtypes = lib.cpi_preintegrate_streams.argtypes

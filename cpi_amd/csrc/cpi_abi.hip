@@ -762,6 +762,50 @@ extern "C" int cpi_query_open_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t
                         base, base_N);
 }
 
+// cpi_merge_batch: consecutive preintegrated windows joined into one measurement (cpi_merge_kernel, cpi_merge.hip).  Everything
+// the call can refuse is refused BEFORE the context is looked at, so the contract can be exercised where no device exists
+// (cpi_last_error(NULL) holds the text then).
+static int merge_check(cpi_ctx *ctx, const char *who, int32_t model, int64_t M, int32_t G, int64_t in_rows, const cpi_outputs *in,
+                       const cpi_outputs *out, Request *rq) {
+    if (!in || !out) return refuse(ctx, who, "in/out is NULL");
+    if (model != CPI_MODEL_V1)
+        return refuse(ctx, who, "model must be 1 (model 2 is not composable from its outputs: alpha and beta carry gravity through each "
+                                "window's own q_k_lin; the Forster comparator's covariance does not come from this recursion)");
+    if (G < 1) return refuse(ctx, who, "G (the largest group) must be >= 1");
+    if (M < 0 || in_rows < 0) return refuse(ctx, who, "negative size");
+    if (out->O_a || out->O_b) return refuse(ctx, who, "O_a / O_b are model-2 fields: not available");
+    *rq = request_of(out);
+    if (in_rows > 0 && rq->any()) {
+        if (!in->DT || !in->alpha || !in->beta || !in->q) return refuse(ctx, who, "in must hold DT, alpha, beta and q");
+        if ((rq->jac || rq->cov) && (!in->J_q || !in->J_a || !in->J_b || !in->H_a || !in->H_b))
+            return refuse(ctx, who, "in must hold all five Jacobians (J_q J_a J_b H_a H_b) when out asks for a Jacobian or for P / P_sym");
+        if (rq->cov && !in->P && !in->P_sym) return refuse(ctx, who, "in must hold P or P_sym when out asks for P / P_sym");
+    }
+    for (int a = 0; a < kOutFields; a++)
+        for (int b = 0; b < kOutFields; b++) {
+            const double *pi = out_field_c(in, a), *po = out_field_c(out, b);
+            if (pi && po && pi < po + M * OUT_N[b] && po < pi + in_rows * OUT_N[a]) return refuse(ctx, who, "an array of out overlaps an array of in");
+        }
+    return CPI_OK;
+}
+extern "C" int cpi_merge_batch(cpi_ctx *ctx, int32_t model, int64_t M, int32_t G, int64_t in_rows, const cpi_outputs *in,
+                               const int64_t *first, const int32_t *count, const cpi_outputs *out) {
+    static const char who[] = "cpi_merge_batch";
+    Request rq;
+    CPI_TRY(merge_check(ctx, who, model, M, G, in_rows, in, out, &rq));
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (M == 0 || !rq.any()) return CPI_OK;
+    if (!grid_ok((M + 3) / 4)) return refuse(ctx, who, "M exceeds the 32-bit grid (4 output rows per workgroup)");
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    MergeArgs a;
+    memset(&a, 0, sizeof a);
+    a.M = M; a.G = G; a.in_rows = in_rows; a.in = *in; a.first = (const long long *)first; a.count = count; a.out = *out;
+    launch::merge(rq.jac, rq.cov, a, ctx->stream);
+    CPI_HIP(ctx, hipGetLastError());
+    return CPI_OK;
+}
+
 // Replaces the caller-side loop of GraphSolver::createimufactor_cpi_v1 / _v2 (GraphSolver_IMU.cpp:43-75, 97-130) for ALL the
 // windows of a trajectory at once, with ZERO copies of the IMU data: cpi_cut_windows_kernel finds, per update time, where the
 // reference's deque would stand (28 bytes per window into the caller's workspace), and the preintegration kernels read the
@@ -1748,7 +1792,8 @@ int stage_windows(Staging &st, int64_t W, int64_t n_knots, const double *knots, 
 // 52 / 56 ms.  Page-locked bounce buffers + copy threads for pageable destinations were built and measured: no faster
 // than the runtime's own path (112 ms) -- what costs is FRESH pageable output memory (first-touch page faults: 375-450 ms
 // for the same call), so callers should re-use their output buffers.
-constexpr int kPipeArrays = 6;   // per-window arrays of a chunk: knots, count, lin, q_k_lin and two of the caller's (the carry records)
+constexpr int kPipeArrays = 11;   // per-window arrays of a chunk: knots, count, lin, q_k_lin and two of the caller's (the carry records);
+                                  // cpi_merge_batch_host: the ten operand fields a request can read and count
 // One per-window array that travels with a chunk: `stride` bytes per window, uploaded from `up` before the chunk's kernels or
 // downloaded to `down` after them (both NULL: absent); whole groups of `group` windows are copied (64: tiles).
 struct PipeArray {
@@ -2200,6 +2245,60 @@ extern "C" int cpi_query_open_batch_host(cpi_ctx *ctx, const cpi_params *prm, in
     if (Q > 0) CPI_TRY(cpi_query_open_batch(ctx, prm, W, N, in.knots, in.first, in.count, in.lin, in.qk, &drows, Q, dqwin, dqtime, &d, &dbase, 1));
     CPI_TRY(st.download(out, d, (size_t)Q));
     CPI_TRY(st.download(carry_out, (const double *)dco, cd));
+    return st.finish();
+}
+
+// cpi_merge_batch from host memory.  The dense layout (first == NULL) with every group inside in_rows runs through the chunked
+// pipeline: the G operand rows of a group travel with it, field by field, and one output row comes down.  A ragged layout (or a
+// last group clipped by in_rows) is staged whole.
+static cpi_outputs merge_in_mask(const cpi_outputs *in, const Request &rq) {
+    cpi_outputs m = {};
+    m.DT = in->DT; m.alpha = in->alpha; m.beta = in->beta; m.q = in->q;
+    if (rq.jac || rq.cov) { m.J_q = in->J_q; m.J_a = in->J_a; m.J_b = in->J_b; m.H_a = in->H_a; m.H_b = in->H_b; }
+    if (rq.cov) { if (in->P) m.P = in->P; else m.P_sym = in->P_sym; }
+    return m;
+}
+extern "C" int cpi_merge_batch_host(cpi_ctx *ctx, int32_t model, int64_t M, int32_t G, int64_t in_rows, const cpi_outputs *in,
+                                    const int64_t *first, const int32_t *count, const cpi_outputs *out) {
+    static const char who[] = "cpi_merge_batch_host";
+    Request rq;
+    CPI_TRY(merge_check(ctx, who, model, M, G, in_rows, in, out, &rq));
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (M == 0 || !rq.any()) return CPI_OK;
+    if (!grid_ok((M + 3) / 4)) return refuse(ctx, who, "M exceeds the 32-bit grid (4 output rows per workgroup)");
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    const cpi_outputs need = merge_in_mask(in, rq);   // what the request reads: nothing else crosses PCIe
+    if (!first && in_rows > 0 && M <= in_rows / G) {
+        PipeArrays arr = {};
+        static const char *const names[kOutFields] = { "DT", "alpha", "beta", "q", "J_q", "J_a", "J_b", "H_a", "H_b", "O_a", "O_b", "P", "P_sym" };
+        int slot[kOutFields], na = 0;
+        for (int k = 0; k < kOutFields; k++) {
+            slot[k] = -1;
+            if (const double *h = out_field_c(&need, k)) { slot[k] = na; arr.a[na++] = {names[k], h, nullptr, (size_t)G * OUT_N[k] * sizeof(double), 1}; }
+        }
+        const int cslot = count ? na : -1;
+        if (count) arr.a[na++] = {"count", count, nullptr, sizeof(int32_t), 1};
+        return preintegrate_host_pipeline(ctx, who, M, 1, arr, out, [&](int64_t mn, void *const *dev, const cpi_outputs *d) {
+            cpi_outputs din = {};
+            for (int k = 0; k < kOutFields; k++) if (slot[k] >= 0) *out_field(&din, k) = (double *)dev[slot[k]];
+            return cpi_merge_batch(ctx, model, mn, G, mn * G, &din, nullptr, cslot >= 0 ? (const int32_t *)dev[cslot] : nullptr, d);
+        });
+    }
+    Staging st(ctx);
+    cpi_outputs din = {}, d;
+    const int64_t *dfirst;
+    const int32_t *dcount;
+    for (int k = 0; k < kOutFields; k++) {
+        const double *dk;
+        CPI_TRY(st.upload(in_rows > 0 ? (const double *)out_field_c(&need, k) : nullptr, (size_t)in_rows * OUT_N[k], &dk));
+        *out_field(&din, k) = const_cast<double *>(dk);
+    }
+    CPI_TRY(st.upload(first, (size_t)M, &dfirst));
+    CPI_TRY(st.upload(count, (size_t)M, &dcount));
+    CPI_TRY(st.mirror(out, (size_t)M, &d));
+    CPI_TRY(cpi_merge_batch(ctx, model, M, G, in_rows, &din, dfirst, dcount, &d));
+    CPI_TRY(st.download(out, d, (size_t)M));
     return st.finish();
 }
 

@@ -1,6 +1,6 @@
 // cpi_args.hpp -- kernel argument blocks and the launcher interface between the translation units of libcpi_amd.so.
 //
-// The library is twelve translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
+// The library is thirteen translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
 //   cpi_mean.hip    cpi_mean_kernel / cpi_mean_tiled_kernel / cpi_tile_*_kernel       (cpi_mean_kernels.hpp)
 //   cpi_running.hip cpi_mean_running_kernel / cpi_mean_stream_running_kernel: a row after every interval, from plain knots /
 //                   from windows cut out of IMU stream(s) in place         (cpi_running_kernels.hpp, cpi_running_body.inc)
@@ -21,6 +21,8 @@
 //   cpi_query_open.hip  cpi_query_open_kernel / cpi_query_cov_open_kernel / cpi_query_stj_open_kernel: the three query kernels for
 //                   windows that continue from a carried state -- the same bodies, their i == 0 gather reading a base row
 //                                                    (cpi_query_open_kernels.hpp over the three query bodies)
+//   cpi_merge.hip   cpi_merge_kernel: consecutive preintegrated windows joined into one measurement, a segmented left fold over
+//                   measurement rows (no IMU data is read)                             (cpi_merge_kernels.hpp)
 //   cpi_factor.hip  evaluateError sweeps, square-root information, Hessian blocks, state prediction
 //                                                                                      (cpi_factor_kernels.hpp)
 //   cpi_abi.hip     the C-ABI of include/cpi_amd.h: argument checks, launch heuristics, device sets (RCCL), the
@@ -164,6 +166,18 @@ struct StreamQueryArgs {
     cpi_outputs out;         // arrays of Q rows
 };
 
+// cpi_merge_batch: output row j = in[first[j]] o in[first[j] + 1] o ... (count[j] consecutive rows, oldest first).  first and count
+// live in device memory and are CLAMPED where they are read (cpi_merge_kernels.hpp: group_range).
+struct MergeArgs {
+    long long M;             // output rows (groups)
+    int G;                   // the largest group, >= 1
+    long long in_rows;
+    cpi_outputs in;          // DT / alpha / beta / q always; J_q ... H_b and P or P_sym when the request needs them
+    const long long *first;  // [M] or NULL: group j starts at row j * G
+    const int *count;        // [M] or NULL: every group has G rows
+    cpi_outputs out;         // arrays of M rows
+};
+
 struct FactorArgs {
     long long F;
     double grav[3];
@@ -252,6 +266,8 @@ void query_stj_open(bool avg, const QueryArgs &a, const QueryBase &b, hipStream_
 void squery_mean(int model, bool jac, bool avg, const StreamQueryArgs &a, hipStream_t st);
 void squery_cov(int model, bool avg, const StreamQueryArgs &a, const double q4[4], hipStream_t st);
 void squery_jac2(bool avg, const StreamQueryArgs &a, hipStream_t st);
+// ---- cpi_merge.hip (cpi_merge_batch; jac: a.out asks for a Jacobian, cov: a.out asks for P / P_sym)
+void merge(bool jac, bool cov, const MergeArgs &a, hipStream_t st);
 // ---- cpi_factor.hip
 void factor(int model, bool whiten, int lpf, const FactorArgs &a, hipStream_t st);            // lpf 16 | 8 | 4
 void factor_packed(int model, int lpf, const FactorArgs &a, double *packed, hipStream_t st);  // lpf 2 | 3 | 4 | 6 | 8

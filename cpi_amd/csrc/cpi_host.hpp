@@ -863,6 +863,58 @@ inline std::vector<CpiResult> query_stream_results(const Context &ctx, const cpi
     return res;
 }
 
+// Consecutive preintegrated windows JOINED (cpi_merge_batch_host): result j = rows[first[j]] o ... o rows[first[j] + count[j] - 1],
+// oldest first -- keyframe decimation, or the one factor that replaces the two that met at a removed state -- without the IMU
+// readings.  Model-1 results (CpiV1 / CpiBatch / ImuStream with model 1: the five bias Jacobians and P_meas filled), ALL
+// PREINTEGRATED AT THE SAME b_w_lin / b_a_lin: the call cannot check that.  count is clamped into [0, G] and groups are clipped at
+// the end of rows; count 0 gives the zero state, count 1 the row itself bit for bit.
+inline std::vector<CpiResult> merge(const Context &ctx, const std::vector<CpiResult> &rows, int32_t G,
+                                    const std::vector<int64_t> *first = nullptr, const std::vector<int32_t> *count = nullptr) {
+    const size_t R = rows.size();
+    if (G < 1) throw std::invalid_argument("cpi_host::merge: G must be >= 1");
+    if (first && count && first->size() != count->size()) throw std::invalid_argument("cpi_host::merge: first and count differ in length");
+    const size_t M = first ? first->size() : count ? count->size() : (R + (size_t)G - 1) / (size_t)G;
+    std::vector<CpiResult> res(M);
+    if (M == 0) return res;
+    struct Rows {
+        std::vector<double> DT, al, be, q, Jq, Ja, Jb, Ha, Hb, P;
+        cpi_outputs bind(size_t n) {
+            DT.resize(n); al.resize(n * 3); be.resize(n * 3); q.resize(n * 4); P.resize(n * 225);
+            Jq.resize(n * 9); Ja.resize(n * 9); Jb.resize(n * 9); Ha.resize(n * 9); Hb.resize(n * 9);
+            cpi_outputs o{};
+            o.DT = DT.data(); o.alpha = al.data(); o.beta = be.data(); o.q = q.data(); o.P = P.data();
+            o.J_q = Jq.data(); o.J_a = Ja.data(); o.J_b = Jb.data(); o.H_a = Ha.data(); o.H_b = Hb.data();
+            return o;
+        }
+    } in, out;
+    const cpi_outputs i = in.bind(R), o = out.bind(M);
+    for (size_t r = 0; r < R; r++) {
+        const CpiResult &x = rows[r];
+        in.DT[r] = x.DT;
+        for (int k = 0; k < 3; k++) { in.al[r * 3 + k] = x.alpha_tau[k]; in.be[r * 3 + k] = x.beta_tau[k]; }
+        for (int k = 0; k < 4; k++) in.q[r * 4 + k] = x.q_k2tau[k];
+        for (int k = 0; k < 9; k++) {
+            in.Jq[r * 9 + k] = x.J_q[k]; in.Ja[r * 9 + k] = x.J_a[k]; in.Jb[r * 9 + k] = x.J_b[k];
+            in.Ha[r * 9 + k] = x.H_a[k]; in.Hb[r * 9 + k] = x.H_b[k];
+        }
+        for (int k = 0; k < 225; k++) in.P[r * 225 + k] = x.P_meas[k];
+    }
+    ctx.check(cpi_merge_batch_host(ctx.get(), CPI_MODEL_V1, (int64_t)M, G, (int64_t)R, &i, first ? first->data() : nullptr,
+                                   count ? count->data() : nullptr, &o));
+    for (size_t r = 0; r < M; r++) {
+        CpiResult &x = res[r];
+        x.DT = out.DT[r];
+        for (int k = 0; k < 3; k++) { x.alpha_tau[k] = out.al[r * 3 + k]; x.beta_tau[k] = out.be[r * 3 + k]; }
+        for (int k = 0; k < 4; k++) x.q_k2tau[k] = out.q[r * 4 + k];
+        for (int k = 0; k < 9; k++) {
+            x.J_q[k] = out.Jq[r * 9 + k]; x.J_a[k] = out.Ja[r * 9 + k]; x.J_b[k] = out.Jb[r * 9 + k];
+            x.H_a[k] = out.Ha[r * 9 + k]; x.H_b[k] = out.Hb[r * 9 + k];
+        }
+        for (int k = 0; k < 225; k++) x.P_meas[k] = out.P[r * 225 + k];
+    }
+    return res;
+}
+
 // ---- the caller's loop for MANY windows at once --------------------------------------------------------------------
 // What GraphSolver keeps between two states is a deque of IMU readings (GraphSolver.h: imu_times / imu_linaccs /
 // imu_angvel, filled by addmeasurement_imu); createimufactor_cpi_v1 / _v2 (GraphSolver_IMU.cpp:34-134) walk it up to the

@@ -520,6 +520,61 @@ class Engine:
                                                        C.byref(o)))
         return out, carry_out
 
+    # ------------------------------------------------------------------ joining consecutive windows
+    def _merge_args(self, meas, G, first, count, cuda):
+        m = {k: v for k, v in meas.items() if not k.startswith("_")}
+        assert "DT" in m, "meas: a measurement dict ([rows, ...] tensors) as the preintegration entries return it"
+        in_rows = m["DT"].shape[0]
+        for k, v in m.items():
+            assert v.is_cuda == cuda and v.is_contiguous() and v.dtype == torch.float64 and v.shape[0] == in_rows, \
+                "meas: contiguous float64 %s tensors of %d rows" % ("CUDA" if cuda else "CPU", in_rows)
+        for t, dt, name in ((first, torch.int64, "first [M] int64"), (count, torch.int32, "count [M] int32")):
+            assert t is None or (t.is_cuda == cuda and t.is_contiguous() and t.dtype == dt and t.dim() == 1), name
+        assert first is None or count is None or first.shape == count.shape, "first and count are both [M]"
+        if G is None:
+            assert first is None and count is None, "G (the largest group) is required with first / count"
+            G = max(in_rows, 1)                        # one group: everything joined
+        M = first.shape[0] if first is not None else count.shape[0] if count is not None else (in_rows + G - 1) // max(G, 1)
+        return m, in_rows, int(G), M
+
+    def merge(self, meas, G=None, first=None, count=None, want=("mean", "jac", "cov"), packed=False, out=None):
+        """cpi_merge_batch: consecutive preintegrated windows joined into one measurement, without the IMU readings.  meas: a
+        model-1 measurement dict of [rows, ...] CUDA tensors (what preintegrate / preintegrate_stream / ... return), the windows
+        in time order and ALL PREINTEGRATED AT THE SAME lin (the call cannot check that).  Output row j = rows first[j] ..
+        first[j] + count[j] - 1 joined, oldest first; first [M] int64 (None: group j starts at row j * G), count [M] int32 (None:
+        G rows each; clamped into [0, G]; groups are clipped at the end of meas), G = the largest group (None without first /
+        count: everything joined into one row).  Decimation to every 5th update time is merge(meas, G=5).  count 0 gives the zero
+        state, count 1 the row itself bit for bit.  want as in query: "mean", "jac", "cov" (P) and / or "cov_sym" (P_sym); the
+        Jacobians and the covariance need all five Jacobians in meas, the covariance P or P_sym as well.  packed: the outputs are
+        views of one flat buffer (alloc_outputs).  Returns a dict of [M, ...] tensors.  Asynchronous."""
+        m, in_rows, G, M = self._merge_args(meas, G, first, count, True)
+        if out is None:
+            out = self.alloc_outputs(M, tuple(want), 1, packed)
+        o = self._outputs_struct(out)
+        i = self._outputs_struct(m)
+        self._sync_stream()
+        self._check(self.lib.cpi_merge_batch(self.ctx, 1, M, G, in_rows, C.byref(i), _ptr(first), _ptr(count), C.byref(o)))
+        return out
+
+    def merge_host(self, meas, G=None, first=None, count=None, want=("mean", "jac", "cov"), packed=False, out=None, pinned=True):
+        """merge for measurements held in HOST memory (CPU tensors): cpi_merge_batch_host.  Only the fields the request reads go
+        up; the dense layout runs through the chunked pipeline, a ragged one is staged whole.  Returns a dict of CPU tensors
+        [M, ...] (packed: views of one flat buffer); synchronous; bit for bit the device form."""
+        m, in_rows, G, M = self._merge_args(meas, G, first, count, False)
+        if out is None:
+            if packed:
+                from .dist import alloc_packed
+                names = [(name, n) for name, n in OUT_FIELDS if _group_of(name) in want and name not in ("O_a", "O_b")]
+                flat, out = alloc_packed(names, M, torch.device("cpu"))
+                out["_flat"], out["_fields"] = flat, names
+            else:
+                out = self._host_outputs((M,), tuple(want), 1, pinned)
+        o = self._outputs_struct(out)
+        i = self._outputs_struct(m)
+        self._sync_stream()
+        self._check(self.lib.cpi_merge_batch_host(self.ctx, 1, M, G, in_rows, C.byref(i), _ptr(first), _ptr(count), C.byref(o)))
+        return out
+
     def preintegrate_host(self, knots, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), count=None, pinned=True, out=None):
         """Dense batch held in HOST memory (CPU float64 tensors; pinned ones overlap upload / kernels / download):
         cpi_preintegrate_batch_host.  Returns a dict of CPU tensors (page-locked when pinned=True; out= re-uses the

@@ -65,7 +65,9 @@ extern "C" {
                                stream(s): the window and the interval are found on the device);
                                cpi_running_resume_stj_batch, cpi_running_resume_stj_batch_host (model 2's Jacobian rows from a
                                carry record); cpi_query_open_batch, cpi_query_open_batch_host (the query family for a window
-                               that continues from a carried state, given as a base row) */
+                               that continues from a carried state, given as a base row); cpi_merge_batch, cpi_merge_batch_host
+                               (consecutive preintegrated windows joined into one measurement: a segmented fold over measurement
+                               rows, no IMU data) */
 
 enum { CPI_OK = 0, CPI_ERR_INVALID = 1, CPI_ERR_HIP = 2, CPI_ERR_NO_DEVICE = 3, CPI_ERR_RCCL = 4 };
 enum {
@@ -464,6 +466,52 @@ int cpi_query_open_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t
                          const double *lin, const double *q_k_lin, const cpi_outputs *rows,
                          int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out,
                          const cpi_outputs *base, int32_t base_N);
+
+/* Consecutive preintegrated windows JOINED: from the measurements of [t0, t1], [t1, t2], ... to the measurement of [t0, tn], without
+ * the IMU readings.  Keyframe decimation (camera-rate windows of one cpi_preintegrate_stream call turned into keyframe-rate windows),
+ * keyframe removal (a state leaves a smoother and the two IMU factors that met at it become one), and the building block of a
+ * parallel-in-time integration.  A segmented left fold over measurement rows:
+ *     out row j = in[first[j]] o in[first[j] + 1] o ... o in[first[j] + count[j] - 1]        (oldest first)
+ *   in      in_rows measurement rows, ordinary cpi_outputs arrays: what cpi_preintegrate_batch / _stream / ... wrote
+ *   M, G    M output rows (groups); G >= 1 is the largest group
+ *   first   [M] first input row of each group, or NULL: group j is the rows [j G, j G + count[j])
+ *   count   [M] rows of each group, or NULL: every group has G rows.  Clamped into [0, G]; a group is clipped at in_rows (first is
+ *           clamped into [0, in_rows]): both arrays live in device memory and cannot be validated by the call -- a wrong value gives a
+ *           wrong row, never a read outside in.  Groups may share and skip rows
+ *   out     arrays of M rows; any pointer may be NULL = "not wanted"; P and P_sym are independent, and a P_sym row is bit for bit the
+ *           upper triangle of the P row
+ * The composition, for A (earlier) followed by B (later), R_X = quat_2_Rot(q_X), error-state order [theta b_g v b_a p]:
+ *     DT = DT_A + DT_B      R = R_B R_A, q = rot_2_quat(R)  (the sign and branch preintegration itself would emit)
+ *     beta = beta_A + R_A^T beta_B                          alpha = alpha_A + beta_A DT_B + R_A^T alpha_B
+ *     J_q = R_B J_q_A + J_q_B                               H_b = H_b_A + R_A^T H_b_B
+ *     J_b = J_b_A + R_A^T (J_b_B + [beta_B x] J_q_A)        H_a = H_a_A + DT_B H_b_A + R_A^T H_a_B
+ *     J_a = J_a_A + DT_B J_b_A + R_A^T (J_a_B + [alpha_B x] J_q_A)
+ *     P = Phi~ P_A Phi~^T + T P_B T^T, then 0.5 (P + P^T):  T = blkdiag(I, I, R_A^T, I, R_A^T), Phi~ = T Phi(B) T^T, and Phi(B) = the
+ *         identity plus the blocks (theta,theta) R_B - I, (theta,b_g) -J_q, (v,theta) -[beta x], (v,b_g) J_b, (v,b_a) H_b,
+ *         (p,theta) -[alpha x], (p,b_g) J_a, (p,v) DT I, (p,b_a) H_a of B -- the state transition rebuilt from B's public fields.
+ * The means and Jacobians equal one preintegration of the joined window up to rounding; P equals it up to the RK4 truncation of the
+ * reference's own covariance recursion (about 1e-8 relative to sqrt(P_ii P_jj) at 200 Hz and ordinary rates; it grows like
+ * (|w| dt)^5).
+ * CONTRACT: all windows of a group were preintegrated at the SAME linearisation point {b_w_lin, b_a_lin}, with the same sigmas and
+ * imu_avg.  The call cannot see lin: rows of different lin compose into numbers that are no measurement of anything (as a chain of
+ * resume calls must keep lin, cpi_preintegrate_resume).
+ *   - count = 0 writes the zero-state row of cpi_preintegrate_running: DT = 0, alpha = beta = 0, q = [0 0 0 1], Jacobians and P zero;
+ *   - count = 1 copies the input row BIT FOR BIT in every requested field (q as it is, not requantised; with only P_sym in `in` the
+ *     dense P is that triangle mirrored);
+ *   - what out may ask for depends on what in holds (in_rows > 0): the means need DT alpha beta q; any Jacobian needs the means and
+ *     all five Jacobians; P / P_sym need the means, all five Jacobians and P or P_sym (dense P is used when given, else the packed
+ *     triangle).  A request without P / P_sym never reads in's P / P_sym; a request for the means alone reads the four mean fields
+ *     alone.
+ * Model 1 only.  Model 2 is not composable from its outputs: its alpha and beta carry gravity through each window's own q_k_lin, and
+ * q_k_lin of window k + 1 is an estimate, not R_A (x) q_k_lin.  The Forster comparator's P does not come from this recursion.  Both
+ * return CPI_ERR_INVALID, as do: in lacking a field the request needs, O_a or O_b in out, G < 1, M < 0 or in_rows < 0, an array of
+ * out overlapping an array of in, a NULL in / out.  Every refusal comes before the context is looked at.  M == 0 is a no-op.  Row
+ * offsets are computed in 64 bits.  One kernel on the context's stream, no host synchronisation: the call can be captured into a
+ * graph.
+ * Not provided: model 2 and the Forster comparator; rows of different lin; the inverse (taking a prefix away: the measurement
+ * between two running rows). */
+int cpi_merge_batch(cpi_ctx *ctx, int32_t model, int64_t M, int32_t G, int64_t in_rows, const cpi_outputs *in,
+                    const int64_t *first /*[M] or NULL*/, const int32_t *count /*[M] or NULL*/, const cpi_outputs *out);
 
 /* Replaces: the whole caller side of GraphSolver::createimufactor_cpi_v1 / _v2 (GraphSolver_IMU.cpp:43-75, 97-130) for every
  * window of a trajectory at once, reading ONE IMU stream IN PLACE: no knot is copied, for any model and any output.
@@ -866,6 +914,12 @@ int cpi_query_open_batch_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, in
                               const double *knots, const int64_t *first, const int32_t *count, int64_t n_knots,
                               const double *lin, const double *q_k_lin, const double *carry_in, double *carry_out,
                               int64_t Q, const int32_t *qwin, const double *qtime, const cpi_outputs *out);
+/* cpi_merge_batch from host memory: the same arguments, every array a host pointer; synchronous.  Only the fields of `in` that the
+ * request reads are uploaded.  The dense layout (first == NULL) with every group inside in_rows runs through the chunked upload /
+ * kernel / download pipeline of the other _host entries (the G operand rows of a group travel with it); a ragged layout is staged
+ * whole.  Bit for bit the device form on the same arguments (a group's result does not depend on the chunking). */
+int cpi_merge_batch_host(cpi_ctx *ctx, int32_t model, int64_t M, int32_t G, int64_t in_rows, const cpi_outputs *in,
+                         const int64_t *first /*[M] or NULL*/, const int32_t *count /*[M] or NULL*/, const cpi_outputs *out);
 /* cpi_preintegrate_resume from host memory: every pointer a host pointer, n_knots as in cpi_preintegrate_batch_host. */
 int cpi_preintegrate_resume_host(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t N,
                                  const double *knots, const int64_t *first, const int32_t *count,
