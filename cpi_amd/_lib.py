@@ -183,6 +183,16 @@ def load():
     lib.cpi_merge_batch.argtypes = [vp, i32, i64, i32, i64, C.POINTER(CpiOutputs), vp, vp, C.POINTER(CpiOutputs)]
     lib.cpi_merge_batch_host.argtypes = lib.cpi_merge_batch.argtypes
     lib.cpi_merge_batch.restype = lib.cpi_merge_batch_host.restype = C.c_int
+    lib.cpi_retract_batch.argtypes = lib.cpi_retract_batch_host.argtypes = [vp, i64, vp, vp, vp]
+    lib.cpi_local_batch.argtypes = lib.cpi_local_batch_host.argtypes = [vp, i64, vp, vp, vp]
+    lib.cpi_factor_cost_total_doubles.argtypes = [i64]
+    lib.cpi_factor_cost_total_doubles.restype = C.c_size_t
+    lib.cpi_factor_cost_batch.argtypes = [vp, i32, C.POINTER(C.c_double), i64, C.POINTER(CpiOutputs), vp, vp, vp, i64, vp, vp, vp, vp, vp, vp]
+    lib.cpi_factor_cost_tri_batch.argtypes = lib.cpi_factor_cost_batch.argtypes
+    lib.cpi_factor_cost_batch_host.argtypes = [vp, i32, C.POINTER(C.c_double), i64, C.POINTER(CpiOutputs), vp, vp, vp, i64, vp, vp, vp, vp, vp]
+    for f in (lib.cpi_retract_batch, lib.cpi_retract_batch_host, lib.cpi_local_batch, lib.cpi_local_batch_host, lib.cpi_factor_cost_batch,
+              lib.cpi_factor_cost_tri_batch, lib.cpi_factor_cost_batch_host):
+        f.restype = C.c_int
     lib.cpi_preintegrate_stream_running.argtypes = lib.cpi_preintegrate_stream.argtypes
     lib.cpi_preintegrate_stream_running_host.argtypes = lib.cpi_preintegrate_stream_host.argtypes
     lib.cpi_preintegrate_streams_running.argtypes = lib.cpi_preintegrate_streams.argtypes

@@ -170,6 +170,7 @@ static int probe_lds() { static int v = env_int("CPI_AMD_PROBE_LDS", 0); return 
 static bool no_overlap() { static int v = env_int("CPI_AMD_NO_OVERLAP", 0); return v != 0; }
 static bool no_fused_cut() { static int v = env_int("CPI_AMD_NO_FUSED_CUT", 0); return v != 0; }   // A/B: the workspace route for mean-only streams
 static int factor_lanes() { static int v = env_int("CPI_AMD_FACTOR_LANES", 0); return (v == 16 || v == 8 || v == 4) ? v : 0; }
+static int cost_lanes() { static int v = env_int("CPI_AMD_COST_LANES", 0); return (v == 16 || v == 8 || v == 4) ? v : 0; }
 static int packed_lpf() { static int v = env_int("CPI_AMD_PACKED_LPF", 0); return (v == 2 || v == 3 || v == 4 || v == 6 || v == 8) ? v : 0; }
 }  // namespace expsw
 #endif
@@ -1240,6 +1241,111 @@ extern "C" int cpi_predict_batch(cpi_ctx *ctx, int32_t model, const double grav[
     return CPI_OK;
 }
 
+
+// ============================================================================================
+// the optimiser's trial step: retract / localCoordinates of the states, the whitened cost at the trial states (cpi_trial.hip)
+// ============================================================================================
+// Everything these entries can refuse is refused BEFORE the context is looked at (cpi_last_error(NULL) holds the text then), as
+// cpi_merge_batch does.
+static bool bytes_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    const char *pa = (const char *)a, *pb = (const char *)b;
+    return pa && pb && na && nb && pa < pb + nb && pb < pa + na;
+}
+extern "C" int cpi_retract_batch(cpi_ctx *ctx, int64_t S, const double *states_in, const double *delta, double *states_out) {
+    static const char who[] = "cpi_retract_batch";
+    if (S < 0) return refuse(ctx, who, "negative size");
+    if (S > 0 && (!states_in || !delta || !states_out)) return refuse(ctx, who, "NULL argument");
+    const size_t ns = (size_t)S * 16 * sizeof(double), nd = (size_t)S * 15 * sizeof(double);
+    if ((states_out != states_in && bytes_overlap(states_out, ns, states_in, ns)) || bytes_overlap(states_out, ns, delta, nd) ||
+        bytes_overlap(states_in, ns, delta, nd))
+        return refuse(ctx, who, "states_out overlaps states_in or delta (states_out == states_in exactly is the in-place form), or delta overlaps states_in");
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (S == 0) return CPI_OK;
+    if (!grid_ok((S + 63) / 64)) return refuse(ctx, who, "S exceeds the 32-bit grid (64 states per workgroup)");
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    launch::retract((long long)S, states_in, delta, states_out, ctx->stream);
+    CPI_HIP(ctx, hipGetLastError());
+    return CPI_OK;
+}
+extern "C" int cpi_local_batch(cpi_ctx *ctx, int64_t S, const double *x, const double *other, double *xi) {
+    static const char who[] = "cpi_local_batch";
+    if (S < 0) return refuse(ctx, who, "negative size");
+    if (S > 0 && (!x || !other || !xi)) return refuse(ctx, who, "NULL argument");
+    const size_t ns = (size_t)S * 16 * sizeof(double), nx = (size_t)S * 15 * sizeof(double);
+    if (bytes_overlap(xi, nx, x, ns) || bytes_overlap(xi, nx, other, ns)) return refuse(ctx, who, "xi overlaps x or other");
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (S == 0) return CPI_OK;
+    if (!grid_ok((S + 63) / 64)) return refuse(ctx, who, "S exceeds the 32-bit grid (64 states per workgroup)");
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    launch::local_coordinates((long long)S, x, other, xi, ctx->stream);
+    CPI_HIP(ctx, hipGetLastError());
+    return CPI_OK;
+}
+
+extern "C" size_t cpi_factor_cost_total_doubles(int64_t F) { return launch::cost_total_doubles(F > 0 ? (long long)F : 0); }
+
+// Lanes per factor of the cost kernel (cpi_trial_kernels.hpp).  Measured on an MI355X (tools/trial_step_bench.py, 1 M factors, R packed,
+// model 1 / 2, ms): 16 lanes 0.39-0.40 / 0.42-0.43, 8 lanes 0.38 / 0.41, 4 lanes 0.43 / 0.46 -- sixteen idle fifteen lanes of sixteen through the
+// core, four need 32 KB of LDS per wavefront.  Eight at every size (profiles/trial_step.md).
+static int cost_lanes(int64_t F) {
+#ifdef CPI_EXPERIMENTS
+    if (expsw::cost_lanes()) return expsw::cost_lanes();
+#endif
+    (void)F;
+    return 8;
+}
+static int factor_cost_impl(cpi_ctx *ctx, const char *who, int32_t model, const double grav[3], int64_t F, const cpi_outputs *meas,
+                            const double *lin, const double *q_k_lin, const double *states, int64_t S, const int32_t *idx_i,
+                            const int32_t *idx_j, const double *R, bool tri, double *chi2, double *werr, double *total) {
+    if (model != CPI_MODEL_V1 && model != CPI_MODEL_V2) return refuse(ctx, who, "model must be 1 or 2");
+    if (F < 0) return refuse(ctx, who, "negative size");
+    FactorArgs a;
+    if (F > 0) {
+        if (!chi2) return refuse(ctx, who, "chi2 is NULL");
+        if (!R) return refuse(ctx, who, tri ? "R_tri is NULL" : "sqrt_info is NULL");
+        CPI_TRY(factor_args(ctx, who, model, grav, F, meas, lin, q_k_lin, states, S, idx_i, idx_j, a));
+        // no output may overlap an input or another output
+        const size_t d = sizeof(double);
+        const void *outp[3] = { chi2, werr, total };
+        const size_t outn[3] = { (size_t)F * d, (size_t)F * 15 * d, cpi_factor_cost_total_doubles(F) * d };
+        for (int o = 0; o < 3; o++) {
+            bool bad = false;
+            for (int k = 0; k < 11; k++) bad = bad || bytes_overlap(outp[o], outn[o], out_field_c(meas, k), (size_t)F * OUT_N[k] * d);
+            bad = bad || bytes_overlap(outp[o], outn[o], lin, (size_t)F * 6 * d) || bytes_overlap(outp[o], outn[o], q_k_lin, (size_t)F * 4 * d) ||
+                  bytes_overlap(outp[o], outn[o], states, (size_t)S * 16 * d) || bytes_overlap(outp[o], outn[o], idx_i, (size_t)F * sizeof(int32_t)) ||
+                  bytes_overlap(outp[o], outn[o], idx_j, (size_t)F * sizeof(int32_t)) ||
+                  bytes_overlap(outp[o], outn[o], R, (size_t)F * (tri ? CPI_TRI_DOUBLES : 225) * d);
+            for (int p = o + 1; p < 3; p++) bad = bad || bytes_overlap(outp[o], outn[o], outp[p], outn[p]);
+            if (bad) return refuse(ctx, who, o == 0 ? "chi2 overlaps an input or another output" : o == 1 ? "werr overlaps an input or another output"
+                                                                                                    : "total (the workspace) overlaps an input or another output");
+        }
+    }
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (F == 0 && !total) return CPI_OK;
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    if (F > 0) {
+        a.sqrt_info = R; a.r_tri = tri ? 1 : 0;
+        launch::factor_cost(model, cost_lanes(F), a, chi2, werr, ctx->stream);
+    }
+    if (total) launch::cost_total((long long)F, chi2, total, ctx->stream);   // F == 0: the empty sum, 0
+    CPI_HIP(ctx, hipGetLastError());
+    return CPI_OK;
+}
+extern "C" int cpi_factor_cost_batch(cpi_ctx *ctx, int32_t model, const double grav[3], int64_t F,
+                                     const cpi_outputs *meas, const double *lin, const double *q_k_lin,
+                                     const double *states, int64_t S, const int32_t *idx_i, const int32_t *idx_j,
+                                     const double *sqrt_info, double *chi2, double *werr, double *total) {
+    return factor_cost_impl(ctx, "cpi_factor_cost_batch", model, grav, F, meas, lin, q_k_lin, states, S, idx_i, idx_j, sqrt_info, false, chi2, werr, total);
+}
+extern "C" int cpi_factor_cost_tri_batch(cpi_ctx *ctx, int32_t model, const double grav[3], int64_t F,
+                                         const cpi_outputs *meas, const double *lin, const double *q_k_lin,
+                                         const double *states, int64_t S, const int32_t *idx_i, const int32_t *idx_j,
+                                         const double *R_tri, double *chi2, double *werr, double *total) {
+    return factor_cost_impl(ctx, "cpi_factor_cost_tri_batch", model, grav, F, meas, lin, q_k_lin, states, S, idx_i, idx_j, R_tri, true, chi2, werr, total);
+}
 
 extern "C" size_t cpi_outputs_slab_doubles(const cpi_outputs *mask, int64_t Wb) {
     if (!mask || Wb <= 0) return 0;
@@ -2532,5 +2638,109 @@ extern "C" int cpi_factor_eval_batch_host(cpi_ctx *ctx, int32_t model, const dou
     CPI_TRY(st.download(err, (const double *)de, (size_t)F * 15));
     if (H1) CPI_TRY(st.download(H1, (const double *)dh1, (size_t)F * 225));
     if (H2) CPI_TRY(st.download(H2, (const double *)dh2, (size_t)F * 225));
+    return st.finish();
+}
+
+// cpi_retract_batch / cpi_local_batch from host memory: staged whole, synchronous.
+extern "C" int cpi_retract_batch_host(cpi_ctx *ctx, int64_t S, const double *states_in, const double *delta, double *states_out) {
+    static const char who[] = "cpi_retract_batch_host";
+    if (S < 0) return refuse(ctx, who, "negative size");
+    if (S > 0 && (!states_in || !delta || !states_out)) return refuse(ctx, who, "NULL argument");
+    const size_t ns = (size_t)S * 16 * sizeof(double), nd = (size_t)S * 15 * sizeof(double);
+    if ((states_out != states_in && bytes_overlap(states_out, ns, states_in, ns)) || bytes_overlap(states_out, ns, delta, nd) ||
+        bytes_overlap(states_in, ns, delta, nd))
+        return refuse(ctx, who, "states_out overlaps states_in or delta (states_out == states_in exactly is the in-place form), or delta overlaps states_in");
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (S == 0) return CPI_OK;
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    Staging st(ctx);
+    const double *ds, *dd;
+    CPI_TRY(st.upload(states_in, (size_t)S * 16, &ds));
+    CPI_TRY(st.upload(delta, (size_t)S * 15, &dd));
+    double *dso = const_cast<double *>(ds);   // in place on the device copy
+    CPI_TRY(cpi_retract_batch(ctx, S, ds, dd, dso));
+    CPI_TRY(st.download(states_out, (const double *)dso, (size_t)S * 16));
+    return st.finish();
+}
+extern "C" int cpi_local_batch_host(cpi_ctx *ctx, int64_t S, const double *x, const double *other, double *xi) {
+    static const char who[] = "cpi_local_batch_host";
+    if (S < 0) return refuse(ctx, who, "negative size");
+    if (S > 0 && (!x || !other || !xi)) return refuse(ctx, who, "NULL argument");
+    const size_t ns = (size_t)S * 16 * sizeof(double), nx = (size_t)S * 15 * sizeof(double);
+    if (bytes_overlap(xi, nx, x, ns) || bytes_overlap(xi, nx, other, ns)) return refuse(ctx, who, "xi overlaps x or other");
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (S == 0) return CPI_OK;
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    Staging st(ctx);
+    const double *dx, *dox;
+    double *dxi;
+    CPI_TRY(st.upload(x, (size_t)S * 16, &dx));
+    CPI_TRY(st.upload(other, (size_t)S * 16, &dox));
+    CPI_TRY(st.alloc((size_t)S * 15, &dxi));
+    CPI_TRY(cpi_local_batch(ctx, S, dx, dox, dxi));
+    CPI_TRY(st.download(xi, (const double *)dxi, (size_t)S * 15));
+    return st.finish();
+}
+
+// GTSAM's factor.error(values) for F factors held in host memory: the covariance of the measurement (P_sym when set, else the
+// dense P packed here) is factorised on the device (cpi_sqrt_information_packed_batch), then cpi_factor_cost_tri_batch.
+extern "C" int cpi_factor_cost_batch_host(cpi_ctx *ctx, int32_t model, const double grav[3], int64_t F,
+                                          const cpi_outputs *meas, const double *lin, const double *q_k_lin,
+                                          const double *states, int64_t S, const int32_t *idx_i, const int32_t *idx_j,
+                                          double *chi2, double *werr, double *total) {
+    static const char who[] = "cpi_factor_cost_batch_host";
+    if (model != CPI_MODEL_V1 && model != CPI_MODEL_V2) return refuse(ctx, who, "model must be 1 or 2");
+    if (F < 0) return refuse(ctx, who, "negative size");
+    if (F > 0) {
+        if (!chi2) return refuse(ctx, who, "chi2 is NULL");
+        if (!meas || !lin || !states || !grav) return refuse(ctx, who, "NULL argument");
+        if (!meas->P_sym && !meas->P) return refuse(ctx, who, "meas must hold P_sym or P (the covariance that is factorised)");
+        // host pointers: the indices can be (and are) validated here; the device-pointer entries clamp them instead
+        if (S <= 0 || (!idx_i && S < F) || (!idx_j && S < F + 1)) return refuse(ctx, who, "too few states");
+        for (int64_t f = 0; f < F; f++)
+            if ((idx_i && (idx_i[f] < 0 || idx_i[f] >= S)) || (idx_j && (idx_j[f] < 0 || idx_j[f] >= S)))
+                return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": state index out of range at factor " + std::to_string(f));
+    }
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (F == 0) { if (total) total[0] = 0.0; return CPI_OK; }
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    std::vector<double> packed;   // declared BEFORE the staging: its destructor drains the stream while this buffer still exists
+    Staging st(ctx);
+    cpi_outputs d;
+    memset(&d, 0, sizeof d);
+    for (int k = 0; k < 11; k++) {   // the measurement: every field but P / P_sym
+        const double *dm;
+        CPI_TRY(st.upload((const double *)out_field_c(meas, k), (size_t)F * OUT_N[k], &dm));
+        *out_field(&d, k) = const_cast<double *>(dm);
+    }
+    const double *psym = meas->P_sym;
+    if (!psym) {   // the upper triangle of the dense P, CPI_TRI_INDEX order
+        packed.resize((size_t)F * CPI_TRI_DOUBLES);
+        for (int64_t f = 0; f < F; f++)
+            for (int k = 0; k < 15; k++)
+                for (int i = 0; i <= k; i++) packed[(size_t)f * CPI_TRI_DOUBLES + CPI_TRI_INDEX(i, k)] = meas->P[(size_t)f * 225 + k * 15 + i];
+        psym = packed.data();
+    }
+    const double *dl, *dq, *ds, *dp;
+    const int32_t *di, *dj;
+    double *dr, *dc, *dw = nullptr, *dt = nullptr;
+    CPI_TRY(st.upload(psym, (size_t)F * CPI_TRI_DOUBLES, &dp));
+    CPI_TRY(st.upload(lin, (size_t)F * 6, &dl));
+    CPI_TRY(st.upload(q_k_lin, (size_t)F * 4, &dq));
+    CPI_TRY(st.upload(states, (size_t)S * 16, &ds));
+    CPI_TRY(st.upload(idx_i, (size_t)F, &di));
+    CPI_TRY(st.upload(idx_j, (size_t)F, &dj));
+    CPI_TRY(st.alloc((size_t)F * CPI_TRI_DOUBLES, &dr));
+    CPI_TRY(st.alloc((size_t)F, &dc));
+    if (werr) CPI_TRY(st.alloc((size_t)F * 15, &dw));
+    if (total) CPI_TRY(st.alloc(cpi_factor_cost_total_doubles(F), &dt));
+    CPI_TRY(cpi_sqrt_information_packed_batch(ctx, F, dp, dr));
+    CPI_TRY(cpi_factor_cost_tri_batch(ctx, model, grav, F, &d, dl, dq, ds, S, di, dj, dr, dc, dw, dt));
+    CPI_TRY(st.download(chi2, (const double *)dc, (size_t)F));
+    if (werr) CPI_TRY(st.download(werr, (const double *)dw, (size_t)F * 15));
+    if (total) CPI_TRY(st.download(total, (const double *)dt, (size_t)1));
     return st.finish();
 }

@@ -1,6 +1,6 @@
 // cpi_args.hpp -- kernel argument blocks and the launcher interface between the translation units of libcpi_amd.so.
 //
-// The library is thirteen translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
+// The library is fourteen translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
 //   cpi_mean.hip    cpi_mean_kernel / cpi_mean_tiled_kernel / cpi_tile_*_kernel       (cpi_mean_kernels.hpp)
 //   cpi_running.hip cpi_mean_running_kernel / cpi_mean_stream_running_kernel: a row after every interval, from plain knots /
 //                   from windows cut out of IMU stream(s) in place         (cpi_running_kernels.hpp, cpi_running_body.inc)
@@ -23,6 +23,9 @@
 //                                                    (cpi_query_open_kernels.hpp over the three query bodies)
 //   cpi_merge.hip   cpi_merge_kernel: consecutive preintegrated windows joined into one measurement, a segmented left fold over
 //                   measurement rows (no IMU data is read)                             (cpi_merge_kernels.hpp)
+//   cpi_trial.hip   cpi_retract_kernel / cpi_local_kernel / cpi_factor_cost_kernel / cpi_cost_*_kernel: the optimiser's trial step --
+//                   states moved along a step, and the whitened cost of the factors there with its deterministic total
+//                                                            (cpi_trial_kernels.hpp over cpi_factor_kernels.hpp's input fetch)
 //   cpi_factor.hip  evaluateError sweeps, square-root information, Hessian blocks, state prediction
 //                                                                                      (cpi_factor_kernels.hpp)
 //   cpi_abi.hip     the C-ABI of include/cpi_amd.h: argument checks, launch heuristics, device sets (RCCL), the
@@ -268,6 +271,12 @@ void squery_cov(int model, bool avg, const StreamQueryArgs &a, const double q4[4
 void squery_jac2(bool avg, const StreamQueryArgs &a, hipStream_t st);
 // ---- cpi_merge.hip (cpi_merge_batch; jac: a.out asks for a Jacobian, cov: a.out asks for P / P_sym)
 void merge(bool jac, bool cov, const MergeArgs &a, hipStream_t st);
+// ---- cpi_trial.hip (cpi_retract_batch, cpi_local_batch, cpi_factor_cost[_tri]_batch; a.sqrt_info / a.r_tri say where R is)
+void retract(long long S, const double *states_in, const double *delta, double *states_out, hipStream_t st);
+void local_coordinates(long long S, const double *x, const double *other, double *xi, hipStream_t st);
+void factor_cost(int model, int lpf, const FactorArgs &a, double *chi2, double *werr, hipStream_t st);   // lpf 16 | 8 | 4
+size_t cost_total_doubles(long long F);
+void cost_total(long long F, const double *chi2, double *workspace, hipStream_t st);   // workspace[0] = 0.5 sum chi2
 // ---- cpi_factor.hip
 void factor(int model, bool whiten, int lpf, const FactorArgs &a, hipStream_t st);            // lpf 16 | 8 | 4
 void factor_packed(int model, int lpf, const FactorArgs &a, double *packed, hipStream_t st);  // lpf 2 | 3 | 4 | 6 | 8

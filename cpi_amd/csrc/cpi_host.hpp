@@ -915,6 +915,22 @@ inline std::vector<CpiResult> merge(const Context &ctx, const std::vector<CpiRes
     return res;
 }
 
+// JPLNavState::retract / localCoordinates (JPLNavState.cpp:37-88) over batches of states held as flat vectors: states [S * 16] =
+// [q(4) bg(3) v(3) ba(3) p(3)] per state, delta / the result of local_coordinates [S * 15] = [dtheta bg v ba p]
+// (cpi_retract_batch_host / cpi_local_batch_host: the device kernels' bits).
+inline std::vector<double> retract(const Context &ctx, const std::vector<double> &states, const std::vector<double> &delta) {
+    if (states.size() % 16 || delta.size() != states.size() / 16 * 15) throw std::invalid_argument("cpi_host::retract: states [S * 16], delta [S * 15]");
+    std::vector<double> out(states.size());
+    ctx.check(cpi_retract_batch_host(ctx.get(), (int64_t)(states.size() / 16), states.data(), delta.data(), out.data()));
+    return out;
+}
+inline std::vector<double> local_coordinates(const Context &ctx, const std::vector<double> &x, const std::vector<double> &other) {
+    if (x.size() % 16 || other.size() != x.size()) throw std::invalid_argument("cpi_host::local_coordinates: x and other [S * 16]");
+    std::vector<double> xi(x.size() / 16 * 15);
+    ctx.check(cpi_local_batch_host(ctx.get(), (int64_t)(x.size() / 16), x.data(), other.data(), xi.data()));
+    return xi;
+}
+
 // ---- the caller's loop for MANY windows at once --------------------------------------------------------------------
 // What GraphSolver keeps between two states is a deque of IMU readings (GraphSolver.h: imu_times / imu_linaccs /
 // imu_angvel, filled by addmeasurement_imu); createimufactor_cpi_v1 / _v2 (GraphSolver_IMU.cpp:34-134) walk it up to the
@@ -1199,6 +1215,16 @@ public:
         cpi_outputs o = CpiBase::outputs_of(m_);
         ctx.check(cpi_factor_eval_batch_host(ctx.get(), model_, grav_.data(), 1, &o, lin_, qk_.data(), states, 2, nullptr, nullptr,
                                              error, H1, H2));
+    }
+    // GTSAM's NoiseModelFactor::error(values) = 0.5 |R e|^2 at the two states, R = chol_upper(P_meas^-1) of the factor's own
+    // covariance, factorised on the device (cpi_factor_cost_batch_host): what an optimiser accepts or rejects a step by.
+    double error(const Context &ctx, const double *state_i, const double *state_j) {
+        double states[32], chi2 = 0.0, total = 0.0;
+        for (int i = 0; i < 16; i++) { states[i] = state_i[i]; states[16 + i] = state_j[i]; }
+        cpi_outputs o = CpiBase::outputs_of(m_);
+        ctx.check(cpi_factor_cost_batch_host(ctx.get(), model_, grav_.data(), 1, &o, lin_, qk_.data(), states, 2, nullptr, nullptr,
+                                             &chi2, nullptr, &total));
+        return total;
     }
 private:
     int model_;

@@ -1452,6 +1452,73 @@ CPI_HD NavState predict_state(const NavState &xi, V3 alpha, V3 beta, Q4 q_KtoK1,
     return o;
 }
 
+// ------------------------------------------------------------------------------------------
+// The optimiser's trial step (cpi_trial_kernels.hpp; tests/hostsim/hostsim_trial.cpp is the host restatement).
+// JPLNavState::retract (JPLNavState.cpp:37-71), in the reference's order: n = |dtheta|, dq = [sin(n/2)/n dtheta, cos(n/2)], normalise,
+// negate if dq.w < 0, the identity where that produced NaN, q' = quat_multiply(dq, q); the other twelve entries are x + delta.
+// |dtheta| and 1 / |dtheta| come from one reciprocal-square-root seed (mag_and_inverse).  The reference reaches the identity at
+// n == 0 through 0 / 0 = NaN; here |dtheta|^2 < 1e-280 (exact zero, or entries that underflow when squared) meets the clamp of
+// mag_and_inverse -- the factor sin(n/2)/n is 0.5 (device) or 0 (host) and multiplies entries of at most 1e-140, so dq is the
+// identity to 1e-140 either way -- and the NaN rule is left for non-finite steps.
+CPI_HD Q4 retract_dq(V3 dth) {
+    double n, in, s, c;
+    mag_and_inverse(dot(dth, dth), n, in);
+    sincos_fast(0.5 * n, s, c);
+    const double k = s * in;
+    Q4 dq;
+    dq.x = k * dth.x; dq.y = k * dth.y; dq.z = k * dth.z; dq.w = c;
+    const double r = inv_sqrt_unclamped(dq.x * dq.x + dq.y * dq.y + dq.z * dq.z + dq.w * dq.w);
+    dq.x *= r; dq.y *= r; dq.z *= r; dq.w *= r;
+    if (dq.w < 0) { dq.x = -dq.x; dq.y = -dq.y; dq.z = -dq.z; dq.w = -dq.w; }
+    const double chk = (dq.x + dq.y) + (dq.z + dq.w);
+    if (!(chk == chk)) { dq.x = 0.0; dq.y = 0.0; dq.z = 0.0; dq.w = 1.0; }
+    return dq;
+}
+CPI_HD NavState retract_state(const NavState &x, const double *d /*[15] = dtheta bg v ba p*/) {
+    NavState o;
+    o.q = quat_multiply(retract_dq(mk(d[0], d[1], d[2])), x.q);
+    o.bg = x.bg + ldv(d + 3); o.v = x.v + ldv(d + 6); o.ba = x.ba + ldv(d + 9); o.p = x.p + ldv(d + 12);
+    return o;
+}
+// JPLNavState::localCoordinates (JPLNavState.cpp:80-88): xi = [2 vec(quat_multiply(other.q, inv(x.q))), other - x]
+CPI_HD void local_coordinates(const NavState &x, const NavState &o, double *xi /*[15]*/) {
+    const Q4 qd = quat_multiply(o.q, quat_inv(x.q));
+    xi[0] = 2 * qd.x; xi[1] = 2 * qd.y; xi[2] = 2 * qd.z;
+    put3(xi + 3, o.bg - x.bg); put3(xi + 6, o.v - x.v); put3(xi + 9, o.ba - x.ba); put3(xi + 12, o.p - x.p);
+}
+// The whitened residual and the cost of one factor: what cpi_factor_cost_kernel calls, lane by lane.  Row i of R e: the terms
+// k = i .. 14 ascending as ONE fma chain from zero.  The loop runs k = 0 .. 14 with a zero coefficient below the diagonal, as the
+// whitening of cpi_factor_kernel does: fma(0, e[k], 0) is an exact no-op in front of the chain (for finite e), the trip count is
+// fixed and i may differ from lane to lane.  R: dense column-major [225], or the packed upper triangle [120] (TRI), whose entry
+// (i, k), i <= k, sits at i + k (k + 1) / 2 -- for k < i that index stays inside the 120 doubles and the value read is discarded.
+template <bool TRI>
+CPI_HD double whiten_row(const double *R, const double *e, int i) {
+    double acc = 0.0;
+    for (int k = 0; k < 15; k++) acc = fma((k >= i) ? (TRI ? R[k * (k + 1) / 2 + i] : R[k * 15 + i]) : 0.0, e[k], acc);
+    return acc;
+}
+// chi2 = sum_i werr_i^2, THE SUMMATION ORDER (tests reproduce it bit for bit): every square is rounded by itself (no fused
+// multiply-add), and the fifteen squares are added in ascending order, left to right:
+//     chi2 = (...((w0*w0 + w1*w1) + w2*w2) + ...) + w14*w14
+// (The library is compiled with contraction allowed everywhere, so every square passes through an empty asm statement on the device:
+// the product is a value of its own before the addition sees it.  Host builds of this header for tests use -ffp-contract=off.)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define CPI_ROUNDED(v) asm volatile("" : "+v"(v))
+#else
+#define CPI_ROUNDED(v) ((void)0)
+#endif
+CPI_HD double chi2_of(const double *w) {
+    double acc = w[0] * w[0];
+    CPI_ROUNDED(acc);
+#pragma unroll
+    for (int i = 1; i < 15; i++) {
+        double sq = w[i] * w[i];
+        CPI_ROUNDED(sq);
+        acc = acc + sq;
+    }
+    return acc;
+}
+
 // ==========================================================================================
 // Forster / GTSAM discrete preintegration comparator: what
 // GraphSolver::createimufactor_discrete (GraphSolver_IMU.cpp:141-232) obtains from GTSAM's

@@ -1182,6 +1182,135 @@ class Engine:
                                                _ptr(idx_i), _ptr(xj)))
         return xj
 
+    # ------------------------------------------------------------------ the optimiser's trial step
+    @staticmethod
+    def _trial_tensor(t, cols, cuda, name, rows=None):
+        assert (t.dtype == torch.float64 and t.is_contiguous() and t.is_cuda == cuda and t.dim() == 2 and t.shape[1] == cols
+                and (rows is None or t.shape[0] == rows)), \
+            "%s: a contiguous float64 %s tensor [%s, %d]" % (name, "CUDA" if cuda else "CPU", "S" if rows is None else rows, cols)
+
+    def _retract(self, fn, states, delta, out, cuda):
+        self._trial_tensor(states, 16, cuda, "states")
+        S = states.shape[0]
+        self._trial_tensor(delta, 15, cuda, "delta", S)
+        if out is None:
+            out = torch.empty_like(states)
+        self._trial_tensor(out, 16, cuda, "out", S)
+        self._sync_stream()
+        self._check(fn(self.ctx, S, _ptr(states), _ptr(delta), _ptr(out)))
+        return out
+
+    def retract(self, states, delta, out=None):
+        """cpi_retract_batch: out[s] = JPLNavState::retract(states[s], delta[s]) -- the map along which H1 / H2 of the factor sweeps
+        are derivatives.  states [S,16] = [q bg v ba p], delta [S,15] = [dtheta bg v ba p], CUDA float64.  out=states is the
+        in-place form (same bits); any other overlap is refused.  Asynchronous."""
+        return self._retract(self.lib.cpi_retract_batch, states, delta, out, True)
+
+    def retract_host(self, states, delta, out=None):
+        """retract on CPU tensors (cpi_retract_batch_host): synchronous, the device form's bits."""
+        return self._retract(self.lib.cpi_retract_batch_host, states, delta, out, False)
+
+    def _local(self, fn, x, other, out, cuda):
+        self._trial_tensor(x, 16, cuda, "x")
+        S = x.shape[0]
+        self._trial_tensor(other, 16, cuda, "other", S)
+        if out is None:
+            out = torch.empty((S, 15), dtype=torch.float64, device=x.device)
+        self._trial_tensor(out, 15, cuda, "out", S)
+        self._sync_stream()
+        self._check(fn(self.ctx, S, _ptr(x), _ptr(other), _ptr(out)))
+        return out
+
+    def local_coordinates(self, x, other, out=None):
+        """cpi_local_batch: xi[s] = JPLNavState::localCoordinates(x[s], other[s]) = [2 vec(other.q (x) inv(x.q)), other - x], [S,15].
+        Asynchronous."""
+        return self._local(self.lib.cpi_local_batch, x, other, out, True)
+
+    def local_coordinates_host(self, x, other, out=None):
+        """local_coordinates on CPU tensors (cpi_local_batch_host): synchronous, the device form's bits."""
+        return self._local(self.lib.cpi_local_batch_host, x, other, out, False)
+
+    def factor_cost_total_doubles(self, F):
+        """Doubles of the workspace behind the total of factor_cost (cpi_factor_cost_total_doubles)."""
+        return int(self.lib.cpi_factor_cost_total_doubles(int(F)))
+
+    def _cost_common(self, meas, lin, q_k_lin, states, idx_i, idx_j, cuda):
+        F = lin.shape[0]
+        self._trial_tensor(lin, 6, cuda, "lin")
+        self._trial_tensor(states, 16, cuda, "states")
+        if q_k_lin is not None:
+            self._trial_tensor(q_k_lin, 4, cuda, "q_k_lin", F)
+        for name, t in (("idx_i", idx_i), ("idx_j", idx_j)):
+            assert t is None or (t.dtype == torch.int32 and t.is_contiguous() and t.is_cuda == cuda and t.shape == (F,)), \
+                "%s: a contiguous int32 %s tensor [F]" % (name, "CUDA" if cuda else "CPU")
+        for k, v in meas.items():
+            if not k.startswith("_"):
+                assert v.dtype == torch.float64 and v.is_contiguous() and v.is_cuda == cuda and v.shape[0] == F, \
+                    "meas[%r]: a contiguous float64 %s tensor of F rows" % (k, "CUDA" if cuda else "CPU")
+        return F
+
+    def factor_cost(self, model, meas, lin, q_k_lin, states, sqrt_info, idx_i=None, idx_j=None, grav=DEFAULT_GRAV, want_err=False,
+                    want_total=True, out=None):
+        """cpi_factor_cost_batch / _tri_batch: the cost of the F factors at `states` -- GTSAM's NoiseModelFactor::error summed over the
+        graph -- without the 3.7 KB of Jacobians per factor of factor_eval.  sqrt_info [F,225] or its packed triangle [F,120] (from
+        sqrt_information; same bits).  Returns a dict:
+          "chi2"       [F]     |R e|^2 per factor, always
+          "werr"       [F,15]  R e (want_err)
+          "workspace"  [factor_cost_total_doubles(F)]  the caller-visible buffer behind the total (want_total)
+          "total"      [1]     0.5 sum chi2: a view of workspace[:1] -- reading it never synchronises, and its bits do not depend on
+                               the run or on want_err
+        out= re-uses the tensors of an earlier call (graph capture): a dict with "chi2", with "werr" when want_err and with
+        "workspace" when want_total (asserted; "total" is set to the view when missing).  A "werr" or "workspace" that out holds
+        beyond the flags is written too: the keys of out say what the call fills.  Asynchronous."""
+        F = self._cost_common(meas, lin, q_k_lin, states, idx_i, idx_j, True)
+        assert sqrt_info.dim() == 2 and sqrt_info.shape[0] == F and sqrt_info.shape[1] in (225, 120), \
+            "sqrt_info: [F,225] dense or [F,120] packed triangle"
+        self._trial_tensor(sqrt_info, sqrt_info.shape[1], True, "sqrt_info", F)
+        if out is None:
+            out = {"chi2": torch.empty((F,), dtype=torch.float64, device=self.device)}
+            if want_err:
+                out["werr"] = torch.empty((F, 15), dtype=torch.float64, device=self.device)
+            if want_total:
+                out["workspace"] = torch.empty((self.factor_cost_total_doubles(F),), dtype=torch.float64, device=self.device)
+        else:
+            assert "chi2" in out and (not want_err or "werr" in out) and (not want_total or "workspace" in out), \
+                "out: a dict with 'chi2', with 'werr' when want_err and with 'workspace' when want_total"
+        chi2, werr, ws = out["chi2"], out.get("werr"), out.get("workspace")
+        assert chi2.dtype == torch.float64 and chi2.is_cuda and chi2.is_contiguous() and chi2.shape == (F,), "out['chi2']: CUDA float64 [F]"
+        if werr is not None:
+            self._trial_tensor(werr, 15, True, "out['werr']", F)
+        assert ws is None or (ws.dtype == torch.float64 and ws.is_cuda and ws.is_contiguous() and ws.dim() == 1
+                              and ws.numel() >= self.factor_cost_total_doubles(F)), \
+            "out['workspace']: CUDA float64, factor_cost_total_doubles(F) elements"
+        if ws is not None:
+            out["total"] = ws[:1]
+        m = self._outputs_struct(meas)
+        g = (C.c_double * 3)(*grav)
+        self._sync_stream()
+        fn = self.lib.cpi_factor_cost_batch if sqrt_info.shape[1] == 225 else self.lib.cpi_factor_cost_tri_batch
+        self._check(fn(self.ctx, int(model), g, F, C.byref(m), _ptr(lin), _ptr(q_k_lin), _ptr(states), states.shape[0], _ptr(idx_i),
+                       _ptr(idx_j), _ptr(sqrt_info), _ptr(chi2), _ptr(werr), _ptr(ws)))
+        return out
+
+    def factor_cost_host(self, model, meas, lin, q_k_lin, states, idx_i=None, idx_j=None, grav=DEFAULT_GRAV, want_err=False,
+                         want_total=True):
+        """cpi_factor_cost_batch_host on CPU tensors: GTSAM's factor.error(values) for F factors in one call.  meas holds the
+        measurement with its covariance ("P_sym" [F,120] when present, else "P" [F,225]); the square-root information is
+        factorised on the device.  Returns CPU tensors {"chi2", "werr" (want_err), "total" [1] (want_total)}; synchronous."""
+        F = self._cost_common(meas, lin, q_k_lin, states, idx_i, idx_j, False)
+        out = {"chi2": torch.empty((F,), dtype=torch.float64)}
+        if want_err:
+            out["werr"] = torch.empty((F, 15), dtype=torch.float64)
+        if want_total:
+            out["total"] = torch.empty((1,), dtype=torch.float64)
+        m = self._outputs_struct(meas)
+        g = (C.c_double * 3)(*grav)
+        self._sync_stream()
+        self._check(self.lib.cpi_factor_cost_batch_host(self.ctx, int(model), g, F, C.byref(m), _ptr(lin), _ptr(q_k_lin), _ptr(states),
+                                                        states.shape[0], _ptr(idx_i), _ptr(idx_j), _ptr(out["chi2"]),
+                                                        _ptr(out.get("werr")), _ptr(out.get("total"))))
+        return out
+
 
 def unpack_factor(packed, meas):
     """Dense (err [F,15], H1 [F,225], H2 [F,225], column-major) from the packed evaluation and the measurement it was
@@ -1217,6 +1346,21 @@ def default_engine():
     if _default_engine is None:
         _default_engine = Engine()
     return _default_engine
+
+
+def retract(states, delta, out=None):
+    """Engine.retract on the default engine."""
+    return default_engine().retract(states, delta, out)
+
+
+def local_coordinates(x, other, out=None):
+    """Engine.local_coordinates on the default engine."""
+    return default_engine().local_coordinates(x, other, out)
+
+
+def factor_cost(*args, **kw):
+    """Engine.factor_cost on the default engine."""
+    return default_engine().factor_cost(*args, **kw)
 
 
 # ---------------------------------------------------------------------- reference-shaped classes

@@ -67,7 +67,11 @@ extern "C" {
                                carry record); cpi_query_open_batch, cpi_query_open_batch_host (the query family for a window
                                that continues from a carried state, given as a base row); cpi_merge_batch, cpi_merge_batch_host
                                (consecutive preintegrated windows joined into one measurement: a segmented fold over measurement
-                               rows, no IMU data) */
+                               rows, no IMU data); cpi_retract_batch, cpi_local_batch, cpi_factor_cost_batch,
+                               cpi_factor_cost_tri_batch, cpi_factor_cost_total_doubles and the host forms
+                               cpi_retract_batch_host, cpi_local_batch_host, cpi_factor_cost_batch_host (the optimiser's trial
+                               step: the states moved along a solved step, and the whitened cost 0.5 |R e|^2 of the factors at
+                               the trial states with a deterministic total) */
 
 enum { CPI_OK = 0, CPI_ERR_INVALID = 1, CPI_ERR_HIP = 2, CPI_ERR_NO_DEVICE = 3, CPI_ERR_RCCL = 4 };
 enum {
@@ -791,6 +795,53 @@ int cpi_predict_batch(cpi_ctx *ctx, int32_t model, const double grav[3], int64_t
                       const cpi_outputs *meas, const double *states_i, int64_t S, const int32_t *idx_i,
                       double *states_j);
 
+/* ---- The optimiser's trial step.  With cpi_factor_hessian_* these close the loop
+ *     linearise -> solve (the caller's) -> retract -> cost -> accept / reject
+ * on the device: none of them synchronises the host, and each is a chain of kernels without branches on the context's stream, so
+ * the whole iteration captures into one graph.  No solver is provided.
+ *
+ * cpi_retract_batch replaces: JPLNavState::retract (gtsam/JPLNavState.cpp:37-71), the map along which every H1 / H2 of the
+ * evaluateError sweeps is a derivative.  states_out[s] = retract(states_in[s], delta[s]):
+ *   states  [S][16] = [q(4) bg(3) v(3) ba(3) p(3)];  delta [S][15] = [dtheta bg v ba p]
+ *   n = |dtheta|, dq = [sin(n/2)/n dtheta, cos(n/2)], normalised, negated if dq.w < 0, the identity where that gave NaN (the
+ *   reference's n == 0: 0 / 0), q_out = quat_multiply(dq, q) with its own normalisation and w >= 0 flip; the other twelve entries
+ *   are x + delta, bit for bit the IEEE sums.  A zero step therefore gives quat_multiply(identity, q), not a copy of q.
+ * IN PLACE: states_out may equal states_in exactly (same bits as the out-of-place call).  Any other overlap among the three arrays
+ * is CPI_ERR_INVALID ("overlaps" in cpi_last_error).
+ * cpi_local_batch replaces: JPLNavState::localCoordinates (JPLNavState.cpp:80-88):
+ *   xi[s][0..2] = 2 vec(quat_multiply(other[s].q, inv(x[s].q))),  xi[s][3..14] = other[s][4..15] - x[s][4..15]  (IEEE differences).
+ * xi may not overlap x or other.  Both: S == 0 is a no-op; NULL pointers and S < 0 are CPI_ERR_INVALID; every refusal comes
+ * before the context is looked at. */
+int cpi_retract_batch(cpi_ctx *ctx, int64_t S, const double *states_in, const double *delta, double *states_out);
+int cpi_local_batch(cpi_ctx *ctx, int64_t S, const double *x, const double *other, double *xi);
+
+/* The cost of F factors at the given states.  Replaces: GTSAM's NoiseModelFactor::error(values) = 0.5 |R e|^2 for every factor of
+ * the graph, and their sum (GTSAM is absent from the reference tree: PARITY UNPINNED like the other entries of SURVEY.md 8 f1) --
+ * what Levenberg-Marquardt / dogleg accept or reject a step by, what a line search evaluates, what gates outliers (chi2 is the
+ * squared Mahalanobis distance).  Arguments as cpi_factor_eval_whitened_batch / _tri_batch; state indices are clamped into [0, S).
+ *   sqrt_info [F][225] dense column-major upper-triangular R (cpi_sqrt_information_batch) / R_tri [F][120] its packed triangle
+ *   chi2   [F]      required: chi2[f] = sum_i werr_i^2 -- every square rounded by itself (no fused multiply-add), added in ascending
+ *                   order left to right, (..((w0 w0 + w1 w1) + w2 w2) + ..) + w14 w14.  It is the `f` entry (30, 30) of
+ *                   cpi_factor_hessian_* up to rounding (that one is e^T (R^T R) e)
+ *   werr   [F][15]  or NULL: R e, bit for bit the err of cpi_factor_eval_whitened[_tri]_batch on the same inputs
+ *   total  NULL, or a workspace of cpi_factor_cost_total_doubles(F) doubles: element 0 receives 0.5 * sum_f chi2[f], the rest is
+ *          scratch for partial sums.  The library allocates nothing.  A reduction of fixed shape without floating-point atomics,
+ *          enqueued behind the cost kernel: the same inputs give the same bits on every run, with or without werr.
+ * The dense and the packed form give the same bits.  A factor whose R holds NaN (cpi_sqrt_information_* met a non-positive pivot)
+ * gets chi2 = NaN and makes total NaN; the other factors are not affected.
+ * No output may overlap an input or another output: CPI_ERR_INVALID, "overlaps" in cpi_last_error.  Also refused: a model other
+ * than 1 and 2, F < 0, NULL chi2 / R / required input, what cpi_factor_eval_batch refuses.  Every refusal comes before the context
+ * is looked at.  F == 0 writes total[0] = 0 when total is given. */
+size_t cpi_factor_cost_total_doubles(int64_t F);
+int cpi_factor_cost_batch(cpi_ctx *ctx, int32_t model, const double grav[3], int64_t F,
+                          const cpi_outputs *meas, const double *lin, const double *q_k_lin,
+                          const double *states, int64_t S, const int32_t *idx_i, const int32_t *idx_j,
+                          const double *sqrt_info, double *chi2, double *werr, double *total);
+int cpi_factor_cost_tri_batch(cpi_ctx *ctx, int32_t model, const double grav[3], int64_t F,
+                              const cpi_outputs *meas, const double *lin, const double *q_k_lin,
+                              const double *states, int64_t S, const int32_t *idx_i, const int32_t *idx_j,
+                              const double *R_tri, double *chi2, double *werr, double *total);
+
 /* ---- Device sets: the 8-GPU path of a single-process host (nothing in the reference, which is a
  * single-threaded CPU program).  Windows (and factors) are independent units: rank r of n owns the contiguous block
  * [lo, hi) = cpi_shard_bounds(W, r, n) (block size ceil(W / n); trailing ranks may be short or empty), runs the ordinary
@@ -979,6 +1030,20 @@ int cpi_factor_eval_batch_host(cpi_ctx *ctx, int32_t model, const double grav[3]
                                const cpi_outputs *meas, const double *lin, const double *q_k_lin,
                                const double *states, int64_t S, const int32_t *idx_i,
                                const int32_t *idx_j, double *err, double *H1, double *H2);
+
+/* cpi_retract_batch / cpi_local_batch from host memory: every pointer a host pointer, synchronous, the same rules (states_out may
+ * equal states_in); the device forms' bits. */
+int cpi_retract_batch_host(cpi_ctx *ctx, int64_t S, const double *states_in, const double *delta, double *states_out);
+int cpi_local_batch_host(cpi_ctx *ctx, int64_t S, const double *x, const double *other, double *xi);
+/* GTSAM's factor.error(values) for F factors in ONE call, from host memory: the covariance of each measurement -- meas->P_sym when
+ * set, else the dense meas->P, whose upper triangle is packed first -- is factorised on the device
+ * (cpi_sqrt_information_packed_batch) and cpi_factor_cost_tri_batch runs on the result.  idx_i / idx_j are validated as
+ * cpi_factor_eval_batch_host validates them.  chi2 [F] required, werr [F][15] or NULL, total [1] or NULL (0.5 * sum chi2; no
+ * workspace: the staging holds it).  Synchronous. */
+int cpi_factor_cost_batch_host(cpi_ctx *ctx, int32_t model, const double grav[3], int64_t F,
+                               const cpi_outputs *meas, const double *lin, const double *q_k_lin,
+                               const double *states, int64_t S, const int32_t *idx_i, const int32_t *idx_j,
+                               double *chi2, double *werr, double *total);
 
 #ifdef __cplusplus
 }
