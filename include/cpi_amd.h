@@ -493,6 +493,15 @@ int cpi_query_open_batch(cpi_ctx *ctx, const cpi_params *prm, int64_t W, int32_t
  *     P = Phi~ P_A Phi~^T + T P_B T^T, then 0.5 (P + P^T):  T = blkdiag(I, I, R_A^T, I, R_A^T), Phi~ = T Phi(B) T^T, and Phi(B) = the
  *         identity plus the blocks (theta,theta) R_B - I, (theta,b_g) -J_q, (v,theta) -[beta x], (v,b_g) J_b, (v,b_a) H_b,
  *         (p,theta) -[alpha x], (p,b_g) J_a, (p,v) DT I, (p,b_a) H_a of B -- the state transition rebuilt from B's public fields.
+ *         The (v,v) and (p,p) blocks of Phi~ are I and its (p,v) block is DT_B I BY CONSTRUCTION: the products R_A^T I R_A and
+ *         R_A^T (DT_B I) R_A are never formed.
+ * Operand quaternions are taken AS GIVEN and not normalised: R_X = quat_2_Rot(q_X) is orthonormal only as far as q_X is unit.  A q
+ * off unit by eps (| |q|^2 - 1 | = eps; 6e-8 for a q that went through float32) moves the joined means and Jacobians by O(eps)
+ * times their size: the caller's input error, passed on and not amplified.  With the three blocks above held at I, I and DT_B I the
+ * covariance of such operands stays the covariance of the NORMALISED quaternions to O(eps) as well (a fold of 8 float32 operands: 4e-7
+ * relative; the dense triple product would put R_A^T R_A there and be ten times further off).  The q written for a joined row is normalised, with w >= 0.  -q is the same
+ * operand as q (quat_2_Rot is even in q): every output is the same bit for bit.  A zero-state row among the operands (first, last or
+ * inside a group) is the identity of the composition: every field but q comes out bit for bit as without it, q to rounding.
  * The means and Jacobians equal one preintegration of the joined window up to rounding; P equals it up to the RK4 truncation of the
  * reference's own covariance recursion (about 1e-8 relative to sqrt(P_ii P_jj) at 200 Hz and ordinary rates; it grows like
  * (|w| dt)^5).

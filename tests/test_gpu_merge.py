@@ -6,7 +6,11 @@ composition (tests/merge_cases.py: dense 15 x 15 algebra) folded over the SAME r
 composition equals one integration of the joined window is tests/test_merge_cpu.py's claim, and the end-to-end test's below.
 
 Floor (MI355X, this file's cases, profiles/merge_bench.md): see FLOOR_*; the gates are about 100 x the floor, following the policy at
-the top of tests/tol.py."""
+the top of tests/tol.py.
+
+Section 9 asks the same of hard operands (merge_cases.hard_rows: rotations past 3 rad and every branch of rot_2_quat, negated and
+float32 quaternions, zero-state rows as operands), of a fold of 40, of merged rows merged again, and of the merge against one
+preintegration at 20 rad/s."""
 import ctypes as C
 import itertools
 
@@ -25,6 +29,9 @@ W, N, S = 257, 40, 8
 # (profiles/merge_bench.md): means 8.9e-16 (beta, G = 8), Jacobians 1.1e-16 (J_b, G = 8), P 2.5e-14 relative to sqrt(P_ii P_jj)
 # (G = 8; 2e-15 to 4.5e-15 at G = 3).  Gates = about 100 x the floor; they replace the provisional gates the issue set until the
 # measurement (REG_MEAN = 2e-13, REG_JAC = 3e-11, 1e-10 relative for P) and are tighter than each of them.
+# The 2.5e-14 for P was the restatement's own: its dense T Phi(B) T^T carried R_A^T R_A where the kernel keeps I.  Against the
+# restatement with those blocks set (merge_cases.compose, identity_blocks, the default now) the same cases measure 8.4e-16, and the
+# hard rows of section 9 below 6.8e-16 (means 4.4e-16, Jacobians 8.3e-17).  The gates stay as they were.
 FLOOR_MEAN, FLOOR_JAC, FLOOR_COV = 8.9e-16, 1.1e-16, 2.5e-14
 GATE_MEAN, GATE_JAC, GATE_COV = 1e-13, 1e-14, 3e-12
 assert GATE_MEAN <= REG_MEAN and GATE_JAC <= REG_JAC and GATE_COV <= 1e-10
@@ -66,15 +73,7 @@ def _only(d, *drop):
 
 def _ragged(M, G, in_rows, seed):
     """first / count with every count 0 .. G, counts past G and below 0, groups that reach and pass the end of the input."""
-    g = np.random.default_rng(seed)
-    first = g.integers(0, in_rows - G, size=M).astype(np.int64)
-    count = g.integers(0, G + 1, size=M).astype(np.int32)
-    if M >= 4:
-        first[-1], count[-1] = in_rows - 1, G          # clipped to one row (G > 1) -> the row itself
-        count[0] = G + 3                               # clamped to G
-        count[1] = -2                                  # clamped to 0
-        first[2] = in_rows                             # nothing left
-    return first, count
+    return mc.ragged_groups(M, G, in_rows, seed)
 
 
 def _check(got, want, label):
@@ -203,6 +202,221 @@ def test_decimated_stream_matches_preintegration_at_every_fifth_update_time(eng,
     bad = [(k, e) for k, e in d.items() if not e <= (TOL_MEAN if k in mc.MEAN else TOL_COV if k == "P" else TOL_JAC)]
     assert got["DT"].shape == (8,) and not bad, bad
     assert cov_rel_err(got["P"], ref["P"]) > 0                          # two different computations, not one copied
+
+
+# ------------------------------------------------------------------------------------------------ 9. hard operands
+# merge_cases.hard_rows written by Engine.preintegrate: rates of up to 20 rad/s (joined rotations past 3 rad, all four branches of
+# rot_2_quat), q negated, q unit only to float32, a zero-state row among the operands, and the 40 x 64 one-interval rows of a long
+# fold.  The gates of the hard rows are GATE_* above, unchanged.  The long fold (G = 40) has gates of its own: LONG_*.
+ULP = 2.0 ** -52
+HARD_ROWS = mc.HARD_W * mc.HARD_S
+# Measured on the MI355X against the longdouble restatement, the worse of the uniform and the mixed-count call of
+# test_device_matches_the_restatement_on_a_fold_of_forty (profiles/merge_bench.md 4): means 8.9e-16 (beta, uniform), Jacobians
+# 1.7e-16 (J_b, uniform), P 1.7e-15 relative to sqrt(P_ii P_jj) (uniform; mixed 1.3e-15).  Gates = about 100 x the floor (the policy
+# at the top of tests/tol.py); the first run was made with GATE_* as provisional gates and passed them.
+LONG_FLOOR_MEAN, LONG_FLOOR_JAC, LONG_FLOOR_COV = 8.9e-16, 1.7e-16, 1.7e-15
+LONG_GATE_MEAN, LONG_GATE_JAC, LONG_GATE_COV = 1e-13, 2e-14, 2e-13
+assert LONG_GATE_MEAN <= TOL_MEAN and LONG_GATE_JAC <= TOL_JAC and LONG_GATE_COV <= TOL_COV
+
+
+class _Hard:
+    """The hard rows on the host (what was read back, then the regimes) and on the device, the rows as Engine.preintegrate wrote them
+    (raw: the end-to-end test's), and the longdouble references every test below shares: each computed once, never written to."""
+    def __init__(self, eng):
+        self.prm = eng.make_params(1, True)
+        parts = []
+
+        def measure(kn, lin):
+            parts.append(eng.preintegrate(kn.to(eng.device), lin.to(eng.device), params=self.prm, want=WANTS))
+            return parts[-1]
+        self.host, self.regime, self.long_host = mc.hard_rows(measure)
+        self.raw = mc.stack_rows(parts[:mc.HARD_S])
+        up = lambda d: {k: torch.from_numpy(v).to(eng.device) for k, v in d.items()}
+        self.dev, self.long_dev, self.raw_dev = up(self.host), up(self.long_host), up(self.raw)
+        self._refs = {}
+
+    def ref(self, which, M, G, layout):
+        """(reference, the branch of rot_2_quat of every row, first, count).  A dense reference is computed for all its groups once
+        and cut to M rows: row j does not depend on M."""
+        full = {"rows": mc.HARD_W, "long": mc.LONG_W}[which] if layout != "ragged" else M
+        key = (which, full, G, layout)
+        if key not in self._refs:
+            meas = self.host if which == "rows" else self.long_host
+            first, count = mc.ragged_groups(M, G, HARD_ROWS, 100 * M + G) if layout == "ragged" else (None, None)
+            if layout == "mixed":
+                count = mc.long_counts()
+            want, S = mc.merge_ref(meas, full, G, first, count, np.longdouble, state=True)
+            self._refs[key] = (want, mc.branch_of(S["R"]), first, count)
+        want, branch, first, count = self._refs[key]
+        return {k: v[:M] for k, v in want.items()}, branch[:M], first, count
+
+
+@pytest.fixture(scope="module")
+def hard(eng):
+    return _Hard(eng)
+
+
+def _gated(got, want, label, gates=(GATE_MEAN, GATE_JAC, GATE_COV)):
+    d = mc.deviations(got, want)
+    print("%s: %s" % (label, ", ".join("%s %.2e" % kv for kv in d.items())))
+    bad = [(k, e) for k, e in d.items() if not e <= (gates[0] if k in mc.MEAN else gates[2] if k == "P" else gates[1])]
+    assert not bad, (label, bad)
+    return d
+
+
+def _by(got, want, label_of, names, head):
+    for name, dd in mc.deviations_by(got, want, label_of, names).items():
+        print("    %s %-28s means %.2e  Jacobians %.2e  P %.2e" % ((head, name) + mc.worst(dd)))
+
+
+def _q_is_canonical(q, label):
+    q = np.asarray(q, dtype=np.longdouble)
+    assert (q[:, 3] >= 0).all(), label
+    assert np.abs(np.sqrt((q * q).sum(-1)) - 1).max(initial=0) <= 4 * ULP, label
+
+
+def _dev(eng, a, dtype=None):
+    return None if a is None else torch.from_numpy(np.asarray(a, dtype=dtype)).to(eng.device)
+
+
+def test_hard_rows_reach_every_branch_of_rot_2_quat_on_the_reference(hard):
+    """The coverage the tests below rely on, asserted on the longdouble reference of the rows the device wrote, never on an output."""
+    want, branch, _, _ = hard.ref("rows", mc.HARD_W, mc.HARD_S, "dense")
+    taken, angle = np.bincount(branch, minlength=4), mc.joined_angle(want["q"])
+    print("hard rows, G 8: branches %s taken %s times, largest angle %.3f rad, smallest |w| %.2e" % (mc.BRANCHES, taken, angle.max(), np.abs(want["q"][:, 3]).min()))
+    assert taken.min() >= 30 and angle.max() > 3.0 and np.abs(want["q"][:, 3]).min() >= 1e-3, (taken, angle.max())
+    off = np.abs((hard.host["q"] ** 2).sum(-1) - 1).reshape(mc.HARD_W, mc.HARD_S)
+    assert 1e-9 < off[hard.regime == 2].max() <= 2.0 ** -22 and off[hard.regime != 2].max() <= 4 * ULP
+
+
+@pytest.mark.parametrize("G", (2, 3, 8))
+@pytest.mark.parametrize("M", (1, 3, 4, 5, 256))
+def test_device_matches_the_longdouble_restatement_on_the_hard_rows(eng, hard, M, G):
+    """The gates of the gentle rows, unchanged, on every row of every regime: dense and ragged, P read dense and packed (bit for bit
+    the same).  -s prints the worst error per regime and per branch of rot_2_quat (the branch the REFERENCE takes)."""
+    for layout in ("dense", "ragged"):
+        want, branch, first, count = hard.ref("rows", M, G, layout)
+        f = _dev(eng, first)
+        c = _dev(eng, count) if count is not None else torch.full((M,), G, dtype=torch.int32, device=eng.device)
+        got = _np(eng.merge(_only(hard.dev, "P_sym"), G=G, first=f, count=c, want=WANTS))
+        _gated(got, want, "hard rows, %s M %d G %d" % (layout, M, G))
+        if M == mc.HARD_W:
+            _by(got, want, mc.group_regime(M, G, first), mc.REGIMES, "regime")
+            _by(got, want, branch, mc.BRANCHES, "branch")
+        tri = _np(eng.merge(_only(hard.dev, "P"), G=G, first=f, count=c, want=WANTS))
+        for k in FIELDS:
+            assert np.array_equal(tri[k], got[k]), ("P_sym input", layout, k)
+        n = np.full(M, G) if first is None else np.minimum(np.clip(count, 0, G), HARD_ROWS - np.clip(first, 0, HARD_ROWS))
+        _q_is_canonical(got["q"][n > 1], (layout, M, G))
+
+
+@pytest.mark.parametrize("layout", ("dense", "mixed"))
+def test_device_matches_the_restatement_on_a_fold_of_forty(eng, hard, layout):
+    """64 groups of 40 one-interval rows: every count 40, and counts of 0 .. 40 with 40, 0, 1 and 39 inside one wavefront -- groups
+    that are done idle through up to 40 trips while their neighbours exchange through LDS."""
+    want, _, first, count = hard.ref("long", mc.LONG_W, mc.LONG_G, layout)
+    n = np.full(mc.LONG_W, mc.LONG_G, dtype=np.int32) if count is None else count
+    got = _np(eng.merge(hard.long_dev, G=mc.LONG_G, count=_dev(eng, n), want=WANTS))
+    _gated(got, want, "fold of 40, %s" % layout, (LONG_GATE_MEAN, LONG_GATE_JAC, LONG_GATE_COV))
+    _q_is_canonical(got["q"][n > 1], layout)
+    zero = mc.meas_of(mc.zero_state(1))
+    for j in np.nonzero(n == 0)[0]:
+        for k in FIELDS:
+            assert np.array_equal(got[k][j], np.asarray(zero[k][0], dtype=np.float64)), (j, k)
+    for j in np.nonzero(n == 1)[0]:
+        for k in FIELDS:
+            assert np.array_equal(got[k][j], hard.long_host[k][j * mc.LONG_G]), (j, k)
+
+
+def test_zero_state_operands_and_negated_quaternions_on_the_device(eng, hard):
+    """A zero-state row before or after a row X gives X bit for bit in everything but q, and q within 4 ulp; -q is the same operand
+    as q: every output field bit for bit."""
+    X = {k: v.reshape(mc.HARD_W, mc.HARD_S, -1)[hard.regime == 0].reshape(64 * mc.HARD_S, -1) for k, v in hard.host.items()}
+    zero = {k: np.zeros_like(v) for k, v in X.items()}
+    zero["q"][:, 3] = 1.0
+    for name, pair in (("zero first", (zero, X)), ("zero second", (X, zero))):
+        rows = {k: np.stack([pair[0][k], pair[1][k]], 1).reshape(2 * 64 * mc.HARD_S, -1) for k in X}
+        rows["DT"] = rows["DT"].reshape(-1)
+        out = _np(eng.merge({k: _dev(eng, v) for k, v in rows.items()}, G=2, want=WANTS))
+        for k in FIELDS:
+            if k != "q":
+                assert np.array_equal(out[k].reshape(X[k].shape), X[k]), (name, k)
+        assert np.abs(out["q"] - X["q"]).max() <= 4 * ULP, name
+    flipped = dict(hard.dev)
+    flipped["q"] = hard.dev["q"].clone()
+    flipped["q"][1::2] *= -1
+    for G in (2, 3, 8):
+        a, b = _np(eng.merge(flipped, G=G, want=WANTS)), _np(eng.merge(hard.dev, G=G, want=WANTS))
+        for k in FIELDS:
+            assert np.array_equal(a[k][:HARD_ROWS // G], b[k][:HARD_ROWS // G]), (G, k)      # (a last group of one row copies its q)
+
+
+def test_merged_rows_merge_again(eng, hard):
+    """8 -> 4 -> 2 -> 1 rows per window through three calls, each reading what the one before wrote on the device.  Against the flat
+    longdouble fold of 8 at GATE_*, and against the device's own flat fold within twice the gates.
+    The 64 windows whose operand quaternions are unit only to float32 are held to a bound of their own, from their defect and not
+    from a measurement: every pairwise call normalises the q it writes, the flat fold carries the product of the eight un-normalised
+    rotations, so the two differ by the operands' own defect.  | |q|^2 - 1 | <= 2^-22 moves an operand's R by as much, relative;
+    eight operands: the means and Jacobians move by at most 8 x 2^-22 x their largest magnitude, and P, which takes a rotation factor
+    of A and one of B on each side at every step, by at most four times that relative to sqrt(P_ii P_jj).  This is the O(eps) input
+    error include/cpi_amd.h speaks of.  Figures: profiles/merge_bench.md 4."""
+    level = hard.dev
+    for _ in range(3):
+        level = eng.merge(level, G=2, want=WANTS)
+    got = _np(level)
+    want, _, _, _ = hard.ref("rows", mc.HARD_W, mc.HARD_S, "dense")
+    flat = _np(eng.merge(hard.dev, G=mc.HARD_S, want=WANTS))
+    unit = hard.regime != 2
+    cut = lambda d, m: {k: np.asarray(v)[m] for k, v in d.items()}
+    _gated(cut(got, unit), cut(want, unit), "three pairwise levels vs the flat longdouble fold, unit q")
+    _gated(cut(got, unit), cut(flat, unit), "three pairwise levels vs the device's flat fold, unit q", (2 * GATE_MEAN, 2 * GATE_JAC, 2 * GATE_COV))
+    d = mc.deviations(cut(got, ~unit), cut(want, ~unit))
+    print("three pairwise levels vs the flat longdouble fold, float32 q: %s" % ", ".join("%s %.2e" % kv for kv in d.items()))
+    scale = max(1.0, max(np.abs(want[k][~unit]).max() for k in mc.MEAN + mc.JAC))
+    eps = 8 * 2.0 ** -22
+    assert all(e <= eps * scale for k, e in d.items() if k != "P") and d["P"] <= 4 * eps, (d, scale)
+    assert max(v for k, v in d.items()) > 1e-9                          # and they do differ: the defect is real
+    _q_is_canonical(got["q"], "hierarchy")
+
+
+def test_merge_matches_one_preintegration_at_these_rates(eng, hard):
+    """merge(G = 8) of the rows as Engine.preintegrate wrote them against ONE Engine.preintegrate of the 40-interval window.  Means
+    and Jacobians compose to rounding: REG_MEAN / REG_JAC.  P differs by the (|w| dt)^5 truncation of the reference's covariance
+    recursion (include/cpi_amd.h), 2.9e-6 relative at these rates by the oracle: the device's figure has to be the figure the
+    longdouble restatement of the merge has against the same integration, within a factor 2."""
+    kn, lin, _ = mc.hard_knots()
+    whole = _np(eng.preintegrate(kn.to(eng.device), lin.to(eng.device), params=hard.prm, want=("mean", "jac", "cov")))
+    got = _np(eng.merge(hard.raw_dev, G=mc.HARD_S, want=("mean", "jac", "cov")))
+    d = mc.deviations(got, whole)
+    ref = mc.deviations(mc.merge_ref(_only(hard.raw, "P_sym"), mc.HARD_W, mc.HARD_S, dtype=np.longdouble), whole)
+    print("merge G 8 vs one preintegration, 20 rad/s: %s" % ", ".join("%s %.2e" % kv for kv in d.items()))
+    print("    P: device %.3e, longdouble restatement %.3e" % (d["P"], ref["P"]))
+    bad = [(k, e) for k, e in d.items() if k != "P" and not e <= (REG_MEAN if k in mc.MEAN else REG_JAC)]
+    assert not bad, bad
+    assert 0.5 * ref["P"] <= d["P"] <= 2 * ref["P"], (d["P"], ref["P"])
+
+
+def test_merge_host_gives_the_bits_of_the_device_on_the_hard_rows(eng, hard):
+    cpu = {k: torch.from_numpy(v) for k, v in hard.host.items()}
+    d = _np(eng.merge(hard.dev, G=mc.HARD_S, want=WANTS))
+    h = _np(eng.merge_host(cpu, G=mc.HARD_S, want=WANTS, pinned=False))
+    for k in FIELDS:
+        assert np.array_equal(h[k], d[k]), ("dense", k)
+    first, count = _ragged(200, 5, HARD_ROWS, 11)
+    d = _np(eng.merge(hard.dev, G=5, first=_dev(eng, first), count=_dev(eng, count), want=WANTS))
+    h = _np(eng.merge_host(_only(cpu, "P_sym"), G=5, first=torch.from_numpy(first), count=torch.from_numpy(count), want=WANTS, pinned=False))
+    for k in FIELDS:
+        assert np.array_equal(h[k], d[k]), ("ragged", k)
+
+
+@pytest.mark.parametrize("mutation,field", (("drop_beta_x_Jq", "J_b"), ("no_T_on_PB", "P"), ("wrong_sign_theta_bg", "P")))
+def test_a_broken_term_misses_the_gate_on_the_hard_rows(eng, hard, mutation, field):
+    """The device against the restatement with one term broken: the gate is missed by a factor 1000 and more."""
+    got = _np(eng.merge(hard.dev, G=mc.HARD_S, want=WANTS))
+    d = mc.deviations(got, mc.merge_ref(_only(hard.host, "P_sym"), mc.HARD_W, mc.HARD_S, mutate=mutation))
+    print("hard rows G 8, %s: %s %.1e" % (mutation, field, d[field]))
+    assert d[field] > 1e3 * (GATE_COV if field == "P" else GATE_JAC), (mutation, d[field])
+    assert all(e <= GATE_MEAN for k, e in d.items() if k in mc.MEAN), d
 
 
 # ------------------------------------------------------------------------------------------------ 8. graph

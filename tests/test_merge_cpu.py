@@ -10,6 +10,9 @@
    three exchanges, lanes as loops) against the restatement on the same cases and on ragged first / count (0, 1, > G), a group
    clipped by in_rows, P_sym input.  Bound: 1e-13 absolute on means and Jacobians, 1e-12 relative on P -- two 15 x 15 f64 triple
    products per fold step carry a few ulp each, 40 steps at most; the f64 and longdouble restatements differ by as much.
+   The same on HARD operands (merge_cases.hard_rows from the oracle: rates of up to 20 rad/s, joined rotations past 3 rad and every
+   branch of rot_2_quat, q negated, q unit only to float32, a zero-state row as operand), on a fold of 40 with uniform and mixed
+   counts, on merged rows merged again; the coverage is asserted on the longdouble reference alone, the bounds are the same two.
 3. The contract through ctypes: every refusal comes before the context is looked at, so a NULL context shows code and text.
 4. Declarations: header, binding, unit table, resource report."""
 import ctypes as C
@@ -171,6 +174,190 @@ def test_hostsim_ragged_groups_clipping_and_corners(cases, hs):
     means = hs_merge(hs, meas, M, G, first, count, jac=False, cov=False)
     for k in mc.MEAN:
         assert np.array_equal(means[k], got[k]), k
+
+
+# ---------------------------------------------------------------- hard operands: large rotations, odd quaternions, long folds
+ULP = 2.0 ** -52
+HARD_ROWS = mc.HARD_W * mc.HARD_S
+
+
+class _Hard:
+    """merge_cases.hard_rows from the oracle (model 1, imu_avg), and the longdouble references the tests below share: each is
+    computed once and never written to."""
+    def __init__(self):
+        prm = op.make_params(1, 1, 1)
+        self.rows, self.regime, self.long_rows = mc.hard_rows(
+            lambda kn, lin: {k: v.copy() for k, v in op.oracle().run(prm, kn.numpy(), lin.numpy()).items()})
+        self._refs = {}
+
+    def ref(self, which, M, G, layout):
+        """(reference, its folded state, first, count); layout: dense, ragged (hard rows), mixed (the long fold's counts)."""
+        key = (which, M, G, layout)
+        if key not in self._refs:
+            meas = self.rows if which == "rows" else self.long_rows
+            first, count = mc.ragged_groups(M, G, HARD_ROWS, 100 * M + G) if layout == "ragged" else (None, None)
+            if layout == "mixed":
+                count = mc.long_counts()
+            self._refs[key] = mc.merge_ref(meas, M, G, first, count, np.longdouble, state=True) + (first, count)
+        return self._refs[key]
+
+
+@pytest.fixture(scope="module")
+def hard():
+    return _Hard()
+
+
+def _dense_M(G):
+    return -(-HARD_ROWS // G)
+
+
+def test_hard_rows_reach_every_branch_of_rot_2_quat(hard):
+    """What the hard rows are for, asserted on the longdouble reference alone, after the regimes are applied (measured: branches
+    r00 / r11 / r22 / w taken 47 / 37 / 58 / 114 times, largest angle 3.12 rad, smallest |w| 1.2e-2; no row is left out below)."""
+    want, S, _, _ = hard.ref("rows", mc.HARD_W, mc.HARD_S, "dense")
+    taken = np.bincount(mc.branch_of(S["R"]), minlength=4)
+    angle = mc.joined_angle(want["q"])
+    print("hard rows, G 8: branches %s taken %s times, largest angle %.3f rad, smallest |w| %.2e" % (mc.BRANCHES, taken, angle.max(), np.abs(want["q"][:, 3]).min()))
+    assert taken.min() >= 30, taken
+    assert angle.max() > 3.0
+    assert np.abs(want["q"][:, 3]).min() >= 1e-3
+    for G in (2, 3):
+        w2, S2, _, _ = hard.ref("rows", _dense_M(G), G, "dense")
+        print("hard rows, G %d: branches taken %s times, largest angle %.3f rad" % (G, np.bincount(mc.branch_of(S2["R"]), minlength=4), mc.joined_angle(w2["q"]).max()))
+    # the regimes are what they say
+    q = hard.rows["q"].reshape(mc.HARD_W, mc.HARD_S, 4)
+    off = np.abs((q * q).sum(-1) - 1)
+    assert off[hard.regime == 0].max() <= 4 * ULP and (q[hard.regime == 0][:, :, 3] >= 0).all()
+    assert (q[hard.regime == 1][:, 1::2, 3] <= 0).all() and (q[hard.regime == 1][:, 0::2, 3] >= 0).all()
+    assert 1e-9 < off[hard.regime == 2].max() <= 2.0 ** -22         # four components rounded to 2^-24 relative each
+    zero = (hard.rows["DT"].reshape(mc.HARD_W, mc.HARD_S) == 0)
+    assert np.array_equal(zero.sum(1), (hard.regime == 3).astype(int)) and set(np.nonzero(zero)[1]) == set(mc.ZERO_AT)
+    assert all(np.bincount(hard.regime[4 * i:4 * i + 4], minlength=4).min() == 1 for i in range(mc.HARD_W // 4))   # every wavefront: all four
+
+
+def _hs_check(got, want, label, label_of=None, names=None):
+    d = mc.deviations(got, want)
+    print("%s: %s" % (label, ", ".join("%s %.1e" % kv for kv in d.items())))
+    if label_of is not None:
+        for name, dd in mc.deviations_by(got, want, label_of, names).items():
+            print("    %-28s means %.1e  Jacobians %.1e  P %.1e" % ((name,) + mc.worst(dd)))
+    _gate(d, label, HS_EXACT, HS_EXACT, HS_COV)
+    return d
+
+
+def _q_is_canonical(q, label):
+    q = np.asarray(q, dtype=np.longdouble)
+    assert (q[:, 3] >= 0).all(), label
+    assert np.abs(np.sqrt((q * q).sum(-1)) - 1).max(initial=0) <= 4 * ULP, label
+
+
+@pytest.mark.parametrize("G", (2, 3, 8))
+def test_hostsim_matches_the_restatement_on_the_hard_rows(hard, hs, G):
+    """Every row of every regime is compared; dense (all 2048 rows) and ragged, P read dense and packed."""
+    for layout, M in (("dense", _dense_M(G)), ("ragged", 256)):
+        want, S, first, count = hard.ref("rows", M, G, layout)
+        got = hs_merge(hs, hard.rows, M, G, first, count)
+        _hs_check(got, want, "hostsim, hard rows, %s M %d G %d, per regime" % (layout, M, G), mc.group_regime(M, G, first), mc.REGIMES)
+        for name, dd in mc.deviations_by(got, want, mc.branch_of(S["R"]), mc.BRANCHES).items():
+            print("    branch %-21s means %.1e  Jacobians %.1e  P %.1e" % ((name,) + mc.worst(dd)))
+        assert np.array_equal(mc.hs_rows(hs_merge(hs, hard.rows, M, G, first, count, tri=True)), mc.hs_rows(got)), "P_sym input"
+        if layout == "dense":
+            n = np.minimum(G, HARD_ROWS - np.arange(M) * G)
+            _q_is_canonical(got["q"][n > 1], (layout, G))
+
+
+@pytest.mark.parametrize("layout", ("dense", "mixed"))
+def test_hostsim_matches_the_restatement_on_a_fold_of_forty(hard, hs, layout):
+    """64 groups of 40 one-interval rows, every count 40 and counts of 0 .. 40.  The bounds are the file's HS_EXACT / HS_COV
+    (measured here: means 1.3e-15, Jacobians 2.8e-16, P 2.2e-15 relative)."""
+    want, S, first, count = hard.ref("long", mc.LONG_W, mc.LONG_G, layout)
+    got = hs_merge(hs, hard.long_rows, mc.LONG_W, mc.LONG_G, first, count)
+    _hs_check(got, want, "hostsim, fold of 40, %s" % layout)
+    n = np.full(mc.LONG_W, mc.LONG_G) if count is None else count
+    _q_is_canonical(got["q"][n > 1], layout)
+    assert set(n) >= {0, 1, mc.LONG_G} if layout == "mixed" else True
+
+
+def _windows(rows, which):
+    """the rows of the windows `which` (bool [256]) of the hard rows, window-major."""
+    m = np.repeat(which, mc.HARD_S)
+    return {k: v[m] for k, v in rows.items()}
+
+
+def test_float32_quaternions_are_what_the_identity_blocks_are_for(hard, hs):
+    """Operands whose q is unit only to float32: the kernel's arithmetic agrees with the restatement whose Phi~ has I, I and DT I in
+    its (v,v), (p,p) and (p,v) blocks to the bounds of every other case, and is more than 1e-7 away from the dense triple product
+    (R_A^T R_A in those blocks) in P and in P alone: the switch makes the reference valid, no gate was loosened."""
+    sub = _windows(hard.rows, hard.regime == 2)
+    for G in (2, 8):
+        M = 64 * mc.HARD_S // G
+        got = hs_merge(hs, sub, M, G)
+        _hs_check(got, mc.merge_ref(sub, M, G, dtype=np.longdouble), "hostsim, float32 q, G %d, identity blocks" % G)
+        d = mc.deviations(got, mc.merge_ref(sub, M, G, dtype=np.longdouble, identity_blocks=False))
+        print("hostsim, float32 q, G %d, dense triple product: P %.1e" % (G, d["P"]))
+        assert d.pop("P") > 1e-7
+        assert max(d.values()) <= HS_EXACT, d
+
+
+@pytest.mark.parametrize("W,N", SHAPES)
+def test_the_two_forms_of_phi_agree_for_unit_quaternions(cases, W, N):
+    """The operands of the existing cases have unit quaternions (to an ulp): R_A^T R_A = I to a few ulp, so the restatement with the
+    three blocks set and the dense triple product agree to rounding -- HS_EXACT / HS_COV, as two f64 evaluations of one formula."""
+    for avg in (0, 1):
+        ref, segs = cases[W, N, avg]
+        for name, parts in segs.items():
+            d = mc.deviations(mc.fold(parts, identity_blocks=False), mc.fold(parts))
+            _gate(d, (avg, name), HS_EXACT, HS_EXACT, HS_COV)
+            assert all(d[k] == 0 for k in mc.MEAN + mc.JAC), d
+
+
+def test_zero_state_operands_and_negated_quaternions(hard, hs):
+    """A zero-state row (what count = 0 writes) before or after a row X gives X bit for bit in everything but q, and q within 4 ulp;
+    -q is the same operand as q: every output field bit for bit."""
+    X = mc.hs_rows(_windows(hard.rows, hard.regime == 0))
+    zero = np.zeros_like(X)
+    zero[:, 10] = 1.0
+    notq = np.r_[0:7, 11:mc.HS_ROW]
+    for name, pair in (("zero first", (zero, X)), ("zero second", (X, zero))):
+        out = mc.hs_rows(hs_merge(hs, mc.hs_meas(np.stack(pair, 1).reshape(-1, mc.HS_ROW)), X.shape[0], 2))
+        assert np.array_equal(out[:, notq], X[:, notq]), name
+        assert np.abs(out[:, 7:11] - X[:, 7:11]).max() <= 4 * ULP, name
+    flipped = dict(hard.rows)
+    flipped["q"] = hard.rows["q"].copy()
+    flipped["q"][1::2] *= -1
+    for G in (2, 3, 8):
+        M = HARD_ROWS // G
+        assert np.array_equal(mc.hs_rows(hs_merge(hs, flipped, M, G)), mc.hs_rows(hs_merge(hs, hard.rows, M, G))), G
+
+
+def test_merged_rows_merge_again(hard, hs):
+    """8 -> 4 -> 2 -> 1 rows per window, outputs fed back in, against the flat longdouble fold of 8.  The windows whose operand
+    quaternions are unit only to float32 differ from the flat fold by that defect (every pairwise step normalises the q it writes):
+    8 x 2^-22 x the largest magnitude for means and Jacobians, four times that for P (tests/test_gpu_merge.py has the reasoning)."""
+    level = hard.rows
+    for _ in range(3):
+        level = hs_merge(hs, level, np.asarray(level["DT"]).shape[0] // 2, 2)
+    want = hard.ref("rows", mc.HARD_W, mc.HARD_S, "dense")[0]
+    unit = hard.regime != 2
+    cut = lambda d, m: {k: np.asarray(v)[m] for k, v in d.items()}
+    _hs_check(cut(level, unit), cut(want, unit), "hostsim, three pairwise levels vs the flat longdouble fold, unit q")
+    d = mc.deviations(cut(level, ~unit), cut(want, ~unit))
+    print("hostsim, three pairwise levels, float32 q: %s" % ", ".join("%s %.1e" % kv for kv in d.items()))
+    scale = max(1.0, max(np.abs(want[k][~unit]).max() for k in mc.MEAN + mc.JAC))
+    eps = 8 * 2.0 ** -22
+    assert all(e <= eps * scale for k, e in d.items() if k != "P") and d["P"] <= 4 * eps, (d, scale)
+    assert max(d.values()) > 1e-9
+    _q_is_canonical(level["q"], "hierarchy")
+
+
+@pytest.mark.parametrize("mutation,field", (("drop_beta_x_Jq", "J_b"), ("no_T_on_PB", "P"), ("wrong_sign_theta_bg", "P")))
+def test_a_broken_term_misses_the_gate_on_the_hard_rows(hard, hs, mutation, field):
+    """The comparison of the hard rows would fail with any of the three terms broken, by a factor 1000 and more over its bound."""
+    for G in (2, 8):
+        d = mc.deviations(hs_merge(hs, hard.rows, mc.HARD_W, G), mc.merge_ref(hard.rows, mc.HARD_W, G, mutate=mutation))
+        print("hostsim, hard rows G %d, %s: %s %.1e" % (G, mutation, field, d[field]))
+        assert d[field] > 1e3 * (HS_COV if field == "P" else HS_EXACT), (mutation, G, d[field])
+        assert all(e <= HS_EXACT for k, e in d.items() if k in mc.MEAN), d
 
 
 # ---------------------------------------------------------------- contract, declarations
