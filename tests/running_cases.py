@@ -46,3 +46,34 @@ def tumbling_stream(n, phase, seed=None):
 def wdt(kn, lin):
     """|w - b_w| dt per interval of dense windows [W, N + 1, 7] (the opening reading of each interval)."""
     return np.linalg.norm(kn[:, :-1, 1:4] - lin[:, None, 0:3], axis=2) * np.diff(kn[:, :, 0], axis=1)
+
+
+# ---- model 2's Jacobian rows and queries (tests/test_gpu_stj_edges.py, tests/test_hostsim_stj.py)
+STJ_EDGE_N = [1, 2, 22, 23, 24, 46, 47]      # 1, 2 and CH - 1, CH, CH + 1, 2 CH, 2 CH + 1 of cov_body<2> (PASS[2])
+STJ_CHAIN_N = 3 * PASS[2] + 1                # 70: the chains of tests/test_gpu_open_resume_stj.py
+
+
+# seeds at which 32 (8) windows hold intervals on the short polynomial, on the long one and on the reduced path and stay below
+# |w| dt = 1.3 (tests/test_running_cases_cpu.py asserts it; make_windows draws one rate profile per seed, whatever N)
+STJ_LAYOUT_SEED = 950          # _ragged_layout(kn, STJ_LAYOUT_SEED): counts that keep the three regimes at every N of STJ_EDGE_N
+STJ_EDGE_SEED = {1: 944, 2: 944, 22: 961, 23: 961, 24: 961, 46: 978, 47: 901}
+
+
+def stj_edge_windows(N):
+    """32 tumbling windows of N intervals (N of STJ_EDGE_N; N = 47 is tumbling_windows() itself)."""
+    return tumbling_windows(32, N, seed=STJ_EDGE_SEED[N])
+
+
+def stj_chain_windows():
+    """8 tumbling windows of STJ_CHAIN_N intervals: the chains cut on and beside the passes."""
+    return tumbling_windows(8, STJ_CHAIN_N, seed=988)
+
+
+def stj_open_windows(model):
+    """8 tumbling windows of 2 CH + 1 intervals of the model: the open views and the chains queried while open."""
+    return tumbling_windows(8, 2 * PASS[model] + 1, seed=947)
+
+
+def sincos_regimes(a):
+    """Intervals of |w| dt on the short polynomial of sincos_fast, on the long one and on the reduced path."""
+    return int((a <= 0.25).sum()), int(((a > 0.25) & (a <= 1.0)).sum()), int((a > 1.0).sum())

@@ -56,8 +56,15 @@ def _times(kn, m):
 @pytest.mark.parametrize("model,avg", [(1, 0), (1, 1), (2, 0), (2, 1)])
 def test_open_view_of_a_closed_window_is_exact(eng, model, avg, layout):
     ch = CH if model == 2 else CH1
-    N, W = 2 * ch + 1, 3
-    kn, lin, q = (x[:W] for x in _windows(N))
+    _open_view_is_exact(eng, model, avg, layout, tuple(x[:3] for x in _windows(2 * ch + 1)))
+
+
+def _open_view_is_exact(eng, model, avg, layout, windows):
+    """The exact test on dense windows (kn, lin, q) of 2 ch + 1 intervals (tests/test_gpu_stj_edges.py repeats it on tumbling ones)."""
+    ch = CH if model == 2 else CH1
+    kn, lin, q = windows
+    W, N = kn.shape[0], kn.shape[1] - 1
+    assert N == 2 * ch + 1
     prm = eng.make_params(model, bool(avg))
     rows = _closed_rows(eng, model, kn, lin, q, prm)
     fields = MEAN + (JAC7 if model == 2 else JAC5) + ("P", "P_sym")

@@ -10,11 +10,15 @@ import pytest
 import torch
 
 from tests.test_gpu_stj import ALL, CH, JAC7, MEAN, _bits, _dev, _flat, _np, _trace, _windows
-from tests.tol import check_pre
+from tests.tol import FieldTable, check_pre, field_gates
 
 pytestmark = pytest.mark.gpu
 NT = 3 * CH + 1        # intervals of a whole window: segments of CH - 1 | 2 CH + 2, CH | 2 CH + 1, CH + 1 | 2 CH and three-segment chains
 KEYS = MEAN + JAC7 + ("P",)
+# Per-field regression gates beside TOL_JAC (tests/tol.py: field_gates): 100 x the largest error against the oracle measured on an
+# MI355X over test_chains_match_the_oracle_and_the_older_entries (both layouts and imu_avg settings), never below 2^-53 x max |ref|
+# of the field (the table: profiles/stj_edges.md)
+FLOOR_CHAIN = {"J_q": 5.55e-16, "J_a": 1.80e-16, "J_b": 1.11e-15, "H_a": 8.33e-17, "H_b": 5.55e-16, "O_a": 8.88e-16, "O_b": 8.44e-15}
 CHAINS = [(CH - 1, 2 * CH + 2), (CH, 2 * CH + 1), (CH + 1, 2 * CH), (CH, CH + 1, CH), (CH + 1, CH - 1, CH + 1), (2 * CH + 1, 1, CH - 1)]
 
 
@@ -65,7 +69,7 @@ def test_chains_match_the_oracle_and_the_older_entries(eng, avg, layout):
     kn, lin, q = _windows(NT)
     ref = _trace(avg, kn, lin, q, key=("open", NT))
     prm = eng.make_params(2, bool(avg))
-    worst = {}
+    worst, t = {}, FieldTable(JAC7)
     for ci, lens in enumerate(CHAINS):
         assert sum(lens) == NT
         for W in ((1, 2, 3) if ci == 1 else (3,)):
@@ -76,6 +80,7 @@ def test_chains_match_the_oracle_and_the_older_entries(eng, avg, layout):
                       label="resume stj %s avg%d W%d %s" % (layout, avg, W, lens))
             for k in JAC7:
                 worst[k] = max(worst.get(k, 0.0), float(np.abs(got[k] - ref[k][:W]).max()))
+            t.add(got, {k: v[:W] for k, v in ref.items()}, "W%d %s" % (W, lens))
             for si, (a, b, rows, cin, cout) in enumerate(segs):
                 if si == 0:
                     closed = _np(eng.preintegrate_running_stj(_dev(kn[:W, a:b + 1], eng), _dev(lin[:W], eng), _dev(q[:W], eng), prm, want=ALL))
@@ -96,6 +101,8 @@ def test_chains_match_the_oracle_and_the_older_entries(eng, avg, layout):
                 for k in JAC7 + MEAN + ("P",):
                     assert _bits(fin[k], rows[k][:, -1]), (lens, W, si, k)
     print("resume stj %s avg %d: largest error per field vs oracle.trace: %s" % (layout, avg, ", ".join("%s %.2e" % kv for kv in sorted(worst.items()))))
+    t.report("resume stj chains %s avg %d, per field" % (layout, avg), field_gates(FLOOR_CHAIN))
+    t.check(field_gates(FLOOR_CHAIN), "resume stj chains %s avg %d" % (layout, avg))
 
 
 @pytest.mark.parametrize("avg", [0, 1])

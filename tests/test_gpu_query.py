@@ -27,6 +27,10 @@ JAC = ("J_q", "J_a", "J_b", "H_a", "H_b")
 CALL_SIZES = (1, 63, 64, 65, 200)     # queries per call: one lane, a wavefront less one, exactly one, one more, several blocks
 # name -> (W, N): the bisection runs 1, 2 and 4 trips on the seeded windows, 6 on the tumbling ones (large rotations)
 CASES = {"n1": (5, 1), "n2": (5, 2), "n13": (5, 13), "tumbling": (8, 47)}
+# + a case for tests/test_gpu_stj_edges.py, not part of the tests below: "tumbling" stays on the polynomials of sincos_fast (largest
+# |w| dt 0.96), the windows of "reduced" hold intervals on the Cody-Waite reduction as well, in the ragged layout too
+ALL_CASES = dict(CASES, reduced=(8, 47))
+TUMBLING_SEED = {"tumbling": 901, "reduced": 947}
 
 # Largest error against the oracle over test_parity (all modes, cases and layouts) measured on an MI355X, per group of fields as
 # in tests/tol.py (per field and mode: profiles/query_bench.md): beta of the tumbling windows under model 2 for the means, J_q /
@@ -70,9 +74,9 @@ def _case(name):
     """Dense windows [W, N + 1, 7] with one dt == 0 interval in window 2, and the counts of the ragged layout (0, 1 and N among
     them)."""
     if name not in _case_cache:
-        W, N = CASES[name]
-        if name == "tumbling":
-            kn, lin, q = running_cases.tumbling_windows(W=W, N=N)
+        W, N = ALL_CASES[name]
+        if name in TUMBLING_SEED:
+            kn, lin, q = running_cases.tumbling_windows(W=W, N=N, seed=TUMBLING_SEED[name])
         else:
             kn, lin, q = (t.numpy() for t in synth.make_windows(W, N, seed=4711 + N, edge_cases=False))
         kn = kn.copy()
@@ -88,7 +92,7 @@ def _layout(name, layout):
     """(knots, first, count, N, counts as the kernel sees them) of a case: "dense" = knots [W, N + 1, 7] and no count; "ragged" =
     one knot array the windows lie in in shuffled order, with gaps of unused knots between them."""
     kn, lin, q, count = _case(name)
-    W, N = CASES[name]
+    W, N = ALL_CASES[name]
     if layout == "dense":
         return kn, None, None, np.full(W, N, dtype=np.int32)
     rng = np.random.default_rng(17)
@@ -127,7 +131,7 @@ def _reference(name, layout, model, avg):
     key = (name, layout, model, avg)
     if key not in _ref_cache:
         kn, lin, q, _ = _case(name)
-        W, N = CASES[name]
+        W, N = ALL_CASES[name]
         counts = _layout(name, layout)[3]
         qw, qt = _queries(kn, counts)
         perm = np.random.default_rng(5).permutation(len(qw))

@@ -4,7 +4,9 @@ Engine.preintegrate_running_stj[_host], Engine.query_stj[_host], cpi_host::CpiBa
 References: every running row against oracle_py.oracle().trace (state_transition_jacobians = 1: it returns O_a / O_b after every
 feed_IMU) at TOL_JAC and against tests/golden/trace_v2.npz at REG_JAC; every query against the oracle on the cut window [knot 0 ..
 knot i, {t_q, w_i, a_i}] (tests/test_gpu_query.py's _reference, as it is) at TOL_JAC.  The bit rules (repeat rows, stamp hits, the
-twins' mean and P rows, host forms) are checked for exact equality.  The largest error of a test is printed (pytest -s)."""
+twins' mean and P rows, host forms) are checked for exact equality.  Beside TOL_JAC every Jacobian field has a regression gate of its
+own (FLOOR_ROWS / FLOOR_QUERY below).  The largest error of a test is printed (pytest -s).  The same entries under large rotations:
+tests/test_gpu_stj_edges.py."""
 import ctypes as C
 import os
 import re
@@ -19,7 +21,7 @@ from cpi_amd import synth
 from oracle import oracle_py as op
 from tests.test_gpu_query import CASES, _case, _layout, _queries, _reference
 from tests.test_gpu_running import _ragged_layout
-from tests.tol import REG_JAC, TOL_FACTOR, TOL_JAC, check_pre
+from tests.tol import REG_JAC, TOL_FACTOR, TOL_JAC, FieldTable, check_pre, field_gates
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,6 +40,13 @@ def _pass_length():
 
 CH = _pass_length()
 RUN_N = sorted({1, CH - 1, CH, CH + 1, 2 * CH + 1})
+
+# Per-field regression gates beside TOL_JAC (tests/tol.py: field_gates): 100 x the largest error against the oracle measured on an
+# MI355X over these tests, imu_avg 0 and 1, never below 2^-53 x max |ref| of the field (the tables: profiles/stj_edges.md).
+#   rows:    test_running_rows_dense and test_running_rows_ragged, every N of RUN_N; every floor is set at N = 2 CH + 1
+#   queries: test_query_parity_and_bit_rules, cases n1 and n13, dense and ragged; every floor is set by n13
+FLOOR_ROWS = {"J_q": 2.50e-16, "J_a": 3.47e-17, "J_b": 4.44e-16, "H_a": 2.43e-17, "H_b": 2.50e-16, "O_a": 3.33e-16, "O_b": 3.55e-15}
+FLOOR_QUERY = {"J_q": 4.16e-17, "J_a": 2.71e-19, "J_b": 1.73e-17, "H_a": 1.08e-18, "H_b": 4.16e-17, "O_a": 1.04e-17, "O_b": 4.44e-16}
 
 
 @pytest.fixture(scope="module")
@@ -114,12 +123,13 @@ def test_running_rows_dense(eng, N, avg):
     kn, lin, q = _windows(N)
     ref = _trace(avg, kn, lin, q, key=("dense", N))
     prm = eng.make_params(2, bool(avg))
-    worst, last_bits = {}, []
+    worst, last_bits, t = {}, [], FieldTable(JAC7)
     for W in (1, 2, 3):
         a = [_dev(x[:W], eng) for x in (kn, lin, q)]
         got = _np(eng.preintegrate_running_stj(*a, params=prm, want=ALL))
         assert set(got) == set(MEAN + JAC7 + ("P", "P_sym")) and all(v.shape[:2] == (W, N) for v in got.values())
         _check_all(got, {k: v[:W] for k, v in ref.items()}, "stj dense N%d avg%d W%d" % (N, avg, W), worst)
+        t.add(got, {k: v[:W] for k, v in ref.items()}, "W%d" % W)
         twin = _np(eng.preintegrate_running(*a, params=prm, want=("mean", "cov", "cov_sym")))
         for k in twin:
             assert _bits(got[k], twin[k]), (W, k)
@@ -133,6 +143,8 @@ def test_running_rows_dense(eng, N, avg):
         last_bits.append(all(_bits(got[k][:, N - 1], fin[k]) for k in JAC7))
     print("running stj dense N %d avg %d: largest error per field vs oracle.trace: %s; last row bit-equal to Engine.preintegrate (W = 1, 2, 3): %s"
           % (N, avg, ", ".join("%s %.2e" % kv for kv in sorted(worst.items())), last_bits))
+    t.report("running stj dense N %d avg %d, per field" % (N, avg), field_gates(FLOOR_ROWS))
+    t.check(field_gates(FLOOR_ROWS), "running stj dense N %d avg %d" % (N, avg))
 
 
 @pytest.mark.parametrize("avg", [0, 1])
@@ -164,6 +176,10 @@ def test_running_rows_ragged(eng, N, avg):
             for i in range(max(n, 1), N):
                 assert _bits(got[k][w, i], got[k][w, i - 1]), (w, i, k)
     print("running stj ragged N %d avg %d (counts %s): %s" % (N, avg, list(given), ", ".join("%s %.2e" % kv for kv in sorted(worst.items()))))
+    t = FieldTable(JAC7)
+    t.add(got, ref, "ragged")
+    t.report("running stj ragged N %d avg %d, per field" % (N, avg), field_gates(FLOOR_ROWS))
+    t.check(field_gates(FLOOR_ROWS), "running stj ragged N %d avg %d" % (N, avg))
 
 
 def test_running_rows_match_the_golden_trace(eng, golden_dir):
@@ -285,6 +301,10 @@ def test_query_parity_and_bit_rules(eng, avg, name, layout):
     for k in JAC7:
         assert np.isnan(o_n[k][holes]).all() and _bits(o_n[k][keep], got[k][keep]), k
     print("query stj %s %s avg %d (%d queries, %d stepped): %s" % (name, layout, avg, M, stepped.sum(), ", ".join("%s %.2e" % kv for kv in sorted(err.items()))))
+    t = FieldTable(JAC7)
+    t.add(got, ref, "%s %s" % (name, layout))
+    t.report("query stj %s %s avg %d, per field" % (name, layout, avg), field_gates(FLOOR_QUERY))
+    t.check(field_gates(FLOOR_QUERY), "query stj %s %s avg %d" % (name, layout, avg))
 
 
 def _raw(eng, entry, prm, W, N, t, rows, out, Q=None, **ch):

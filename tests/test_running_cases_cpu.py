@@ -67,3 +67,85 @@ def test_tumbling_streams_put_the_tail_where_they_should(n, phase):
         for w in range(U):
             tr = op.oracle().trace(prm, wins[w], lin[w], q[w])
             assert all(np.isfinite(tr[k]).all() for k in NAMES), (model, avg, w)
+
+
+# ---- the inputs of tests/test_gpu_stj_edges.py and of the tumbling cases of tests/test_hostsim_stj.py
+JAC7 = ("J_q", "J_a", "J_b", "H_a", "H_b", "O_a", "O_b")
+
+
+def _stj_inputs():
+    """name -> dense windows (kn, lin, q) and the counts the GPU tests cut them at (None: whole windows)."""
+    from tests.test_gpu_query import _case, _layout
+    from tests.test_gpu_running import _ragged_layout
+    out = {}
+    for N in rc.STJ_EDGE_N:
+        kn, lin, q = rc.stj_edge_windows(N)
+        out["edge N%d" % N] = (kn, lin, q, None if N == 47 else _ragged_layout(kn, rc.STJ_LAYOUT_SEED, garbage=True)[2])
+    out["dense N47 cut as the ragged layout"] = rc.stj_edge_windows(47) + (_ragged_layout(rc.stj_edge_windows(47)[0], rc.STJ_LAYOUT_SEED, garbage=True)[2],)
+    out["chains"] = rc.stj_chain_windows() + (None,)
+    for model in (1, 2):
+        out["open m%d" % model] = rc.stj_open_windows(model) + (None,)
+    for case in ("tumbling", "reduced"):
+        kn, lin, q, _ = _case(case)
+        out["query %s dense" % case] = (kn, lin, q, None)
+        out["query %s ragged" % case] = (kn, lin, q, _layout(case, "ragged")[3])
+    return out
+
+
+@pytest.mark.parametrize("avg", [0, 1])
+def test_stj_tumbling_inputs_reach_what_they_are_for(avg):
+    """Every tumbling input of the model-2 Jacobian tests: |w| dt inside the stability region of the covariance's RK4, intervals on
+    the short polynomial, the long one and the reduced path of sincos_fast, a finite oracle trace in all seven Jacobian fields (and
+    the means and P) over every interval the tests integrate -- so that no row and no query has to be left out -- and every branch of
+    rot_2_quat among the oracle's q rows (per input from one pass length on; a window of one or two intervals cannot turn far
+    enough, there the branches are reached by the set of edge lengths as a whole)."""
+    prm = op.make_params(2, avg, 1)
+    union = np.zeros(4, dtype=np.int64)
+    for name, (kn, lin, q, count) in _stj_inputs().items():
+        W, N = kn.shape[0], kn.shape[1] - 1
+        a = rc.wdt(kn, lin)
+        if count is not None:                                   # the intervals past a window's count are not integrated
+            a = np.where(np.arange(N)[None, :] < np.asarray(count)[:, None], a, 0.0)
+        reg = rc.sincos_regimes(a)
+        assert a.max() < 1.3, (name, a.max())
+        # case "tumbling" of tests/test_gpu_query.py stays on the two polynomials; the reduced path of the queries is case "reduced"
+        assert min(reg[:2] if name.startswith("query tumbling") else reg) > 0 and sum(reg) == a.size, (name, reg)
+        # a wavefront mixes the regimes: windows that never leave the short polynomial beside windows on the wide path
+        assert 0 < (a > 0.25).any(axis=1).sum() < W, name
+        qs = []
+        for w in range(W):
+            n = N if count is None else int(count[w])
+            if n == 0:
+                continue
+            tr = op.oracle().trace(prm, kn[w, :n + 1], lin[w], q[w])
+            assert all(np.isfinite(tr[k]).all() for k in NAMES + JAC7[5:]), (name, avg, w)
+            qs.append(tr["q"])
+        largest = np.bincount(np.abs(np.concatenate(qs)).argmax(axis=1), minlength=4)
+        print("%s imu_avg %d: max |w| dt %.4f, intervals short / long / reduced %s, largest quaternion component x / y / z / w in %s rows"
+              % (name, avg, a.max(), reg, " / ".join(map(str, largest))))
+        if name.startswith("edge"):
+            union += largest
+        if N >= rc.PASS[2]:
+            assert largest.min() >= 1, (name, avg, largest)
+    assert union.min() >= 1, union
+
+
+@pytest.mark.parametrize("avg", [0, 1])
+@pytest.mark.parametrize("n,phase", [(23, 0.37), (46, 0.37)])
+def test_stj_tumbling_streams_have_finite_jacobian_traces(n, phase, avg):
+    """The stream cases of the model-2 Jacobian rows: a finite trace in all seven fields and |w| dt inside the stability region.  The
+    streams are there for the tail interval that opens a pass; the wide path of sincos_fast is the windows' part (the rates of
+    tumbling_stream stay on the short polynomial once the bias is taken off)."""
+    s, u, lin, q = rc.tumbling_stream(n, phase)
+    knots, first, count = st.assemble_windows(s, u)
+    prm = op.make_params(2, avg, 1)
+    reg = np.zeros(3, dtype=np.int64)
+    for w in range(len(u)):
+        k = knots[first[w]:first[w] + count[w] + 1]
+        a = rc.wdt(k[None], lin[w:w + 1])
+        assert a.max() < 1.3
+        reg += rc.sincos_regimes(a)
+        tr = op.oracle().trace(prm, k, lin[w], q[w])
+        assert all(np.isfinite(tr[f]).all() for f in NAMES + JAC7[5:]), (n, avg, w)
+    print("tumbling stream n %d phase %g: intervals short / long / reduced %s" % (n, phase, tuple(int(r) for r in reg)))
+    assert reg.sum() == int(count.sum()) and np.all(count == n + 1)

@@ -85,3 +85,62 @@ def sqrt_info_longdouble(P):
         for i in range(j - 1, -1, -1):
             U[:, i, j] = -(B[:, i, i + 1:j + 1] * U[:, i + 1:j + 1, j]).sum(axis=1) / B[:, i, i]
     return np.asarray(U, dtype=np.float64)
+
+
+# ---- per-field regression gates (tests/test_gpu_stj_edges.py, tests/test_hostsim_stj.py; profiles/stj_edges.md)
+# A floor is the largest error of one field measured against the oracle, never below the rounding of the field itself
+# (2^-53 x max |ref|); the gate is 100 x the floor and never looser than the contractual gate of the field's group.
+EPS_HALF = 2.0 ** -53
+MEAN_FIELDS = ("DT", "alpha", "beta", "q")
+
+
+def contract_gate(field):
+    return TOL_MEAN if field in MEAN_FIELDS else (TOL_COV if field == "P" else TOL_JAC)
+
+
+def field_gates(floors):
+    """{field: floor} -> {field: gate}."""
+    return {k: min(contract_gate(k), 100.0 * f) for k, f in floors.items()}
+
+
+class FieldTable:
+    """Largest error per field over the comparisons of a test, the rounding floor of the reference beside it, and where the largest
+    error sits -- printed before anything is asserted, so that a failure shows the oracle's margin first."""
+
+    def __init__(self, fields):
+        self.fields = tuple(fields)
+        self.err = {k: 0.0 for k in self.fields}
+        self.ulp = {k: 0.0 for k in self.fields}
+        self.where = {k: "" for k in self.fields}
+
+    def add(self, got, ref, label=""):
+        for k in self.fields:
+            g, r = np.asarray(got[k]), np.asarray(ref[k])
+            assert g.shape == r.shape, (label, k, g.shape, r.shape)
+            assert np.isfinite(r).all(), (label, k, "the reference is not finite")
+            if k == "P":
+                e, at, u = (cov_rel_err(g, r) if np.isfinite(g).all() else np.inf), "", EPS_HALF
+            else:
+                d = np.abs(g - r)
+                d = np.where(np.isnan(d), np.inf, d)               # a row that was not written fails
+                e = float(d.max()) if d.size else 0.0
+                at = " at %s (ref %.3g)" % (tuple(int(i) for i in np.unravel_index(int(d.argmax()), d.shape)), r.flat[int(d.argmax())]) if d.size else ""
+                u = EPS_HALF * float(np.abs(r).max()) if r.size else 0.0
+            self.ulp[k] = max(self.ulp[k], u)
+            if e >= self.err[k]:
+                self.err[k], self.where[k] = e, "%s%s" % (label, at)
+
+    def floors(self):
+        return {k: max(self.err[k], self.ulp[k]) for k in self.fields}
+
+    def report(self, title, gates=None):
+        print("%s" % title)
+        print("| field | largest error | 2^-53 max abs ref | floor | gate | worst |")
+        print("|---|---|---|---|---|---|")
+        for k in self.fields:
+            print("| `%s` | %.2e | %.2e | %.2e | %s | %s |" % (k, self.err[k], self.ulp[k], self.floors()[k],
+                                                           "%.2e" % gates[k] if gates else "-", self.where[k]))
+
+    def check(self, gates, title):
+        bad = ["%s %.3e > %.2e (%s)" % (k, self.err[k], gates[k], self.where[k]) for k in self.fields if not self.err[k] <= gates[k]]
+        assert not bad, title + ": " + "; ".join(bad)
