@@ -193,6 +193,11 @@ def load():
     for f in (lib.cpi_retract_batch, lib.cpi_retract_batch_host, lib.cpi_local_batch, lib.cpi_local_batch_host, lib.cpi_factor_cost_batch,
               lib.cpi_factor_cost_tri_batch, lib.cpi_factor_cost_batch_host):
         f.restype = C.c_int
+    lib.cpi_chain_solve_workspace_doubles.argtypes = [i64]
+    lib.cpi_chain_solve_workspace_doubles.restype = C.c_size_t
+    lib.cpi_chain_solve_batch.argtypes = [vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
+    lib.cpi_chain_solve_batch_host.argtypes = [vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, i32, vp, vp]
+    lib.cpi_chain_solve_batch.restype = lib.cpi_chain_solve_batch_host.restype = C.c_int
     lib.cpi_preintegrate_stream_running.argtypes = lib.cpi_preintegrate_stream.argtypes
     lib.cpi_preintegrate_stream_running_host.argtypes = lib.cpi_preintegrate_stream_host.argtypes
     lib.cpi_preintegrate_streams_running.argtypes = lib.cpi_preintegrate_streams.argtypes

@@ -1347,6 +1347,61 @@ extern "C" int cpi_factor_cost_tri_batch(cpi_ctx *ctx, int32_t model, const doub
     return factor_cost_impl(ctx, "cpi_factor_cost_tri_batch", model, grav, F, meas, lin, q_k_lin, states, S, idx_i, idx_j, R_tri, true, chi2, werr, total);
 }
 
+// ============================================================================================
+// cpi_chain_solve_batch: the damped block-tridiagonal solve of chains of IMU factors (cpi_chain_solve_kernel, cpi_chain.hip)
+// ============================================================================================
+extern "C" size_t cpi_chain_solve_workspace_doubles(int64_t S) { return launch::chain_workspace_doubles(S > 0 ? (long long)S : 0); }
+
+// what both forms refuse alike, before the context is looked at; host: the arrays are the caller's host arrays (no workspace)
+static int chain_check(cpi_ctx *ctx, const char *who, int64_t C, int64_t G, int64_t S, int64_t F, const int64_t *first, const int32_t *count,
+                       const int64_t *ffirst, const double *hess, const double *prior, const double *lambda, int32_t damping,
+                       double *delta, int32_t *status, double *workspace, bool host) {
+    if (C < 0 || S < 0 || F < 0) return refuse(ctx, who, "negative size");
+    if (G < 1) return refuse(ctx, who, "G (the longest chain in states) must be >= 1");
+    if (G > 0x7fffffffLL) return refuse(ctx, who, "G exceeds 2^31 - 1 states per chain");
+    if (damping != CPI_DAMP_IDENTITY && damping != CPI_DAMP_DIAGONAL) return refuse(ctx, who, "damping must be CPI_DAMP_IDENTITY or CPI_DAMP_DIAGONAL");
+    if (C == 0) return CPI_OK;
+    if (!hess && G > 1) return refuse(ctx, who, "hess is NULL (only chains of one state, G == 1, need none)");
+    if (!delta) return refuse(ctx, who, "delta is NULL");
+    if (!host && !workspace) return refuse(ctx, who, "workspace is NULL");
+    const size_t d = sizeof(double);
+    const void *outp[3] = { delta, status, workspace };
+    const size_t outn[3] = { (size_t)S * 15 * d, (size_t)C * sizeof(int32_t), workspace ? cpi_chain_solve_workspace_doubles(S) * d : 0 };
+    static const char *const outname[3] = { "delta", "status", "workspace" };
+    const void *inp[6] = { first, count, ffirst, hess, prior, lambda };
+    const size_t inn[6] = { (size_t)C * sizeof(int64_t), (size_t)C * sizeof(int32_t), (size_t)C * sizeof(int64_t), (size_t)F * 496 * d,
+                            (size_t)S * 136 * d, (size_t)C * d };
+    for (int o = 0; o < 3; o++) {
+        bool bad = false;
+        for (int k = 0; k < 6; k++) bad = bad || bytes_overlap(outp[o], outn[o], inp[k], inn[k]);
+        for (int q = o + 1; q < 3; q++) bad = bad || bytes_overlap(outp[o], outn[o], outp[q], outn[q]);
+        if (bad) return refuse(ctx, who, outname[o], " overlaps an input or another output");
+    }
+    return CPI_OK;
+}
+
+extern "C" int cpi_chain_solve_batch(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_t F,
+                                     const int64_t *first, const int32_t *count, const int64_t *ffirst,
+                                     const double *hess, const double *prior, const double *lambda, int32_t damping,
+                                     double *delta, int32_t *status, double *workspace) {
+    static const char who[] = "cpi_chain_solve_batch";
+    CPI_TRY(chain_check(ctx, who, C, G, S, F, first, count, ffirst, hess, prior, lambda, damping, delta, status, workspace, false));
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (C == 0) return CPI_OK;
+    if (!grid_ok((C + 3) / 4)) return refuse(ctx, who, "C exceeds the 32-bit grid (4 chains per workgroup)");
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    ChainArgs a;
+    memset(&a, 0, sizeof a);
+    a.C = C; a.G = (int)G; a.S = S; a.F = F;
+    a.first = (const long long *)first; a.count = count; a.ffirst = (const long long *)ffirst;
+    a.hess = hess; a.prior = prior; a.lambda = lambda; a.diagonal = damping == CPI_DAMP_DIAGONAL;
+    a.delta = delta; a.status = status; a.workspace = workspace;
+    launch::chain_solve(a, ctx->stream);
+    CPI_HIP(ctx, hipGetLastError());
+    return CPI_OK;
+}
+
 extern "C" size_t cpi_outputs_slab_doubles(const cpi_outputs *mask, int64_t Wb) {
     if (!mask || Wb <= 0) return 0;
     size_t n = 0;
@@ -2742,5 +2797,59 @@ extern "C" int cpi_factor_cost_batch_host(cpi_ctx *ctx, int32_t model, const dou
     CPI_TRY(st.download(chi2, (const double *)dc, (size_t)F));
     if (werr) CPI_TRY(st.download(werr, (const double *)dw, (size_t)F * 15));
     if (total) CPI_TRY(st.download(total, (const double *)dt, (size_t)1));
+    return st.finish();
+}
+
+// cpi_chain_solve_batch from host memory: every array a host array, staged whole, synchronous.  Host pointers: every chain's state
+// and factor range can be (and is) validated here; the device form clamps or refuses them per chain instead.  delta travels up first,
+// so that the rows of no chain come back as the caller left them.
+extern "C" int cpi_chain_solve_batch_host(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_t F,
+                                          const int64_t *first, const int32_t *count, const int64_t *ffirst,
+                                          const double *hess, const double *prior, const double *lambda, int32_t damping,
+                                          double *delta, int32_t *status) {
+    static const char who[] = "cpi_chain_solve_batch_host";
+    CPI_TRY(chain_check(ctx, who, C, G, S, F, first, count, ffirst, hess, prior, lambda, damping, delta, status, nullptr, true));
+    for (int64_t c = 0; c < C; c++) {
+        const int64_t f = first ? first[c] : c * G;
+        int64_t n = count ? count[c] : G;
+        n = n < 0 ? 0 : (n > G ? G : n);
+        if (f < 0 || f > S || n > S - f)
+            return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": the states of chain " + std::to_string(c) + " leave [0, S)");
+        const int64_t ff = ffirst ? ffirst[c] : f - c;
+        if (n > 1 && (ff < 0 || ff > F - (n - 1)))
+            return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": the factor rows of chain " + std::to_string(c) + " leave [0, F)");
+    }
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (C == 0) return CPI_OK;
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    Staging st(ctx);
+    const int64_t *dfirst, *dffirst;
+    const int32_t *dcount;
+    const double *dh, *dp, *dl, *dd0 = nullptr;
+    double *dd = nullptr, *dw;
+    int32_t *ds = nullptr;
+    CPI_TRY(st.upload(first, (size_t)C, &dfirst));
+    CPI_TRY(st.upload(count, (size_t)C, &dcount));
+    CPI_TRY(st.upload(ffirst, (size_t)C, &dffirst));
+    CPI_TRY(st.upload(F > 0 ? hess : nullptr, (size_t)F * 496, &dh));
+    CPI_TRY(st.upload(S > 0 ? prior : nullptr, (size_t)S * 136, &dp));
+    CPI_TRY(st.upload(lambda, (size_t)C, &dl));
+    if (S > 0) {
+        CPI_TRY(st.upload((const double *)delta, (size_t)S * 15, &dd0));
+        dd = const_cast<double *>(dd0);
+    } else {
+        CPI_TRY(st.alloc((size_t)1, &dd));
+    }
+    if (status) CPI_TRY(st.alloc((size_t)C, &ds));
+    CPI_TRY(st.alloc(cpi_chain_solve_workspace_doubles(S), &dw));
+    if (!dh && G > 1) {   // F == 0: no chain has a factor (validated above), and the device form wants a pointer it never reads
+        double *none;
+        CPI_TRY(st.alloc((size_t)1, &none));
+        dh = none;
+    }
+    CPI_TRY(cpi_chain_solve_batch(ctx, C, G, S, F, dfirst, dcount, dffirst, dh, dp, dl, damping, dd, ds, dw));
+    if (S > 0) CPI_TRY(st.download(delta, (const double *)dd, (size_t)S * 15));
+    if (status) CPI_TRY(st.download(status, (const int32_t *)ds, (size_t)C));
     return st.finish();
 }

@@ -1,6 +1,6 @@
 // cpi_args.hpp -- kernel argument blocks and the launcher interface between the translation units of libcpi_amd.so.
 //
-// The library is fourteen translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
+// The library is fifteen translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
 //   cpi_mean.hip    cpi_mean_kernel / cpi_mean_tiled_kernel / cpi_tile_*_kernel       (cpi_mean_kernels.hpp)
 //   cpi_running.hip cpi_mean_running_kernel / cpi_mean_stream_running_kernel: a row after every interval, from plain knots /
 //                   from windows cut out of IMU stream(s) in place         (cpi_running_kernels.hpp, cpi_running_body.inc)
@@ -26,6 +26,8 @@
 //   cpi_trial.hip   cpi_retract_kernel / cpi_local_kernel / cpi_factor_cost_kernel / cpi_cost_*_kernel: the optimiser's trial step --
 //                   states moved along a step, and the whitened cost of the factors there with its deterministic total
 //                                                            (cpi_trial_kernels.hpp over cpi_factor_kernels.hpp's input fetch)
+//   cpi_chain.hip   cpi_chain_solve_kernel: the damped block-tridiagonal solve of chains of IMU factors, on the rows of the Hessian
+//                   sweep                                    (cpi_chain_kernels.hpp over cpi_factor_kernels.hpp's DPP multiply-adds)
 //   cpi_factor.hip  evaluateError sweeps, square-root information, Hessian blocks, state prediction
 //                                                                                      (cpi_factor_kernels.hpp)
 //   cpi_abi.hip     the C-ABI of include/cpi_amd.h: argument checks, launch heuristics, device sets (RCCL), the
@@ -198,6 +200,24 @@ struct FactorArgs {
     int r_tri;                 // sqrt_info is the packed upper triangle [F][120] (include/cpi_amd.h: CPI_TRI_INDEX)
 };
 
+// cpi_chain_solve_batch: chain c owns the states [first[c], first[c] + count[c]) and the hess rows from ffirst[c] on.  first, count,
+// ffirst and lambda live in device memory; the ranges are CLAMPED or refused where they are read (cpi_chain_kernels.hpp: chain_range).
+struct ChainArgs {
+    long long C;             // chains
+    int G;                   // the longest chain in states, >= 1
+    long long S, F;          // rows of delta / prior / workspace records; rows of hess
+    const long long *first;  // [C] or NULL: chain c starts at state c * G
+    const int *count;        // [C] or NULL: every chain has G states
+    const long long *ffirst; // [C] or NULL: first[c] - c
+    const double *hess;      // [F][496]
+    const double *prior;     // [S][136] or NULL
+    const double *lambda;    // [C] or NULL (0)
+    int diagonal;            // CPI_DAMP_DIAGONAL
+    double *delta;           // [S][15]
+    int *status;             // [C] or NULL
+    double *workspace;       // [S][chn::WS_D]
+};
+
 struct PredictArgs {
     long long F;
     double grav[3];
@@ -277,6 +297,9 @@ void local_coordinates(long long S, const double *x, const double *other, double
 void factor_cost(int model, int lpf, const FactorArgs &a, double *chi2, double *werr, hipStream_t st);   // lpf 16 | 8 | 4
 size_t cost_total_doubles(long long F);
 void cost_total(long long F, const double *chi2, double *workspace, hipStream_t st);   // workspace[0] = 0.5 sum chi2
+// ---- cpi_chain.hip (cpi_chain_solve_batch)
+size_t chain_workspace_doubles(long long S);
+void chain_solve(const ChainArgs &a, hipStream_t st);
 // ---- cpi_factor.hip
 void factor(int model, bool whiten, int lpf, const FactorArgs &a, hipStream_t st);            // lpf 16 | 8 | 4
 void factor_packed(int model, int lpf, const FactorArgs &a, double *packed, hipStream_t st);  // lpf 2 | 3 | 4 | 6 | 8

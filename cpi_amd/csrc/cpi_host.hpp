@@ -931,6 +931,25 @@ inline std::vector<double> local_coordinates(const Context &ctx, const std::vect
     return xi;
 }
 
+// The Gauss-Newton / Levenberg-Marquardt step of chains of IMU factors (cpi_chain_solve_batch_host: the device kernel's bits).  C
+// chains of G states each, back to back: hess [C * (G - 1) * 496] the rows of the Hessian sweep in chain order, prior empty or
+// [C * G * 136], lambda empty or [C]; diagonal: CPI_DAMP_DIAGONAL instead of CPI_DAMP_IDENTITY.  Returns delta [C * G * 15] (what
+// retract takes); status, when given, receives the per-chain codes of include/cpi_amd.h (a failed chain's rows are NaN).
+inline std::vector<double> chain_solve(const Context &ctx, int64_t C, int64_t G, const std::vector<double> &hess,
+                                       const std::vector<double> &prior = {}, const std::vector<double> &lambda = {},
+                                       bool diagonal = false, std::vector<int32_t> *status = nullptr) {
+    if (C < 0 || G < 1 || hess.size() != (size_t)(C * (G - 1)) * 496 || (!prior.empty() && prior.size() != (size_t)(C * G) * 136) ||
+        (!lambda.empty() && lambda.size() != (size_t)C))
+        throw std::invalid_argument("cpi_host::chain_solve: hess [C * (G - 1) * 496], prior empty or [C * G * 136], lambda empty or [C]");
+    std::vector<double> delta((size_t)(C * G) * 15);
+    if (status) status->assign((size_t)C, 0);
+    static const double none = 0.0;      // G == 1: no factor rows, and the entry wants no pointer either; G > 1 with C == 0: never read
+    ctx.check(cpi_chain_solve_batch_host(ctx.get(), C, G, C * G, C * (G - 1), nullptr, nullptr, nullptr, hess.empty() ? &none : hess.data(),
+                                         prior.empty() ? nullptr : prior.data(), lambda.empty() ? nullptr : lambda.data(),
+                                         diagonal ? CPI_DAMP_DIAGONAL : CPI_DAMP_IDENTITY, delta.data(), status ? status->data() : nullptr));
+    return delta;
+}
+
 // ---- the caller's loop for MANY windows at once --------------------------------------------------------------------
 // What GraphSolver keeps between two states is a deque of IMU readings (GraphSolver.h: imu_times / imu_linaccs /
 // imu_angvel, filled by addmeasurement_imu); createimufactor_cpi_v1 / _v2 (GraphSolver_IMU.cpp:34-134) walk it up to the

@@ -1648,4 +1648,113 @@ CPI_HD void theta_noise_add(double *x, const Rec &r, V3 jdrow, double on) {
 }
 }  // namespace fsd
 
+// ------------------------------------------------------------------------------------------
+// cpi_chain_solve_batch: damped block-tridiagonal solve of one chain of IMU factors (include/cpi_amd.h).  Factor k joins states k
+// and k + 1; hess row k is the packed upper triangle of its 31 x 31 [G g; g^T f] (cpi_factor_hessian_*), prior row s the packed
+// upper triangle of the 16 x 16 [Lam eta; eta^T .] of state s.  Block Cholesky along the chain on the AUGMENTED 15 x 16 block
+// [D_s g_s]: column 15 carries the right-hand side through the same eliminations, so y_s = L_s^-1 g_s falls out of the
+// factorisation and W_s^T y_s out of the Schur update.  Per state, in this order:
+//   N        the carried block: rows / columns 15 .. 29 (and column 30) of factor s - 1, minus W^T [W y] of state s - 1
+//            (one fused multiply-add per term, k = 0 .. 14 ascending); zeros for state 0
+//   A        = (N + H_s[0:15, 0:15 | 30]) + Pr_s, a missing factor or prior adding +0.0
+//   damping  A[j][j] += lambda (identity);  A[j][j] = fma(lambda, d_j, A[j][j]) with d_j = (raw_j + cur_j) + pr_j, the diagonal of
+//            the three sums WITHOUT the Schur term (diagonal)
+//   pivots   k = 0 .. 14: inv = pivot_rsqrt(A[k][k]); R[k][j] = A[k][j] inv (j > k, j = 15: y_k); every column j > k:
+//            A[i][j] = fma(A[i][k], -(inv R[k][j]), A[i][j]), i > k.  The full symmetric block is kept (lane j of the kernel owns
+//            column j), so A[i][k] is column k's own, lower, entry.  A pivot that is not > 0 (NaN included) fails the chain.
+//   W        column c of W = L^-1 U (U = H_s[0:15, 15:30]): w_k = fma(inv_k, u_k, 0); u_i = fma(-R[k][i], w_k, u_i), i > k
+// and back: t_k = y_k - sum_c W[k][c] delta_{s+1}[c] (c ascending, fused; skipped at the last state), then k = 14 .. 0:
+// delta_k = t_k inv_k; t_i = fma(-delta_k, R[i][k], t_i), i < k.
+// The workspace record of a state (WS_D doubles): row k of [R y] from column k on -- 16 - k entries at row_off(k), 1 / R[k][k] in
+// place of the diagonal --, then W row-major.  The kernel (cpi_chain_kernels.hpp) is the lane-mapped form of these functions: the
+// same terms in the same order, its products with another lane's entries DPP broadcast operands; tests/hostsim runs them as they are.
+// Not bit for bit the kernel's results: inv_sqrt_unclamped is 1 / sqrt on the host and a Newton sequence on the device.
+namespace chn {
+static const int HESS_D = 496, PRIOR_D = 136, WS_R = 135, WS_D = 360;
+CPI_HD constexpr int tri(int d) { return d * (d + 1) / 2; }                       // packed column d starts here
+CPI_HD constexpr int row_off(int k) { return 16 * k - k * (k - 1) / 2; }           // row k of [R y] in the workspace record
+CPI_HD double sym_at(const double *P, int i, int d) { return (i <= d) ? P[tri(d) + i] : P[tri(i) + d]; }
+
+// pivots of the augmented block A [15 rows][16 columns]; on return A[k][j], j >= k, holds [R y] with 1 / R[k][k] on the diagonal.
+// Returns false when a pivot was not positive.
+CPI_HD bool factor_block(double (&A)[15][16]) {
+    bool ok = true;
+    for (int k = 0; k < 15; k++) {
+        if (!(A[k][k] > 0.0)) ok = false;
+        const double inv = inv_sqrt_unclamped(A[k][k]);
+        double colk[15];
+        for (int i = k + 1; i < 15; i++) colk[i] = A[i][k];
+        for (int j = k + 1; j < 16; j++) {
+            const double r = A[k][j] * inv, ca = -inv * r;
+            for (int i = k + 1; i < 15; i++) A[i][j] = fma(colk[i], ca, A[i][j]);
+            A[k][j] = r;
+        }
+        A[k][k] = inv;
+    }
+    return ok;
+}
+// W = L^-1 U in place (U[i][c], column c independent of the others)
+CPI_HD void solve_w(const double (&A)[15][16], double (&U)[15][15]) {
+    for (int c = 0; c < 15; c++)
+        for (int k = 0; k < 15; k++) {
+            U[k][c] = fma(A[k][k], U[k][c], 0.0);
+            for (int i = k + 1; i < 15; i++) U[i][c] = fma(-A[k][i], U[k][c], U[i][c]);
+        }
+}
+// N -= W^T [W y]
+CPI_HD void schur(const double (&W)[15][15], const double (&A)[15][16], double (&N)[15][16]) {
+    for (int j = 0; j < 16; j++)
+        for (int i = 0; i < 15; i++)
+            for (int k = 0; k < 15; k++) N[i][j] = fma(-W[k][i], (j < 15) ? W[k][j] : A[k][15], N[i][j]);
+}
+// One chain of n states: hess = its n - 1 factor rows, prior = its n rows or NULL, ws = n records, delta = n rows.
+// Returns 0, or s + 1 for the first state whose block was not positive definite (delta is all NaN then).
+CPI_HD int solve_chain(int n, const double *hess, const double *prior, double lam, int diagonal, double *ws, double *delta) {
+    double N[15][16], raw[15];
+    int status = 0;
+    for (int i = 0; i < 15; i++) { raw[i] = 0.0; for (int j = 0; j < 16; j++) N[i][j] = 0.0; }
+    for (int s = 0; s < n; s++) {
+        const double *H = (s < n - 1) ? hess + (long long)s * HESS_D : nullptr, *Pr = prior ? prior + (long long)s * PRIOR_D : nullptr;
+        double A[15][16], U[15][15];
+        for (int j = 0; j < 16; j++) {
+            const int cj = (j < 15) ? j : 30, pj = j;
+            for (int i = 0; i < 15; i++) A[i][j] = (N[i][j] + (H ? sym_at(H, i, cj) : 0.0)) + (Pr ? sym_at(Pr, i, pj) : 0.0);
+        }
+        for (int j = 0; j < 15; j++) {
+            const double d = (raw[j] + (H ? H[tri(j) + j] : 0.0)) + (Pr ? Pr[tri(j) + j] : 0.0);
+            A[j][j] = diagonal ? fma(lam, d, A[j][j]) : A[j][j] + lam;
+        }
+        if (!factor_block(A) && status == 0) status = s + 1;
+        for (int i = 0; i < 15; i++) {
+            for (int c = 0; c < 15; c++) U[i][c] = H ? H[tri(15 + c) + i] : 0.0;
+            for (int j = 0; j < 16; j++) N[i][j] = H ? sym_at(H, 15 + i, (j < 15) ? 15 + j : 30) : 0.0;
+            raw[i] = H ? H[tri(15 + i) + 15 + i] : 0.0;
+        }
+        solve_w(A, U);
+        schur(U, A, N);
+        double *rec = ws + (long long)s * WS_D;
+        for (int k = 0; k < 15; k++) {
+            for (int j = k; j < 16; j++) rec[row_off(k) + j - k] = A[k][j];
+            for (int c = 0; c < 15; c++) rec[WS_R + k * 15 + c] = U[k][c];
+        }
+    }
+    for (int s = n - 1; s >= 0; s--) {
+        const double *rec = ws + (long long)s * WS_D;
+        double t[15], *x = delta + (long long)s * 15;
+        for (int k = 0; k < 15; k++) {
+            t[k] = rec[row_off(k) + 15 - k];
+            if (s < n - 1)
+                for (int c = 0; c < 15; c++) t[k] = fma(-x[15 + c], rec[WS_R + k * 15 + c], t[k]);
+        }
+        for (int k = 14; k >= 0; k--) {
+            x[k] = t[k] * rec[row_off(k)];
+            for (int i = 0; i < k; i++) t[i] = fma(-x[k], rec[row_off(i) + k - i], t[i]);
+        }
+    }
+    if (status)
+        for (int i = 0; i < n * 15; i++) delta[i] = NAN;
+    return status;
+}
+}  // namespace chn
+
 }  // namespace cpi

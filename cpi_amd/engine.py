@@ -1311,6 +1311,94 @@ class Engine:
                                                         _ptr(out.get("werr")), _ptr(out.get("total"))))
         return out
 
+    # ------------------------------------------------------------------ the step itself, for chains of IMU factors
+    DAMPING = {"identity": 0, "diagonal": 1}
+
+    def chain_solve_workspace_doubles(self, S):
+        """Doubles of the workspace of chain_solve for S states (cpi_chain_solve_workspace_doubles)."""
+        return int(self.lib.cpi_chain_solve_workspace_doubles(int(S)))
+
+    @staticmethod
+    def chain_indices(C, G, first=None, count=None):
+        """int32 (idx_i, idx_j) of the factors of C chains for the Hessian / cost sweeps, in the order chain_solve reads them with
+        ffirst=None when the chains tile the states back to back: factor k of chain c joins states first[c] + k and first[c] + k + 1.
+        first [C] int64 (None: c * G), count [C] int32 states per chain (None: G; clamped into [0, G]).  Plain torch ops on the
+        device of first / count (CPU when both are None)."""
+        dev = first.device if first is not None else (count.device if count is not None else torch.device("cpu"))
+        f = first.to(torch.int64) if first is not None else torch.arange(C, dtype=torch.int64, device=dev) * G
+        n = count.to(torch.int64).clamp(0, G) if count is not None else torch.full((C,), G, dtype=torch.int64, device=dev)
+        nf = (n - 1).clamp(min=0)
+        k = torch.arange(max(G - 1, 0), dtype=torch.int64, device=dev)[None, :]
+        idx_i = (f[:, None] + k)[k < nf[:, None]]
+        return idx_i.to(torch.int32).contiguous(), (idx_i + 1).to(torch.int32).contiguous()
+
+    def _chain_args(self, hess, C, G, first, count, ffirst, prior, lam, damping, out, status, cuda):
+        where = "CUDA" if cuda else "CPU"
+        assert damping in self.DAMPING, "damping: 'identity' or 'diagonal'"
+        for name, t, dt in (("first", first, torch.int64), ("count", count, torch.int32), ("ffirst", ffirst, torch.int64)):
+            assert t is None or (t.dtype == dt and t.is_contiguous() and t.is_cuda == cuda and t.dim() == 1), \
+                "%s: a contiguous %s %s tensor [C]" % (name, str(dt).split(".")[1], where)
+        if C is None:
+            C = next((t.shape[0] for t in (first, count, ffirst) if t is not None), None)
+        assert C is not None, "C: the number of chains (or first / count / ffirst, which have it)"
+        assert all(t is None or t.shape[0] == C for t in (first, count, ffirst)), "first / count / ffirst: [C]"
+        assert G is not None and G >= 1, "G: the longest chain in states, >= 1"
+        if hess is not None:
+            self._trial_tensor(hess, 496, cuda, "hess")
+        if prior is not None:
+            self._trial_tensor(prior, 136, cuda, "prior")
+        S = out.shape[0] if out is not None else (prior.shape[0] if prior is not None else C * G)
+        if out is None:
+            # rows of no chain are not written: they read NaN rather than whatever the allocator left there
+            out = torch.full((S, 15), float("nan"), dtype=torch.float64, device=self.device if cuda else "cpu")
+        self._trial_tensor(out, 15, cuda, "out", S)
+        assert prior is None or prior.shape[0] == S, "prior: [S, 136] with the S of out"
+        if lam is not None:
+            if not torch.is_tensor(lam):
+                lam = torch.full((C,), float(lam), dtype=torch.float64, device=out.device)
+            elif lam.numel() == 1 and C != 1:
+                lam = lam.reshape(1).expand(C).contiguous()      # torch ops on the tensor's device: no host read
+            lam = lam.reshape(-1)
+            assert lam.dtype == torch.float64 and lam.is_contiguous() and lam.is_cuda == cuda and lam.shape == (C,), \
+                "lam: a number, or a float64 %s tensor with one element or C" % where
+        assert status is None or (status.dtype == torch.int32 and status.is_contiguous() and status.is_cuda == cuda and status.shape == (C,)), \
+            "status: a contiguous int32 %s tensor [C]" % where
+        F = hess.shape[0] if hess is not None else 0
+        return C, int(G), S, F, lam, out
+
+    def chain_solve(self, hess, C=None, G=None, first=None, count=None, ffirst=None, prior=None, lam=None, damping="identity", out=None,
+                    status=None, workspace=None):
+        """cpi_chain_solve_batch: the Gauss-Newton / Levenberg-Marquardt step delta [S,15] of C chains of IMU factors -- the damped
+        block-tridiagonal system of include/cpi_amd.h, solved by a block Cholesky along every chain on the rows of factor_hessian as
+        they are.  hess [F,496] (None only with G == 1); chain c owns the states first[c] .. first[c] + count[c] - 1 (None: c * G
+        and G) and the hess rows ffirst[c] + k (None: first[c] - c: chain_indices gives the matching idx_i / idx_j); prior None or
+        [S,136] packed [Lam eta; eta^T .] per state; lam None, a number, or a CUDA float64 tensor of one element or C (expanded with
+        torch ops: no host read; a Levenberg-Marquardt loop keeps it on the device); damping "identity" or "diagonal".  S comes from
+        out, else prior, else C * G.  status: an int32 [C] tensor to fill (0 solved, s + 1 the block of state s was not positive
+        definite, -1 the chain's factor rows leave hess); a failed chain's rows are NaN.  workspace: float64,
+        chain_solve_workspace_doubles(S) elements (allocated when None; pass one for graph capture).  Rows of no chain are not written
+        (NaN in a tensor this call allocates).  retract takes delta as it is.  Asynchronous."""
+        C_, G_, S, F, lam, out = self._chain_args(hess, C, G, first, count, ffirst, prior, lam, damping, out, status, True)
+        need = self.chain_solve_workspace_doubles(S)
+        if workspace is None:
+            workspace = torch.empty((need,), dtype=torch.float64, device=self.device)
+        assert (workspace.dtype == torch.float64 and workspace.is_cuda and workspace.is_contiguous() and workspace.dim() == 1
+                and workspace.numel() >= need), "workspace: CUDA float64, chain_solve_workspace_doubles(S) elements"
+        self._sync_stream()
+        self._check(self.lib.cpi_chain_solve_batch(self.ctx, C_, G_, S, F, _ptr(first), _ptr(count), _ptr(ffirst), _ptr(hess), _ptr(prior),
+                                                   _ptr(lam), self.DAMPING[damping], _ptr(out), _ptr(status), _ptr(workspace)))
+        return out
+
+    def chain_solve_host(self, hess, C=None, G=None, first=None, count=None, ffirst=None, prior=None, lam=None, damping="identity",
+                         out=None, status=None):
+        """chain_solve on CPU tensors (cpi_chain_solve_batch_host): every chain's state and factor range is validated (CpiError names
+        the chain), synchronous, the device form's bits."""
+        C_, G_, S, F, lam, out = self._chain_args(hess, C, G, first, count, ffirst, prior, lam, damping, out, status, False)
+        self._sync_stream()
+        self._check(self.lib.cpi_chain_solve_batch_host(self.ctx, C_, G_, S, F, _ptr(first), _ptr(count), _ptr(ffirst), _ptr(hess),
+                                                        _ptr(prior), _ptr(lam), self.DAMPING[damping], _ptr(out), _ptr(status)))
+        return out
+
 
 def unpack_factor(packed, meas):
     """Dense (err [F,15], H1 [F,225], H2 [F,225], column-major) from the packed evaluation and the measurement it was
@@ -1361,6 +1449,11 @@ def local_coordinates(x, other, out=None):
 def factor_cost(*args, **kw):
     """Engine.factor_cost on the default engine."""
     return default_engine().factor_cost(*args, **kw)
+
+
+def chain_solve(*args, **kw):
+    """Engine.chain_solve on the default engine."""
+    return default_engine().chain_solve(*args, **kw)
 
 
 # ---------------------------------------------------------------------- reference-shaped classes

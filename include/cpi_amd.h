@@ -71,7 +71,9 @@ extern "C" {
                                cpi_factor_cost_tri_batch, cpi_factor_cost_total_doubles and the host forms
                                cpi_retract_batch_host, cpi_local_batch_host, cpi_factor_cost_batch_host (the optimiser's trial
                                step: the states moved along a solved step, and the whitened cost 0.5 |R e|^2 of the factors at
-                               the trial states with a deterministic total) */
+                               the trial states with a deterministic total); cpi_chain_solve_batch,
+                               cpi_chain_solve_workspace_doubles, cpi_chain_solve_batch_host (the damped block-tridiagonal
+                               solve of chains of IMU factors on the rows of cpi_factor_hessian_*: the step of the loop above) */
 
 enum { CPI_OK = 0, CPI_ERR_INVALID = 1, CPI_ERR_HIP = 2, CPI_ERR_NO_DEVICE = 3, CPI_ERR_RCCL = 4 };
 enum {
@@ -807,7 +809,8 @@ int cpi_predict_batch(cpi_ctx *ctx, int32_t model, const double grav[3], int64_t
 /* ---- The optimiser's trial step.  With cpi_factor_hessian_* these close the loop
  *     linearise -> solve (the caller's) -> retract -> cost -> accept / reject
  * on the device: none of them synchronises the host, and each is a chain of kernels without branches on the context's stream, so
- * the whole iteration captures into one graph.  No solver is provided.
+ * the whole iteration captures into one graph.  No general sparse solver is provided; for graphs whose factors form chains
+ * (IMU factors between consecutive states, plus whatever touches one state at a time) cpi_chain_solve_batch below is the solve.
  *
  * cpi_retract_batch replaces: JPLNavState::retract (gtsam/JPLNavState.cpp:37-71), the map along which every H1 / H2 of the
  * evaluateError sweeps is a derivative.  states_out[s] = retract(states_in[s], delta[s]):
@@ -850,6 +853,49 @@ int cpi_factor_cost_tri_batch(cpi_ctx *ctx, int32_t model, const double grav[3],
                               const cpi_outputs *meas, const double *lin, const double *q_k_lin,
                               const double *states, int64_t S, const int32_t *idx_i, const int32_t *idx_j,
                               const double *R_tri, double *chi2, double *werr, double *total);
+
+/* The step of the loop above for CHAINS of IMU factors.  Replaces: the elimination of a chain by GTSAM's linear solver (the
+ * GaussianFactorGraph of the linearised IMU factors and single-state priors, eliminated along the trajectory; GTSAM is absent from
+ * the reference tree: PARITY UNPINNED like the other entries of SURVEY.md 8 f1, checked against a long-double dense solve of the
+ * definition below).  NOT replicated: the minDiagonal / maxDiagonal clamps of GTSAM's LevenbergMarquardtParams on the damping
+ * diagonal -- a caller who wants them clamps the prior's diagonal or lambda.  Not a general sparse solver: factors that couple
+ * non-adjacent states (visual factors) are out of scope.
+ * Chain c has n_c states s = 0 .. n_c - 1 and n_c - 1 factors, factor k joining states k and k + 1.  With H_k the 31 x 31 matrix of
+ * hess row k (the packing of cpi_factor_hessian_*) and Pr_s the optional 16 x 16 prior [Lam eta; eta^T .] of state s:
+ *     D_s = H_{s-1}[15:30, 15:30] + H_s[0:15, 0:15] + Pr_s[0:15, 0:15]       (a missing neighbour contributes nothing)
+ *     U_s = H_s[0:15, 15:30]                                                  (block (s, s + 1))
+ *     g_s = H_{s-1}[15:30, 30] + H_s[0:15, 30] + Pr_s[0:15, 15]
+ *     D_s += lambda_c I (CPI_DAMP_IDENTITY)   or   D_s += lambda_c diag(D_s) (CPI_DAMP_DIAGONAL; diag taken after the sums above)
+ *     A delta = g,   A = blocktridiag(U_{s-1}^T, D_s, U_s)
+ * g is taken as hess holds it (g = A^T b, b = -R e): delta is the Gauss-Newton / Levenberg-Marquardt step, and cpi_retract_batch
+ * takes it as it is.  Block Cholesky along the chain (L_s = chol(D_s - W_{s-1}^T W_{s-1}), W_s = L_s^-1 U_s), forward and back.
+ *   C chains; G >= 1 the longest chain in states; S rows of delta / prior; F rows of hess            (the layout of cpi_merge_batch)
+ *   first  [C] the chain's first state, NULL: c * G;  count [C] its number of states, clamped into [0, G], NULL: G; a chain is
+ *          clipped at S.  ffirst [C]: the factor joining states first + k and first + k + 1 is hess row ffirst[c] + k; NULL:
+ *          first_c - c (factors in chain order when the chains tile the states back to back).  The idx_i / idx_j of the Hessian
+ *          sweep are these pairs.
+ *   hess   [F][496];  prior NULL or [S][136], the packed upper triangle in the same column-major rule ((i, d) at i + d (d + 1) / 2;
+ *          entry 135 is never read);  lambda NULL or [C] DEVICE doubles (a Levenberg-Marquardt loop keeps lambda on the device);
+ *          NULL gives the bits of lambda = 0
+ *   delta  [S][15]; rows of no chain are not written.  status NULL or [C]: 0 solved; s + 1: the pivot block of state s was not
+ *          positive definite (a pivot that is not > 0, the rule of cpi_sqrt_information_*); -1: the chain's factor rows leave
+ *          [0, F) -- such a chain reads nothing outside the arrays.  A failed or refused chain has NaN in every delta row of its
+ *          own; no other chain is affected.  count = 1 solves (Lam + damping) delta = eta; count = 0 writes nothing, status 0.
+ *   workspace  cpi_chain_solve_workspace_doubles(S) doubles of the caller's ([R y] and W of every state, 360 doubles each); its
+ *          contents after the call are not declared.  The library allocates nothing.
+ * A chain's bits depend on its own data only, not on C or on its position.  Chains that share states are the caller's error: the
+ * contents are unspecified, no access goes out of bounds.  One kernel on the context's stream, no host synchronisation: capturable.
+ * 16 lanes work on a chain, 4 chains share a wavefront; there is no parallelism ALONG a chain, so one long chain runs at the
+ * latency of its states in sequence (profiles/chain_solve.md).
+ * Refused before the context is looked at (CPI_ERR_INVALID): NULL hess when G > 1, NULL delta / workspace, negative sizes, G < 1 or
+ * G > 2^31 - 1, a damping other than the two, any output that overlaps an input or another output ("overlaps" in cpi_last_error).  C == 0 is a
+ * no-op. */
+enum { CPI_DAMP_IDENTITY = 0, CPI_DAMP_DIAGONAL = 1 };
+size_t cpi_chain_solve_workspace_doubles(int64_t S);
+int cpi_chain_solve_batch(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_t F,
+                          const int64_t *first, const int32_t *count, const int64_t *ffirst,
+                          const double *hess, const double *prior, const double *lambda, int32_t damping,
+                          double *delta, int32_t *status, double *workspace);
 
 /* ---- Device sets: the 8-GPU path of a single-process host (nothing in the reference, which is a
  * single-threaded CPU program).  Windows (and factors) are independent units: rank r of n owns the contiguous block
@@ -1053,6 +1099,14 @@ int cpi_factor_cost_batch_host(cpi_ctx *ctx, int32_t model, const double grav[3]
                                const cpi_outputs *meas, const double *lin, const double *q_k_lin,
                                const double *states, int64_t S, const int32_t *idx_i, const int32_t *idx_j,
                                double *chi2, double *werr, double *total);
+
+/* cpi_chain_solve_batch from host memory: every pointer a host pointer (lambda too), no workspace, synchronous; the device form's
+ * bits.  Every chain's state range and factor range is validated first: a chain whose states leave [0, S) or whose factor rows
+ * leave [0, F) is CPI_ERR_INVALID, the text names the chain.  Rows of delta that belong to no chain keep the caller's values. */
+int cpi_chain_solve_batch_host(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_t F,
+                               const int64_t *first, const int32_t *count, const int64_t *ffirst,
+                               const double *hess, const double *prior, const double *lambda, int32_t damping,
+                               double *delta, int32_t *status);
 
 #ifdef __cplusplus
 }
