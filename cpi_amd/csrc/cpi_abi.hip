@@ -1402,6 +1402,53 @@ extern "C" int cpi_chain_solve_batch(cpi_ctx *ctx, int64_t C, int64_t G, int64_t
     return CPI_OK;
 }
 
+// ============================================================================================
+// cpi_chain_marginals_batch: the state covariances of solved chains (cpi_marginals_kernel, cpi_marginals.hip)
+// ============================================================================================
+// what both forms refuse alike, before the context is looked at; host: no workspace, status is an output
+static int marginals_check(cpi_ctx *ctx, const char *who, int64_t C, int64_t G, int64_t S, const int64_t *first, const int32_t *count,
+                           const int32_t *status, const double *workspace, double *cov, double *cross, bool host) {
+    if (C < 0 || S < 0) return refuse(ctx, who, "negative size");
+    if (G < 1) return refuse(ctx, who, "G (the longest chain in states) must be >= 1");
+    if (G > 0x7fffffffLL) return refuse(ctx, who, "G exceeds 2^31 - 1 states per chain");
+    if (S > 0 && !host && !workspace) return refuse(ctx, who, "workspace is NULL");
+    if (S > 0 && !cov) return refuse(ctx, who, "cov is NULL");
+    const size_t d = sizeof(double);
+    const void *outp[3] = { cov, cross, host ? (const void *)status : nullptr };
+    const size_t outn[3] = { (size_t)S * 120 * d, (size_t)S * 225 * d, (size_t)C * sizeof(int32_t) };
+    static const char *const outname[3] = { "cov", "cross", "status" };
+    const void *inp[4] = { workspace, first, count, host ? nullptr : (const void *)status };
+    const size_t inn[4] = { workspace ? cpi_chain_solve_workspace_doubles(S) * d : 0, (size_t)C * sizeof(int64_t), (size_t)C * sizeof(int32_t),
+                            (size_t)C * sizeof(int32_t) };
+    for (int o = 0; o < 3; o++) {
+        bool bad = false;
+        for (int k = 0; k < 4; k++) bad = bad || bytes_overlap(outp[o], outn[o], inp[k], inn[k]);
+        for (int q = o + 1; q < 3; q++) bad = bad || bytes_overlap(outp[o], outn[o], outp[q], outn[q]);
+        if (bad) return refuse(ctx, who, outname[o], " overlaps an input or another output");
+    }
+    return CPI_OK;
+}
+
+extern "C" int cpi_chain_marginals_batch(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S,
+                                         const int64_t *first, const int32_t *count, const int32_t *status,
+                                         const double *workspace, double *cov, double *cross) {
+    static const char who[] = "cpi_chain_marginals_batch";
+    CPI_TRY(marginals_check(ctx, who, C, G, S, first, count, status, workspace, cov, cross, false));
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (C == 0 || S == 0) return CPI_OK;               // no chain has a state
+    if (!grid_ok((C + 3) / 4)) return refuse(ctx, who, "C exceeds the 32-bit grid (4 chains per workgroup)");
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    MarginalsArgs a;
+    memset(&a, 0, sizeof a);
+    a.C = C; a.G = (int)G; a.S = S;
+    a.first = (const long long *)first; a.count = count; a.status = status;
+    a.workspace = workspace; a.cov = cov; a.cross = cross;
+    launch::chain_marginals(a, ctx->stream);
+    CPI_HIP(ctx, hipGetLastError());
+    return CPI_OK;
+}
+
 extern "C" size_t cpi_outputs_slab_doubles(const cpi_outputs *mask, int64_t Wb) {
     if (!mask || Wb <= 0) return 0;
     size_t n = 0;
@@ -2850,6 +2897,70 @@ extern "C" int cpi_chain_solve_batch_host(cpi_ctx *ctx, int64_t C, int64_t G, in
     }
     CPI_TRY(cpi_chain_solve_batch(ctx, C, G, S, F, dfirst, dcount, dffirst, dh, dp, dl, damping, dd, ds, dw));
     if (S > 0) CPI_TRY(st.download(delta, (const double *)dd, (size_t)S * 15));
+    if (status) CPI_TRY(st.download(status, (const int32_t *)ds, (size_t)C));
+    return st.finish();
+}
+
+// cpi_chain_marginals_batch from host memory: the undamped solve of the host arrays on the device, the marginals kernel on the
+// workspace it left, cov / cross / status back.  cov and cross travel up first, so that the rows nobody writes come back as the caller
+// left them.  The ranges are validated as in cpi_chain_solve_batch_host.
+extern "C" int cpi_chain_marginals_batch_host(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_t F,
+                                              const int64_t *first, const int32_t *count, const int64_t *ffirst,
+                                              const double *hess, const double *prior,
+                                              double *cov, double *cross, int32_t *status) {
+    static const char who[] = "cpi_chain_marginals_batch_host";
+    if (F < 0) return refuse(ctx, who, "negative size");
+    CPI_TRY(marginals_check(ctx, who, C, G, S, first, count, status, nullptr, cov, cross, true));
+    if (C > 0 && !hess && G > 1) return refuse(ctx, who, "hess is NULL (only chains of one state, G == 1, need none)");
+    {
+        const size_t d = sizeof(double);
+        const void *outp[3] = { cov, cross, status };
+        const size_t outn[3] = { (size_t)S * 120 * d, (size_t)S * 225 * d, (size_t)C * sizeof(int32_t) };
+        static const char *const outname[3] = { "cov", "cross", "status" };
+        for (int o = 0; o < 3; o++)
+            if (bytes_overlap(outp[o], outn[o], ffirst, (size_t)C * sizeof(int64_t)) || bytes_overlap(outp[o], outn[o], hess, (size_t)F * 496 * d) ||
+                bytes_overlap(outp[o], outn[o], prior, (size_t)S * 136 * d))
+                return refuse(ctx, who, outname[o], " overlaps an input or another output");
+    }
+    for (int64_t c = 0; c < C; c++) {
+        const int64_t f = first ? first[c] : c * G;
+        int64_t n = count ? count[c] : G;
+        n = n < 0 ? 0 : (n > G ? G : n);
+        if (f < 0 || f > S || n > S - f)
+            return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": the states of chain " + std::to_string(c) + " leave [0, S)");
+        const int64_t ff = ffirst ? ffirst[c] : f - c;
+        if (n > 1 && (ff < 0 || ff > F - (n - 1)))
+            return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": the factor rows of chain " + std::to_string(c) + " leave [0, F)");
+    }
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (C == 0 || S == 0) return CPI_OK;
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    Staging st(ctx);
+    const int64_t *dfirst, *dffirst;
+    const int32_t *dcount;
+    const double *dh, *dp, *dc0, *dx0 = nullptr;
+    double *dd, *dw;
+    int32_t *ds;
+    CPI_TRY(st.upload(first, (size_t)C, &dfirst));
+    CPI_TRY(st.upload(count, (size_t)C, &dcount));
+    CPI_TRY(st.upload(ffirst, (size_t)C, &dffirst));
+    CPI_TRY(st.upload(F > 0 ? hess : nullptr, (size_t)F * 496, &dh));
+    CPI_TRY(st.upload(prior, (size_t)S * 136, &dp));
+    CPI_TRY(st.upload((const double *)cov, (size_t)S * 120, &dc0));
+    if (cross) CPI_TRY(st.upload((const double *)cross, (size_t)S * 225, &dx0));
+    CPI_TRY(st.alloc((size_t)S * 15, &dd));
+    CPI_TRY(st.alloc((size_t)C, &ds));
+    CPI_TRY(st.alloc(cpi_chain_solve_workspace_doubles(S), &dw));
+    if (!dh && G > 1) {   // F == 0: no chain has a factor (validated above), and the solve wants a pointer it never reads
+        double *none;
+        CPI_TRY(st.alloc((size_t)1, &none));
+        dh = none;
+    }
+    CPI_TRY(cpi_chain_solve_batch(ctx, C, G, S, F, dfirst, dcount, dffirst, dh, dp, nullptr, CPI_DAMP_IDENTITY, dd, ds, dw));
+    CPI_TRY(cpi_chain_marginals_batch(ctx, C, G, S, dfirst, dcount, ds, dw, const_cast<double *>(dc0), const_cast<double *>(dx0)));
+    CPI_TRY(st.download(cov, dc0, (size_t)S * 120));
+    if (cross) CPI_TRY(st.download(cross, dx0, (size_t)S * 225));
     if (status) CPI_TRY(st.download(status, (const int32_t *)ds, (size_t)C));
     return st.finish();
 }

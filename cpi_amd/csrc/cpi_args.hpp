@@ -1,6 +1,6 @@
 // cpi_args.hpp -- kernel argument blocks and the launcher interface between the translation units of libcpi_amd.so.
 //
-// The library is fifteen translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
+// The library is sixteen translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
 //   cpi_mean.hip    cpi_mean_kernel / cpi_mean_tiled_kernel / cpi_tile_*_kernel       (cpi_mean_kernels.hpp)
 //   cpi_running.hip cpi_mean_running_kernel / cpi_mean_stream_running_kernel: a row after every interval, from plain knots /
 //                   from windows cut out of IMU stream(s) in place         (cpi_running_kernels.hpp, cpi_running_body.inc)
@@ -28,6 +28,9 @@
 //                                                            (cpi_trial_kernels.hpp over cpi_factor_kernels.hpp's input fetch)
 //   cpi_chain.hip   cpi_chain_solve_kernel: the damped block-tridiagonal solve of chains of IMU factors, on the rows of the Hessian
 //                   sweep                                    (cpi_chain_kernels.hpp over cpi_factor_kernels.hpp's DPP multiply-adds)
+//   cpi_marginals.hip  cpi_marginals_kernel: the state covariances of solved chains -- the diagonal and first off-diagonal blocks of
+//                   the inverse, one backward recursion over the factor the solve left in the workspace
+//                                   (cpi_marginals_kernels.hpp over cpi_factor_kernels.hpp's DPP multiply-adds; cpi_chain_util.hpp)
 //   cpi_factor.hip  evaluateError sweeps, square-root information, Hessian blocks, state prediction
 //                                                                                      (cpi_factor_kernels.hpp)
 //   cpi_abi.hip     the C-ABI of include/cpi_amd.h: argument checks, launch heuristics, device sets (RCCL), the
@@ -218,6 +221,19 @@ struct ChainArgs {
     double *workspace;       // [S][chn::WS_D]
 };
 
+// cpi_chain_marginals_batch: C, G, S, first, count as the solve that wrote workspace had them (cpi_chain_util.hpp: chain_states).
+struct MarginalsArgs {
+    long long C;              // chains
+    int G;                    // the longest chain in states, >= 1
+    long long S;              // rows of workspace records / cov / cross
+    const long long *first;   // [C] or NULL: chain c starts at state c * G
+    const int *count;         // [C] or NULL: every chain has G states
+    const int *status;        // [C] or NULL: as the solve wrote it; a chain whose status is not 0 gets NaN
+    const double *workspace;  // [S][chn::WS_D], read only
+    double *cov;              // [S][120]
+    double *cross;            // [S][225] or NULL
+};
+
 struct PredictArgs {
     long long F;
     double grav[3];
@@ -300,6 +316,8 @@ void cost_total(long long F, const double *chi2, double *workspace, hipStream_t 
 // ---- cpi_chain.hip (cpi_chain_solve_batch)
 size_t chain_workspace_doubles(long long S);
 void chain_solve(const ChainArgs &a, hipStream_t st);
+// ---- cpi_marginals.hip (cpi_chain_marginals_batch)
+void chain_marginals(const MarginalsArgs &a, hipStream_t st);
 // ---- cpi_factor.hip
 void factor(int model, bool whiten, int lpf, const FactorArgs &a, hipStream_t st);            // lpf 16 | 8 | 4
 void factor_packed(int model, int lpf, const FactorArgs &a, double *packed, hipStream_t st);  // lpf 2 | 3 | 4 | 6 | 8

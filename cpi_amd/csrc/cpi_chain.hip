@@ -15,6 +15,7 @@ using namespace cpi;
 
 #include "cpi_device_util.hpp"
 #include "cpi_factor_kernels.hpp"
+#include "cpi_chain_util.hpp"
 #include "cpi_chain_kernels.hpp"
 
 namespace cpi {

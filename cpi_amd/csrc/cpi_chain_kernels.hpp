@@ -1,7 +1,8 @@
 // cpi_chain_kernels.hpp -- cpi_chain_solve_kernel: the damped block-tridiagonal solve of chains of IMU factors (cpi_chain_solve_batch;
 // the arithmetic and the workspace record: cpi_math.hpp, namespace chn, whose lane-mapped form this is).
 // Part of the translation unit cpi_chain.hip (included there after cpi_math.hpp / cpi_device_util.hpp / cpi_factor_kernels.hpp, from
-// which it takes row_share, dpp_fmac / dpp_fnmac / dpp_mul and pivot_rsqrt; not a stand-alone header).
+// which it takes row_share, dpp_fmac / dpp_fnmac / dpp_mul and pivot_rsqrt, and after cpi_chain_util.hpp: chain_for, chain_settle,
+// chain_states; not a stand-alone header).
 //
 // 16 lanes (one DPP row) per chain, 4 chains per wavefront, one wavefront per workgroup.  Lane j < 15 keeps column j of the working
 // block in registers -- the FULL symmetric column, so the multiplier of its own trailing update is a static register --, lane 15
@@ -31,11 +32,7 @@ struct __attribute__((packed, aligned(8))) chain_d2u { double a, b; };
 __device__ __forceinline__ long long readlane64(long long v, int l) {
     return ((long long)__builtin_amdgcn_readlane((int)(v >> 32), l) << 32) | (unsigned)__builtin_amdgcn_readlane((int)(v & 0xffffffffll), l);
 }
-// compile-time loops over a DPP control (the broadcast lane is an immediate)
-template <int I, int N, class F>
-__device__ __forceinline__ void chain_for(F &&f) {
-    if constexpr (I < N) { f(std::integral_constant<int, I>()); chain_for<I + 1, N>(f); }
-}
+// compile-time loops over a DPP control: chain_for (ascending) is cpi_chain_util.hpp's
 template <int I, class F>
 __device__ __forceinline__ void chain_for_down(F &&f) {
     if constexpr (I >= 0) { f(std::integral_constant<int, I>()); chain_for_down<I - 1>(f); }
@@ -46,8 +43,7 @@ __device__ __forceinline__ void chain_for_down(F &&f) {
 __device__ __forceinline__ double chain_pick(bool first, double x, double y) { return first ? x : y; }
 // keeps the reads of one group from being issued with the next group's (instruction selection orders memory operations along it)
 __device__ __forceinline__ void chain_read_fence() { asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); }
-// a VALU result that is read as a DPP source next: two wait states, tied to the register so that nothing moves across
-__device__ __forceinline__ void chain_settle(double &v) { asm volatile("s_nop 1" : "+v"(v)); }
+// (chain_settle, the wait states in front of a DPP read of a VALU result: cpi_chain_util.hpp)
 
 // pivot step K of the augmented block (chn::factor_block); a[K] becomes R[K][j] (1 / R[K][K] in lane K)
 // No "finished lane" select in the trailing update: lanes j <= K go on updating rows of columns that are never read again (the
@@ -75,16 +71,10 @@ __device__ __forceinline__ void chain_pivot_step(double (&a)[15], int j, bool &f
 struct ChainRange { long long f, ff; int n; bool bad; };
 __device__ __forceinline__ ChainRange chain_range(const ChainArgs &A, long long c) {
     ChainRange r;
-    const long long cc = (c < A.C) ? c : A.C - 1;
-    long long f = A.first ? A.first[cc] : cc * (long long)A.G;
-    int n = A.count ? A.count[cc] : A.G;
-    n = (n < 0) ? 0 : ((n > A.G) ? A.G : n);
-    f = (f < 0) ? 0 : ((f > A.S) ? A.S : f);
-    if (A.S - f < (long long)n) n = (int)(A.S - f);
-    if (c >= A.C) n = 0;
-    r.f = f; r.n = n;
-    r.ff = A.ffirst ? A.ffirst[cc] : f - cc;
-    r.bad = n > 1 && (r.ff < 0 || r.ff > A.F - (long long)(n - 1));
+    const ChainStates cs = chain_states(A.C, A.G, A.S, A.first, A.count, c);   // the states: the rule cpi_marginals_kernel shares
+    r.f = cs.f; r.n = cs.n;
+    r.ff = A.ffirst ? A.ffirst[cs.cc] : cs.f - cs.cc;
+    r.bad = cs.n > 1 && (r.ff < 0 || r.ff > A.F - (long long)(cs.n - 1));
     return r;
 }
 

@@ -950,6 +950,26 @@ inline std::vector<double> chain_solve(const Context &ctx, int64_t C, int64_t G,
     return delta;
 }
 
+// The covariance of every state of chains of IMU factors at the states hess was linearised at (cpi_chain_marginals_batch_host: the
+// UNDAMPED system of chain_solve's hess / prior, factorised and inverted block by block on the device; the device kernels' bits).
+// Returns cov [C * G * 120]: Sigma[s][s] of every state as the packed upper triangle ((i, j), i <= j, at i + j (j + 1) / 2 -- a row
+// of cpi_sqrt_information_packed_batch_host's input).  cross, when given, receives [C * G * 225]: Sigma[s][s+1] column-major in row s
+// (the row of a chain's last state stays zero); status the solve's per-chain codes (a failed chain's rows are NaN).
+inline std::vector<double> chain_marginals(const Context &ctx, int64_t C, int64_t G, const std::vector<double> &hess,
+                                           const std::vector<double> &prior = {}, std::vector<double> *cross = nullptr,
+                                           std::vector<int32_t> *status = nullptr) {
+    if (C < 0 || G < 1 || hess.size() != (size_t)(C * (G - 1)) * 496 || (!prior.empty() && prior.size() != (size_t)(C * G) * 136))
+        throw std::invalid_argument("cpi_host::chain_marginals: hess [C * (G - 1) * 496], prior empty or [C * G * 136]");
+    std::vector<double> cov((size_t)(C * G) * 120);
+    if (cross) cross->assign((size_t)(C * G) * 225, 0.0);
+    if (status) status->assign((size_t)C, 0);
+    static const double none = 0.0;      // G == 1: no factor rows; G > 1 with C == 0: never read
+    ctx.check(cpi_chain_marginals_batch_host(ctx.get(), C, G, C * G, C * (G - 1), nullptr, nullptr, nullptr, hess.empty() ? &none : hess.data(),
+                                             prior.empty() ? nullptr : prior.data(), cov.data(), cross ? cross->data() : nullptr,
+                                             status ? status->data() : nullptr));
+    return cov;
+}
+
 // ---- the caller's loop for MANY windows at once --------------------------------------------------------------------
 // What GraphSolver keeps between two states is a deque of IMU readings (GraphSolver.h: imu_times / imu_linaccs /
 // imu_angvel, filled by addmeasurement_imu); createimufactor_cpi_v1 / _v2 (GraphSolver_IMU.cpp:34-134) walk it up to the

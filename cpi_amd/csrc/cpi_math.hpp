@@ -1755,6 +1755,69 @@ CPI_HD int solve_chain(int n, const double *hess, const double *prior, double la
         for (int i = 0; i < n * 15; i++) delta[i] = NAN;
     return status;
 }
+
+// cpi_chain_marginals_batch: the diagonal and first off-diagonal blocks of the inverse of the matrix solve_chain factorised, from the
+// n records it left in ws.  With the block factor [R_s W_s] (row s of the upper block-bidiagonal Cholesky factor) one backward
+// recursion: Sigma[n-1][n-1] = R^-1 R^-T; K_s = R_s^-1 W_s; Sigma[s][s+1] = -K_s Sigma[s+1][s+1];
+// Sigma[s][s] = R_s^-1 R_s^-T + K_s Sigma[s+1][s+1] K_s^T.  Per state, in this order (the kernel, cpi_marginals_kernels.hpp, is the
+// lane-mapped form: lane j owns column j of everything, so it is Z = R^-T and KT = K^T that are built, never R^-1 or K by rows):
+//   Z    column j of R^-T: t = e_j; m = 0 .. 14: z_m = fma(1 / R[m][m], t_m, 0); t_k = fma(-R[m][k], z_m, t_k), k > m
+//   KT   = W^T Z: KT[c][j] = sum over k ascending of fma(W[k][c], Z[k][j], .), from 0
+//   Sig  = Z^T Z: Sig[i][j] = sum over k = i .. 14 ascending of fma(Z[k][i], Z[k][j], .), from 0
+//   T    = P KT with P = Sigma[s+1][s+1]: T[i][j] = sum over k ascending of fma(P[i][k], KT[k][j], .), from 0
+//   Sig  += K T: Sig[i][j] = fma(KT[k][i], T[k][j], Sig[i][j]), k ascending;   Sigma[s][s+1] = -T^T
+// Only the upper triangle of Sig (i <= j) is kept and mirrored: the block is symmetric by construction.  At the last state the
+// terms with W are left out (the kernel multiplies by zeros there) and its W record is not read.
+// cov [n][120]: the packed upper triangle, (i, j), i <= j, at tri(j) + i.  cross NULL or [n][225]: Sigma[s][s+1] column-major in row
+// s; the row of the last state is not written.
+CPI_HD void marginals_chain(int n, const double *ws, double *cov, double *cross) {
+    double P[15][15];
+    for (int s = n - 1; s >= 0; s--) {
+        const double *rec = ws + (long long)s * WS_D, *W = rec + WS_R;
+        const bool hasw = s < n - 1;
+        double Z[15][15], KT[15][15], T[15][15], Sg[15][15];
+        for (int j = 0; j < 15; j++) {
+            double t[15];
+            for (int k = 0; k < 15; k++) t[k] = (k == j) ? 1.0 : 0.0;
+            for (int m = 0; m < 15; m++) {
+                t[m] = fma(rec[row_off(m)], t[m], 0.0);
+                for (int k = m + 1; k < 15; k++) t[k] = fma(-rec[row_off(m) + k - m], t[m], t[k]);
+            }
+            for (int k = 0; k < 15; k++) Z[k][j] = t[k];
+        }
+        for (int j = 0; j < 15; j++)
+            for (int i = 0; i < 15; i++) {
+                double g = 0.0;
+                for (int k = i; k < 15; k++) g = fma(Z[k][i], Z[k][j], g);
+                Sg[i][j] = g;
+            }
+        if (hasw) {
+            for (int j = 0; j < 15; j++)
+                for (int c = 0; c < 15; c++) {
+                    double a = 0.0;
+                    for (int k = 0; k < 15; k++) a = fma(W[k * 15 + c], Z[k][j], a);
+                    KT[c][j] = a;
+                }
+            for (int j = 0; j < 15; j++)
+                for (int i = 0; i < 15; i++) {
+                    double a = 0.0;
+                    for (int k = 0; k < 15; k++) a = fma(P[i][k], KT[k][j], a);
+                    T[i][j] = a;
+                }
+            for (int j = 0; j < 15; j++)
+                for (int i = 0; i < 15; i++)
+                    for (int k = 0; k < 15; k++) Sg[i][j] = fma(KT[k][i], T[k][j], Sg[i][j]);
+            if (cross)
+                for (int c = 0; c < 15; c++)
+                    for (int i = 0; i < 15; i++) cross[(long long)s * 225 + i + 15 * c] = -T[c][i];
+        }
+        for (int j = 0; j < 15; j++)
+            for (int i = 0; i <= j; i++) {
+                cov[(long long)s * 120 + tri(j) + i] = Sg[i][j];
+                P[i][j] = Sg[i][j]; P[j][i] = Sg[i][j];
+            }
+    }
+}
 }  // namespace chn
 
 }  // namespace cpi

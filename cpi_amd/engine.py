@@ -1399,6 +1399,67 @@ class Engine:
                                                         _ptr(prior), _ptr(lam), self.DAMPING[damping], _ptr(out), _ptr(status)))
         return out
 
+    # ------------------------------------------------------------------ the covariance of what the loop converged to
+    def _marginals_out(self, S, out, cross, cuda):
+        dev = self.device if cuda else "cpu"
+        if out is None:
+            # rows of no chain are not written: they read NaN rather than whatever the allocator left there
+            out = torch.full((S, 120), float("nan"), dtype=torch.float64, device=dev)
+        self._trial_tensor(out, 120, cuda, "out", S)
+        if cross is True:
+            cross = torch.full((S, 225), float("nan"), dtype=torch.float64, device=dev)
+        elif cross is False:
+            cross = None
+        if cross is not None:
+            self._trial_tensor(cross, 225, cuda, "cross", S)
+        return out, cross
+
+    def chain_marginals(self, workspace, C=None, G=None, first=None, count=None, status=None, out=None, cross=None):
+        """cpi_chain_marginals_batch: the covariance of every state of C solved chains, cov [S,120] -- Sigma[s][s] as the packed upper
+        triangle in the packing of P_sym (unpack_sym gives the dense block, sqrt_information the square-root information of a prior
+        carried on) -- and, with cross=True or a [S,225] tensor, Sigma[s][s+1] column-major per state (the row of a chain's last
+        state is not written): returns cov, or (cov, cross).  workspace, C, G, first, count: those of the chain_solve that wrote the
+        workspace.  What is inverted is the matrix that solve factorised, damping included: the covariance of the estimate comes
+        from a solve with lam=None at the converged states.  status: the int32 [C] tensor the solve filled (a chain whose status is
+        not 0 gets NaN rows); None vouches for every chain.  S comes from out, else cross, else first is None: C * G, else
+        workspace.numel() // 360.  Rows of no chain are not written (NaN in a tensor this call allocates).  Asynchronous."""
+        for name, t, dt in (("first", first, torch.int64), ("count", count, torch.int32), ("status", status, torch.int32)):
+            assert t is None or (t.dtype == dt and t.is_contiguous() and t.is_cuda and t.dim() == 1), \
+                "%s: a contiguous %s CUDA tensor [C]" % (name, str(dt).split(".")[1])
+        if C is None:
+            C = next((t.shape[0] for t in (first, count, status) if t is not None), None)
+        assert C is not None, "C: the number of chains (or first / count / status, which have it)"
+        assert all(t is None or t.shape[0] == C for t in (first, count, status)), "first / count / status: [C]"
+        assert G is not None and G >= 1, "G: the longest chain in states, >= 1"
+        assert workspace.dtype == torch.float64 and workspace.is_cuda and workspace.is_contiguous() and workspace.dim() == 1, \
+            "workspace: the CUDA float64 workspace of chain_solve"
+        if out is not None:
+            S = out.shape[0]
+        elif torch.is_tensor(cross):
+            S = cross.shape[0]
+        else:
+            S = C * G if first is None else workspace.numel() // 360
+        assert workspace.numel() >= self.chain_solve_workspace_doubles(S), "workspace: chain_solve_workspace_doubles(S) elements"
+        out, cross = self._marginals_out(S, out, cross, True)
+        self._sync_stream()
+        self._check(self.lib.cpi_chain_marginals_batch(self.ctx, C, int(G), S, _ptr(first), _ptr(count), _ptr(status), _ptr(workspace),
+                                                       _ptr(out), _ptr(cross)))
+        return out if cross is None else (out, cross)
+
+    def chain_marginals_host(self, hess, C=None, G=None, first=None, count=None, ffirst=None, prior=None, cross=False, out=None,
+                             status=None):
+        """chain_marginals on CPU tensors (cpi_chain_marginals_batch_host): the UNDAMPED system of hess / prior (the arguments of
+        chain_solve_host) is factorised on the device and inverted block by block; every chain's state and factor range is validated
+        (CpiError names the chain); synchronous, the device forms' bits.  Returns cov [S,120], or (cov, cross) with cross=True or a
+        [S,225] tensor; status: an int32 [C] tensor that receives the solve's codes (a failed chain's rows are NaN)."""
+        C_, G_, S, F, _, _ = self._chain_args(hess, C, G, first, count, ffirst, prior, None, "identity",
+                                              None if out is None else torch.empty((out.shape[0], 15), dtype=torch.float64), status, False)
+        out, cross = self._marginals_out(S, out, cross, False)
+        self._sync_stream()
+        self._check(self.lib.cpi_chain_marginals_batch_host(self.ctx, C_, G_, S, F, _ptr(first), _ptr(count), _ptr(ffirst), _ptr(hess),
+                                                            _ptr(prior), _ptr(out), _ptr(cross), _ptr(status)))
+        return out if cross is None else (out, cross)
+
 
 def unpack_factor(packed, meas):
     """Dense (err [F,15], H1 [F,225], H2 [F,225], column-major) from the packed evaluation and the measurement it was
@@ -1454,6 +1515,11 @@ def factor_cost(*args, **kw):
 def chain_solve(*args, **kw):
     """Engine.chain_solve on the default engine."""
     return default_engine().chain_solve(*args, **kw)
+
+
+def chain_marginals(*args, **kw):
+    """Engine.chain_marginals on the default engine."""
+    return default_engine().chain_marginals(*args, **kw)
 
 
 # ---------------------------------------------------------------------- reference-shaped classes

@@ -73,7 +73,10 @@ extern "C" {
                                step: the states moved along a solved step, and the whitened cost 0.5 |R e|^2 of the factors at
                                the trial states with a deterministic total); cpi_chain_solve_batch,
                                cpi_chain_solve_workspace_doubles, cpi_chain_solve_batch_host (the damped block-tridiagonal
-                               solve of chains of IMU factors on the rows of cpi_factor_hessian_*: the step of the loop above) */
+                               solve of chains of IMU factors on the rows of cpi_factor_hessian_*: the step of the loop above);
+                               cpi_chain_marginals_batch, cpi_chain_marginals_batch_host (the state covariances of solved
+                               chains: the diagonal and first off-diagonal blocks of the inverse, from the factor the solve
+                               left in its workspace) */
 
 enum { CPI_OK = 0, CPI_ERR_INVALID = 1, CPI_ERR_HIP = 2, CPI_ERR_NO_DEVICE = 3, CPI_ERR_RCCL = 4 };
 enum {
@@ -882,7 +885,8 @@ int cpi_factor_cost_tri_batch(cpi_ctx *ctx, int32_t model, const double grav[3],
  *          [0, F) -- such a chain reads nothing outside the arrays.  A failed or refused chain has NaN in every delta row of its
  *          own; no other chain is affected.  count = 1 solves (Lam + damping) delta = eta; count = 0 writes nothing, status 0.
  *   workspace  cpi_chain_solve_workspace_doubles(S) doubles of the caller's ([R y] and W of every state, 360 doubles each); its
- *          contents after the call are not declared.  The library allocates nothing.
+ *          contents after the call are what cpi_chain_marginals_batch reads and are not declared otherwise.  The library
+ *          allocates nothing.
  * A chain's bits depend on its own data only, not on C or on its position.  Chains that share states are the caller's error: the
  * contents are unspecified, no access goes out of bounds.  One kernel on the context's stream, no host synchronisation: capturable.
  * 16 lanes work on a chain, 4 chains share a wavefront; there is no parallelism ALONG a chain, so one long chain runs at the
@@ -896,6 +900,39 @@ int cpi_chain_solve_batch(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_t
                           const int64_t *first, const int32_t *count, const int64_t *ffirst,
                           const double *hess, const double *prior, const double *lambda, int32_t damping,
                           double *delta, int32_t *status, double *workspace);
+
+/* The uncertainty of what the loop above converged to: the covariance of every state of a solved chain, and of every pair of
+ * neighbouring states.  Replaces: GTSAM's Marginals (marginalCovariance of one state, jointMarginalCovariance of two neighbours) for
+ * graphs that are chains; GTSAM is absent from the reference tree: PARITY UNPINNED, checked against a long-double dense inverse.
+ * Covariance blocks further than one state apart are out of scope.
+ * WHAT IS INVERTED: the matrix A that cpi_chain_solve_batch factorised into workspace, DAMPING INCLUDED.  The covariance of the
+ * estimate therefore comes from a solve with lambda = NULL at the converged states (factor_hessian -> chain_solve(lambda = NULL) ->
+ * chain_marginals); the delta of that solve is the remaining Gauss-Newton step -- a convergence check, not something to apply.
+ * After a damped solve the result is (A + damping)^-1, which is no covariance of anything.  The coordinates are the tangent space
+ * of cpi_retract_batch ([theta bg v ba p]) at the states the Hessian was linearised at.
+ * With [R_s | W_s] the block row of the Cholesky factor in the workspace (W_s = R_s^-T U_s), one backward recursion along the chain:
+ *     Sigma[n-1][n-1] = R_{n-1}^-1 R_{n-1}^-T;    s = n - 2 .. 0:  K_s = R_s^-1 W_s,   Sigma[s][s+1] = -K_s Sigma[s+1][s+1],
+ *     Sigma[s][s] = R_s^-1 R_s^-T + K_s Sigma[s+1][s+1] K_s^T
+ *   C, G, S, first, count: the values of the solve that wrote workspace, with the same meaning and the same clamping.
+ *   workspace  cpi_chain_solve_workspace_doubles(S) DEVICE doubles as that solve left them; read only.  (The solve writes no W for a
+ *          chain's last state; it is never read.)
+ *   status NULL or [C] as the solve wrote it: a chain whose status is not 0 gets NaN in every cov and cross row of its own states,
+ *          and no other chain is affected.  NULL: the caller vouches for every chain.
+ *   cov    [S][120]: Sigma[s][s], the packed upper triangle in the packing of cpi_outputs.P_sym ((i, j), i <= j, at
+ *          CPI_TRI_INDEX(i, j) = i + j (j + 1) / 2).  A row is a valid input row of cpi_sqrt_information_packed_batch, which turns a
+ *          marginal into the square-root information of the prior a fixed-lag window carries on.  The block is symmetric by
+ *          construction (one triangle is computed).
+ *   cross  NULL or [S][225]: row s holds Sigma[s][s+1] column-major, rows for state s and columns for state s + 1.  The row of a
+ *          chain's last state is not written.
+ * Rows of states that belong to no chain are not written; count = 0 writes nothing; count = 1 gives (Lam + damping)^-1.
+ * A chain's bits depend on its own records only, not on C or on its position.  The library allocates nothing; one kernel on the
+ * context's stream, no host synchronisation: a capture is a chain without parallel branches.  16 lanes work on a chain and there
+ * is no parallelism ALONG a chain (profiles/chain_marginals.md).
+ * Refused before the context is looked at (CPI_ERR_INVALID): negative sizes, G < 1 or G > 2^31 - 1, a NULL workspace or cov when
+ * S > 0, cov or cross overlapping workspace, first, count, status or each other ("overlaps" in cpi_last_error).  C == 0 is a no-op. */
+int cpi_chain_marginals_batch(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S,
+                              const int64_t *first, const int32_t *count, const int32_t *status,
+                              const double *workspace, double *cov, double *cross);
 
 /* ---- Device sets: the 8-GPU path of a single-process host (nothing in the reference, which is a
  * single-threaded CPU program).  Windows (and factors) are independent units: rank r of n owns the contiguous block
@@ -1107,6 +1144,17 @@ int cpi_chain_solve_batch_host(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, in
                                const int64_t *first, const int32_t *count, const int64_t *ffirst,
                                const double *hess, const double *prior, const double *lambda, int32_t damping,
                                double *delta, int32_t *status);
+
+/* cpi_chain_marginals_batch from host memory: every pointer a host pointer, synchronous.  The UNDAMPED system of hess and prior
+ * (the arguments of cpi_chain_solve_batch_host with lambda = NULL) is factorised on the device by the solve, the marginals kernel
+ * runs on its workspace, and cov [S][120], cross (NULL or [S][225]) and status (NULL or [C], the solve's codes) come back: the device
+ * forms' bits.  A chain that failed has NaN rows whether status is given or not.  Every chain's state range and factor range is
+ * validated first as in cpi_chain_solve_batch_host, and the text names the chain.  Rows of cov / cross that are not written keep the
+ * caller's values. */
+int cpi_chain_marginals_batch_host(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_t F,
+                                   const int64_t *first, const int32_t *count, const int64_t *ffirst,
+                                   const double *hess, const double *prior,
+                                   double *cov, double *cross, int32_t *status);
 
 #ifdef __cplusplus
 }

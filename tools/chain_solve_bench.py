@@ -95,8 +95,8 @@ def state_prior(C, G, dev):
     return P
 
 
-def dense_route(hess, prior, lam, C, G):
-    """The caller's route: [C, 15 G, 15 G] assembled by scatter-adds, Cholesky, two triangular solves."""
+def dense_system(hess, prior, lam, C, G):
+    """(A [C, 15 G, 15 G], g [C, 15 G]) assembled by scatter-adds (tools/chain_marginals_bench.py inverts the same matrices)."""
     dev = hess.device
     n = 15 * G
     r, c = tri_rc(31, dev)
@@ -121,6 +121,12 @@ def dense_route(hess, prior, lam, C, G):
         g[:, o:o + 15] += P[:, s, :15, 15]
     i = torch.arange(n, device=dev)
     A[:, i, i] += lam[:, None]
+    return A, g
+
+
+def dense_route(hess, prior, lam, C, G):
+    """The caller's route: [C, 15 G, 15 G] assembled by scatter-adds, Cholesky, two triangular solves."""
+    A, g = dense_system(hess, prior, lam, C, G)
     L = torch.linalg.cholesky(A)
     return torch.cholesky_solve(g[:, :, None], L)[:, :, 0].reshape(C * G, 15)
 
