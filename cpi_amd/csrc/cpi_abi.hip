@@ -1251,14 +1251,42 @@ static bool bytes_overlap(const void *a, size_t na, const void *b, size_t nb) {
     const char *pa = (const char *)a, *pb = (const char *)b;
     return pa && pb && na && nb && pa < pb + nb && pb < pa + na;
 }
-extern "C" int cpi_retract_batch(cpi_ctx *ctx, int64_t S, const double *states_in, const double *delta, double *states_out) {
-    static const char who[] = "cpi_retract_batch";
+// "No output may overlap an input or another output": the first output, in order, that does is named in the refusal.  A NULL or
+// empty span overlaps nothing.
+struct Span {
+    const void *p;
+    size_t bytes;
+    const char *name;
+};
+static int refuse_overlaps(cpi_ctx *ctx, const char *who, const Span *outs, int n_out, const Span *ins, int n_in) {
+    for (int o = 0; o < n_out; o++) {
+        bool bad = false;
+        for (int k = 0; k < n_in; k++) bad = bad || bytes_overlap(outs[o].p, outs[o].bytes, ins[k].p, ins[k].bytes);
+        for (int q = o + 1; q < n_out; q++) bad = bad || bytes_overlap(outs[o].p, outs[o].bytes, outs[q].p, outs[q].bytes);
+        if (bad) return refuse(ctx, who, outs[o].name, " overlaps an input or another output");
+    }
+    return CPI_OK;
+}
+// what the device and the host forms of retract / local refuse alike, before the context is looked at
+static int retract_check(cpi_ctx *ctx, const char *who, int64_t S, const double *states_in, const double *delta, const double *states_out) {
     if (S < 0) return refuse(ctx, who, "negative size");
     if (S > 0 && (!states_in || !delta || !states_out)) return refuse(ctx, who, "NULL argument");
     const size_t ns = (size_t)S * 16 * sizeof(double), nd = (size_t)S * 15 * sizeof(double);
     if ((states_out != states_in && bytes_overlap(states_out, ns, states_in, ns)) || bytes_overlap(states_out, ns, delta, nd) ||
         bytes_overlap(states_in, ns, delta, nd))
         return refuse(ctx, who, "states_out overlaps states_in or delta (states_out == states_in exactly is the in-place form), or delta overlaps states_in");
+    return CPI_OK;
+}
+static int local_check(cpi_ctx *ctx, const char *who, int64_t S, const double *x, const double *other, const double *xi) {
+    if (S < 0) return refuse(ctx, who, "negative size");
+    if (S > 0 && (!x || !other || !xi)) return refuse(ctx, who, "NULL argument");
+    const size_t ns = (size_t)S * 16 * sizeof(double), nx = (size_t)S * 15 * sizeof(double);
+    if (bytes_overlap(xi, nx, x, ns) || bytes_overlap(xi, nx, other, ns)) return refuse(ctx, who, "xi overlaps x or other");
+    return CPI_OK;
+}
+extern "C" int cpi_retract_batch(cpi_ctx *ctx, int64_t S, const double *states_in, const double *delta, double *states_out) {
+    static const char who[] = "cpi_retract_batch";
+    CPI_TRY(retract_check(ctx, who, S, states_in, delta, states_out));
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
     if (S == 0) return CPI_OK;
     if (!grid_ok((S + 63) / 64)) return refuse(ctx, who, "S exceeds the 32-bit grid (64 states per workgroup)");
@@ -1270,10 +1298,7 @@ extern "C" int cpi_retract_batch(cpi_ctx *ctx, int64_t S, const double *states_i
 }
 extern "C" int cpi_local_batch(cpi_ctx *ctx, int64_t S, const double *x, const double *other, double *xi) {
     static const char who[] = "cpi_local_batch";
-    if (S < 0) return refuse(ctx, who, "negative size");
-    if (S > 0 && (!x || !other || !xi)) return refuse(ctx, who, "NULL argument");
-    const size_t ns = (size_t)S * 16 * sizeof(double), nx = (size_t)S * 15 * sizeof(double);
-    if (bytes_overlap(xi, nx, x, ns) || bytes_overlap(xi, nx, other, ns)) return refuse(ctx, who, "xi overlaps x or other");
+    CPI_TRY(local_check(ctx, who, S, x, other, xi));
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
     if (S == 0) return CPI_OK;
     if (!grid_ok((S + 63) / 64)) return refuse(ctx, who, "S exceeds the 32-bit grid (64 states per workgroup)");
@@ -1306,21 +1331,14 @@ static int factor_cost_impl(cpi_ctx *ctx, const char *who, int32_t model, const 
         if (!chi2) return refuse(ctx, who, "chi2 is NULL");
         if (!R) return refuse(ctx, who, tri ? "R_tri is NULL" : "sqrt_info is NULL");
         CPI_TRY(factor_args(ctx, who, model, grav, F, meas, lin, q_k_lin, states, S, idx_i, idx_j, a));
-        // no output may overlap an input or another output
         const size_t d = sizeof(double);
-        const void *outp[3] = { chi2, werr, total };
-        const size_t outn[3] = { (size_t)F * d, (size_t)F * 15 * d, cpi_factor_cost_total_doubles(F) * d };
-        for (int o = 0; o < 3; o++) {
-            bool bad = false;
-            for (int k = 0; k < 11; k++) bad = bad || bytes_overlap(outp[o], outn[o], out_field_c(meas, k), (size_t)F * OUT_N[k] * d);
-            bad = bad || bytes_overlap(outp[o], outn[o], lin, (size_t)F * 6 * d) || bytes_overlap(outp[o], outn[o], q_k_lin, (size_t)F * 4 * d) ||
-                  bytes_overlap(outp[o], outn[o], states, (size_t)S * 16 * d) || bytes_overlap(outp[o], outn[o], idx_i, (size_t)F * sizeof(int32_t)) ||
-                  bytes_overlap(outp[o], outn[o], idx_j, (size_t)F * sizeof(int32_t)) ||
-                  bytes_overlap(outp[o], outn[o], R, (size_t)F * (tri ? CPI_TRI_DOUBLES : 225) * d);
-            for (int p = o + 1; p < 3; p++) bad = bad || bytes_overlap(outp[o], outn[o], outp[p], outn[p]);
-            if (bad) return refuse(ctx, who, o == 0 ? "chi2 overlaps an input or another output" : o == 1 ? "werr overlaps an input or another output"
-                                                                                                    : "total (the workspace) overlaps an input or another output");
-        }
+        const Span outs[3] = { { chi2, (size_t)F * d, "chi2" }, { werr, (size_t)F * 15 * d, "werr" },
+                               { total, cpi_factor_cost_total_doubles(F) * d, "total (the workspace)" } };
+        Span ins[17] = { { lin, (size_t)F * 6 * d, "" }, { q_k_lin, (size_t)F * 4 * d, "" }, { states, (size_t)S * 16 * d, "" },
+                         { idx_i, (size_t)F * sizeof(int32_t), "" }, { idx_j, (size_t)F * sizeof(int32_t), "" },
+                         { R, (size_t)F * (tri ? CPI_TRI_DOUBLES : 225) * d, "" } };
+        for (int k = 0; k < 11; k++) ins[6 + k] = { out_field_c(meas, k), (size_t)F * OUT_N[k] * d, "" };   // the measurement: every field but P / P_sym
+        CPI_TRY(refuse_overlaps(ctx, who, outs, 3, ins, 17));
     }
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
     if (F == 0 && !total) return CPI_OK;
@@ -1365,19 +1383,11 @@ static int chain_check(cpi_ctx *ctx, const char *who, int64_t C, int64_t G, int6
     if (!delta) return refuse(ctx, who, "delta is NULL");
     if (!host && !workspace) return refuse(ctx, who, "workspace is NULL");
     const size_t d = sizeof(double);
-    const void *outp[3] = { delta, status, workspace };
-    const size_t outn[3] = { (size_t)S * 15 * d, (size_t)C * sizeof(int32_t), workspace ? cpi_chain_solve_workspace_doubles(S) * d : 0 };
-    static const char *const outname[3] = { "delta", "status", "workspace" };
-    const void *inp[6] = { first, count, ffirst, hess, prior, lambda };
-    const size_t inn[6] = { (size_t)C * sizeof(int64_t), (size_t)C * sizeof(int32_t), (size_t)C * sizeof(int64_t), (size_t)F * 496 * d,
-                            (size_t)S * 136 * d, (size_t)C * d };
-    for (int o = 0; o < 3; o++) {
-        bool bad = false;
-        for (int k = 0; k < 6; k++) bad = bad || bytes_overlap(outp[o], outn[o], inp[k], inn[k]);
-        for (int q = o + 1; q < 3; q++) bad = bad || bytes_overlap(outp[o], outn[o], outp[q], outn[q]);
-        if (bad) return refuse(ctx, who, outname[o], " overlaps an input or another output");
-    }
-    return CPI_OK;
+    const Span outs[3] = { { delta, (size_t)S * 15 * d, "delta" }, { status, (size_t)C * sizeof(int32_t), "status" },
+                           { workspace, workspace ? cpi_chain_solve_workspace_doubles(S) * d : 0, "workspace" } };
+    const Span ins[6] = { { first, (size_t)C * sizeof(int64_t), "" }, { count, (size_t)C * sizeof(int32_t), "" }, { ffirst, (size_t)C * sizeof(int64_t), "" },
+                          { hess, (size_t)F * 496 * d, "" }, { prior, (size_t)S * 136 * d, "" }, { lambda, (size_t)C * d, "" } };
+    return refuse_overlaps(ctx, who, outs, 3, ins, 6);
 }
 
 extern "C" int cpi_chain_solve_batch(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_t F,
@@ -1405,35 +1415,33 @@ extern "C" int cpi_chain_solve_batch(cpi_ctx *ctx, int64_t C, int64_t G, int64_t
 // ============================================================================================
 // cpi_chain_marginals_batch: the state covariances of solved chains (cpi_marginals_kernel, cpi_marginals.hip)
 // ============================================================================================
-// what both forms refuse alike, before the context is looked at; host: no workspace, status is an output
-static int marginals_check(cpi_ctx *ctx, const char *who, int64_t C, int64_t G, int64_t S, const int64_t *first, const int32_t *count,
-                           const int32_t *status, const double *workspace, double *cov, double *cross, bool host) {
-    if (C < 0 || S < 0) return refuse(ctx, who, "negative size");
+// what both forms refuse alike, before the context is looked at; host: no workspace, status is an output, and the inputs of the solve
+// (F, ffirst, hess, prior: the device form has none) are checked after everything the forms share
+static int marginals_check(cpi_ctx *ctx, const char *who, int64_t C, int64_t G, int64_t S, int64_t F, const int64_t *first, const int32_t *count,
+                           const int64_t *ffirst, const double *hess, const double *prior, const int32_t *status, const double *workspace,
+                           double *cov, double *cross, bool host) {
+    if (C < 0 || S < 0 || F < 0) return refuse(ctx, who, "negative size");
     if (G < 1) return refuse(ctx, who, "G (the longest chain in states) must be >= 1");
     if (G > 0x7fffffffLL) return refuse(ctx, who, "G exceeds 2^31 - 1 states per chain");
     if (S > 0 && !host && !workspace) return refuse(ctx, who, "workspace is NULL");
     if (S > 0 && !cov) return refuse(ctx, who, "cov is NULL");
     const size_t d = sizeof(double);
-    const void *outp[3] = { cov, cross, host ? (const void *)status : nullptr };
-    const size_t outn[3] = { (size_t)S * 120 * d, (size_t)S * 225 * d, (size_t)C * sizeof(int32_t) };
-    static const char *const outname[3] = { "cov", "cross", "status" };
-    const void *inp[4] = { workspace, first, count, host ? nullptr : (const void *)status };
-    const size_t inn[4] = { workspace ? cpi_chain_solve_workspace_doubles(S) * d : 0, (size_t)C * sizeof(int64_t), (size_t)C * sizeof(int32_t),
-                            (size_t)C * sizeof(int32_t) };
-    for (int o = 0; o < 3; o++) {
-        bool bad = false;
-        for (int k = 0; k < 4; k++) bad = bad || bytes_overlap(outp[o], outn[o], inp[k], inn[k]);
-        for (int q = o + 1; q < 3; q++) bad = bad || bytes_overlap(outp[o], outn[o], outp[q], outn[q]);
-        if (bad) return refuse(ctx, who, outname[o], " overlaps an input or another output");
-    }
-    return CPI_OK;
+    const Span outs[3] = { { cov, (size_t)S * 120 * d, "cov" }, { cross, (size_t)S * 225 * d, "cross" },
+                           { host ? status : nullptr, (size_t)C * sizeof(int32_t), "status" } };
+    const Span ins[4] = { { workspace, workspace ? cpi_chain_solve_workspace_doubles(S) * d : 0, "" }, { first, (size_t)C * sizeof(int64_t), "" },
+                          { count, (size_t)C * sizeof(int32_t), "" }, { host ? nullptr : status, (size_t)C * sizeof(int32_t), "" } };
+    CPI_TRY(refuse_overlaps(ctx, who, outs, 3, ins, 4));
+    if (!host) return CPI_OK;
+    if (C > 0 && !hess && G > 1) return refuse(ctx, who, "hess is NULL (only chains of one state, G == 1, need none)");
+    const Span solve_ins[3] = { { ffirst, (size_t)C * sizeof(int64_t), "" }, { hess, (size_t)F * 496 * d, "" }, { prior, (size_t)S * 136 * d, "" } };
+    return refuse_overlaps(ctx, who, outs, 3, solve_ins, 3);
 }
 
 extern "C" int cpi_chain_marginals_batch(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S,
                                          const int64_t *first, const int32_t *count, const int32_t *status,
                                          const double *workspace, double *cov, double *cross) {
     static const char who[] = "cpi_chain_marginals_batch";
-    CPI_TRY(marginals_check(ctx, who, C, G, S, first, count, status, workspace, cov, cross, false));
+    CPI_TRY(marginals_check(ctx, who, C, G, S, 0, first, count, nullptr, nullptr, nullptr, status, workspace, cov, cross, false));
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
     if (C == 0 || S == 0) return CPI_OK;               // no chain has a state
     if (!grid_ok((C + 3) / 4)) return refuse(ctx, who, "C exceeds the 32-bit grid (4 chains per workgroup)");
@@ -1988,7 +1996,76 @@ int stage_windows(Staging &st, int64_t W, int64_t n_knots, const double *knots, 
     CPI_TRY(st.upload(lin, (size_t)W * 6, &d->lin));
     return st.upload(q_k_lin, (size_t)W * 4, &d->qk);
 }
+
+// the operands of a factor sweep, staged whole: the measurement (every field but P / P_sym), the linearisation points, the states and
+// the state indices
+struct FactorsDev {
+    cpi_outputs meas;
+    const double *lin, *qk, *states;
+    const int32_t *idx_i, *idx_j;
+};
+int stage_factors(Staging &st, int64_t F, int64_t S, const cpi_outputs *meas, const double *lin, const double *q_k_lin, const double *states,
+                  const int32_t *idx_i, const int32_t *idx_j, FactorsDev *d) {
+    memset(&d->meas, 0, sizeof d->meas);
+    for (int k = 0; k < 11; k++) {
+        const double *dm;
+        CPI_TRY(st.upload((const double *)out_field_c(meas, k), (size_t)F * OUT_N[k], &dm));
+        *out_field(&d->meas, k) = const_cast<double *>(dm);
+    }
+    CPI_TRY(st.upload(lin, (size_t)F * 6, &d->lin));
+    CPI_TRY(st.upload(q_k_lin, (size_t)F * 4, &d->qk));
+    CPI_TRY(st.upload(states, (size_t)S * 16, &d->states));
+    CPI_TRY(st.upload(idx_i, (size_t)F, &d->idx_i));
+    return st.upload(idx_j, (size_t)F, &d->idx_j);
+}
+
+// the chains of a solve, staged whole, and the workspace the solve leaves its factorisation in
+struct ChainsDev {
+    const int64_t *first, *ffirst;
+    const int32_t *count;
+    const double *hess, *prior;
+    double *workspace;
+};
+int stage_chains(Staging &st, int64_t C, int64_t G, int64_t S, int64_t F, const int64_t *first, const int32_t *count, const int64_t *ffirst,
+                 const double *hess, const double *prior, ChainsDev *d) {
+    CPI_TRY(st.upload(first, (size_t)C, &d->first));
+    CPI_TRY(st.upload(count, (size_t)C, &d->count));
+    CPI_TRY(st.upload(ffirst, (size_t)C, &d->ffirst));
+    CPI_TRY(st.upload(F > 0 ? hess : nullptr, (size_t)F * 496, &d->hess));
+    CPI_TRY(st.upload(S > 0 ? prior : nullptr, (size_t)S * 136, &d->prior));
+    CPI_TRY(st.alloc(cpi_chain_solve_workspace_doubles(S), &d->workspace));
+    if (!d->hess && G > 1) {   // F == 0: no chain has a factor (the ranges are validated), and the device form wants a pointer it never reads
+        double *none;
+        CPI_TRY(st.alloc((size_t)1, &none));
+        d->hess = none;
+    }
+    return CPI_OK;
+}
 }  // namespace
+
+// Host pointers: the state indices of a factor sweep and the state and factor ranges of every chain can be (and are) validated; the
+// device-pointer entries clamp them, or refuse them per chain, instead.
+static int check_state_indices(cpi_ctx *ctx, const char *who, int64_t F, int64_t S, const int32_t *idx_i, const int32_t *idx_j) {
+    if (S <= 0 || (!idx_i && S < F) || (!idx_j && S < F + 1)) return refuse(ctx, who, "too few states");
+    for (int64_t f = 0; f < F; f++)
+        if ((idx_i && (idx_i[f] < 0 || idx_i[f] >= S)) || (idx_j && (idx_j[f] < 0 || idx_j[f] >= S)))
+            return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": state index out of range at factor " + std::to_string(f));
+    return CPI_OK;
+}
+static int chain_ranges_check(cpi_ctx *ctx, const char *who, int64_t C, int64_t G, int64_t S, int64_t F, const int64_t *first,
+                              const int32_t *count, const int64_t *ffirst) {
+    for (int64_t c = 0; c < C; c++) {
+        const int64_t f = first ? first[c] : c * G;
+        int64_t n = count ? count[c] : G;
+        n = n < 0 ? 0 : (n > G ? G : n);
+        if (f < 0 || f > S || n > S - f)
+            return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": the states of chain " + std::to_string(c) + " leave [0, S)");
+        const int64_t ff = ffirst ? ffirst[c] : f - c;
+        if (n > 1 && (ff < 0 || ff > F - (n - 1)))
+            return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": the factor rows of chain " + std::to_string(c) + " leave [0, F)");
+    }
+    return CPI_OK;
+}
 
 // Dense (and tiled) batches from host memory run as a three-stage pipeline over chunks of <= 65536 windows: upload of
 // chunk i + 1 (copy stream), kernels of chunk i (the context's stream), download of chunk i - 1 (second copy stream) -- PCIe
@@ -2710,33 +2787,17 @@ extern "C" int cpi_factor_eval_batch_host(cpi_ctx *ctx, int32_t model, const dou
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
     if (!meas || !lin || !states || !err || !grav) return fail(ctx, CPI_ERR_INVALID, "cpi_factor_eval_batch_host: NULL argument");
     if (F <= 0) return F == 0 ? CPI_OK : fail(ctx, CPI_ERR_INVALID, "negative size");
-    // host pointers: the indices can be (and are) validated here; the device-pointer entries clamp them instead
-    if (S <= 0 || (!idx_i && S < F) || (!idx_j && S < F + 1)) return fail(ctx, CPI_ERR_INVALID, "cpi_factor_eval_batch_host: too few states");
-    for (int64_t f = 0; f < F; f++)
-        if ((idx_i && (idx_i[f] < 0 || idx_i[f] >= S)) || (idx_j && (idx_j[f] < 0 || idx_j[f] >= S)))
-            return fail(ctx, CPI_ERR_INVALID, "cpi_factor_eval_batch_host: state index out of range at factor " + std::to_string(f));
+    CPI_TRY(check_state_indices(ctx, "cpi_factor_eval_batch_host", F, S, idx_i, idx_j));
     DeviceGuard guard_;
     CPI_HIP(ctx, guard_.enter(ctx->device));
     Staging st(ctx);
-    cpi_outputs d;
-    memset(&d, 0, sizeof d);
-    for (int k = 0; k < 11; k++) {   // the measurement: every field but P / P_sym
-        const double *dm;
-        CPI_TRY(st.upload((const double *)out_field_c(meas, k), (size_t)F * OUT_N[k], &dm));
-        *out_field(&d, k) = const_cast<double *>(dm);
-    }
-    const double *dl, *dq, *ds;
-    const int32_t *di, *dj;
+    FactorsDev in;
     double *de, *dh1 = nullptr, *dh2 = nullptr;
-    CPI_TRY(st.upload(lin, (size_t)F * 6, &dl));
-    CPI_TRY(st.upload(q_k_lin, (size_t)F * 4, &dq));
-    CPI_TRY(st.upload(states, (size_t)S * 16, &ds));
-    CPI_TRY(st.upload(idx_i, (size_t)F, &di));
-    CPI_TRY(st.upload(idx_j, (size_t)F, &dj));
+    CPI_TRY(stage_factors(st, F, S, meas, lin, q_k_lin, states, idx_i, idx_j, &in));
     CPI_TRY(st.alloc((size_t)F * 15, &de));
     if (H1) CPI_TRY(st.alloc((size_t)F * 225, &dh1));
     if (H2) CPI_TRY(st.alloc((size_t)F * 225, &dh2));
-    CPI_TRY(cpi_factor_eval_batch(ctx, model, grav, F, &d, dl, dq, ds, S, di, dj, de, dh1, dh2));
+    CPI_TRY(cpi_factor_eval_batch(ctx, model, grav, F, &in.meas, in.lin, in.qk, in.states, S, in.idx_i, in.idx_j, de, dh1, dh2));
     CPI_TRY(st.download(err, (const double *)de, (size_t)F * 15));
     if (H1) CPI_TRY(st.download(H1, (const double *)dh1, (size_t)F * 225));
     if (H2) CPI_TRY(st.download(H2, (const double *)dh2, (size_t)F * 225));
@@ -2745,13 +2806,7 @@ extern "C" int cpi_factor_eval_batch_host(cpi_ctx *ctx, int32_t model, const dou
 
 // cpi_retract_batch / cpi_local_batch from host memory: staged whole, synchronous.
 extern "C" int cpi_retract_batch_host(cpi_ctx *ctx, int64_t S, const double *states_in, const double *delta, double *states_out) {
-    static const char who[] = "cpi_retract_batch_host";
-    if (S < 0) return refuse(ctx, who, "negative size");
-    if (S > 0 && (!states_in || !delta || !states_out)) return refuse(ctx, who, "NULL argument");
-    const size_t ns = (size_t)S * 16 * sizeof(double), nd = (size_t)S * 15 * sizeof(double);
-    if ((states_out != states_in && bytes_overlap(states_out, ns, states_in, ns)) || bytes_overlap(states_out, ns, delta, nd) ||
-        bytes_overlap(states_in, ns, delta, nd))
-        return refuse(ctx, who, "states_out overlaps states_in or delta (states_out == states_in exactly is the in-place form), or delta overlaps states_in");
+    CPI_TRY(retract_check(ctx, "cpi_retract_batch_host", S, states_in, delta, states_out));
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
     if (S == 0) return CPI_OK;
     DeviceGuard guard_;
@@ -2766,11 +2821,7 @@ extern "C" int cpi_retract_batch_host(cpi_ctx *ctx, int64_t S, const double *sta
     return st.finish();
 }
 extern "C" int cpi_local_batch_host(cpi_ctx *ctx, int64_t S, const double *x, const double *other, double *xi) {
-    static const char who[] = "cpi_local_batch_host";
-    if (S < 0) return refuse(ctx, who, "negative size");
-    if (S > 0 && (!x || !other || !xi)) return refuse(ctx, who, "NULL argument");
-    const size_t ns = (size_t)S * 16 * sizeof(double), nx = (size_t)S * 15 * sizeof(double);
-    if (bytes_overlap(xi, nx, x, ns) || bytes_overlap(xi, nx, other, ns)) return refuse(ctx, who, "xi overlaps x or other");
+    CPI_TRY(local_check(ctx, "cpi_local_batch_host", S, x, other, xi));
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
     if (S == 0) return CPI_OK;
     DeviceGuard guard_;
@@ -2799,11 +2850,7 @@ extern "C" int cpi_factor_cost_batch_host(cpi_ctx *ctx, int32_t model, const dou
         if (!chi2) return refuse(ctx, who, "chi2 is NULL");
         if (!meas || !lin || !states || !grav) return refuse(ctx, who, "NULL argument");
         if (!meas->P_sym && !meas->P) return refuse(ctx, who, "meas must hold P_sym or P (the covariance that is factorised)");
-        // host pointers: the indices can be (and are) validated here; the device-pointer entries clamp them instead
-        if (S <= 0 || (!idx_i && S < F) || (!idx_j && S < F + 1)) return refuse(ctx, who, "too few states");
-        for (int64_t f = 0; f < F; f++)
-            if ((idx_i && (idx_i[f] < 0 || idx_i[f] >= S)) || (idx_j && (idx_j[f] < 0 || idx_j[f] >= S)))
-                return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": state index out of range at factor " + std::to_string(f));
+        CPI_TRY(check_state_indices(ctx, who, F, S, idx_i, idx_j));
     }
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
     if (F == 0) { if (total) total[0] = 0.0; return CPI_OK; }
@@ -2811,13 +2858,6 @@ extern "C" int cpi_factor_cost_batch_host(cpi_ctx *ctx, int32_t model, const dou
     CPI_HIP(ctx, guard_.enter(ctx->device));
     std::vector<double> packed;   // declared BEFORE the staging: its destructor drains the stream while this buffer still exists
     Staging st(ctx);
-    cpi_outputs d;
-    memset(&d, 0, sizeof d);
-    for (int k = 0; k < 11; k++) {   // the measurement: every field but P / P_sym
-        const double *dm;
-        CPI_TRY(st.upload((const double *)out_field_c(meas, k), (size_t)F * OUT_N[k], &dm));
-        *out_field(&d, k) = const_cast<double *>(dm);
-    }
     const double *psym = meas->P_sym;
     if (!psym) {   // the upper triangle of the dense P, CPI_TRI_INDEX order
         packed.resize((size_t)F * CPI_TRI_DOUBLES);
@@ -2826,21 +2866,17 @@ extern "C" int cpi_factor_cost_batch_host(cpi_ctx *ctx, int32_t model, const dou
                 for (int i = 0; i <= k; i++) packed[(size_t)f * CPI_TRI_DOUBLES + CPI_TRI_INDEX(i, k)] = meas->P[(size_t)f * 225 + k * 15 + i];
         psym = packed.data();
     }
-    const double *dl, *dq, *ds, *dp;
-    const int32_t *di, *dj;
+    FactorsDev in;
+    const double *dp;
     double *dr, *dc, *dw = nullptr, *dt = nullptr;
+    CPI_TRY(stage_factors(st, F, S, meas, lin, q_k_lin, states, idx_i, idx_j, &in));
     CPI_TRY(st.upload(psym, (size_t)F * CPI_TRI_DOUBLES, &dp));
-    CPI_TRY(st.upload(lin, (size_t)F * 6, &dl));
-    CPI_TRY(st.upload(q_k_lin, (size_t)F * 4, &dq));
-    CPI_TRY(st.upload(states, (size_t)S * 16, &ds));
-    CPI_TRY(st.upload(idx_i, (size_t)F, &di));
-    CPI_TRY(st.upload(idx_j, (size_t)F, &dj));
     CPI_TRY(st.alloc((size_t)F * CPI_TRI_DOUBLES, &dr));
     CPI_TRY(st.alloc((size_t)F, &dc));
     if (werr) CPI_TRY(st.alloc((size_t)F * 15, &dw));
     if (total) CPI_TRY(st.alloc(cpi_factor_cost_total_doubles(F), &dt));
     CPI_TRY(cpi_sqrt_information_packed_batch(ctx, F, dp, dr));
-    CPI_TRY(cpi_factor_cost_tri_batch(ctx, model, grav, F, &d, dl, dq, ds, S, di, dj, dr, dc, dw, dt));
+    CPI_TRY(cpi_factor_cost_tri_batch(ctx, model, grav, F, &in.meas, in.lin, in.qk, in.states, S, in.idx_i, in.idx_j, dr, dc, dw, dt));
     CPI_TRY(st.download(chi2, (const double *)dc, (size_t)F));
     if (werr) CPI_TRY(st.download(werr, (const double *)dw, (size_t)F * 15));
     if (total) CPI_TRY(st.download(total, (const double *)dt, (size_t)1));
@@ -2848,39 +2884,25 @@ extern "C" int cpi_factor_cost_batch_host(cpi_ctx *ctx, int32_t model, const dou
 }
 
 // cpi_chain_solve_batch from host memory: every array a host array, staged whole, synchronous.  Host pointers: every chain's state
-// and factor range can be (and is) validated here; the device form clamps or refuses them per chain instead.  delta travels up first,
-// so that the rows of no chain come back as the caller left them.
+// and factor range can be (and is) validated here; the device form clamps or refuses them per chain instead.  delta travels up before
+// the solve, so that the rows of no chain come back as the caller left them.
 extern "C" int cpi_chain_solve_batch_host(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_t F,
                                           const int64_t *first, const int32_t *count, const int64_t *ffirst,
                                           const double *hess, const double *prior, const double *lambda, int32_t damping,
                                           double *delta, int32_t *status) {
     static const char who[] = "cpi_chain_solve_batch_host";
     CPI_TRY(chain_check(ctx, who, C, G, S, F, first, count, ffirst, hess, prior, lambda, damping, delta, status, nullptr, true));
-    for (int64_t c = 0; c < C; c++) {
-        const int64_t f = first ? first[c] : c * G;
-        int64_t n = count ? count[c] : G;
-        n = n < 0 ? 0 : (n > G ? G : n);
-        if (f < 0 || f > S || n > S - f)
-            return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": the states of chain " + std::to_string(c) + " leave [0, S)");
-        const int64_t ff = ffirst ? ffirst[c] : f - c;
-        if (n > 1 && (ff < 0 || ff > F - (n - 1)))
-            return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": the factor rows of chain " + std::to_string(c) + " leave [0, F)");
-    }
+    CPI_TRY(chain_ranges_check(ctx, who, C, G, S, F, first, count, ffirst));
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
     if (C == 0) return CPI_OK;
     DeviceGuard guard_;
     CPI_HIP(ctx, guard_.enter(ctx->device));
     Staging st(ctx);
-    const int64_t *dfirst, *dffirst;
-    const int32_t *dcount;
-    const double *dh, *dp, *dl, *dd0 = nullptr;
-    double *dd = nullptr, *dw;
+    ChainsDev in;
+    const double *dl, *dd0 = nullptr;
+    double *dd = nullptr;
     int32_t *ds = nullptr;
-    CPI_TRY(st.upload(first, (size_t)C, &dfirst));
-    CPI_TRY(st.upload(count, (size_t)C, &dcount));
-    CPI_TRY(st.upload(ffirst, (size_t)C, &dffirst));
-    CPI_TRY(st.upload(F > 0 ? hess : nullptr, (size_t)F * 496, &dh));
-    CPI_TRY(st.upload(S > 0 ? prior : nullptr, (size_t)S * 136, &dp));
+    CPI_TRY(stage_chains(st, C, G, S, F, first, count, ffirst, hess, prior, &in));
     CPI_TRY(st.upload(lambda, (size_t)C, &dl));
     if (S > 0) {
         CPI_TRY(st.upload((const double *)delta, (size_t)S * 15, &dd0));
@@ -2889,76 +2911,38 @@ extern "C" int cpi_chain_solve_batch_host(cpi_ctx *ctx, int64_t C, int64_t G, in
         CPI_TRY(st.alloc((size_t)1, &dd));
     }
     if (status) CPI_TRY(st.alloc((size_t)C, &ds));
-    CPI_TRY(st.alloc(cpi_chain_solve_workspace_doubles(S), &dw));
-    if (!dh && G > 1) {   // F == 0: no chain has a factor (validated above), and the device form wants a pointer it never reads
-        double *none;
-        CPI_TRY(st.alloc((size_t)1, &none));
-        dh = none;
-    }
-    CPI_TRY(cpi_chain_solve_batch(ctx, C, G, S, F, dfirst, dcount, dffirst, dh, dp, dl, damping, dd, ds, dw));
+    CPI_TRY(cpi_chain_solve_batch(ctx, C, G, S, F, in.first, in.count, in.ffirst, in.hess, in.prior, dl, damping, dd, ds, in.workspace));
     if (S > 0) CPI_TRY(st.download(delta, (const double *)dd, (size_t)S * 15));
     if (status) CPI_TRY(st.download(status, (const int32_t *)ds, (size_t)C));
     return st.finish();
 }
 
 // cpi_chain_marginals_batch from host memory: the undamped solve of the host arrays on the device, the marginals kernel on the
-// workspace it left, cov / cross / status back.  cov and cross travel up first, so that the rows nobody writes come back as the caller
-// left them.  The ranges are validated as in cpi_chain_solve_batch_host.
+// workspace it left, cov / cross / status back.  cov and cross travel up before the kernels, so that the rows nobody writes come back
+// as the caller left them.  The ranges are validated as in cpi_chain_solve_batch_host.
 extern "C" int cpi_chain_marginals_batch_host(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_t F,
                                               const int64_t *first, const int32_t *count, const int64_t *ffirst,
                                               const double *hess, const double *prior,
                                               double *cov, double *cross, int32_t *status) {
     static const char who[] = "cpi_chain_marginals_batch_host";
-    if (F < 0) return refuse(ctx, who, "negative size");
-    CPI_TRY(marginals_check(ctx, who, C, G, S, first, count, status, nullptr, cov, cross, true));
-    if (C > 0 && !hess && G > 1) return refuse(ctx, who, "hess is NULL (only chains of one state, G == 1, need none)");
-    {
-        const size_t d = sizeof(double);
-        const void *outp[3] = { cov, cross, status };
-        const size_t outn[3] = { (size_t)S * 120 * d, (size_t)S * 225 * d, (size_t)C * sizeof(int32_t) };
-        static const char *const outname[3] = { "cov", "cross", "status" };
-        for (int o = 0; o < 3; o++)
-            if (bytes_overlap(outp[o], outn[o], ffirst, (size_t)C * sizeof(int64_t)) || bytes_overlap(outp[o], outn[o], hess, (size_t)F * 496 * d) ||
-                bytes_overlap(outp[o], outn[o], prior, (size_t)S * 136 * d))
-                return refuse(ctx, who, outname[o], " overlaps an input or another output");
-    }
-    for (int64_t c = 0; c < C; c++) {
-        const int64_t f = first ? first[c] : c * G;
-        int64_t n = count ? count[c] : G;
-        n = n < 0 ? 0 : (n > G ? G : n);
-        if (f < 0 || f > S || n > S - f)
-            return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": the states of chain " + std::to_string(c) + " leave [0, S)");
-        const int64_t ff = ffirst ? ffirst[c] : f - c;
-        if (n > 1 && (ff < 0 || ff > F - (n - 1)))
-            return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": the factor rows of chain " + std::to_string(c) + " leave [0, F)");
-    }
+    CPI_TRY(marginals_check(ctx, who, C, G, S, F, first, count, ffirst, hess, prior, status, nullptr, cov, cross, true));
+    CPI_TRY(chain_ranges_check(ctx, who, C, G, S, F, first, count, ffirst));
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
     if (C == 0 || S == 0) return CPI_OK;
     DeviceGuard guard_;
     CPI_HIP(ctx, guard_.enter(ctx->device));
     Staging st(ctx);
-    const int64_t *dfirst, *dffirst;
-    const int32_t *dcount;
-    const double *dh, *dp, *dc0, *dx0 = nullptr;
-    double *dd, *dw;
+    ChainsDev in;
+    const double *dc0, *dx0 = nullptr;
+    double *dd;
     int32_t *ds;
-    CPI_TRY(st.upload(first, (size_t)C, &dfirst));
-    CPI_TRY(st.upload(count, (size_t)C, &dcount));
-    CPI_TRY(st.upload(ffirst, (size_t)C, &dffirst));
-    CPI_TRY(st.upload(F > 0 ? hess : nullptr, (size_t)F * 496, &dh));
-    CPI_TRY(st.upload(prior, (size_t)S * 136, &dp));
+    CPI_TRY(stage_chains(st, C, G, S, F, first, count, ffirst, hess, prior, &in));
     CPI_TRY(st.upload((const double *)cov, (size_t)S * 120, &dc0));
     if (cross) CPI_TRY(st.upload((const double *)cross, (size_t)S * 225, &dx0));
     CPI_TRY(st.alloc((size_t)S * 15, &dd));
     CPI_TRY(st.alloc((size_t)C, &ds));
-    CPI_TRY(st.alloc(cpi_chain_solve_workspace_doubles(S), &dw));
-    if (!dh && G > 1) {   // F == 0: no chain has a factor (validated above), and the solve wants a pointer it never reads
-        double *none;
-        CPI_TRY(st.alloc((size_t)1, &none));
-        dh = none;
-    }
-    CPI_TRY(cpi_chain_solve_batch(ctx, C, G, S, F, dfirst, dcount, dffirst, dh, dp, nullptr, CPI_DAMP_IDENTITY, dd, ds, dw));
-    CPI_TRY(cpi_chain_marginals_batch(ctx, C, G, S, dfirst, dcount, ds, dw, const_cast<double *>(dc0), const_cast<double *>(dx0)));
+    CPI_TRY(cpi_chain_solve_batch(ctx, C, G, S, F, in.first, in.count, in.ffirst, in.hess, in.prior, nullptr, CPI_DAMP_IDENTITY, dd, ds, in.workspace));
+    CPI_TRY(cpi_chain_marginals_batch(ctx, C, G, S, in.first, in.count, ds, in.workspace, const_cast<double *>(dc0), const_cast<double *>(dx0)));
     CPI_TRY(st.download(cov, dc0, (size_t)S * 120));
     if (cross) CPI_TRY(st.download(cross, dx0, (size_t)S * 225));
     if (status) CPI_TRY(st.download(status, (const int32_t *)ds, (size_t)C));

@@ -35,6 +35,11 @@ def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _fields(d):
+    """The tensors of an output dict: a packed one (alloc_outputs) without its "_flat" / "_fields" entries."""
+    return {k: v for k, v in d.items() if not k.startswith("_")}
+
+
 def _tri_index(device=None):
     """(rows, cols) of the packed upper triangle in storage order: entry k of a packed matrix is (rows[k], cols[k])."""
     cols = torch.repeat_interleave(torch.arange(15, device=device), torch.arange(1, 16, device=device))
@@ -245,6 +250,36 @@ class Engine:
     def _running_views(flat, W, N):
         return {k: (v if k.startswith("_") else v.view((W, N) + tuple(v.shape[1:]))) for k, v in flat.items()}
 
+    def _rows_out(self, W, N, want, params, out, filter_want, cuda=True, packed=False, pinned=None):
+        """(rows, their cpi_outputs): `out`, or [W, N, ...] tensors allocated for the want-groups -- device views of [W * N, ...]
+        arrays (packed as in alloc_outputs) or host tensors (page-locked when pinned).  filter_want: the default want loses model
+        2's "jac" (_running_want); the _stj forms serve it."""
+        if out is None:
+            want = self._running_want(tuple(want), params.model) if filter_want else tuple(want)
+            if cuda:
+                out = self._running_views(self.alloc_outputs(W * N, want, params.model, packed), W, N)
+            else:
+                out = self._host_outputs((W, N), want, params.model, pinned)
+        return out, self._outputs_struct(out)   # which reads the field names only: a packed dict's "_flat" / "_fields" do not reach it
+
+    def _running_args(self, knots, lin, q_k_lin, params, want, first, count, N, carry=None, packed=False, pinned=None, out=None, cuda=True,
+                      filter_want=True):
+        """What the preintegrate_running* methods share, up to the C call: the asserts, then carry_out and the rows where not given,
+        then the engine on torch's stream.  carry: None or (carry_in, carry_out) for the _resume forms; cuda: device tensors (dense
+        or ragged, rows packed on request) or host tensors (dense; fresh ones page-locked when pinned); filter_want: see _rows_out.
+        Returns (the arguments of the entry, rows, carry_out)."""
+        params = params or self.make_params()
+        W, N = self._window_shape(knots, lin, first, count, N, (q_k_lin,) + (carry or ()), cuda)
+        if carry is not None:
+            where = {"device": self.device} if cuda else {"pin_memory": pinned}
+            carry = (carry[0], self._carry_out(W, params.model, carry[0], carry[1], **where))
+        out, o = self._rows_out(W, N, want, params, out, filter_want, cuda, packed, pinned)
+        self._sync_stream()
+        windows = (_ptr(first), _ptr(count)) if cuda else (None, _ptr(count), 0)
+        rest = (C.byref(o),) if carry is None else (_ptr(carry[0]), _ptr(carry[1]), C.byref(o))
+        args = (self.ctx, C.byref(params), W, N, _ptr(knots)) + windows + (_ptr(lin), _ptr(q_k_lin)) + rest
+        return args, out, None if carry is None else carry[1]
+
     def preintegrate_running(self, knots, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), first=None,
                              count=None, N=None, packed=False, out=None):
         """cpi_preintegrate_running: the measurement after EVERY interval.  Inputs as in preintegrate.  Returns a dict of
@@ -253,28 +288,16 @@ class Engine:
         views of [W * N, ...] arrays, so {k: v.reshape(W * N, ...)} is an ordinary measurement dict for predict / factor_eval
         (idx_i[row] = row // N).  Models 1 and 2; Jacobians for model 1 only (the default want drops them for model 2).
         packed / out: as alloc_outputs(W * N, ..., packed) / the dict of an earlier call.  Asynchronous."""
-        params = params or self.make_params()
-        W, N = self._window_shape(knots, lin, first, count, N, (q_k_lin,))
-        if out is None:
-            out = self._running_views(self.alloc_outputs(W * N, self._running_want(tuple(want), params.model), params.model, packed), W, N)
-        o = self._outputs_struct({k: v for k, v in out.items() if not k.startswith("_")})
-        self._sync_stream()
-        self._check(self.lib.cpi_preintegrate_running(self.ctx, C.byref(params), W, N, _ptr(knots), _ptr(first), _ptr(count),
-                                                      _ptr(lin), _ptr(q_k_lin), C.byref(o)))
+        args, out, _ = self._running_args(knots, lin, q_k_lin, params, want, first, count, N, packed=packed, out=out)
+        self._check(self.lib.cpi_preintegrate_running(*args))
         return out
 
     def preintegrate_running_host(self, knots, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), count=None,
                                   pinned=True, out=None):
         """preintegrate_running for a dense batch held in HOST memory (CPU float64 tensors): cpi_preintegrate_running_host.
         Returns a dict of CPU tensors with leading shape [W, N]; synchronous."""
-        params = params or self.make_params()
-        W, N = self._window_shape(knots, lin, count=count, others=(q_k_lin,), cuda=False)
-        if out is None:
-            out = self._host_outputs((W, N), self._running_want(tuple(want), params.model), params.model, pinned)
-        o = self._outputs_struct(out)
-        self._sync_stream()
-        self._check(self.lib.cpi_preintegrate_running_host(self.ctx, C.byref(params), W, N, _ptr(knots), None, _ptr(count), 0,
-                                                           _ptr(lin), _ptr(q_k_lin), C.byref(o)))
+        args, out, _ = self._running_args(knots, lin, q_k_lin, params, want, None, count, None, pinned=pinned, out=out, cuda=False)
+        self._check(self.lib.cpi_preintegrate_running_host(*args))
         return out
 
     def preintegrate_running_stj(self, knots, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), first=None,
@@ -284,28 +307,16 @@ class Engine:
         O_a O_b after every interval, read out of the state transition columns of the covariance recursion.  The mean and P /
         P_sym rows are bit for bit those of preintegrate_running; without "jac", or for model 1, the call is
         preintegrate_running.  Asynchronous."""
-        params = params or self.make_params()
-        W, N = self._window_shape(knots, lin, first, count, N, (q_k_lin,))
-        if out is None:
-            out = self._running_views(self.alloc_outputs(W * N, tuple(want), params.model, packed), W, N)
-        o = self._outputs_struct({k: v for k, v in out.items() if not k.startswith("_")})
-        self._sync_stream()
-        self._check(self.lib.cpi_running_stj_batch(self.ctx, C.byref(params), W, N, _ptr(knots), _ptr(first), _ptr(count),
-                                                          _ptr(lin), _ptr(q_k_lin), C.byref(o)))
+        args, out, _ = self._running_args(knots, lin, q_k_lin, params, want, first, count, N, packed=packed, out=out, filter_want=False)
+        self._check(self.lib.cpi_running_stj_batch(*args))
         return out
 
     def preintegrate_running_stj_host(self, knots, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), count=None,
                                       pinned=True, out=None):
         """preintegrate_running_stj for a dense batch held in HOST memory (CPU float64 tensors):
         cpi_running_stj_batch_host.  Returns a dict of CPU tensors with leading shape [W, N]; synchronous."""
-        params = params or self.make_params()
-        W, N = self._window_shape(knots, lin, count=count, others=(q_k_lin,), cuda=False)
-        if out is None:
-            out = self._host_outputs((W, N), tuple(want), params.model, pinned)
-        o = self._outputs_struct(out)
-        self._sync_stream()
-        self._check(self.lib.cpi_running_stj_batch_host(self.ctx, C.byref(params), W, N, _ptr(knots), None, _ptr(count), 0,
-                                                               _ptr(lin), _ptr(q_k_lin), C.byref(o)))
+        args, out, _ = self._running_args(knots, lin, q_k_lin, params, want, None, count, None, pinned=pinned, out=out, cuda=False, filter_want=False)
+        self._check(self.lib.cpi_running_stj_batch_host(*args))
         return out
 
     def preintegrate_running_resume(self, knots, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), first=None,
@@ -316,30 +327,18 @@ class Engine:
         for plus intervals 0 .. i of this segment), carry_out (allocated when not given, never carry_in itself) as
         preintegrate_resume returns it -- the state of row N - 1.  The records of the two resume entries are interchangeable.
         Models 1 and 2; Jacobians for model 1 only (the default want drops them for model 2).  Asynchronous."""
-        params = params or self.make_params()
-        W, N = self._window_shape(knots, lin, first, count, N, (q_k_lin, carry_in, carry_out))
-        carry_out = self._carry_out(W, params.model, carry_in, carry_out, device=self.device)
-        if out is None:
-            out = self._running_views(self.alloc_outputs(W * N, self._running_want(tuple(want), params.model), params.model, packed), W, N)
-        o = self._outputs_struct({k: v for k, v in out.items() if not k.startswith("_")})
-        self._sync_stream()
-        self._check(self.lib.cpi_preintegrate_running_resume(self.ctx, C.byref(params), W, N, _ptr(knots), _ptr(first), _ptr(count),
-                                                             _ptr(lin), _ptr(q_k_lin), _ptr(carry_in), _ptr(carry_out), C.byref(o)))
+        args, out, carry_out = self._running_args(knots, lin, q_k_lin, params, want, first, count, N, (carry_in, carry_out), packed=packed,
+                                                  out=out)
+        self._check(self.lib.cpi_preintegrate_running_resume(*args))
         return out, carry_out
 
     def preintegrate_running_resume_host(self, knots, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), count=None,
                                          carry_in=None, carry_out=None, pinned=True, out=None):
         """preintegrate_running_resume for a dense batch held in HOST memory (CPU float64 tensors, the records included):
         cpi_preintegrate_running_resume_host.  Returns (rows, carry_out) as CPU tensors; synchronous."""
-        params = params or self.make_params()
-        W, N = self._window_shape(knots, lin, count=count, others=(q_k_lin, carry_in, carry_out), cuda=False)
-        carry_out = self._carry_out(W, params.model, carry_in, carry_out, pin_memory=pinned)
-        if out is None:
-            out = self._host_outputs((W, N), self._running_want(tuple(want), params.model), params.model, pinned)
-        o = self._outputs_struct(out)
-        self._sync_stream()
-        self._check(self.lib.cpi_preintegrate_running_resume_host(self.ctx, C.byref(params), W, N, _ptr(knots), None, _ptr(count), 0,
-                                                                  _ptr(lin), _ptr(q_k_lin), _ptr(carry_in), _ptr(carry_out), C.byref(o)))
+        args, out, carry_out = self._running_args(knots, lin, q_k_lin, params, want, None, count, None, (carry_in, carry_out), pinned=pinned,
+                                                  out=out, cuda=False)
+        self._check(self.lib.cpi_preintegrate_running_resume_host(*args))
         return out, carry_out
 
     def preintegrate_running_resume_stj(self, knots, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), first=None,
@@ -350,35 +349,78 @@ class Engine:
         covariance state whether or not "cov" is wanted).  The mean and P / P_sym rows and carry_out are bit for bit those of
         preintegrate_running_resume; without "jac", or for model 1, the call is preintegrate_running_resume.  A dense call on
         knots [W, 2, 7] with count = zeros reads the record out as one row per window: the base of query_open.  Asynchronous."""
-        params = params or self.make_params()
-        W, N = self._window_shape(knots, lin, first, count, N, (q_k_lin, carry_in, carry_out))
-        carry_out = self._carry_out(W, params.model, carry_in, carry_out, device=self.device)
-        if out is None:
-            out = self._running_views(self.alloc_outputs(W * N, tuple(want), params.model, packed), W, N)
-        o = self._outputs_struct({k: v for k, v in out.items() if not k.startswith("_")})
-        self._sync_stream()
-        self._check(self.lib.cpi_running_resume_stj_batch(self.ctx, C.byref(params), W, N, _ptr(knots), _ptr(first), _ptr(count),
-                                                          _ptr(lin), _ptr(q_k_lin), _ptr(carry_in), _ptr(carry_out), C.byref(o)))
+        args, out, carry_out = self._running_args(knots, lin, q_k_lin, params, want, first, count, N, (carry_in, carry_out), packed=packed,
+                                                  out=out, filter_want=False)
+        self._check(self.lib.cpi_running_resume_stj_batch(*args))
         return out, carry_out
 
     def preintegrate_running_resume_stj_host(self, knots, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), count=None,
                                              carry_in=None, carry_out=None, pinned=True, out=None):
         """preintegrate_running_resume_stj for a dense batch held in HOST memory (CPU float64 tensors, the records included):
         cpi_running_resume_stj_batch_host.  Returns (rows, carry_out) as CPU tensors; synchronous."""
-        params = params or self.make_params()
-        W, N = self._window_shape(knots, lin, count=count, others=(q_k_lin, carry_in, carry_out), cuda=False)
-        carry_out = self._carry_out(W, params.model, carry_in, carry_out, pin_memory=pinned)
-        if out is None:
-            out = self._host_outputs((W, N), tuple(want), params.model, pinned)
-        o = self._outputs_struct(out)
-        self._sync_stream()
-        self._check(self.lib.cpi_running_resume_stj_batch_host(self.ctx, C.byref(params), W, N, _ptr(knots), None, _ptr(count), 0,
-                                                               _ptr(lin), _ptr(q_k_lin), _ptr(carry_in), _ptr(carry_out), C.byref(o)))
+        args, out, carry_out = self._running_args(knots, lin, q_k_lin, params, want, None, count, None, (carry_in, carry_out), pinned=pinned,
+                                                  out=out, cuda=False, filter_want=False)
+        self._check(self.lib.cpi_running_resume_stj_batch_host(*args))
         return out, carry_out
 
     @staticmethod
     def _wants_cov(want):
         return "cov" in want or "cov_sym" in want
+
+    @staticmethod
+    def _check_queries(qwin, qtime):
+        Q = qtime.shape[0]
+        assert qwin.dtype == torch.int32 and qtime.dtype == torch.float64 and qwin.shape == (Q,), "qwin [Q] int32, qtime [Q] float64"
+        return Q
+
+    @staticmethod
+    def _check_rows(rows, W, N, text):
+        """The tensors of a rows dict, each a contiguous CUDA tensor of leading shape [W, N]; text: what the caller says otherwise."""
+        r = _fields(rows)
+        for v in r.values():
+            assert v.is_cuda and v.is_contiguous() and v.shape[:2] == (W, N), text
+        return r
+
+    def _query_args(self, knots, lin, rows, rows_text, qwin, qtime, q_k_lin, params, want, first, count, N, out, base=()):
+        """What query / query_stj / query_open share, up to the C call: the asserts, then the outputs where not given, then the
+        engine on torch's stream.  base: nothing, or (base,) for query_open, whose entry takes the base rows and base_N last.
+        Returns (the arguments of the entry, out)."""
+        params = params or self.make_params()
+        W, N = self._window_shape(knots, lin, first, count, N, (q_k_lin, qwin, qtime))
+        Q = self._check_queries(qwin, qtime)
+        r = self._check_rows(rows, W, N, rows_text)
+        if base:
+            bo, base_N = None, 0
+            if base[0] is not None:
+                b = _fields(base[0])
+                sizes = {v.numel() // (W * n) for k, v in b.items() for name, n in OUT_FIELDS if name == k}
+                assert len(sizes) == 1 and all(v.is_cuda and v.is_contiguous() and v.shape[0] == W for v in b.values()), \
+                    "base: a dict of [W, base_N, ...] tensors with one base_N"
+                base_N = int(sizes.pop())
+                bo = C.byref(self._outputs_struct(b))
+            base = (bo, base_N)
+        if out is None:
+            out = self.alloc_outputs(Q, tuple(want), params.model)
+        o = self._outputs_struct(out)
+        ro = self._outputs_struct(r)
+        self._sync_stream()
+        return (self.ctx, C.byref(params), W, N, _ptr(knots), _ptr(first), _ptr(count), _ptr(lin), _ptr(q_k_lin), C.byref(ro), Q,
+                _ptr(qwin), _ptr(qtime), C.byref(o)) + base, out
+
+    def _query_host_args(self, knots, lin, qwin, qtime, q_k_lin, params, want, count, carry, pinned, out):
+        """What query_host / query_stj_host / query_open_host share, up to the C call.  carry: nothing, or (carry_in, carry_out)
+        for query_open_host.  Returns (the arguments of the entry, out, carry_out)."""
+        params = params or self.make_params()
+        W, N = self._window_shape(knots, lin, count=count, others=(q_k_lin, qwin, qtime) + carry, cuda=False)
+        Q = self._check_queries(qwin, qtime)
+        if carry:
+            carry = (carry[0], self._carry_out(W, params.model, carry[0], carry[1], pin_memory=pinned))
+        if out is None:
+            out = self._host_outputs((Q,), tuple(want), params.model, pinned)
+        o = self._outputs_struct(out)
+        self._sync_stream()
+        return (self.ctx, C.byref(params), W, N, _ptr(knots), None, _ptr(count), 0, _ptr(lin), _ptr(q_k_lin)) + tuple(map(_ptr, carry)) + (
+            Q, _ptr(qwin), _ptr(qtime), C.byref(o)), out, carry and carry[1]
 
     def query(self, knots, lin, rows, qwin, qtime, q_k_lin=None, params=None, want=("mean",), first=None, count=None, N=None,
               out=None):
@@ -392,21 +434,10 @@ class Engine:
         interval that row advanced over the partial interval with the reading held, a time before the window the zero state, a
         NaN time NaN.  The result is an ordinary measurement dict: predict(model, result, states, idx_i=qwin) gives the states
         AT the query times, sqrt_information(result["P_sym"]) the whitening of a factor there.  Asynchronous."""
-        params = params or self.make_params()
-        W, N = self._window_shape(knots, lin, first, count, N, (q_k_lin, qwin, qtime))
-        Q = qtime.shape[0]
-        assert qwin.dtype == torch.int32 and qtime.dtype == torch.float64 and qwin.shape == (Q,), "qwin [Q] int32, qtime [Q] float64"
-        r = {k: v for k, v in rows.items() if not k.startswith("_")}
-        for k, v in r.items():
-            assert v.is_cuda and v.is_contiguous() and v.shape[:2] == (W, N), "rows: the [W, N, ...] dict of preintegrate_running"
-        if out is None:
-            out = self.alloc_outputs(Q, tuple(want), params.model)
-        o = self._outputs_struct(out)
-        ro = self._outputs_struct(r)
-        self._sync_stream()
         entry = self.lib.cpi_query_cov_batch if self._wants_cov(want) else self.lib.cpi_query_batch
-        self._check(entry(self.ctx, C.byref(params), W, N, _ptr(knots), _ptr(first), _ptr(count), _ptr(lin),
-                          _ptr(q_k_lin), C.byref(ro), Q, _ptr(qwin), _ptr(qtime), C.byref(o)))
+        args, out = self._query_args(knots, lin, rows, "rows: the [W, N, ...] dict of preintegrate_running", qwin, qtime, q_k_lin, params,
+                                     want, first, count, N, out)
+        self._check(entry(*args))
         return out
 
     def query_host(self, knots, lin, qwin, qtime, q_k_lin=None, params=None, want=("mean",), count=None, pinned=True, out=None):
@@ -415,17 +446,9 @@ class Engine:
         are validated (CpiError names the window).  want as in query: with "cov" / "cov_sym" the call is
         cpi_query_cov_batch_host and the covariance rows stay on the device as well.  Returns a dict of CPU tensors [Q, ...];
         synchronous."""
-        params = params or self.make_params()
-        W, N = self._window_shape(knots, lin, count=count, others=(q_k_lin, qwin, qtime), cuda=False)
-        Q = qtime.shape[0]
-        assert qwin.dtype == torch.int32 and qtime.dtype == torch.float64 and qwin.shape == (Q,), "qwin [Q] int32, qtime [Q] float64"
-        if out is None:
-            out = self._host_outputs((Q,), tuple(want), params.model, pinned)
-        o = self._outputs_struct(out)
-        self._sync_stream()
         entry = self.lib.cpi_query_cov_batch_host if self._wants_cov(want) else self.lib.cpi_query_batch_host
-        self._check(entry(self.ctx, C.byref(params), W, N, _ptr(knots), None, _ptr(count), 0, _ptr(lin),
-                          _ptr(q_k_lin), Q, _ptr(qwin), _ptr(qtime), C.byref(o)))
+        args, out, _ = self._query_host_args(knots, lin, qwin, qtime, q_k_lin, params, want, count, (), pinned, out)
+        self._check(entry(*args))
         return out
 
     def query_stj(self, knots, lin, rows, qwin, qtime, q_k_lin=None, params=None, want=("mean",), first=None, count=None, N=None,
@@ -435,36 +458,17 @@ class Engine:
         and rows -- the dict of preintegrate_running_stj on the same arguments -- must then hold q and all seven.  The mean
         fields and P / P_sym are bit for bit those of query; the result feeds sqrt_information / factor_eval for model 2 with
         idx_i = qwin.  Asynchronous."""
-        params = params or self.make_params()
-        W, N = self._window_shape(knots, lin, first, count, N, (q_k_lin, qwin, qtime))
-        Q = qtime.shape[0]
-        assert qwin.dtype == torch.int32 and qtime.dtype == torch.float64 and qwin.shape == (Q,), "qwin [Q] int32, qtime [Q] float64"
-        r = {k: v for k, v in rows.items() if not k.startswith("_")}
-        for k, v in r.items():
-            assert v.is_cuda and v.is_contiguous() and v.shape[:2] == (W, N), "rows: the [W, N, ...] dict of preintegrate_running_stj"
-        if out is None:
-            out = self.alloc_outputs(Q, tuple(want), params.model)
-        o = self._outputs_struct(out)
-        ro = self._outputs_struct(r)
-        self._sync_stream()
-        self._check(self.lib.cpi_query_stj_batch(self.ctx, C.byref(params), W, N, _ptr(knots), _ptr(first), _ptr(count), _ptr(lin),
-                                                 _ptr(q_k_lin), C.byref(ro), Q, _ptr(qwin), _ptr(qtime), C.byref(o)))
+        args, out = self._query_args(knots, lin, rows, "rows: the [W, N, ...] dict of preintegrate_running_stj", qwin, qtime, q_k_lin, params,
+                                     want, first, count, N, out)
+        self._check(self.lib.cpi_query_stj_batch(*args))
         return out
 
     def query_stj_host(self, knots, lin, qwin, qtime, q_k_lin=None, params=None, want=("mean",), count=None, pinned=True, out=None):
         """query_stj for a dense batch held in HOST memory (CPU tensors): cpi_query_stj_batch_host.  No rows argument: the running
         rows (for a model-2 Jacobian request all seven Jacobian fields) are computed on the device and stay there.  Returns a
         dict of CPU tensors [Q, ...]; synchronous."""
-        params = params or self.make_params()
-        W, N = self._window_shape(knots, lin, count=count, others=(q_k_lin, qwin, qtime), cuda=False)
-        Q = qtime.shape[0]
-        assert qwin.dtype == torch.int32 and qtime.dtype == torch.float64 and qwin.shape == (Q,), "qwin [Q] int32, qtime [Q] float64"
-        if out is None:
-            out = self._host_outputs((Q,), tuple(want), params.model, pinned)
-        o = self._outputs_struct(out)
-        self._sync_stream()
-        self._check(self.lib.cpi_query_stj_batch_host(self.ctx, C.byref(params), W, N, _ptr(knots), None, _ptr(count), 0, _ptr(lin),
-                                                      _ptr(q_k_lin), Q, _ptr(qwin), _ptr(qtime), C.byref(o)))
+        args, out, _ = self._query_host_args(knots, lin, qwin, qtime, q_k_lin, params, want, count, (), pinned, out)
+        self._check(self.lib.cpi_query_stj_batch_host(*args))
         return out
 
     def query_open(self, knots, lin, rows, qwin, qtime, base, q_k_lin=None, params=None, want=("mean",), first=None, count=None,
@@ -476,29 +480,9 @@ class Engine:
         (preintegrate_running_resume_stj).  It stands where the zero state stands in query: a time on or before the segment's
         first stamp returns the base row bit for bit, a time inside interval 0 advances it.  base must hold what rows must hold
         for the request.  base=None: query_stj.  Returns a dict of [Q, ...] tensors.  Asynchronous."""
-        params = params or self.make_params()
-        W, N = self._window_shape(knots, lin, first, count, N, (q_k_lin, qwin, qtime))
-        Q = qtime.shape[0]
-        assert qwin.dtype == torch.int32 and qtime.dtype == torch.float64 and qwin.shape == (Q,), "qwin [Q] int32, qtime [Q] float64"
-        r = {k: v for k, v in rows.items() if not k.startswith("_")}
-        for k, v in r.items():
-            assert v.is_cuda and v.is_contiguous() and v.shape[:2] == (W, N), "rows: the [W, N, ...] dict of preintegrate_running_resume[_stj]"
-        bo, base_N = None, 0
-        if base is not None:
-            b = {k: v for k, v in base.items() if not k.startswith("_")}
-            sizes = {v.numel() // (W * n) for k, v in b.items() for name, n in OUT_FIELDS if name == k}
-            assert len(sizes) == 1 and all(v.is_cuda and v.is_contiguous() and v.shape[0] == W for v in b.values()), \
-                "base: a dict of [W, base_N, ...] tensors with one base_N"
-            base_N = int(sizes.pop())
-            bo = self._outputs_struct(b)
-        if out is None:
-            out = self.alloc_outputs(Q, tuple(want), params.model)
-        o = self._outputs_struct(out)
-        ro = self._outputs_struct(r)
-        self._sync_stream()
-        self._check(self.lib.cpi_query_open_batch(self.ctx, C.byref(params), W, N, _ptr(knots), _ptr(first), _ptr(count), _ptr(lin),
-                                                  _ptr(q_k_lin), C.byref(ro), Q, _ptr(qwin), _ptr(qtime), C.byref(o),
-                                                  C.byref(bo) if bo is not None else None, base_N))
+        args, out = self._query_args(knots, lin, rows, "rows: the [W, N, ...] dict of preintegrate_running_resume[_stj]", qwin, qtime, q_k_lin,
+                                     params, want, first, count, N, out, (base,))
+        self._check(self.lib.cpi_query_open_batch(*args))
         return out
 
     def query_open_host(self, knots, lin, qwin, qtime, q_k_lin=None, params=None, want=("mean",), count=None, carry_in=None,
@@ -506,23 +490,13 @@ class Engine:
         """One chunk of a live loop from HOST memory (CPU tensors): cpi_query_open_batch_host.  The base rows are read out of
         carry_in (None: the zero state), the chunk's rows and carry_out are computed on the device, the queries run against
         them.  Returns (out, carry_out): a dict of CPU tensors [Q, ...] and the record to continue from; synchronous."""
-        params = params or self.make_params()
-        W, N = self._window_shape(knots, lin, count=count, others=(q_k_lin, qwin, qtime, carry_in, carry_out), cuda=False)
-        Q = qtime.shape[0]
-        assert qwin.dtype == torch.int32 and qtime.dtype == torch.float64 and qwin.shape == (Q,), "qwin [Q] int32, qtime [Q] float64"
-        carry_out = self._carry_out(W, params.model, carry_in, carry_out, pin_memory=pinned)
-        if out is None:
-            out = self._host_outputs((Q,), tuple(want), params.model, pinned)
-        o = self._outputs_struct(out)
-        self._sync_stream()
-        self._check(self.lib.cpi_query_open_batch_host(self.ctx, C.byref(params), W, N, _ptr(knots), None, _ptr(count), 0, _ptr(lin),
-                                                       _ptr(q_k_lin), _ptr(carry_in), _ptr(carry_out), Q, _ptr(qwin), _ptr(qtime),
-                                                       C.byref(o)))
+        args, out, carry_out = self._query_host_args(knots, lin, qwin, qtime, q_k_lin, params, want, count, (carry_in, carry_out), pinned, out)
+        self._check(self.lib.cpi_query_open_batch_host(*args))
         return out, carry_out
 
     # ------------------------------------------------------------------ joining consecutive windows
     def _merge_args(self, meas, G, first, count, cuda):
-        m = {k: v for k, v in meas.items() if not k.startswith("_")}
+        m = _fields(meas)
         assert "DT" in m, "meas: a measurement dict ([rows, ...] tensors) as the preintegration entries return it"
         in_rows = m["DT"].shape[0]
         for k, v in m.items():
@@ -620,6 +594,26 @@ class Engine:
         self._check(self.lib.cpi_assemble_tiles(self.ctx, K, _ptr(stream), U, _ptr(update_times), N, _ptr(tiles), _ptr(count)))
         return tiles, count
 
+    @staticmethod
+    def _check_f64(tensors, cuda=True):
+        where = "CUDA" if cuda else "CPU"
+        for t in tensors:
+            assert t is None or (t.is_cuda == cuda and t.is_contiguous() and t.dtype == torch.float64), "inputs must be contiguous %s float64 tensors" % where
+
+    @staticmethod
+    def _bound_N(N, check_counts, who, bound, why=""):
+        """N as given, else bound() -- with check_counts only: a bound nobody checks the counts against has to be the caller's."""
+        if N is not None:
+            return int(N)
+        if not check_counts:
+            raise ValueError("%s: check_counts=False needs an explicit N%s" % (who, why))
+        return bound()
+
+    @staticmethod
+    def _check_host_counts(cnt, U, N, who):
+        if U and int(cnt.max()) > N:
+            raise ValueError("%s: a window has %d intervals, N = %d" % (who, int(cnt.max()), N))
+
     def preintegrate_stream(self, stream, update_times, lin, q_k_lin=None, params=None, want=("mean", "jac", "cov"), N=None, out=None,
                             return_counts=False, check_counts=True, workspace=None):
         """One IMU stream cut at update times and preintegrated IN PLACE (cpi_preintegrate_stream: the caller-side loop of
@@ -634,8 +628,7 @@ class Engine:
         (and check_counts=False keeps the whole call free of synchronisations)."""
         params = params or self.make_params()
         K, U = stream.shape[0], update_times.shape[0]
-        for t in (stream, update_times, lin, q_k_lin):
-            assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64), "inputs must be contiguous CUDA float64 tensors"
+        self._check_f64((stream, update_times, lin, q_k_lin))
         if N is None:
             N = self.stream_bound(stream, update_times)
         elif isinstance(N, str):
@@ -695,16 +688,14 @@ class Engine:
         params = params or self.make_params()
         K, U = stream.shape[0], update_times.shape[0]
         N = int(N) if N is not None else self._stream_bound(stream, update_times)     # the same default as the device entry: same lane split, same bits
-        for t in (stream, update_times, lin, q_k_lin):
-            assert t is None or (not t.is_cuda and t.is_contiguous() and t.dtype == torch.float64), "inputs must be contiguous CPU float64 tensors"
+        self._check_f64((stream, update_times, lin, q_k_lin), cuda=False)
         out = self._host_outputs((U,), want, params.model, pinned)
         cnt = torch.empty((U,), dtype=torch.int32)
         o = self._outputs_struct(out)
         self._sync_stream()
         self._check(self.lib.cpi_preintegrate_stream_host(self.ctx, C.byref(params), K, _ptr(stream), U, _ptr(update_times), N,
                                                           _ptr(lin), _ptr(q_k_lin), C.byref(o), _ptr(cnt)))
-        if U and int(cnt.max()) > N:
-            raise ValueError("preintegrate_stream_host: a window has %d intervals, N = %d" % (int(cnt.max()), N))
+        self._check_host_counts(cnt, U, N, "preintegrate_stream_host")
         return (out, cnt) if return_counts else out
 
     @staticmethod
@@ -742,8 +733,7 @@ class Engine:
             update_times = torch.empty((0,), dtype=torch.float64, device=self.device)
         R, K, U = soff.shape[0] - 1, stream.shape[0], update_times.shape[0]
         assert uoff.shape[0] == R + 1, "stream_offsets and update_offsets must both hold R + 1 entries"
-        for t in (stream, update_times, lin, q_k_lin):
-            assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64), "inputs must be contiguous CUDA float64 tensors"
+        self._check_f64((stream, update_times, lin, q_k_lin))
         if N is None:
             N = self.streams_bound(stream, soff, update_times, uoff)
         elif isinstance(N, str):
@@ -798,25 +788,17 @@ class Engine:
         uoff = torch.as_tensor(np.asarray(update_offsets, dtype=np.int64))
         R, K, U = soff.shape[0] - 1, stream.shape[0], update_times.shape[0]
         N = int(N) if N is not None else self.streams_bound(stream, soff, update_times, uoff)
-        for t in (stream, update_times, lin, q_k_lin):
-            assert t is None or (not t.is_cuda and t.is_contiguous() and t.dtype == torch.float64), "inputs must be contiguous CPU float64 tensors"
+        self._check_f64((stream, update_times, lin, q_k_lin), cuda=False)
         out = self._host_outputs((U,), want, params.model, pinned)
         cnt = torch.empty((U,), dtype=torch.int32)
         o = self._outputs_struct(out)
         self._sync_stream()
         self._check(self.lib.cpi_preintegrate_streams_host(self.ctx, C.byref(params), R, K, _ptr(stream), _ptr(soff), U, _ptr(update_times),
                                                            _ptr(uoff), N, _ptr(lin), _ptr(q_k_lin), C.byref(o), _ptr(cnt)))
-        if U and int(cnt.max()) > N:
-            raise ValueError("preintegrate_streams_host: a window has %d intervals, N = %d" % (int(cnt.max()), N))
+        self._check_host_counts(cnt, U, N, "preintegrate_streams_host")
         return (out, cnt) if return_counts else out
 
     # ---- running rows from IMU stream(s), cut in place (cpi_preintegrate_stream_running / cpi_preintegrate_streams_running)
-    def _stream_running_out(self, U, N, want, params, packed, out, stj=False):
-        if out is None:
-            want = tuple(want) if stj else self._running_want(tuple(want), params.model)
-            out = self._running_views(self.alloc_outputs(U * N, want, params.model, packed), U, N)
-        return out, self._outputs_struct({k: v for k, v in out.items() if not k.startswith("_")})
-
     def _stream_counts(self, ws, U, N, return_counts, check_counts, who):
         counts = torch.empty((0,), dtype=torch.int32, device=self.device)
         if U and (return_counts or check_counts):
@@ -840,14 +822,10 @@ class Engine:
         a stale N, which only the count check catches.  Models 1 and 2; Jacobians for model 1 only."""
         params = params or self.make_params()
         K, U = stream.shape[0], update_times.shape[0]
-        for t in (stream, update_times, lin, q_k_lin):
-            assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64), "inputs must be contiguous CUDA float64 tensors"
-        if N is None:
-            if not check_counts:
-                raise ValueError("preintegrate_stream_running: check_counts=False needs an explicit N (the cached bound may be stale)")
-            N = self.stream_bound(stream, update_times)
-        N = int(N)
-        out, o = self._stream_running_out(U, N, want, params, packed, out, _stj)
+        self._check_f64((stream, update_times, lin, q_k_lin))
+        N = self._bound_N(N, check_counts, "preintegrate_stream_running", lambda: self.stream_bound(stream, update_times),
+                          " (the cached bound may be stale)")
+        out, o = self._rows_out(U, N, want, params, out, not _stj, packed=packed)
         ws = workspace if workspace is not None else self.stream_workspace(U)
         self._sync_stream()
         if _stj:
@@ -877,14 +855,9 @@ class Engine:
             update_times = torch.empty((0,), dtype=torch.float64, device=self.device)
         R, K, U = soff.shape[0] - 1, stream.shape[0], update_times.shape[0]
         assert uoff.shape[0] == R + 1, "stream_offsets and update_offsets must both hold R + 1 entries"
-        for t in (stream, update_times, lin, q_k_lin):
-            assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64), "inputs must be contiguous CUDA float64 tensors"
-        if N is None:
-            if not check_counts:
-                raise ValueError("preintegrate_streams_running: check_counts=False needs an explicit N")
-            N = self.streams_bound(stream, soff, update_times, uoff)
-        N = int(N)
-        out, o = self._stream_running_out(U, N, want, params, packed, out, _stj)
+        self._check_f64((stream, update_times, lin, q_k_lin))
+        N = self._bound_N(N, check_counts, "preintegrate_streams_running", lambda: self.streams_bound(stream, soff, update_times, uoff))
+        out, o = self._rows_out(U, N, want, params, out, not _stj, packed=packed)
         ws = workspace if workspace is not None else self.streams_workspace(R, U)
         self._sync_stream()
         entry = self.lib.cpi_stream_running_stj_batch if _stj else self.lib.cpi_preintegrate_streams_running
@@ -904,14 +877,10 @@ class Engine:
         than N raises (check_counts=False needs an integer N and returns the truncated rows)."""
         params = params or self.make_params()
         K, U = stream.shape[0], update_times.shape[0]
-        for t in (stream, update_times, lin, q_k_lin):
-            assert t is None or (not t.is_cuda and t.is_contiguous() and t.dtype == torch.float64), "inputs must be contiguous CPU float64 tensors"
-        if N is None and not check_counts:
-            raise ValueError("preintegrate_stream_running_host: check_counts=False needs an explicit N")
-        N = int(N) if N is not None else self._stream_bound(stream, update_times)
-        out = self._host_outputs((U, N), tuple(want) if _stj else self._running_want(tuple(want), params.model), params.model, pinned)
+        self._check_f64((stream, update_times, lin, q_k_lin), cuda=False)
+        N = self._bound_N(N, check_counts, "preintegrate_stream_running_host", lambda: self._stream_bound(stream, update_times))
+        out, o = self._rows_out(U, N, want, params, None, not _stj, cuda=False, pinned=pinned)
         cnt = torch.empty((U,), dtype=torch.int32)
-        o = self._outputs_struct(out)
         self._sync_stream()
         if _stj:
             self._check(self.lib.cpi_stream_running_stj_batch_host(self.ctx, C.byref(params), 1, K, _ptr(stream), None, U, _ptr(update_times),
@@ -919,8 +888,8 @@ class Engine:
         else:
             self._check(self.lib.cpi_preintegrate_stream_running_host(self.ctx, C.byref(params), K, _ptr(stream), U, _ptr(update_times), N,
                                                                       _ptr(lin), _ptr(q_k_lin), C.byref(o), _ptr(cnt)))
-        if check_counts and U and int(cnt.max()) > N:
-            raise ValueError("preintegrate_stream_running_host: a window has %d intervals, N = %d" % (int(cnt.max()), N))
+        if check_counts:
+            self._check_host_counts(cnt, U, N, "preintegrate_stream_running_host")
         return (out, cnt) if return_counts else out
 
     def preintegrate_streams_running_host(self, stream, stream_offsets, update_times, update_offsets, lin, q_k_lin=None, params=None,
@@ -933,20 +902,16 @@ class Engine:
         soff = torch.as_tensor(np.asarray(stream_offsets, dtype=np.int64))
         uoff = torch.as_tensor(np.asarray(update_offsets, dtype=np.int64))
         R, K, U = soff.shape[0] - 1, stream.shape[0], update_times.shape[0]
-        for t in (stream, update_times, lin, q_k_lin):
-            assert t is None or (not t.is_cuda and t.is_contiguous() and t.dtype == torch.float64), "inputs must be contiguous CPU float64 tensors"
-        if N is None and not check_counts:
-            raise ValueError("preintegrate_streams_running_host: check_counts=False needs an explicit N")
-        N = int(N) if N is not None else self.streams_bound(stream, soff, update_times, uoff)
-        out = self._host_outputs((U, N), tuple(want) if _stj else self._running_want(tuple(want), params.model), params.model, pinned)
+        self._check_f64((stream, update_times, lin, q_k_lin), cuda=False)
+        N = self._bound_N(N, check_counts, "preintegrate_streams_running_host", lambda: self.streams_bound(stream, soff, update_times, uoff))
+        out, o = self._rows_out(U, N, want, params, None, not _stj, cuda=False, pinned=pinned)
         cnt = torch.empty((U,), dtype=torch.int32)
-        o = self._outputs_struct(out)
         self._sync_stream()
         entry = self.lib.cpi_stream_running_stj_batch_host if _stj else self.lib.cpi_preintegrate_streams_running_host
         self._check(entry(self.ctx, C.byref(params), R, K, _ptr(stream), _ptr(soff), U, _ptr(update_times), _ptr(uoff), N, _ptr(lin),
                           _ptr(q_k_lin), C.byref(o), _ptr(cnt)))
-        if check_counts and U and int(cnt.max()) > N:
-            raise ValueError("preintegrate_streams_running_host: a window has %d intervals, N = %d" % (int(cnt.max()), N))
+        if check_counts:
+            self._check_host_counts(cnt, U, N, "preintegrate_streams_running_host")
         return (out, cnt) if return_counts else out
 
     # ---- model 2's Jacobian rows from IMU stream(s) (cpi_stream_running_stj_batch) and the query by absolute time (cpi_query_stream_batch)
@@ -982,7 +947,7 @@ class Engine:
         qwin; qwin [Q] int32, the GLOBAL window of every query (-1 and NaN rows for a run without update times) -- the idx_i of
         predict / factor_eval / factor_hessian.  Asynchronous; the call cuts the windows into the workspace itself."""
         params = params or self.make_params()
-        r = {k: v for k, v in rows.items() if not k.startswith("_")}
+        r = _fields(rows)
         K, U, Q = stream.shape[0], update_times.shape[0], qtime.shape[0]
         if N is None:
             N = next(iter(r.values())).shape[1]
@@ -995,11 +960,9 @@ class Engine:
             _, uoff = self._runs(update_times, update_offsets, "update_times", self.device)
             R = soff.shape[0] - 1
             assert uoff.shape[0] == R + 1, "stream_offsets and update_offsets must both hold R + 1 entries"
-        for t in (stream, update_times, lin, q_k_lin, qtime):
-            assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64), "inputs must be contiguous CUDA float64 tensors"
+        self._check_f64((stream, update_times, lin, q_k_lin, qtime))
         assert qrun is None or (qrun.is_cuda and qrun.dtype == torch.int32 and qrun.shape == (Q,)), "qrun [Q] int32"
-        for k, v in r.items():
-            assert v.is_cuda and v.is_contiguous() and v.shape[:2] == (U, N), "rows: the [U, N, ...] dict of preintegrate_stream[s]_running[_stj]"
+        self._check_rows(r, U, N, "rows: the [U, N, ...] dict of preintegrate_stream[s]_running[_stj]")
         if out is None:
             out = self.alloc_outputs(Q, tuple(want), params.model)
         qwin = torch.empty((Q,), dtype=torch.int32, device=self.device)
@@ -1031,8 +994,7 @@ class Engine:
             R = soff.shape[0] - 1
         if N is None:
             N = self._stream_bound(stream, update_times) if one else self.streams_bound(stream, soff, update_times, uoff)
-        for t in (stream, update_times, lin, q_k_lin, qtime):
-            assert t is None or (not t.is_cuda and t.is_contiguous() and t.dtype == torch.float64), "inputs must be contiguous CPU float64 tensors"
+        self._check_f64((stream, update_times, lin, q_k_lin, qtime), cuda=False)
         assert qrun is None or (qrun.dtype == torch.int32 and qrun.shape == (Q,)), "qrun [Q] int32"
         if out is None:
             out = self._host_outputs((Q,), tuple(want), params.model, pinned)

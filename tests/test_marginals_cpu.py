@@ -171,8 +171,13 @@ def test_host_form_refusals_and_the_chain_whose_range_is_wrong(lib):
     for k in ("C_", "S_", "F_"):
         refused("negative size", **{k: -1})
     refused("G (the longest chain in states) must be >= 1", G_=0)
+    refused("G exceeds 2^31 - 1", G_=2 ** 31)
     refused("cov is NULL", cov=None)
     refused("hess is NULL", hess=None)
+    refused("negative size", F_=-1, G_=0)                                     # which refusal wins when two apply: sizes, then pointers,
+    refused("cov is NULL", cov=None, hess=None)                               # then overlaps, then the ranges
+    refused("hess is NULL", hess=None, ffirst=ptr(a["cov"], 4))
+    refused("cov overlaps", cov=ptr(a["hess"], 8), F_=F - 1)
     for o in ("cov", "cross", "status"):
         for i in ("first", "count", "ffirst", "hess", "prior"):
             refused("overlaps", **{o: ptr(a[i], a[i].nbytes - 4)})

@@ -220,8 +220,9 @@ def test_host_cost_refusals(lib):
     P = np.zeros(F * 225)
     d = lambda x: x.ctypes.data
 
-    def call(model=2, meas=m, chi2_=d(chi2), ii_=ii, S_=S):
-        rc = f(None, model, g, F, C.byref(meas), d(lin), d(qk), d(st), S_, d(ii_), d(jj), chi2_, None, None)
+    def call(model=2, meas=m, chi2_=d(chi2), ii_=ii, S_=S, F_=F, st_=d(st), jj_=jj):
+        rc = f(None, model, g, F_, C.byref(meas), d(lin), d(qk), st_, S_, None if ii_ is None else d(ii_), None if jj_ is None else d(jj_),
+               chi2_, None, None)
         return rc, _err(lib)
 
     assert call()[0] == 1 and "P_sym or P" in call()[1]
@@ -234,6 +235,18 @@ def test_host_cost_refusals(lib):
     rc, msg = call(ii_=bad)
     assert rc == 1 and msg.startswith(entry + ": ") and "state index out of range at factor 2" in msg
     assert "too few states" in call(S_=0)[1]
+    # the rest of what the entry refuses before the context, text and all; chained states (no index array) need F + 1 of them
+    assert call(F_=-1) == (1, entry + ": negative size")
+    assert call(st_=None) == (1, entry + ": NULL argument")
+    assert call(ii_=None, S_=F - 1) == (1, entry + ": too few states")
+    assert call(jj_=None, S_=F) == (1, entry + ": too few states")
+    assert call(ii_=None, jj_=None, S_=F + 1) == (1, "ctx is NULL")
+    bad = jj.copy()
+    bad[1] = -1
+    assert call(jj_=bad) == (1, entry + ": state index out of range at factor 1")
+    assert call(jj_=bad, S_=0) == (1, entry + ": too few states")            # the count of states is looked at before the indices
+    assert call(jj_=bad, chi2_=None) == (1, entry + ": chi2 is NULL")
+    assert call(F_=0, chi2_=None, st_=None) == (1, "ctx is NULL")            # F == 0 is a no-op: nothing to refuse
 
 
 def test_total_workspace_size(lib):
