@@ -884,6 +884,10 @@ int cpi_factor_cost_tri_batch(cpi_ctx *ctx, int32_t model, const double grav[3],
  *          positive definite (a pivot that is not > 0, the rule of cpi_sqrt_information_*); -1: the chain's factor rows leave
  *          [0, F) -- such a chain reads nothing outside the arrays.  A failed or refused chain has NaN in every delta row of its
  *          own; no other chain is affected.  count = 1 solves (Lam + damping) delta = eta; count = 0 writes nothing, status 0.
+ *          A NaN in g alone (D and U finite) meets no pivot: the status is not affected by it (0 when every block is positive
+ *          definite) and every delta row of the chain is NaN; a NaN in D or U is a pivot that is not > 0.  A block that is exactly
+ *          zero is a failed pivot (0 is not > 0): no prior, one state and lambda = 0 give status 1, and so does CPI_DAMP_DIAGONAL
+ *          on a zero diagonal whatever lambda is (lambda * 0).
  *   workspace  cpi_chain_solve_workspace_doubles(S) doubles of the caller's ([R y] and W of every state, 360 doubles each); its
  *          contents after the call are what cpi_chain_marginals_batch reads and are not declared otherwise.  The library
  *          allocates nothing.

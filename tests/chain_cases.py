@@ -23,6 +23,8 @@ below the rounding of the format (2^-53 for (a); for (b) the unit is already con
 ((a): the 1000 chains of 5 states; (b): the ragged chains without a prior, identity damping; LAPACK's row is over the layouts of the
 table in the profile).
 """
+import functools
+
 import numpy as np
 
 EPS_HALF = 2.0 ** -53
@@ -238,3 +240,205 @@ DAMPINGS = (("none", None, False), ("identity", 3.0, False), ("diagonal", 0.25, 
 def lam_of(batch, value):
     """per-chain lambda: the value scaled a little differently per chain, or None."""
     return None if value is None else value * (1.0 + 0.125 * (np.arange(batch.C) % 4))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The edges of the contract (tests/test_gpu_chain_edges.py and the twin tests of tests/test_chain_cpu.py / test_marginals_cpu.py):
+# one call of an entry with any subset of first / count / ffirst, a G and an S of its own, and the builders of the cases.  What a
+# case must give is asserted by tests/chain_edge_checks.py, for the twins and for the device alike.
+class Call:
+    """One call of cpi_chain_solve_batch (and of cpi_chain_marginals_batch after it) on the arrays of batch b.  first / count / ffirst:
+    arrays [C], or None for NULL; G and S default to the batch's; S < b.S passes the leading S rows of delta / prior / cov / cross."""
+
+    def __init__(self, b, first=None, count=None, ffirst=None, G=None, S=None, lam=None, diagonal=False, with_prior=True, C=None):
+        arr = lambda v, dt: None if v is None else np.ascontiguousarray(v, dtype=dt)
+        self.b, self.first, self.count, self.ffirst = b, arr(first, np.int64), arr(count, np.int32), arr(ffirst, np.int64)
+        given = [v for v in (self.first, self.count, self.ffirst) if v is not None]
+        self.C = (len(given[0]) if given else b.C) if C is None else C
+        self.G, self.S = int(b.G if G is None else G), int(b.S if S is None else S)
+        self.lam, self.diagonal, self.with_prior = arr(lam, np.float64), bool(diagonal), with_prior
+
+    @classmethod
+    def explicit(cls, b, chains=None, lam=None, **kw):
+        """first, count and ffirst of the batch, all three given; chains: only these, in this order."""
+        idx = np.arange(b.C) if chains is None else np.asarray(chains)
+        lam = None if lam is None else np.asarray(lam, dtype=np.float64)[idx]
+        return cls(b, first=b.first[idx], count=b.count[idx], ffirst=b.ffirst[idx], lam=lam, **kw)
+
+    def states(self, c):
+        """(first state, number of states) of chain c as include/cpi_amd.h clamps them: count into [0, G], first into [0, S], the
+        chain clipped at S."""
+        f = int(self.first[c]) if self.first is not None else c * self.G
+        n = int(self.count[c]) if self.count is not None else self.G
+        n = min(max(n, 0), self.G)
+        f = min(max(f, 0), self.S)
+        return f, min(n, self.S - f)
+
+    def rows(self, c):
+        f, n = self.states(c)
+        return slice(f, f + n)
+
+    def owned(self):
+        """(rows [b.S] that belong to a chain, rows that are a chain's last state: their cross row is not written)."""
+        own, last = np.zeros(self.b.S, dtype=bool), np.zeros(self.b.S, dtype=bool)
+        for c in range(self.C):
+            f, n = self.states(c)
+            own[f:f + n] = True
+            if n > 0:
+                last[f + n - 1] = True
+        return own, last
+
+
+def clone(b):
+    """The batch with arrays of its own."""
+    n = Batch.__new__(Batch)
+    n.__dict__.update(b.__dict__)
+    n.count, n.first, n.ffirst, n.hess, n.prior = b.count.copy(), b.first.copy(), b.ffirst.copy(), b.hess.copy(), b.prior.copy()
+    return n
+
+
+# chain -> (state s, pivot k) of a non-positive pivot: all four chains of wavefront 0 at different states, the chain in lanes 48 .. 63,
+# pivots 0, 7 and 14, a chain's first and last state; chains 4 and 7 stay as they are
+FAILURES = {0: (0, 0), 1: (0, 14), 2: (3, 14), 3: (2, 7), 5: (3, 0), 6: (1, 14)}
+FAILURE_STATUS = [1, 1, 4, 3, 0, 4, 2, 0]
+
+
+def failure_plan():
+    """(the clean call, the call with the pivots of FAILURES made negative, the status it must give).  -1e12 on the diagonal of the
+    state's prior block, where the factors and the prior add a few times SCALES^2 <= 1e8."""
+    good = Batch([4] * 8, seed=7, prior_all=True)
+    bad = clone(good)
+    for c, (s, k) in FAILURES.items():
+        bad.prior[bad.first[c] + s, k + k * (k + 1) // 2] = -1e12
+    return Call(good), Call(bad), FAILURE_STATUS
+
+
+def tri(d):
+    return d * (d + 1) // 2
+
+
+# chain -> (factor, entry of its hess row, status): a NaN in a D block (twice: from the factor's leading and from its trailing block),
+# in a U block, and in g of the chain's last state alone -- every pivot is fine then, and every delta row of the chain is NaN
+NANS = {0: (1, tri(3) + 3, 2), 1: (1, tri(20) + 20, 3), 2: (1, tri(20) + 3, 3), 3: (2, tri(30) + 29, 0)}
+
+
+def nan_plan():
+    """(the clean call, the call with the NaN entries of NANS, the status it must give)."""
+    good = Batch([4] * 4, seed=7, prior_all=True)
+    bad = clone(good)
+    for c, (k, e, _) in NANS.items():
+        bad.hess[bad.ffirst[c] + k, e] = np.nan
+    return Call(good), Call(bad), [NANS[c][2] for c in range(4)]
+
+
+def ffirst_boundary_cases():
+    """(the unmoved call, [(chain, ffirst, call, status)]): the last valid and the first invalid factor row of a chain of three and of
+    two states, and a chain of one state with an ffirst far outside.  F = 16, rows 14 and 15 are gap rows; where the new ffirst is
+    valid the chain's own factor rows are copied there first, so status 0 comes with the bits of the unmoved call."""
+    base = Batch([3, 2, 1, 4], seed=3, layout="gaps")
+    assert base.F == 16 and int(base.ffirst[3]) + 3 == 14
+    cases = []
+    for c, ff, status in ((0, 14, 0), (0, 15, -1), (0, -1, -1), (1, 15, 0), (1, 16, -1), (2, -100, 0), (2, base.F + 100, 0)):
+        b = clone(base)
+        n = int(b.count[c])
+        if status == 0 and n > 1:
+            b.hess[ff:ff + n - 1] = base.hess[base.ffirst[c]:base.ffirst[c] + n - 1]
+        b.ffirst[c] = ff
+        cases.append((c, ff, Call.explicit(b), status))
+    return Call.explicit(base), cases
+
+
+def ffirst_null_case(counts=(5, 3, 5, 1, 2)):
+    """(the tile call, the call with first = c (G + 1) given and ffirst NULL): G = 5, so the factor rows of chain c start at
+    first[c] - c = c G, which is neither the tile rule c (G - 1) nor first[c]; every row that is not used holds NaN."""
+    G, Cn = 5, len(counts)
+    src = Batch(list(counts), seed=3, prior_all=True)
+    assert src.G == G
+    first = np.arange(Cn, dtype=np.int64) * (G + 1)
+    hess, prior = np.full((Cn * G, 496), np.nan), np.full((Cn * (G + 1), 136), np.nan)
+    for c, n in enumerate(counts):
+        prior[first[c]:first[c] + n] = src.prior[src.rows(c)]
+        hess[first[c] - c:first[c] - c + max(n - 1, 0)] = src.chain(c)[0]
+    b = Batch.from_arrays(list(counts), first, first - np.arange(Cn), hess, prior)
+    return Call(src, count=src.count), Call(b, first=b.first, count=b.count)
+
+
+def clamp_cases():
+    """[(name, the call as given, the call with the values already clamped)] on the ragged chains with gaps: a negative first and
+    count, a first beyond S, a G below the longest counts, an S that cuts the last chain in two.  The two calls of a case must agree
+    in status and bit for bit, and rows of no clamped chain keep the sentinel."""
+    b = Batch(RAGGED, seed=3, layout="gaps")
+    cases = []
+    raw, cl = clone(b), clone(b)
+    raw.first[0], raw.count[0] = -5, -3
+    cl.first[0], cl.count[0] = 0, 0
+    cases.append(("negative first and count", Call.explicit(raw), Call.explicit(cl)))
+    raw, cl = clone(b), clone(b)
+    raw.first[9] = b.S + 7
+    cl.first[9], cl.count[9] = b.S, 0
+    cases.append(("first beyond S", Call.explicit(raw), Call.explicit(cl)))
+    cl = clone(b)
+    cl.count = np.minimum(b.count, 17).astype(np.int32)
+    cases.append(("G = 17", Call.explicit(b, G=17), Call.explicit(cl)))
+    cut = int(b.first[10]) + 1                                               # the last chain has two states: one is left
+    assert b.count[10] == 2 and b.first[10] == b.first.max()
+    cl = clone(b)
+    cl.count[10] = 1
+    cases.append(("S cuts the last chain", Call.explicit(b, S=cut), Call.explicit(cl)))
+    return cases
+
+
+LONG = [64, 1, 0, 2]                 # a trip count of 64 beside 1, 0 and 2: the carried registers of the short chains idle for 62 trips
+EMPTY_WAVE = [0, 0, 0, 0, 3, 0, 2]   # a wavefront whose four chains have no states, next to one that has some
+SCALED_EXPONENTS = (0, 300, -300, 301)
+
+
+@functools.lru_cache(maxsize=None)
+def long_case():
+    """(batch, reference) of LONG: tile layout, the prior on the first state only (cond 1.6e10)."""
+    b = Batch(LONG, seed=5)
+    ref = Reference(b)
+    ref.check_inputs()
+    return b, ref
+
+
+@functools.lru_cache(maxsize=None)
+def scaled_reference():
+    """(the unscaled batch, its reference).  scaled_batch(e) multiplies hess and prior by 2^e: A and g are scaled by a power of two,
+    exactly, so delta is the unscaled one and this reference serves every exponent (cond 2.9e5)."""
+    b = Batch(RAGGED, seed=3, prior_all=True)
+    ref = Reference(b)
+    ref.check_inputs()
+    return b, ref
+
+
+def scaled_batch(e):
+    b = clone(scaled_reference()[0])
+    b.hess *= 2.0 ** e
+    b.prior *= 2.0 ** e
+    return b
+
+
+@functools.lru_cache(maxsize=None)
+def empty_wave_case():
+    b = Batch(EMPTY_WAVE, seed=3)
+    ref = Reference(b)
+    ref.check_inputs()
+    return b, ref
+
+
+def zero_pivot_case(diagonal):
+    """(call, status): no prior, lambda = [0, 2, 2] on chains of 1, 1 and 2 states.  The block of a chain of one state is exactly
+    zero: with lambda = 0 its first pivot is 0, and so it is under diagonal damping whatever lambda is (lambda * 0)."""
+    b = Batch([1, 1, 2], seed=7)
+    return Call(b, count=b.count, lam=[0.0, 2.0, 2.0], diagonal=diagonal, with_prior=False), ([1, 1, 0] if diagonal else [1, 0, 0])
+
+
+@functools.lru_cache(maxsize=None)
+def no_prior_diagonal_case():
+    """(batch, lam, reference): no prior, diagonal damping 0.25 on chains of two states and more (cond 4.3e3)."""
+    b = Batch([2, 3, 17, 40, 5, 16], seed=3)
+    lam = lam_of(b, 0.25)
+    ref = Reference(b, lam, True, with_prior=False)
+    ref.check_inputs()
+    return b, lam, ref

@@ -154,3 +154,34 @@ def untouched_rows(b, chains=None):
 def last_rows(b, chains=None):
     """The last state of every chain with states: its cross row is not written."""
     return np.array([int(b.first[c]) + int(b.count[c]) - 1 for c in (range(b.C) if chains is None else chains) if b.count[c] > 0], dtype=np.int64)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The edge cases of tests/chain_cases.py that have a reference: the same batches, the blocks of their dense inverses.
+@functools.lru_cache(maxsize=None)
+def long_case():
+    """(batch, reference) of cc.LONG."""
+    b, _ = cc.long_case()
+    ref = Reference(b)
+    ref.check_inputs()
+    return b, ref
+
+
+@functools.lru_cache(maxsize=None)
+def scaled_reference():
+    """(the unscaled batch, its reference): with hess and prior times 2^e the inverse is 2^-e times this one, exactly, so
+    metric(cov * 2^e, cross * 2^e) against this reference is the metric of the scaled call."""
+    b, _ = cc.scaled_reference()
+    ref = Reference(b)
+    ref.check_inputs()
+    return b, ref
+
+
+@functools.lru_cache(maxsize=None)
+def diagonal_case():
+    """(batch, lam, reference): the ragged chains under diagonal damping 0.25, against the damped matrix's own inverse."""
+    b = cc.Batch(cc.RAGGED, seed=SEED)
+    lam = cc.lam_of(b, 0.25)
+    ref = Reference(b, lam, True)
+    ref.check_inputs()
+    return b, lam, ref

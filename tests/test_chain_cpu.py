@@ -7,7 +7,10 @@
    pair (output, input) and (output, output) that may not overlap is tried.  The host form names the chain whose range is wrong.
 3. The inputs of tests/chain_cases.py are what they claim to be (finite float64 Cholesky, cond <= 1e11), and the host twin
    (tests/hostsim/hostsim_chain.cpp over namespace chn of cpi_math.hpp, compiled with -ffp-contract=off) meets the gates against the
-   longdouble reference on every layout, damping and prior variant of the GPU tests.  Both metrics are printed first."""
+   longdouble reference on every layout, damping and prior variant of the GPU tests.  Both metrics are printed first.
+4. The edges of the contract (the cases of tests/chain_cases.py, the checks of tests/chain_edge_checks.py) on the twin, before
+   tests/test_gpu_chain_edges.py asks the same of the device; and the twin with one rule of the contract broken, built in tmp_path,
+   fails the check that states the rule."""
 import ctypes as C
 import os
 import re
@@ -17,6 +20,7 @@ import numpy as np
 import pytest
 
 from tests import chain_cases as cc
+from tests import chain_edge_checks as ck
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -302,3 +306,112 @@ def test_the_reference_step_lowers_the_cost_of_the_device_hess_case():
     r = cp.cpu_case()
     print("cond max %.1e: cost before %.6e, after the reference step %.6e" % (r["cond"], r["before"], r["after"]))
     assert r["after"] < 1e-3 * r["before"]
+
+
+# ---------------------------------------------------------------- the edges of the contract, on the twin first
+def _bind(path):
+    lib = C.CDLL(path)
+    vp = C.c_void_p
+    lib.hsc_chain_solve.argtypes = [C.c_longlong] * 4 + [vp] * 6 + [C.c_int, vp, vp, vp]
+    return lib
+
+
+def twin_run(hs):
+    """run(call) of tests/chain_edge_checks.py on the solve's twin.  hess gets one more row of NaN behind its F rows: a twin whose range
+    rule is a row too lax (the mutants below) reads that instead of memory that is not the test's."""
+    def run(call, status_in=None):
+        b = call.b
+        p = lambda x: None if x is None else x.ctypes.data
+        delta = np.full((b.S, 15), ck.SENTINEL)
+        status = np.full(call.C, 99, dtype=np.int32)
+        ws = np.full(max(call.S, 1) * hs.hsc_ws_doubles(), np.nan)
+        hess = np.concatenate([b.hess, np.full((1, 496), np.nan)])
+        assert hs.hsc_chain_solve(call.C, call.G, call.S, b.F, p(call.first), p(call.count), p(call.ffirst), p(hess),
+                                  p(b.prior if call.with_prior else None), p(call.lam), int(call.diagonal), p(delta), p(status), p(ws)) == 0
+        return ck.Result(delta, status)
+    return run
+
+
+def test_twin_status_names_the_state_of_the_first_failure(hs):
+    ck.check_failure_plan(twin_run(hs))
+
+
+def test_twin_nan_in_the_inputs(hs):
+    ck.check_nan_plan(twin_run(hs))
+
+
+def test_twin_refusal_boundary_of_ffirst(hs):
+    ck.check_ffirst_boundaries(twin_run(hs))
+
+
+def test_twin_ffirst_null_with_an_explicit_first(hs):
+    ck.check_ffirst_null(twin_run(hs))
+
+
+def test_twin_clamps_of_first_count_G_and_S(hs):
+    ck.check_clamps(twin_run(hs))
+
+
+def test_twin_a_wavefront_of_empty_chains(hs):
+    ck.check_empty_wave(twin_run(hs), cc.GATE_BACKWARD_HOST, cc.GATE_FORWARD_HOST)
+
+
+def test_twin_a_zero_block_is_a_failed_pivot(hs):
+    ck.check_zero_pivot(twin_run(hs))
+
+
+def test_twin_long_chain_beside_short_ones(hs):
+    b, ref = cc.long_case()
+    r = twin_run(hs)(cc.Call(b, count=b.count))
+    a, bb = ref.metrics(r.delta)
+    print("LONG %s: cond max %.1e, twin (a) %.3e (b) %.3e" % (cc.LONG, ref.cond.max(), a, bb))
+    assert r.status.tolist() == [0] * 4 and a <= cc.GATE_BACKWARD_HOST and bb <= cc.GATE_FORWARD_HOST
+    ck.unowned(r, cc.Call(b, count=b.count))
+
+
+@pytest.mark.parametrize("e", cc.SCALED_EXPONENTS)
+def test_twin_scaled_by_a_power_of_two(hs, e):
+    _, ref = cc.scaled_reference()
+    b = cc.scaled_batch(e)
+    r = twin_run(hs)(cc.Call(b, count=b.count))
+    a, bb = ref.metrics(r.delta)
+    print("hess, prior x 2^%d: cond max %.1e, twin (a) %.3e (b) %.3e" % (e, ref.cond.max(), a, bb))
+    assert (r.status == 0).all() and a <= cc.GATE_BACKWARD_HOST and bb <= cc.GATE_FORWARD_HOST
+
+
+def test_twin_diagonal_damping_without_a_prior(hs):
+    b, lam, ref = cc.no_prior_diagonal_case()
+    r = twin_run(hs)(cc.Call(b, count=b.count, lam=lam, diagonal=True, with_prior=False))
+    a, bb = ref.metrics(r.delta)
+    print("no prior, diagonal damping 0.25: cond max %.1e, twin (a) %.3e (b) %.3e" % (ref.cond.max(), a, bb))
+    assert (r.status == 0).all() and a <= cc.GATE_BACKWARD_HOST and bb <= cc.GATE_FORWARD_HOST
+
+
+# the rules the edge tests are there for, each broken in a copy of the twin: (file, old, new, the check that must notice)
+MUTANTS = {
+    "the ffirst range one row too lax": ("tests/hostsim/hostsim_chain.cpp", "ff > F - (n - 1)", "ff > F - (n - 2)", ck.check_ffirst_boundaries),
+    "the last failure wins": ("cpi_amd/csrc/cpi_math.hpp", "if (!factor_block(A) && status == 0) status = s + 1;",
+                              "if (!factor_block(A)) status = s + 1;", ck.check_failure_plan),
+    "ffirst NULL is the tile rule": ("tests/hostsim/hostsim_chain.cpp", "ffirst[c] : f - c;", "ffirst[c] : c * (G - 1);", ck.check_ffirst_null),
+    "count is not clamped to G": ("tests/hostsim/hostsim_chain.cpp", "n = n < 0 ? 0 : (n > G ? G : n);", "n = n < 0 ? 0 : n;",
+                                  lambda run: ck.check_clamps(run, only="G = 17")),
+}
+
+
+@pytest.mark.parametrize("what", list(MUTANTS))
+def test_a_broken_rule_fails_its_edge_test(hs, tmp_path, what):
+    """Do the edge tests bite?  The twin with one rule of the contract broken, built in tmp_path, fails the check that states the rule
+    (every access of these mutants stays inside the arrays: see twin_run), and the twin as it is passes it."""
+    rel, old, new, check = MUTANTS[what]
+    files = {"tests/hostsim/hostsim_chain.cpp": open(_SRC).read(), "cpi_amd/csrc/cpi_math.hpp": open(_HDRS[0]).read()}
+    assert files[rel].count(old) == 1, old
+    files[rel] = files[rel].replace(old, new)
+    for name, text in files.items():
+        os.makedirs(tmp_path / os.path.dirname(name), exist_ok=True)
+        (tmp_path / name).write_text(text)
+    out = str(tmp_path / "libmutant.so")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-ffp-contract=off", "-o", out,
+                           str(tmp_path / "tests/hostsim/hostsim_chain.cpp")])
+    check(twin_run(hs))
+    with pytest.raises(AssertionError):
+        check(twin_run(_bind(out)))

@@ -8,7 +8,9 @@
 3. The host twin (tests/hostsim/hostsim_marginals.cpp over chn::solve_chain and chn::marginals_chain of cpi_math.hpp, compiled with
    -ffp-contract=off) against the longdouble dense inverse of tests/marginals_cases.py on every layout; the metric is printed first.
    The twin's solve writes a W record for a chain's last state; it is overwritten with NaN before the marginals run, so a read of it
-   would show.  Mutations of the twin built in tmp_path (the R^-1 R^-T term dropped, the sign of cross) must fail the gate."""
+   would show.  Mutations of the twin built in tmp_path (the R^-1 R^-T term dropped, the sign of cross) must fail the gate.
+4. The edges of the contract (the cases of tests/chain_cases.py, the checks of tests/chain_edge_checks.py) on the twins of the solve
+   and of the marginals together, before tests/test_gpu_chain_edges.py asks the same of the device."""
 import ctypes as C
 import os
 import re
@@ -19,6 +21,7 @@ import numpy as np
 import pytest
 
 from tests import chain_cases as cc
+from tests import chain_edge_checks as ck
 from tests import marginals_cases as mc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -334,3 +337,88 @@ def test_a_wrong_term_fails_the_gate(hs, tmp_path, what):
     m_bad = ref.metric(*twin(mutant, b)[:2])
     print("%s wrong: metric %.3e (the twin as it is: %.3e, gate %.2e)" % (what, m_bad, m_good, mc.GATE_HOST))
     assert m_good <= mc.GATE_HOST < 1e3 * mc.GATE_HOST < m_bad
+
+
+# ---------------------------------------------------------------- the edges of the contract, on the twin first
+def twin_run(hs):
+    """run(call, status_in) of tests/chain_edge_checks.py on the twins of the solve and of the marginals, the W record of every last
+    state poisoned in between.  cov and cross are pre-filled with the sentinel: a poisoned row and an unwritten one differ."""
+    def run(call, status_in=None):
+        b = call.b
+        p = lambda x: None if x is None else x.ctypes.data
+        delta = np.full((b.S, 15), ck.SENTINEL)
+        status = np.full(call.C, 99, dtype=np.int32)
+        ws = np.full(max(call.S, 1) * hs.hsm_ws_doubles(), np.nan)
+        hess = np.concatenate([b.hess, np.full((1, 496), np.nan)])
+        assert hs.hsm_chain_solve(call.C, call.G, call.S, b.F, p(call.first), p(call.count), p(call.ffirst), p(hess),
+                                  p(b.prior if call.with_prior else None), p(call.lam), int(call.diagonal), p(delta), p(status), p(ws), 1) == 0
+        cov, cross = np.full((b.S, 120), ck.SENTINEL), np.full((b.S, 225), ck.SENTINEL)
+        st = status if status_in is None else np.ascontiguousarray(status_in, dtype=np.int32)
+        assert hs.hsm_chain_marginals(call.C, call.G, call.S, p(call.first), p(call.count), p(st), p(ws), p(cov), p(cross)) == 0
+        return ck.Result(delta, status, cov, cross, fill=ck.SENTINEL)
+    return run
+
+
+def test_twin_failed_chains_of_the_failure_plan_are_nan(hs):
+    ck.check_failure_plan(twin_run(hs))
+
+
+def test_twin_nan_in_g_leaves_the_covariances(hs):
+    ck.check_nan_plan(twin_run(hs))
+
+
+def test_twin_refused_chains_are_nan(hs):
+    ck.check_ffirst_boundaries(twin_run(hs))
+
+
+def test_twin_ffirst_null_with_an_explicit_first(hs):
+    ck.check_ffirst_null(twin_run(hs))
+
+
+def test_twin_clamps_of_first_count_G_and_S(hs):
+    ck.check_clamps(twin_run(hs))
+
+
+def test_twin_a_wavefront_of_empty_chains(hs):
+    ck.check_empty_wave(twin_run(hs), cc.GATE_BACKWARD_HOST, cc.GATE_FORWARD_HOST)
+
+
+def test_twin_a_zero_block_is_a_failed_pivot(hs):
+    identity, _ = ck.check_zero_pivot(twin_run(hs))
+    row = cc.zero_pivot_case(False)[0].rows(1).start
+    # (0 + 2 I)^-1: 1 / sqrt (two roundings), squared (one more, the error doubled): below 8 x 2^-53
+    assert np.abs(mc.unpack_cov(identity.cov[row]) - 0.5 * np.eye(15)).max() <= 8 * cc.EPS_HALF
+
+
+def test_twin_a_status_of_the_callers_poisons_exactly_its_chain(hs):
+    ck.check_status_overlay(twin_run(hs))
+
+
+def test_twin_long_chain_beside_short_ones(hs):
+    b, ref = mc.long_case()
+    r = twin_run(hs)(cc.Call(b, count=b.count))
+    m = ref.metric(r.cov, r.cross)
+    print("LONG %s: cond max %.1e, smallest correlation eigenvalue %.2e, twin metric %.3e (gate %.2e)"
+          % (cc.LONG, ref.cond.max(), ref.min_correlation_eigenvalue(), m, mc.GATE_HOST))
+    assert r.status.tolist() == [0] * 4 and m <= mc.GATE_HOST
+    own, _ = cc.Call(b, count=b.count).owned()
+    assert np.isfinite(np.linalg.cholesky(mc.unpack_cov(r.cov[own]))).all()
+    ck.unowned(r, cc.Call(b, count=b.count))
+
+
+@pytest.mark.parametrize("e", [300, -300])
+def test_twin_scaled_by_a_power_of_two(hs, e):
+    _, ref = mc.scaled_reference()
+    b = cc.scaled_batch(e)
+    r = twin_run(hs)(cc.Call(b, count=b.count))
+    m = ref.metric(r.cov * 2.0 ** e, r.cross * 2.0 ** e)
+    print("hess, prior x 2^%d: cond max %.1e, twin metric %.3e (gate %.2e)" % (e, ref.cond.max(), m, mc.GATE_HOST))
+    assert (r.status == 0).all() and m <= mc.GATE_HOST
+
+
+def test_twin_with_diagonal_damping_inverts_the_damped_matrix(hs):
+    b, lam, ref = mc.diagonal_case()
+    r = twin_run(hs)(cc.Call(b, count=b.count, lam=lam, diagonal=True))
+    m = ref.metric(r.cov, r.cross)
+    print("diagonal damping 0.25: cond max %.1e, twin metric %.3e (gate %.2e)" % (ref.cond.max(), m, mc.GATE_HOST))
+    assert (r.status == 0).all() and m <= mc.GATE_HOST
