@@ -1169,12 +1169,21 @@ extern "C" int cpi_factor_eval_packed_batch(cpi_ctx *ctx, int32_t model, const d
     return CPI_OK;
 }
 
+static bool bytes_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    const char *pa = (const char *)a, *pb = (const char *)b;
+    return pa && pb && na && nb && pa < pb + nb && pb < pa + na;
+}
 static int sqrt_information_impl(cpi_ctx *ctx, int64_t F, const double *P, double *R, bool packed) {
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
     if (F < 0) return fail(ctx, CPI_ERR_INVALID, "cpi_sqrt_information_batch: negative size");
     if (F == 0) return CPI_OK;
     if (!P || !R) return fail(ctx, CPI_ERR_INVALID, "cpi_sqrt_information_batch: NULL argument");
     if (!grid_ok(F)) return fail(ctx, CPI_ERR_INVALID, "cpi_sqrt_information_batch: F exceeds 2^31 - 1 factors per call");
+    // The kernel stages a wavefront's four factors before it stores any of them: R == P is safe, a shifted R is not.
+    const size_t bytes = (size_t)F * (packed ? 120 : 225) * sizeof(double);
+    if (R != P && bytes_overlap(R, bytes, P, bytes))
+        return packed ? refuse(ctx, "cpi_sqrt_information_packed_batch", "R_tri overlaps P_sym (R_tri == P_sym exactly is the in-place form)")
+                      : refuse(ctx, "cpi_sqrt_information_batch", "sqrt_info overlaps P (sqrt_info == P exactly is the in-place form)");
     DeviceGuard guard_;
     CPI_HIP(ctx, guard_.enter(ctx->device));
     launch::sqrt_info((long long)F, P, R, packed, ctx->stream);
@@ -1247,10 +1256,6 @@ extern "C" int cpi_predict_batch(cpi_ctx *ctx, int32_t model, const double grav[
 // ============================================================================================
 // Everything these entries can refuse is refused BEFORE the context is looked at (cpi_last_error(NULL) holds the text then), as
 // cpi_merge_batch does.
-static bool bytes_overlap(const void *a, size_t na, const void *b, size_t nb) {
-    const char *pa = (const char *)a, *pb = (const char *)b;
-    return pa && pb && na && nb && pa < pb + nb && pb < pa + na;
-}
 // "No output may overlap an input or another output": the first output, in order, that does is named in the refusal.  A NULL or
 // empty span overlaps nothing.
 struct Span {

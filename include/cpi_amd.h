@@ -764,12 +764,21 @@ int cpi_factor_eval_packed_batch(cpi_ctx *ctx, int32_t model, const double grav[
  * Gaussian::Information(cov.inverse()) -> Eigen::LLT::matrixU) once per factor, R^T R = P^-1.
  * Here R = B^-1 with P = B B^T, B upper triangular (the same matrix, obtained without forming P^-1).
  * P [F][225] column-major symmetric positive definite; sqrt_info [F][225] column-major upper triangular
- * (strict lower part written as zeros).  A non-positive pivot yields NaNs in that factor's R. */
+ * (strict lower part written as zeros, +0.0).
+ * A failing pivot: the factorisation runs from pivot 14 up to pivot 0, pivot k being P[k][k] less what rows k + 1 .. 14 explain of
+ * it.  A pivot that is zero, -0.0, negative, NaN or +inf fails, and then rows 0 .. k of that factor's R are NaN in every entry of
+ * the upper triangle, while rows k + 1 .. 14 hold what they hold for a P whose leading rows are healthy (for k = 0 that is ONE
+ * row of NaNs).  Row 0 multiplies every residual, so chi2 of that factor (cpi_factor_cost_*) and its Hessian block
+ * (cpi_factor_hessian_*: f and everything row 0 reaches) are NaN; no other factor of the call is touched.
+ * Both triangles of P are read: P must be mirrored bit for bit.  A caller who holds one triangle uses the packed form.
+ * Binary scaling is exact: P x 4^k gives R x 2^-k bit for bit as long as every value and intermediate stays in the normal range.
+ * sqrt_info == P exactly (in place) is allowed and gives the same bits; any other overlap of the two arrays is refused. */
 int cpi_sqrt_information_batch(cpi_ctx *ctx, int64_t F, const double *P, double *sqrt_info);
 /* The same factorisation on packed triangles (ABI 3): P_sym [F][120] in (cpi_outputs.P_sym of the covariance kernels), R_tri
  * [F][120] out -- 1 920 bytes per factor instead of 3 600, of which the dense form spends 840 on the mirrored half of P and
  * 840 on zeros it writes below R's diagonal.  Entry for entry the same values as cpi_sqrt_information_batch computes from the
- * dense form of the same P (same arithmetic, same order: bit-identical). */
+ * dense form of the same P (same arithmetic, same order: bit-identical) -- the failing-pivot rule, the exact binary scaling and
+ * the aliasing rule (R_tri == P_sym exactly allowed, any other overlap refused) included.  Only the given triangle is read. */
 int cpi_sqrt_information_packed_batch(cpi_ctx *ctx, int64_t F, const double *P_sym, double *R_tri);
 
 /* cpi_factor_eval_batch followed by GTSAM's NoiseModelFactor::linearize whitening

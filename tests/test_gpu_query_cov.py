@@ -17,7 +17,8 @@ import torch
 
 from cpi_amd import synth
 from tests.test_gpu_query import CASES, _case, _layout, _queries, _reference
-from tests.tol import TOL_COV, cov_rel_err, sqrt_info_longdouble
+from tests.sqrt_info_cases import e_row
+from tests.tol import REG_SQRT_INFO_ROW, TOL_COV, cov_rel_err, sqrt_info_longdouble
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -422,9 +423,11 @@ def test_sqrt_information_at_query_times(eng, model, avg):
     rel = float((np.abs(R - Rref).max(axis=(1, 2)) / np.abs(Rref).max(axis=(1, 2))).max())
     A = np.array(R, dtype=np.longdouble)
     ident = float(np.abs(np.asarray(A.transpose(0, 2, 1) @ A @ np.array(Pref, dtype=np.longdouble) - np.eye(15), dtype=np.float64)).max())
-    print("sqrt information at query times model %d avg %d (%d factors): |R - R_ref| / max |R_ref| %.3e, |R^T R P - I| %.3e"
-          % (model, avg, sel.sum(), rel, ident))
+    row = float(e_row(R, Rref).max())                                            # row by row: rel sees the largest rows of R only
+    print("sqrt information at query times model %d avg %d (%d factors): |R - R_ref| / max |R_ref| %.3e, row-wise %.3e, |R^T R P - I| %.3e"
+          % (model, avg, sel.sum(), rel, row, ident))
     assert ident <= 1e-6 and rel <= 100.0 * FLOOR_SQRT
+    assert row < REG_SQRT_INFO_ROW
 
 
 # ------------------------------------------------------------------------------------------------ 7. graph

@@ -46,6 +46,10 @@ def test_sqrt_information_and_whitened_sweep(eng, model):
     from tests.tol import REG_SQRT_INFO, sqrt_info_longdouble
     Rl = sqrt_info_longdouble(P)
     assert (np.abs(Rg - Rl) / np.abs(Rl).max(axis=(1, 2))[:, None, None]).max() < REG_SQRT_INFO
+    # (3c) and row by row: the rows of R differ by 1.2e3 in scale here, so (3b) sees rows 3-5 only (tests/test_gpu_sqrt_info_edges.py)
+    from tests.sqrt_info_cases import e_row
+    from tests.tol import REG_SQRT_INFO_ROW
+    assert e_row(Rg, Rl).max() < REG_SQRT_INFO_ROW
     # (4) whitened sweep = R @ unwhitened sweep
     e = plain["err"].cpu().numpy(); H1 = plain["H1"].cpu().numpy().reshape(F, 15, 15).transpose(0, 2, 1)
     H2 = plain["H2"].cpu().numpy().reshape(F, 15, 15).transpose(0, 2, 1)

@@ -26,6 +26,25 @@ REG_FORSTER_MEAN = 1e-12
 REG_FORSTER_JAC = 3e-13
 REG_FORSTER_COV = 1e-12
 REG_SQRT_INFO = 5e-14
+# The same factorisation judged ROW BY ROW (tests/sqrt_info_cases.py: e_row = max_k max_j |R - R_ref|[k][j] / max_j |R_ref[k][j]|, and
+# e_id = max |R P R^T - I| in long double) -- relative to max |R| of the factor, rows 0-2 of a realistic R (4e2 .. 8e2 against 5e5 in
+# rows 3-5) could be wrong by 6e-11 of themselves under REG_SQRT_INFO.  Floors on MI355X against the long-double reference
+# (profiles/sqrt_info_edges.md; the float64 restatement on the CPU beside them), gates = 100 x, never looser than 1e-12:
+#   realistic (the oracle's P, N = 1 and 50, edge cases in)        e_row 6.409e-15 (CPU 3.22e-15)   e_id 4.122e-15 (CPU 2.15e-15)
+#   scaled    (D C D, rows of R differing by up to 3.5e17)         e_row 9.524e-15 (CPU 4.19e-15)   e_id 3.401e-15 (CPU 5.57e-16)
+# (the `exact` family -- realistic factors x 4^+-200 and diagonal matrices -- is held to the realistic gate: 3.3e-15, 2.0e-15)
+REG_SQRT_INFO_EDGES = {"realistic": {"e_row": 6.409e-13, "e_id": 4.122e-13},
+                       "scaled": {"e_row": 9.524e-13, "e_id": 3.401e-13}}
+REG_SQRT_INFO_ROW = REG_SQRT_INFO_EDGES["realistic"]["e_row"]
+# `graded` (condition numbers 1 .. 1e10: forward error grows with the condition number for any float64 algorithm): the gate is per
+# case, a multiple of what float64 baselines achieve on that matrix against long double, each floored at 2^-52.  Two baselines, and
+# the smaller gate holds:
+#   max(restatement, LAPACK's chol(inv(P)))   worst device / baseline ratio on MI355X 1.98  -> multiple 10 x 1.98 = 20
+#   the restatement alone                     worst ratio 10.15 (e_id, cond 1e4)           -> 10 x 10.15, capped at 100
+# The second is there because chol(inv(P)) squares the condition number: from 1e8 up its own error is 1e-3 and more, and a multiple
+# of it would hold nothing.
+SQRT_INFO_GRADED_MULTIPLE = 20.0
+SQRT_INFO_GRADED_MULTIPLE_RESTATEMENT = 100.0
 
 
 def cov_rel_err(P, Pref):

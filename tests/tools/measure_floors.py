@@ -14,6 +14,7 @@ def main():
     import cpi_amd
     from cpi_amd import synth
     from oracle import oracle_py as op
+    from tests.sqrt_info_cases import e_row
     from tests.tol import cov_rel_err, sqrt_info_longdouble
     eng = cpi_amd.Engine(device=0)
     d = dict(np.load(os.path.join(ROOT, "tests", "golden", "pre_w48.npz")))
@@ -40,6 +41,8 @@ def main():
         scale = np.abs(Rl).max(axis=(1, 2))[:, None, None]
         print("model %d sqrt_info: HIP vs longdouble %.2e   LAPACK(f64) vs longdouble %.2e   (relative to max |R| per factor)" % (
             model, float((np.abs(Rg - Rl) / scale).max()), float((np.abs(Rn - Rl) / scale).max())))
+        print("model %d sqrt_info: HIP vs longdouble %.2e   LAPACK(f64) vs longdouble %.2e   (e_row: relative to max |R| per ROW)" % (
+            model, float(e_row(Rg, Rl).max()), float(e_row(Rn, Rl).max())))
 
 
 if __name__ == "__main__":
