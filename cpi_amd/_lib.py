@@ -201,6 +201,9 @@ def load():
     lib.cpi_chain_marginals_batch.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp]
     lib.cpi_chain_marginals_batch_host.argtypes = [vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.cpi_chain_marginals_batch.restype = lib.cpi_chain_marginals_batch_host.restype = C.c_int
+    lib.cpi_chain_marginalize_batch.argtypes = [vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp]
+    lib.cpi_chain_marginalize_batch_host.argtypes = [vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp]
+    lib.cpi_chain_marginalize_batch.restype = lib.cpi_chain_marginalize_batch_host.restype = C.c_int
     lib.cpi_preintegrate_stream_running.argtypes = lib.cpi_preintegrate_stream.argtypes
     lib.cpi_preintegrate_stream_running_host.argtypes = lib.cpi_preintegrate_stream_host.argtypes
     lib.cpi_preintegrate_streams_running.argtypes = lib.cpi_preintegrate_streams.argtypes

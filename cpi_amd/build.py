@@ -7,7 +7,7 @@
     python -m cpi_amd.build --test-hooks         # additionally libcpi_amd_test.so (-DCPI_TEST_HOOKS: the two entries of
                                                  # include/cpi_amd_test.h; the PRODUCT library exports nothing but include/cpi_amd.h)
 
-The library is sixteen translation units (cpi_amd/csrc/cpi_args.hpp) compiled IN PARALLEL into cpi_amd/csrc/_obj/*.o and
+The library is seventeen translation units (cpi_amd/csrc/cpi_args.hpp) compiled IN PARALLEL into cpi_amd/csrc/_obj/*.o and
 linked into one shared object; an object is rebuilt only when the sources it includes (or the flags) change, so touching
 one kernel family costs one TU.  hipcc cross-compiles gfx950 without a GPU present; the .so is git-ignored but ships to
 the GPU box.
@@ -38,7 +38,8 @@ UNIT_REPORTS = {"cpi_running_resume": os.path.join(CSRC, "resource_usage_running
                 "cpi_merge": os.path.join(CSRC, "resource_usage_merge.txt"),
                 "cpi_trial": os.path.join(CSRC, "resource_usage_trial.txt"),
                 "cpi_chain": os.path.join(CSRC, "resource_usage_chain.txt"),
-                "cpi_marginals": os.path.join(CSRC, "resource_usage_marginals.txt")}
+                "cpi_marginals": os.path.join(CSRC, "resource_usage_marginals.txt"),
+                "cpi_marginalize": os.path.join(CSRC, "resource_usage_marginalize.txt")}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Rpass-analysis=kernel-resource-usage"]
 COMMON = ["cpi_args.hpp", "../../include/cpi_amd.h", "exports.map"]   # exports.map: the link step's version script
@@ -61,6 +62,7 @@ UNITS = {
     "cpi_trial": DEVICE + ["cpi_trial.hip", "cpi_factor_kernels.hpp", "cpi_trial_kernels.hpp"],
     "cpi_chain": DEVICE + ["cpi_chain_util.hpp", "cpi_chain.hip", "cpi_factor_kernels.hpp", "cpi_chain_kernels.hpp"],
     "cpi_marginals": DEVICE + ["cpi_marginals.hip", "cpi_factor_kernels.hpp", "cpi_chain_util.hpp", "cpi_marginals_kernels.hpp"],
+    "cpi_marginalize": DEVICE + ["cpi_marginalize.hip", "cpi_factor_kernels.hpp", "cpi_chain_util.hpp", "cpi_marginalize_kernels.hpp"],
     "cpi_abi": COMMON + ["cpi_abi.hip", "../../include/cpi_amd_test.h"],   # the test header: -DCPI_TEST_HOOKS builds only
 }
 EXP_EXTRA = {"cpi_mean": ["cpi_mean_experimental.hpp"]}   # additional includes under -DCPI_EXPERIMENTS
@@ -244,7 +246,7 @@ def _build_locked(force, report, experiments, test_hooks):
     for variant, wanted in (("", True), ("exp", experiments), ("test", test_hooks)):
         if wanted and (force or stale(VARIANTS[variant][0], variant=variant)):
             todo.append(variant)
-    # every object of every wanted variant in ONE pool (the default build's sixteen units + the units a variant compiles with its own
+    # every object of every wanted variant in ONE pool (the default build's seventeen units + the units a variant compiles with its own
     # define): __graft_entry__.build() rebuilds three libraries in the time of the slowest translation unit
     jobs = {}
     for variant in todo:

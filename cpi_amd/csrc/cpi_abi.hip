@@ -1462,6 +1462,48 @@ extern "C" int cpi_chain_marginals_batch(cpi_ctx *ctx, int64_t C, int64_t G, int
     return CPI_OK;
 }
 
+// ============================================================================================
+// cpi_chain_marginalize_batch: the oldest states of chains eliminated into a prior (cpi_marginalize_kernel, cpi_marginalize.hip)
+// ============================================================================================
+// what both forms refuse alike, before the context is looked at
+static int marginalize_check(cpi_ctx *ctx, const char *who, int64_t C, int64_t G, int64_t S, int64_t F, const int64_t *first, const int32_t *count,
+                             const int64_t *ffirst, const double *hess, const double *prior, const int32_t *drop, double *out, int32_t *status) {
+    if (C < 0 || S < 0 || F < 0) return refuse(ctx, who, "negative size");
+    if (G < 1) return refuse(ctx, who, "G (the longest chain in states) must be >= 1");
+    if (G > 0x7fffffffLL) return refuse(ctx, who, "G exceeds 2^31 - 1 states per chain");
+    if (C == 0) return CPI_OK;
+    if (!hess && G > 1) return refuse(ctx, who, "hess is NULL (only chains of one state, G == 1, need none)");
+    if (!out) return refuse(ctx, who, "out is NULL");
+    const size_t d = sizeof(double);
+    const Span outs[2] = { { out, (size_t)C * 136 * d, "out" }, { status, (size_t)C * sizeof(int32_t), "status" } };
+    const Span ins[6] = { { first, (size_t)C * sizeof(int64_t), "" }, { count, (size_t)C * sizeof(int32_t), "" }, { ffirst, (size_t)C * sizeof(int64_t), "" },
+                          { hess, (size_t)F * 496 * d, "" }, { prior, (size_t)S * 136 * d, "" }, { drop, (size_t)C * sizeof(int32_t), "" } };
+    return refuse_overlaps(ctx, who, outs, 2, ins, 6);
+}
+
+extern "C" int cpi_chain_marginalize_batch(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_t F,
+                                           const int64_t *first, const int32_t *count, const int64_t *ffirst,
+                                           const double *hess, const double *prior,
+                                           int32_t M, const int32_t *drop,
+                                           double *out, int32_t *status) {
+    static const char who[] = "cpi_chain_marginalize_batch";
+    CPI_TRY(marginalize_check(ctx, who, C, G, S, F, first, count, ffirst, hess, prior, drop, out, status));
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (C == 0) return CPI_OK;
+    if (!grid_ok((C + 3) / 4)) return refuse(ctx, who, "C exceeds the 32-bit grid (4 chains per workgroup)");
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    MarginalizeArgs a;
+    memset(&a, 0, sizeof a);
+    a.C = C; a.G = (int)G; a.S = S; a.F = F;
+    a.first = (const long long *)first; a.count = count; a.ffirst = (const long long *)ffirst;
+    a.hess = hess; a.prior = prior; a.M = M; a.drop = drop;
+    a.out = out; a.status = status;
+    launch::chain_marginalize(a, ctx->stream);
+    CPI_HIP(ctx, hipGetLastError());
+    return CPI_OK;
+}
+
 extern "C" size_t cpi_outputs_slab_doubles(const cpi_outputs *mask, int64_t Wb) {
     if (!mask || Wb <= 0) return 0;
     size_t n = 0;
@@ -2032,13 +2074,14 @@ struct ChainsDev {
     double *workspace;
 };
 int stage_chains(Staging &st, int64_t C, int64_t G, int64_t S, int64_t F, const int64_t *first, const int32_t *count, const int64_t *ffirst,
-                 const double *hess, const double *prior, ChainsDev *d) {
+                 const double *hess, const double *prior, ChainsDev *d, bool workspace = true) {
     CPI_TRY(st.upload(first, (size_t)C, &d->first));
     CPI_TRY(st.upload(count, (size_t)C, &d->count));
     CPI_TRY(st.upload(ffirst, (size_t)C, &d->ffirst));
     CPI_TRY(st.upload(F > 0 ? hess : nullptr, (size_t)F * 496, &d->hess));
     CPI_TRY(st.upload(S > 0 ? prior : nullptr, (size_t)S * 136, &d->prior));
-    CPI_TRY(st.alloc(cpi_chain_solve_workspace_doubles(S), &d->workspace));
+    d->workspace = nullptr;
+    if (workspace) CPI_TRY(st.alloc(cpi_chain_solve_workspace_doubles(S), &d->workspace));   // cpi_chain_marginalize_batch has none
     if (!d->hess && G > 1) {   // F == 0: no chain has a factor (the ranges are validated), and the device form wants a pointer it never reads
         double *none;
         CPI_TRY(st.alloc((size_t)1, &none));
@@ -2950,6 +2993,42 @@ extern "C" int cpi_chain_marginals_batch_host(cpi_ctx *ctx, int64_t C, int64_t G
     CPI_TRY(cpi_chain_marginals_batch(ctx, C, G, S, in.first, in.count, ds, in.workspace, const_cast<double *>(dc0), const_cast<double *>(dx0)));
     CPI_TRY(st.download(cov, dc0, (size_t)S * 120));
     if (cross) CPI_TRY(st.download(cross, dx0, (size_t)S * 225));
+    if (status) CPI_TRY(st.download(status, (const int32_t *)ds, (size_t)C));
+    return st.finish();
+}
+
+// cpi_chain_marginalize_batch from host memory: every array a host array (drop too), staged whole, synchronous.  The ranges are
+// validated as in cpi_chain_solve_batch_host, and every chain that has states must eliminate fewer than it has.
+extern "C" int cpi_chain_marginalize_batch_host(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_t F,
+                                                const int64_t *first, const int32_t *count, const int64_t *ffirst,
+                                                const double *hess, const double *prior,
+                                                int32_t M, const int32_t *drop,
+                                                double *out, int32_t *status) {
+    static const char who[] = "cpi_chain_marginalize_batch_host";
+    CPI_TRY(marginalize_check(ctx, who, C, G, S, F, first, count, ffirst, hess, prior, drop, out, status));
+    CPI_TRY(chain_ranges_check(ctx, who, C, G, S, F, first, count, ffirst));
+    for (int64_t c = 0; c < C; c++) {
+        int64_t n = count ? count[c] : G;
+        n = n < 0 ? 0 : (n > G ? G : n);
+        const int64_t m = drop ? drop[c] : M;
+        if (n > 0 && (m < 0 || m >= n))
+            return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": drop of chain " + std::to_string(c) + " leaves [0, count)");
+    }
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (C == 0) return CPI_OK;
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    Staging st(ctx);
+    ChainsDev in;
+    const int32_t *dm;
+    double *dout;
+    int32_t *ds = nullptr;
+    CPI_TRY(stage_chains(st, C, G, S, F, first, count, ffirst, hess, prior, &in, false));
+    CPI_TRY(st.upload(drop, (size_t)C, &dm));
+    CPI_TRY(st.alloc((size_t)C * 136, &dout));
+    if (status) CPI_TRY(st.alloc((size_t)C, &ds));
+    CPI_TRY(cpi_chain_marginalize_batch(ctx, C, G, S, F, in.first, in.count, in.ffirst, in.hess, in.prior, M, dm, dout, ds));
+    CPI_TRY(st.download(out, (const double *)dout, (size_t)C * 136));
     if (status) CPI_TRY(st.download(status, (const int32_t *)ds, (size_t)C));
     return st.finish();
 }

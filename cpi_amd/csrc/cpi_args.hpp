@@ -1,6 +1,6 @@
 // cpi_args.hpp -- kernel argument blocks and the launcher interface between the translation units of libcpi_amd.so.
 //
-// The library is sixteen translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
+// The library is seventeen translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
 //   cpi_mean.hip    cpi_mean_kernel / cpi_mean_tiled_kernel / cpi_tile_*_kernel       (cpi_mean_kernels.hpp)
 //   cpi_running.hip cpi_mean_running_kernel / cpi_mean_stream_running_kernel: a row after every interval, from plain knots /
 //                   from windows cut out of IMU stream(s) in place         (cpi_running_kernels.hpp, cpi_running_body.inc)
@@ -31,6 +31,9 @@
 //   cpi_marginals.hip  cpi_marginals_kernel: the state covariances of solved chains -- the diagonal and first off-diagonal blocks of
 //                   the inverse, one backward recursion over the factor the solve left in the workspace
 //                                   (cpi_marginals_kernels.hpp over cpi_factor_kernels.hpp's DPP multiply-adds; cpi_chain_util.hpp)
+//   cpi_marginalize.hip  cpi_marginalize_kernel: the leading states of every chain eliminated into a prior on the first
+//                   state that stays -- the forward half of the solve, undamped, no workspace
+//                                 (cpi_marginalize_kernels.hpp over cpi_factor_kernels.hpp's DPP multiply-adds; cpi_chain_util.hpp)
 //   cpi_factor.hip  evaluateError sweeps, square-root information, Hessian blocks, state prediction
 //                                                                                      (cpi_factor_kernels.hpp)
 //   cpi_abi.hip     the C-ABI of include/cpi_amd.h: argument checks, launch heuristics, device sets (RCCL), the
@@ -234,6 +237,23 @@ struct MarginalsArgs {
     double *cross;            // [S][225] or NULL
 };
 
+// cpi_chain_marginalize_batch: the chains of cpi_chain_solve_batch (the same clamps), the leading drop[c] states of chain c eliminated
+// into one prior row per chain.  drop lives in device memory; a value outside [0, n_c) refuses the chain where it is read.
+struct MarginalizeArgs {
+    long long C;             // chains
+    int G;                   // the longest chain in states, >= 1
+    long long S, F;          // rows of prior; rows of hess
+    const long long *first;  // [C] or NULL: chain c starts at state c * G
+    const int *count;        // [C] or NULL: every chain has G states
+    const long long *ffirst; // [C] or NULL: first[c] - c
+    const double *hess;      // [F][496]
+    const double *prior;     // [S][136] or NULL
+    int M;                   // states to eliminate where drop is NULL
+    const int *drop;         // [C] or NULL
+    double *out;             // [C][136]
+    int *status;             // [C] or NULL
+};
+
 struct PredictArgs {
     long long F;
     double grav[3];
@@ -318,6 +338,8 @@ size_t chain_workspace_doubles(long long S);
 void chain_solve(const ChainArgs &a, hipStream_t st);
 // ---- cpi_marginals.hip (cpi_chain_marginals_batch)
 void chain_marginals(const MarginalsArgs &a, hipStream_t st);
+// ---- cpi_marginalize.hip (cpi_chain_marginalize_batch)
+void chain_marginalize(const MarginalizeArgs &a, hipStream_t st);
 // ---- cpi_factor.hip
 void factor(int model, bool whiten, int lpf, const FactorArgs &a, hipStream_t st);            // lpf 16 | 8 | 4
 void factor_packed(int model, int lpf, const FactorArgs &a, double *packed, hipStream_t st);  // lpf 2 | 3 | 4 | 6 | 8

@@ -970,6 +970,23 @@ inline std::vector<double> chain_marginals(const Context &ctx, int64_t C, int64_
     return cov;
 }
 
+// What a fixed-lag window carries on when it slides (cpi_chain_marginalize_batch_host: the device kernel's bits): the leading drop
+// states of every chain eliminated into a prior on the first state that stays.  C chains of G states back to back, hess and prior as
+// chain_solve takes them, 0 <= drop < G.  Returns [C * 136]: per chain the packed [Lam eta; eta^T .] of state drop -- the row to put
+// there in the next window's prior; status, when given, receives the per-chain codes of include/cpi_amd.h (a failed chain's row is NaN).
+inline std::vector<double> chain_marginalize(const Context &ctx, int64_t C, int64_t G, const std::vector<double> &hess,
+                                             const std::vector<double> &prior = {}, int32_t drop = 1,
+                                             std::vector<int32_t> *status = nullptr) {
+    if (C < 0 || G < 1 || hess.size() != (size_t)(C * (G - 1)) * 496 || (!prior.empty() && prior.size() != (size_t)(C * G) * 136))
+        throw std::invalid_argument("cpi_host::chain_marginalize: hess [C * (G - 1) * 496], prior empty or [C * G * 136]");
+    std::vector<double> out((size_t)C * 136);
+    if (status) status->assign((size_t)C, 0);
+    static const double none = 0.0;      // G == 1: no factor rows; G > 1 with C == 0: never read
+    ctx.check(cpi_chain_marginalize_batch_host(ctx.get(), C, G, C * G, C * (G - 1), nullptr, nullptr, nullptr, hess.empty() ? &none : hess.data(),
+                                               prior.empty() ? nullptr : prior.data(), drop, nullptr, out.data(), status ? status->data() : nullptr));
+    return out;
+}
+
 // ---- the caller's loop for MANY windows at once --------------------------------------------------------------------
 // What GraphSolver keeps between two states is a deque of IMU readings (GraphSolver.h: imu_times / imu_linaccs /
 // imu_angvel, filled by addmeasurement_imu); createimufactor_cpi_v1 / _v2 (GraphSolver_IMU.cpp:34-134) walk it up to the

@@ -1818,6 +1818,46 @@ CPI_HD void marginals_chain(int n, const double *ws, double *cov, double *cross)
             }
     }
 }
+
+// cpi_chain_marginalize_batch: the leading m states of a chain of n eliminated into the prior row of state m -- the forward half of
+// solve_chain stopped at state m, UNDAMPED and without the workspace.  States s = 0 .. m - 1, per state: A = (N + H_s[0:15, 0:15 | 30])
+// + Pr_s, the pivots, W = L^-1 U, then N = H_s[15:30, 15:30 | 30] - W^T [W y] (factor_block, solve_w, schur: the terms and the order
+// of solve_chain).  What state m receives is the sum solve_chain would form there without its own factor: out = (N + 0.0) + Pr_m --
+// Lam = Pr_m + H_{m-1}[15:30, 15:30] - A_mE A_EE^-1 A_Em and eta likewise, the Schur complement of the eliminated states over the
+// factors < m and the priors <= m.  H_m and everything later is not read.  hess = the chain's factor rows, prior = its rows or NULL,
+// 0 <= m < n (the caller checks it); out [136] in the packing of a prior row, entry 135 written as 0.0 (that of Pr_m is not read).
+// One triangle of N is stored: schur's products commute, so N is symmetric to the bit.  Returns 0, or s + 1 for the first ELIMINATED
+// state whose block was not positive definite (out is all NaN then).  The kernel (cpi_marginalize_kernels.hpp) is the lane-mapped form.
+CPI_HD int marginalize_chain(int n, int m, const double *hess, const double *prior, double *out) {
+    double N[15][16];
+    int status = 0;
+    (void)n;
+    for (int i = 0; i < 15; i++)
+        for (int j = 0; j < 16; j++) N[i][j] = 0.0;
+    for (int s = 0; s < m; s++) {
+        const double *H = hess + (long long)s * HESS_D, *Pr = prior ? prior + (long long)s * PRIOR_D : nullptr;
+        double A[15][16], U[15][15];
+        for (int j = 0; j < 16; j++) {
+            const int cj = (j < 15) ? j : 30;
+            for (int i = 0; i < 15; i++) A[i][j] = (N[i][j] + sym_at(H, i, cj)) + (Pr ? sym_at(Pr, i, j) : 0.0);
+        }
+        const bool pd = factor_block(A);
+        if (!pd && status == 0) status = s + 1;
+        for (int i = 0; i < 15; i++) {
+            for (int c = 0; c < 15; c++) U[i][c] = H[tri(15 + c) + i];
+            for (int j = 0; j < 16; j++) N[i][j] = sym_at(H, 15 + i, (j < 15) ? 15 + j : 30);
+        }
+        solve_w(A, U);
+        schur(U, A, N);
+    }
+    const double *Pr = prior ? prior + (long long)m * PRIOR_D : nullptr;
+    for (int j = 0; j < 16; j++)
+        for (int i = 0; i < 15 && i <= j; i++) out[tri(j) + i] = (N[i][j] + 0.0) + (Pr ? Pr[tri(j) + i] : 0.0);
+    out[PRIOR_D - 1] = 0.0;
+    if (status)
+        for (int i = 0; i < PRIOR_D; i++) out[i] = NAN;
+    return status;
+}
 }  // namespace chn
 
 }  // namespace cpi

@@ -1422,6 +1422,61 @@ class Engine:
                                                             _ptr(prior), _ptr(out), _ptr(cross), _ptr(status)))
         return out if cross is None else (out, cross)
 
+    # ------------------------------------------------------------------ the window slides: the oldest states become a prior
+    def _marginalize_args(self, hess, C, G, first, count, ffirst, prior, drop, out, status, cuda):
+        where = "CUDA" if cuda else "CPU"
+        for name, t, dt in (("first", first, torch.int64), ("count", count, torch.int32), ("ffirst", ffirst, torch.int64),
+                            ("status", status, torch.int32)):
+            assert t is None or (t.dtype == dt and t.is_contiguous() and t.is_cuda == cuda and t.dim() == 1), \
+                "%s: a contiguous %s %s tensor [C]" % (name, str(dt).split(".")[1], where)
+        if C is None:
+            C = next((t.shape[0] for t in (first, count, ffirst) if t is not None), None)
+        assert C is not None, "C: the number of chains (or first / count / ffirst, which have it)"
+        assert all(t is None or t.shape[0] == C for t in (first, count, ffirst, status)), "first / count / ffirst / status: [C]"
+        assert G is not None and G >= 1, "G: the longest chain in states, >= 1"
+        if hess is not None:
+            self._trial_tensor(hess, 496, cuda, "hess")
+        C_, G_, F = int(C), int(G), (hess.shape[0] if hess is not None else 0)
+        if prior is not None:
+            self._trial_tensor(prior, 136, cuda, "prior")
+            S = prior.shape[0]
+        else:
+            S = C_ * G_ if first is None else 1 << 40        # without a prior no array has S rows: S only clips the chains
+        M = 0
+        if torch.is_tensor(drop):
+            assert drop.dtype == torch.int32 and drop.is_contiguous() and drop.is_cuda == cuda and drop.shape == (C_,), \
+                "drop: an int, or a contiguous int32 %s tensor [C]" % where
+        else:
+            M, drop = int(drop), None
+        if out is None:
+            out = torch.empty((C_, 136), dtype=torch.float64, device=self.device if cuda else "cpu")
+        self._trial_tensor(out, 136, cuda, "out", C_)
+        return C_, G_, S, F, M, drop, out
+
+    def chain_marginalize(self, hess, C=None, G=None, first=None, count=None, ffirst=None, prior=None, drop=1, out=None, status=None):
+        """cpi_chain_marginalize_batch: the leading drop states of every chain eliminated into a prior on the first state that stays
+        -- out [C,136], row c the packed [Lam eta; eta^T .] of state drop_c of the reduced chain: the Schur complement of the
+        eliminated states over the factors and priors that touch only them (include/cpi_amd.h; undamped, no workspace).  hess, C, G,
+        first, count, ffirst, prior: those of chain_solve.  drop: an int for every chain, or an int32 [C] CUDA tensor; 0 <= drop <
+        the chain's states.  status: an int32 [C] tensor to fill (0; s + 1: the block of eliminated state s was not positive
+        definite; -1: the factor rows leave hess or drop is outside the chain); such a chain's row is NaN.  Put row c at state
+        first[c] + drop_c of prior and solve first + drop, count - drop, ffirst + drop on the same arrays: the full chain's delta for
+        the states that stay.  S comes from prior, else C * G.  Asynchronous."""
+        C_, G_, S, F, M, drop, out = self._marginalize_args(hess, C, G, first, count, ffirst, prior, drop, out, status, True)
+        self._sync_stream()
+        self._check(self.lib.cpi_chain_marginalize_batch(self.ctx, C_, G_, S, F, _ptr(first), _ptr(count), _ptr(ffirst), _ptr(hess), _ptr(prior),
+                                                         M, _ptr(drop), _ptr(out), _ptr(status)))
+        return out
+
+    def chain_marginalize_host(self, hess, C=None, G=None, first=None, count=None, ffirst=None, prior=None, drop=1, out=None, status=None):
+        """chain_marginalize on CPU tensors (cpi_chain_marginalize_batch_host): every chain's state range, factor range and drop is
+        validated (CpiError names the chain), synchronous, the device form's bits."""
+        C_, G_, S, F, M, drop, out = self._marginalize_args(hess, C, G, first, count, ffirst, prior, drop, out, status, False)
+        self._sync_stream()
+        self._check(self.lib.cpi_chain_marginalize_batch_host(self.ctx, C_, G_, S, F, _ptr(first), _ptr(count), _ptr(ffirst), _ptr(hess),
+                                                              _ptr(prior), M, _ptr(drop), _ptr(out), _ptr(status)))
+        return out
+
 
 def unpack_factor(packed, meas):
     """Dense (err [F,15], H1 [F,225], H2 [F,225], column-major) from the packed evaluation and the measurement it was
@@ -1482,6 +1537,11 @@ def chain_solve(*args, **kw):
 def chain_marginals(*args, **kw):
     """Engine.chain_marginals on the default engine."""
     return default_engine().chain_marginals(*args, **kw)
+
+
+def chain_marginalize(*args, **kw):
+    """Engine.chain_marginalize on the default engine."""
+    return default_engine().chain_marginalize(*args, **kw)
 
 
 # ---------------------------------------------------------------------- reference-shaped classes

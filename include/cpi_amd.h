@@ -76,7 +76,9 @@ extern "C" {
                                solve of chains of IMU factors on the rows of cpi_factor_hessian_*: the step of the loop above);
                                cpi_chain_marginals_batch, cpi_chain_marginals_batch_host (the state covariances of solved
                                chains: the diagonal and first off-diagonal blocks of the inverse, from the factor the solve
-                               left in its workspace) */
+                               left in its workspace); cpi_chain_marginalize_batch, cpi_chain_marginalize_batch_host (the
+                               oldest states of a chain eliminated into a prior on the first state that stays: the step of a
+                               fixed-lag smoother between two optimisations) */
 
 enum { CPI_OK = 0, CPI_ERR_INVALID = 1, CPI_ERR_HIP = 2, CPI_ERR_NO_DEVICE = 3, CPI_ERR_RCCL = 4 };
 enum {
@@ -947,6 +949,46 @@ int cpi_chain_marginals_batch(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S,
                               const int64_t *first, const int32_t *count, const int32_t *status,
                               const double *workspace, double *cov, double *cross);
 
+/* What a fixed-lag smoother does between two optimisations: the window slides, the oldest m states of a chain leave, and what they
+ * knew becomes a prior on the first state that stays.  Replaces: GTSAM's marginalisation of the leading variables of a chain (the
+ * elimination of those variables and the LinearContainerFactor that carries the resulting marginal factor on; GTSAM is absent from
+ * the reference tree: PARITY UNPINNED, checked against a long-double Schur complement of the definition below).  Out of scope:
+ * eliminating states from a chain's tail or interior, damping (marginalisation is of the UNDAMPED system: there is no lambda),
+ * the constant term of the marginal cost.
+ * With the chains, H_k, Pr_s, D_s, U_s and g_s of cpi_chain_solve_batch (lambda = 0), E the eliminated states 0 .. m - 1, A_EE and g_E
+ * their part of the system built from the factors 0 .. m - 1 and the priors 0 .. m - 1 alone, and A_Em = U_{m-1} the one block that
+ * couples them to state m:
+ *     Lam = Pr_m[0:15, 0:15] + H_{m-1}[15:30, 15:30] - A_mE A_EE^-1 A_Em
+ *     eta = Pr_m[0:15, 15]   + H_{m-1}[15:30, 30]    - A_mE A_EE^-1 g_E                  (Pr_* absent when prior is NULL)
+ * the Schur complement of the eliminated states onto state m.  H_m and everything later do NOT enter: the factors the next window
+ * keeps are counted once.  (The marginal covariance of cpi_chain_marginals_batch is the right prior only for a window that starts
+ * at the LAST state and shares no factor with this one.)  The arithmetic is the forward half of the solve, stopped at state m.
+ *   C G S F first count ffirst hess prior: those of cpi_chain_solve_batch, with the same clamps and the same rule for ffirst
+ *   M, drop   drop NULL or [C] DEVICE int32: m_c, the number of leading states of chain c to eliminate; NULL: M for every chain.
+ *          0 <= m_c < n_c is required per chain, n_c the chain's clamped number of states.
+ *   out    [C][136]: row c is the prior row of state m_c of the reduced chain in the packing of prior ([Lam eta; eta^T .], (i, d) at
+ *          i + d (d + 1) / 2).  Entry 135 is written as 0.0; entry 135 of the input priors is never read.  One triangle is written:
+ *          Lam is symmetric by construction.  m = 0 gives Pr_0 with entry 135 zeroed (zeros without a prior): the values pass
+ *          through as they are.
+ *   status NULL or [C]: 0 success; s + 1: the block of the ELIMINATED state s was not positive definite (a block at a state >= m
+ *          is not looked at); -1: the chain's factor rows leave [0, F) (the solve's rule) or m_c is outside [0, n_c) -- a chain
+ *          without states is refused this way.  A chain whose status is not 0 gets a NaN row; no other chain is affected.
+ * WHAT IT GUARANTEES: replace row first_c + m_c of prior by out[c] and solve the chain first + m, count - m, ffirst + m on the SAME
+ * hess and prior arrays (the ragged arguments of cpi_chain_solve_batch): with lambda = NULL the delta rows are those the full
+ * chain's solve gives for the kept states, and cpi_chain_marginals_batch of the reduced chain gives the full chain's cov and cross
+ * rows of the kept states, to rounding.  The result is a LINEAR prior at the states hess was linearised at.
+ * Only the rows of hess at factors < m_c and of prior at states <= m_c are read.  A chain's bits depend on its own data only, not
+ * on C or on its position.  The library allocates nothing and there is no workspace; one kernel on the context's stream, no host
+ * synchronisation: a capture is a chain without parallel branches.  16 lanes work on a chain, 4 chains share a wavefront, and
+ * there is no parallelism ALONG a chain (profiles/chain_marginalize.md).
+ * Refused before the context is looked at (CPI_ERR_INVALID): negative sizes, G < 1 or G > 2^31 - 1, NULL hess when G > 1, NULL out,
+ * out or status overlapping an input or each other ("overlaps" in cpi_last_error).  C == 0 is a no-op. */
+int cpi_chain_marginalize_batch(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_t F,
+                                const int64_t *first, const int32_t *count, const int64_t *ffirst,
+                                const double *hess, const double *prior,
+                                int32_t M, const int32_t *drop,
+                                double *out, int32_t *status);
+
 /* ---- Device sets: the 8-GPU path of a single-process host (nothing in the reference, which is a
  * single-threaded CPU program).  Windows (and factors) are independent units: rank r of n owns the contiguous block
  * [lo, hi) = cpi_shard_bounds(W, r, n) (block size ceil(W / n); trailing ranks may be short or empty), runs the ordinary
@@ -1168,6 +1210,16 @@ int cpi_chain_marginals_batch_host(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S
                                    const int64_t *first, const int32_t *count, const int64_t *ffirst,
                                    const double *hess, const double *prior,
                                    double *cov, double *cross, int32_t *status);
+
+/* cpi_chain_marginalize_batch from host memory: every pointer a host pointer (drop too), synchronous; the device form's bits.
+ * Every chain's state range and factor range is validated first as in cpi_chain_solve_batch_host, and so is its m_c: a chain with
+ * states whose m_c is outside [0, n_c) is CPI_ERR_INVALID, the text names the chain.  (A chain without states is not an error
+ * here: it gets status -1 and a NaN row, as in the device form.) */
+int cpi_chain_marginalize_batch_host(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_t F,
+                                     const int64_t *first, const int32_t *count, const int64_t *ffirst,
+                                     const double *hess, const double *prior,
+                                     int32_t M, const int32_t *drop,
+                                     double *out, int32_t *status);
 
 #ifdef __cplusplus
 }
