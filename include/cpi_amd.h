@@ -973,6 +973,12 @@ int cpi_chain_marginals_batch(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S,
  *   status NULL or [C]: 0 success; s + 1: the block of the ELIMINATED state s was not positive definite (a block at a state >= m
  *          is not looked at); -1: the chain's factor rows leave [0, F) (the solve's rule) or m_c is outside [0, n_c) -- a chain
  *          without states is refused this way.  A chain whose status is not 0 gets a NaN row; no other chain is affected.
+ *          Status 0 does not promise a finite row: only the pivots of the eliminated blocks are looked at.  A NaN in Pr_m, in the
+ *          trailing block, U or g of factor m - 1, or in a right-hand side (g, eta) further back reaches the entries of the row it
+ *          touches and leaves the status as it is; the solve of the reduced chain reports it (a status, or a NaN delta where only
+ *          eta is hit).  An exactly zero block of either sign (0.0 or -0.0) is a failed pivot (0 is not > 0): no prior and a zero
+ *          factor row give status 1.  Scaling hess and prior by 4^k scales out by 4^k exactly (bit for bit) as long as every
+ *          intermediate stays inside the normal range: every term is homogeneous of degree one in them.
  * WHAT IT GUARANTEES: replace row first_c + m_c of prior by out[c] and solve the chain first + m, count - m, ffirst + m on the SAME
  * hess and prior arrays (the ragged arguments of cpi_chain_solve_batch): with lambda = NULL the delta rows are those the full
  * chain's solve gives for the kept states, and cpi_chain_marginals_batch of the reduced chain gives the full chain's cov and cross

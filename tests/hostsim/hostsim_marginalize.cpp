@@ -4,7 +4,8 @@
 //
 // Compile with -ffp-contract=off like its siblings: every fused multiply-add of the restatement is written as fma().  With
 // -DHOSTSIM_MARGINALIZE_MAIN the file is a stand-alone program (seeded chains; the carried prior reproduces the Schur complement
-// computed densely in long double), the one to build with -fsanitize=address,undefined.
+// computed densely in long double; a refused chain with status == NULL; failures with an m of its own per chain), the one to build
+// with -fsanitize=address,undefined.
 #include "../../cpi_amd/csrc/cpi_math.hpp"
 #include <stdint.h>
 #include <vector>
@@ -111,6 +112,54 @@ int main() {
     bool same = out[135] == 0.0 && out[136 + 135] == 0.0;     // chain 1, m = 0: the prior row as it is
     for (int i = 0; i < 135; i++) same = same && out[136 + i] == prior[n * 136 + i];
     printf("status %d %d %d, |out - Schur complement| %.3g, m = 0 passes the prior through: %d\n", status[0], status[1], status[2], worst, (int)same);
-    return (status[0] == 0 && status[1] == 0 && status[2] == 0 && worst < 1e-9 && same) ? 0 : 1;
+    bool ok = status[0] == 0 && status[1] == 0 && status[2] == 0 && worst < 1e-9 && same;
+
+    // one refused chain (m = n on the LAST chain: what a lax rule would read lies past both allocations) and status == NULL: the row
+    // of the refused chain is NaN, the others are the rows of the call above
+    std::vector<double> out2(C * 136, -7.0);
+    std::vector<int> drop2 = {m, 0, n};
+    if (hsz_chain_marginalize(C, n, S, F, nullptr, nullptr, nullptr, hess.data(), prior.data(), 0, drop2.data(), out2.data(), nullptr)) return 2;
+    bool refused = true, kept = true;
+    for (int i = 0; i < 136; i++) {
+        refused = refused && out2[2 * 136 + i] != out2[2 * 136 + i];
+        kept = kept && out2[i] == out[i] && out2[136 + i] == out[136 + i];
+    }
+    printf("m = n with status == NULL: the row is NaN: %d, the other rows are kept: %d\n", (int)refused, (int)kept);
+    ok = ok && refused && kept;
+
+    // failures with an m of its own per chain: 8 chains of 4 states (arrays of their own, the factor rows above repeated), pivot k of
+    // the block of state s of chain c made -1e12; status = s + 1 if s < m_c, else 0, a failed row is NaN and every other row is finite
+    {
+        const int C8 = 8, n4 = 4;
+        const int fail_s[C8] = {0, 0, 3, 2, -1, 3, 1, -1}, fail_k[C8] = {0, 14, 14, 7, 0, 0, 14, 0};
+        const int drops[2][C8] = {{1, 3, 0, 2, 3, 1, 2, 0}, {3, 1, 2, 3, 0, 3, 1, 2}};
+        std::vector<double> h8(C8 * (n4 - 1) * 496), p8(C8 * n4 * 136, 0.0), o8(C8 * 136);
+        for (size_t i = 0; i < h8.size(); i++) h8[i] = hess[i % hess.size()];
+        for (int s = 0; s < C8 * n4; s++)
+            for (int i = 0; i < 15; i++) { p8[s * 136 + chn::tri(i) + i] = 0.1; p8[s * 136 + chn::tri(15) + i] = 0.01 * rnd(); }
+        for (int c = 0; c < C8; c++)
+            if (fail_s[c] >= 0) p8[(c * n4 + fail_s[c]) * 136 + chn::tri(fail_k[c]) + fail_k[c]] = -1e12;
+        for (int r = 0; r < 2; r++) {
+            std::vector<int> st8(C8, 99), d8(drops[r], drops[r] + C8);
+            for (size_t i = 0; i < o8.size(); i++) o8[i] = -7.0;
+            if (hsz_chain_marginalize(C8, n4, C8 * n4, C8 * (n4 - 1), nullptr, nullptr, nullptr, h8.data(), p8.data(), 0, d8.data(), o8.data(), st8.data())) return 2;
+            bool law = true;
+            printf("drop");
+            for (int c = 0; c < C8; c++) printf(" %d", d8[c]);
+            printf(": status");
+            for (int c = 0; c < C8; c++) {
+                const int want = (fail_s[c] >= 0 && fail_s[c] < d8[c]) ? fail_s[c] + 1 : 0;
+                printf(" %d", st8[c]);
+                law = law && st8[c] == want;
+                for (int i = 0; i < 136; i++) {
+                    const double v = o8[c * 136 + i];
+                    law = law && (want ? v != v : (v == v && v != -7.0));
+                }
+            }
+            printf(", the rule holds: %d\n", (int)law);
+            ok = ok && law;
+        }
+    }
+    return ok ? 0 : 1;
 }
 #endif

@@ -29,6 +29,10 @@ measured against the longdouble reference (profiles/chain_marginalize.md):
 ((c): dense_9x17 with the prior on the first state (host) and the ragged chains with it (device); (d): the prior on every state.)
 The largest cond_2(A_EE) of these inputs is 3.8e7.  The equivalence (e) measures 0.052 (host) and 0.059 (device) of cond_2(A) 2^-53.
 A wrong term shows as a metric of 1e13 and more (the mutation checks of tests/test_marginalize_cpu.py).
+
+The edges of the contract (the second half of this file) add cases, not gates: frozen chains beside failing ones, NaN at status 0, a
+zero block, ffirst, clamps, call sizes and powers of two, on chains of 1 to 4 states with 4 to 8 chains per call, cc.RAGGED for the
+clamps and cc.LONG once (profiles/chain_marginalize_edges.md).
 """
 import functools
 
@@ -190,3 +194,120 @@ def equivalence(full, drop, status, delta):
             d[rows.start:rows.start + int(drop[c])] = cc.solve_longdouble(A[None, :N, :N], rhs[None])[0].reshape(-1, 15)
         chains.append(c)
     return full.metrics(d, chains)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The edges of the contract (tests/test_gpu_marginalize_edges.py and the twin tests of tests/test_marginalize_cpu.py).  The chains are
+# those of tests/chain_cases.py; what a case must give is asserted by tests/marginalize_edge_checks.py, for twin and device alike.
+# No gate is added: the reference-gated cases below (LONG, the odd power of two) use GATE_LAM_* / GATE_ETA_* above as they are.
+#
+# (a) the bad batch of cc.failure_plan() with an m of its own per chain: in both plans every wavefront holds chains that are FROZEN
+# (m below the wavefront's largest) while a mate fails, and chains whose broken block sits exactly at state m -- in Pr_m, which a
+# frozen chain goes on adding to its carried block in every later trip without it counting as a failure.
+FREEZE_DROPS = ([1, 3, 0, 2, 3, 1, 2, 0], [3, 1, 2, 3, 0, 3, 1, 2])
+FREEZE_STATUS = ([1, 1, 0, 0, 0, 0, 2, 0], [1, 1, 0, 3, 0, 0, 0, 0])
+# (b) the good batch: wavefront 0 and wavefront 1 each freeze chains at trip 0 (m = 0) and at trip 1 beside an m of 3
+POISON_DROP = [1, 3, 0, 2, 1, 3, 0, 2]
+POISON_CHAINS = (0, 2, 4, 6)
+POISON_ENTRY = 7                                   # packed (1, 3)
+LONG_DROP = [63, 0, 0, 1]                          # the chain without states is refused whatever its m is
+NAN_STATUS = {1: [0, 0, 0, 0], 2: [2, 0, 0, 0], 3: [2, 3, 3, 0]}
+SCALE_EXPONENTS = (2, -2, 300, -300, 301)
+FFIRST_NULL_DROPS = (((5, 3, 5, 1, 2), [2, 1, 4, 0, 1]), ((5,) * 5, 3))
+
+
+def failure_status(drop):
+    """What cc.failure_plan()'s bad batch must report under drop [8]: s + 1 of cc.FAILURES[c] if s < m_c, else 0."""
+    return [cc.FAILURES[c][0] + 1 if c in cc.FAILURES and cc.FAILURES[c][0] < int(drop[c]) else 0 for c in range(8)]
+
+
+def freeze_failure_case(k):
+    """(the clean batch, the bad batch, drop [8], the status the bad batch must give) of plan k of (a)."""
+    good, bad, _ = cc.failure_plan()
+    drop = np.asarray(FREEZE_DROPS[k], dtype=np.int32)
+    assert failure_status(drop) == FREEZE_STATUS[k]
+    return good.b, bad.b, drop, FREEZE_STATUS[k]
+
+
+def prior_row_m(b, drop, c):
+    """The row of b.prior that is Pr_m of chain c."""
+    return int(b.first[c]) + int(drop[c])
+
+
+def without_prior_m(b, drop):
+    """b.prior with Pr_m of every chain zeroed: out is then (N + 0.0) + 0.0 = N, the carried block itself, to the bit."""
+    prior = b.prior.copy()
+    for c in range(b.C):
+        if 0 <= drop[c] < b.count[c]:
+            prior[prior_row_m(b, drop, c)] = 0.0
+    return prior
+
+
+def poison_case(what):
+    """(the good batch of cc.failure_plan(), its prior with Pr_m of POISON_CHAINS poisoned, drop [8]).  what = "negative": -1e12 on
+    all 15 diagonal entries (every pivot of every frozen trip fails); "nan": a NaN at packed entry POISON_ENTRY."""
+    b = cc.failure_plan()[0].b
+    drop = np.asarray(POISON_DROP, dtype=np.int32)
+    prior = b.prior.copy()
+    for c in POISON_CHAINS:
+        row = prior_row_m(b, drop, c)
+        if what == "negative":
+            prior[row, cc.tri(np.arange(15)) + np.arange(15)] = -1e12
+        else:
+            prior[row, POISON_ENTRY] = np.nan
+    return b, prior, drop
+
+
+def long_freeze_case():
+    """(the batch of cc.LONG, its prior with a NaN at POISON_ENTRY of state 1 of the chain of two states, drop [4]).  That row is the
+    chain's Pr_m: the chain is frozen from trip 1 on and re-reads it in each of the 62 trips the chain of 64 states still makes."""
+    b = cc.long_case()[0]
+    drop = np.asarray(LONG_DROP, dtype=np.int32)
+    assert b.count.tolist() == cc.LONG == [64, 1, 0, 2]
+    prior = b.prior.copy()
+    prior[prior_row_m(b, drop, 3), POISON_ENTRY] = np.nan
+    return b, prior, drop
+
+
+def nan_sets(M):
+    """chain -> the packed entries of its out row that cc.nan_plan() under M must make NaN at status 0 (the rows of chains whose
+    status is not 0 are all NaN; every other entry has the bits of the clean call):
+        M = 2, chain 1   the NaN sits at (5, 5) of the TRAILING block of factor 1, which state 2 receives as it is
+        M = 2, chain 2   at (3, 5) of U of factor 1: column 5 of W = L^-1 U, hence row and column 5 of W^T W and entry 5 of W^T y
+        M = 3, chain 3   in g of the trailing part of factor 2: eta[14]"""
+    col5 = {cc.tri(5) + i for i in range(6)} | {cc.tri(j) + 5 for j in range(6, 15)} | {cc.tri(15) + 5}
+    return {1: {}, 2: {1: {cc.tri(5) + 5}, 2: col5}, 3: {3: {cc.tri(15) + 14}}}[M]
+
+
+def rhs_nan_case():
+    """(the clean batch of cc.nan_plan(), its prior with a NaN in eta[3] of state 0 of chain 0): a right-hand side further back than
+    what state m receives directly, for M = 2."""
+    b = cc.nan_plan()[0].b
+    prior = b.prior.copy()
+    prior[b.first[0], cc.tri(15) + 3] = np.nan
+    return b, prior
+
+
+def zero_block_case(negative):
+    """(batch, hess with chain 0's one factor row all 0.0 or all -0.0): two chains of 2 and 3 states, to be run without a prior."""
+    b = cc.Batch([2, 3], seed=7)
+    hess = b.hess.copy()
+    hess[b.ffirst[0]] = -0.0 if negative else 0.0
+    return b, hess
+
+
+def ffirst_drops(count):
+    """The m of the ffirst boundary cases: n - 1 (every factor row is read), 0 (none is) and 1 where the chain has two states (fewer
+    rows are read than the refusal looks at)."""
+    n = np.asarray(count, dtype=np.int32)
+    return [np.maximum(n - 1, 0), np.zeros_like(n), np.minimum(1, np.maximum(n - 1, 0))]
+
+
+@functools.lru_cache(maxsize=None)
+def scaled_case():
+    """(the unscaled batch of cc.scaled_batch, drop [C] of plan mixed2, the longdouble Schur reference): computed once, not changed."""
+    b = cc.scaled_reference()[0]
+    drop = plan_drop(b, "mixed2")
+    ref = Reference(b, drop)
+    ref.check_inputs()
+    return b, drop, ref

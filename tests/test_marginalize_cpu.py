@@ -10,7 +10,10 @@
    -ffp-contract=off) against the longdouble Schur complement of tests/marginalize_cases.py on every layout, both priors and every
    drop plan; the metrics are printed first.  Equivalence: the twin of the solve on the reduced chains gives the full chains' delta.
    What the twin must not read is NaN; m = 0 passes the prior through; a failed eliminated block is NaN and alone; mutations of the
-   twin built in tmp_path must fail the gates."""
+   twin built in tmp_path must fail the gates.
+4. The edges of the contract (tests/marginalize_edge_checks.py, which tests/test_gpu_marginalize_edges.py runs on the device): frozen
+   chains beside failing ones, NaN at status 0, the status across marginalize and the reduced solve, a zero block, ffirst, the clamps,
+   status == NULL, call sizes, powers of two.  Four rules of the contract, each broken in a copy of the twin, fail their check."""
 import ctypes as C
 import inspect
 import os
@@ -23,6 +26,7 @@ import pytest
 
 from tests import chain_cases as cc
 from tests import marginalize_cases as mz
+from tests import marginalize_edge_checks as mk
 from tests import test_marginals_cpu as tm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -369,3 +373,119 @@ def test_a_wrong_term_fails_the_gate(hz, tmp_path, what):
     print("%s wrong: (c) %.3e (d) %.3e (the twin as it is: %.3e, %.3e)" % (what, b_c, b_d, g_c, g_d))
     assert g_c <= mz.GATE_LAM_HOST and g_d <= mz.GATE_ETA_HOST
     assert max(b_c / mz.GATE_LAM_HOST, b_d / mz.GATE_ETA_HOST) > 1e3
+
+
+# ---------------------------------------------------------------- the edges of the contract, on the twin first
+def twin_run(hz):
+    """run(b, drop, **kw) of tests/marginalize_edge_checks.py on the twin.  hess and prior get one more row of NaN behind their F and S
+    rows: a twin whose range rule is a row too lax (the mutants below) reads that instead of memory that is not the test's."""
+    def run(b, drop, with_prior=True, hess=None, prior=None, G=None, S=None, status_in=None, no_status=False, **kw):
+        p = lambda x: None if x is None else x.ctypes.data
+        ptr = {"first": (b.first, np.int64), "count": (b.count, np.int32), "ffirst": (b.ffirst, np.int64)}
+        arr = {k: None if kw.get(k, own) is None else np.ascontiguousarray(kw.get(k, own), dtype=dt) for k, (own, dt) in ptr.items()}
+        assert set(kw) <= set(ptr), kw
+        Cn = next((len(v) for v in arr.values() if v is not None), b.C)
+        hess = np.concatenate([b.hess if hess is None else hess, np.full((1, 496), np.nan)])
+        prior = np.concatenate([b.prior if prior is None else prior, np.full((1, 136), np.nan)]) if with_prior else None
+        out = np.full((Cn + 1, 136), mk.SENTINEL)
+        status = np.full(Cn + 1, 99, dtype=np.int32)
+        if status_in is not None:
+            status[:Cn] = status_in
+        M, d = (int(drop), None) if np.isscalar(drop) else (0, np.ascontiguousarray(drop, dtype=np.int32))
+        assert d is None or len(d) == Cn
+        assert hz.hsz_chain_marginalize(Cn, b.G if G is None else G, b.S if S is None else S, b.F, p(arr["first"]), p(arr["count"]), p(arr["ffirst"]),
+                                        p(hess), p(prior), M, p(d), p(out), None if no_status else p(status)) == 0
+        assert (out[Cn] == mk.SENTINEL).all() and status[Cn] == 99
+        if no_status:
+            assert (status[:Cn] == (99 if status_in is None else status_in)).all()
+        return out[:Cn], (None if no_status else status[:Cn])
+    return run
+
+
+def twin_solve_run(hs):
+    def solve(b, first, count, ffirst, prior):
+        return twin_solve(hs, b, first, count, ffirst, prior)
+    return solve
+
+
+def test_twin_frozen_chains_and_failures_with_an_m_per_chain(hz):
+    mk.check_frozen_failures(twin_run(hz))
+
+
+def test_twin_frozen_pivots_do_not_count(hz):
+    mk.check_frozen_pivots_do_not_count(twin_run(hz))
+
+
+def test_twin_long_chain_freezes_its_mates(hz):
+    mk.check_long_freeze(twin_run(hz), mz.GATE_LAM_HOST, mz.GATE_ETA_HOST)
+
+
+def test_twin_nan_in_the_inputs(hz):
+    mk.check_nan_inputs(twin_run(hz))
+
+
+def test_twin_status_law_across_marginalize_and_solve(hz, hs):
+    mk.check_status_law(twin_run(hz), twin_solve_run(hs))
+
+
+def test_twin_a_zero_block_is_a_failed_pivot(hz):
+    mk.check_zero_block(twin_run(hz))
+
+
+def test_twin_refusal_boundary_of_ffirst(hz):
+    mk.check_ffirst_boundaries(twin_run(hz))
+
+
+def test_twin_ffirst_null_with_an_explicit_first(hz):
+    mk.check_ffirst_null(twin_run(hz))
+
+
+def test_twin_clamps_of_first_count_G_and_S(hz):
+    mk.check_clamps(twin_run(hz))
+
+
+def test_twin_scalar_M_is_an_array_filled_with_M(hz):
+    mk.check_scalar_against_array(twin_run(hz))
+
+
+def test_twin_status_null(hz):
+    mk.check_status_null(twin_run(hz))
+
+
+def test_twin_call_sizes_around_a_wavefront(hz):
+    mk.check_call_sizes(twin_run(hz))
+
+
+def test_twin_scaled_by_a_power_of_two(hz):
+    mk.check_scaling(twin_run(hz), mz.GATE_LAM_HOST, mz.GATE_ETA_HOST)
+
+
+# the rules the edge tests are there for, each broken in a copy of the twin: (file, old, new, the check that must notice)
+_TWIN = "tests/hostsim/hostsim_marginalize.cpp"
+MUTANTS = {
+    "the last failure wins": ("cpi_amd/csrc/cpi_math.hpp", "if (!pd && status == 0) status = s + 1;", "if (!pd) status = s + 1;", mk.check_frozen_failures),
+    "a failed row is not filled with NaN": ("cpi_amd/csrc/cpi_math.hpp", "    if (status)\n        for (int i = 0; i < PRIOR_D; i++) out[i] = NAN;\n    return status;",
+                                            "    return status;", mk.check_zero_block),
+    "m = n is let through": (_TWIN, "|| m < 0 || m >= n) {", "|| m < 0 || m > n) {", mk.check_scalar_against_array),
+    "ffirst is judged over the m rows that are read": (_TWIN, "if ((n > 1 && (ff < 0 || ff > F - (n - 1))) ||", "if ((m > 0 && (ff < 0 || ff > F - m)) ||",
+                                                      mk.check_ffirst_boundaries),
+}
+
+
+@pytest.mark.parametrize("what", list(MUTANTS))
+def test_a_broken_rule_fails_its_edge_test(hz, tmp_path, what):
+    """Do the edge tests bite?  The twin with one rule of the contract broken, built in tmp_path, fails the check that states the rule
+    (every access of these mutants stays inside the arrays: see twin_run and the tile layout of the chains that m = n is tried on),
+    and the twin as it is passes it."""
+    rel, old, new, check = MUTANTS[what]
+    files = {_TWIN: open(_SRC).read(), "cpi_amd/csrc/cpi_math.hpp": open(_MATH).read()}
+    assert files[rel].count(old) == 1, old
+    files[rel] = files[rel].replace(old, new)
+    for name, text in files.items():
+        os.makedirs(tmp_path / os.path.dirname(name), exist_ok=True)
+        (tmp_path / name).write_text(text)
+    out = str(tmp_path / "libmutant.so")
+    tm._build(str(tmp_path / _TWIN), out)
+    check(twin_run(hz))
+    with pytest.raises(AssertionError):
+        check(twin_run(_bind(out)))
