@@ -51,13 +51,14 @@ UNITS = {
     "cpi_cov": DEVICE + ["cpi_cov.hip", "cpi_cov_kernels.hpp"],
     "cpi_factor": DEVICE + ["cpi_factor.hip", "cpi_factor_kernels.hpp"],
     "cpi_running_resume": DEVICE + ["cpi_running_resume.hip", "cpi_running_kernels.hpp", "cpi_running_body.inc", "cpi_cov_kernels.hpp"],
-    "cpi_query": DEVICE + ["cpi_query_body.inc"] + ["cpi_query.hip", "cpi_query_kernels.hpp"],
-    "cpi_query_cov": DEVICE + ["cpi_covq_common.hpp", "cpi_covq_body.inc"] + ["cpi_query_cov.hip", "cpi_query_cov_kernels.hpp"],
-    "cpi_stj": DEVICE + ["cpi_query_stj_body.inc"] + ["cpi_stj.hip", "cpi_cov_kernels.hpp", "cpi_stj_kernels.hpp"],
-    "cpi_query_stream": DEVICE + ["cpi_query_body.inc"] + ["cpi_query_stream.hip", "cpi_query_kernels.hpp", "cpi_query_stream_kernels.hpp"],
+    "cpi_query": DEVICE + ["cpi_query_locate.hpp"] + ["cpi_query.hip", "cpi_query_kernels.hpp"],
+    "cpi_query_cov": DEVICE + ["cpi_query_locate.hpp", "cpi_covq_body.hpp", "cpi_covq_body.inc"] + ["cpi_query_cov.hip", "cpi_query_cov_kernels.hpp"],
+    "cpi_stj": DEVICE + ["cpi_query_locate.hpp"] + ["cpi_stj.hip", "cpi_cov_kernels.hpp", "cpi_stj_kernels.hpp"],
+    "cpi_query_stream": DEVICE + ["cpi_query_locate.hpp", "cpi_query_stream.hip", "cpi_covq_body.hpp", "cpi_covq_body.inc", "cpi_stj_kernels.hpp",
+                                 "cpi_query_kernels.hpp", "cpi_query_stream_kernels.hpp"],
     "cpi_running_resume_stj": DEVICE + ["cpi_running_resume_stj.hip", "cpi_cov_kernels.hpp"],
-    "cpi_query_open": DEVICE + ["cpi_query_open.hip", "cpi_query_kernels.hpp", "cpi_query_body.inc", "cpi_stj_kernels.hpp",
-                               "cpi_query_stj_body.inc", "cpi_covq_common.hpp", "cpi_covq_body.inc", "cpi_query_open_kernels.hpp"],
+    "cpi_query_open": DEVICE + ["cpi_query_locate.hpp", "cpi_query_open.hip", "cpi_query_kernels.hpp", "cpi_covq_body.hpp", "cpi_covq_body.inc",
+                               "cpi_stj_kernels.hpp", "cpi_query_open_kernels.hpp"],
     "cpi_merge": DEVICE + ["cpi_merge.hip", "cpi_merge_kernels.hpp"],
     "cpi_trial": DEVICE + ["cpi_trial.hip", "cpi_factor_kernels.hpp", "cpi_trial_kernels.hpp"],
     "cpi_chain": DEVICE + ["cpi_chain_util.hpp", "cpi_chain.hip", "cpi_factor_kernels.hpp", "cpi_chain_kernels.hpp"],

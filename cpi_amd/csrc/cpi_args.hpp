@@ -10,14 +10,16 @@
 //   cpi_running_resume_stj.hip  cpi_cov_running_stj_carry_kernel: cov_body with the read-out of model 2's Discrete_J_b columns after
 //                   every interval for windows that continue from carry records (cpi_running_resume_stj_batch)
 //   cpi_query.hip   cpi_query_kernel: the measurement at arbitrary times inside a window, one partial interval from a running row
-//                                                                                      (cpi_query_kernels.hpp)
+//                                                    (cpi_query_kernels.hpp: query_mean_body; cpi_query_locate.hpp)
 //   cpi_query_cov.hip  cpi_query_cov_kernel: the covariance at arbitrary times, one partial interval of the covariance recursion
-//                   from a running P / P_sym row                                       (cpi_query_cov_kernels.hpp)
+//                   from a running P / P_sym row               (cpi_query_cov_kernels.hpp over cpi_covq_body.hpp; cpi_query_locate.hpp)
 //   cpi_stj.hip     cpi_cov_running_stj_kernel / cpi_query_stj_kernel: model 2's bias Jacobians (the Discrete_J_b columns of cov_body)
-//                   after every interval and at arbitrary times                (cpi_cov_kernels.hpp, cpi_stj_kernels.hpp)
+//                   after every interval and at arbitrary times
+//                                              (cpi_cov_kernels.hpp, cpi_stj_kernels.hpp: query_stj_body; cpi_query_locate.hpp)
 //   cpi_query_stream.hip  cpi_squery_mean_kernel / cpi_squery_cov_kernel / cpi_squery_jac2_kernel: the three query kernels by
 //                   ABSOLUTE time over IMU stream(s) read in place -- window lookup over the update times, search over the
-//                   patched stamps of the cut, then the same arithmetic                 (cpi_query_stream_kernels.hpp)
+//                   patched stamps of the cut, then the same bodies
+//                                                    (cpi_query_stream_kernels.hpp: StreamLocator, over the three query bodies)
 //   cpi_query_open.hip  cpi_query_open_kernel / cpi_query_cov_open_kernel / cpi_query_stj_open_kernel: the three query kernels for
 //                   windows that continue from a carried state -- the same bodies, their i == 0 gather reading a base row
 //                                                    (cpi_query_open_kernels.hpp over the three query bodies)

@@ -1,8 +1,8 @@
 // cpi_chain_kernels.hpp -- cpi_chain_solve_kernel: the damped block-tridiagonal solve of chains of IMU factors (cpi_chain_solve_batch;
 // the arithmetic and the workspace record: cpi_math.hpp, namespace chn, whose lane-mapped form this is).
 // Part of the translation unit cpi_chain.hip (included there after cpi_math.hpp / cpi_device_util.hpp / cpi_factor_kernels.hpp, from
-// which it takes row_share, dpp_fmac / dpp_fnmac / dpp_mul and pivot_rsqrt, and after cpi_chain_util.hpp: chain_for, chain_settle,
-// chain_states; not a stand-alone header).
+// which it takes dpp_fnmac, and after cpi_chain_util.hpp, which holds what one elimination step shares with cpi_marginalize_kernel:
+// chain_range, the staged pieces, chain_pick, chain_pivot_step, chain_w, chain_schur; not a stand-alone header).
 //
 // 16 lanes (one DPP row) per chain, 4 chains per wavefront, one wavefront per workgroup.  Lane j < 15 keeps column j of the working
 // block in registers -- the FULL symmetric column, so the multiplier of its own trailing update is a static register --, lane 15
@@ -27,63 +27,16 @@
 
 namespace {
 
-struct __attribute__((packed, aligned(8))) chain_d2u { double a, b; };
-
-__device__ __forceinline__ long long readlane64(long long v, int l) {
-    return ((long long)__builtin_amdgcn_readlane((int)(v >> 32), l) << 32) | (unsigned)__builtin_amdgcn_readlane((int)(v & 0xffffffffll), l);
-}
 // compile-time loops over a DPP control: chain_for (ascending) is cpi_chain_util.hpp's
 template <int I, class F>
 __device__ __forceinline__ void chain_for_down(F &&f) {
     if constexpr (I >= 0) { f(std::integral_constant<int, I>()); chain_for_down<I - 1>(f); }
 }
-// Entry (i, d) of a packed symmetric matrix sits at T(d) + i or at T(i) + d.  BOTH are read -- each a lane's base plus a constant the
-// instruction carries -- and one is kept: an address per entry, picked first, is a register per entry that the compiler computes
-// once and holds through the whole chain (75 of them).  The one not kept lies inside the same row (static_assert in the kernel).
-__device__ __forceinline__ double chain_pick(bool first, double x, double y) { return first ? x : y; }
-// keeps the reads of one group from being issued with the next group's (instruction selection orders memory operations along it)
-__device__ __forceinline__ void chain_read_fence() { asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); }
-// (chain_settle, the wait states in front of a DPP read of a VALU result: cpi_chain_util.hpp)
-
-// pivot step K of the augmented block (chn::factor_block); a[K] becomes R[K][j] (1 / R[K][K] in lane K)
-// No "finished lane" select in the trailing update: lanes j <= K go on updating rows of columns that are never read again (the
-// broadcasts of the later steps come from lanes > K, and a lane's a[k], k <= K, is already final), as in cpi_sqrt_info_kernel.
-template <int K>
-__device__ __forceinline__ void chain_pivot_step(double (&a)[15], int j, bool &fail) {
-    if constexpr (K < 15) {
-        double mine = a[K];
-        if (j == K) {
-            if (!(mine > 0.0)) fail = true;
-            mine = pivot_rsqrt(mine);
-        }
-        chain_settle(mine);
-        const double inv = row_share<K>(mine);
-        const double r = a[K] * inv, ca = -inv * r;
-        a[K] = (j == K) ? inv : r;
-#pragma unroll
-        for (int i = K + 1; i < 15; i++) dpp_fmac<K>(a[i], a[i], ca);   // rows ascend: a[K + 1], the next pivot, is the oldest write
-        asm volatile("s_nop 1");
-        __builtin_amdgcn_sched_barrier(0);
-        chain_pivot_step<K + 1>(a, j, fail);
-    }
-}
-
-struct ChainRange { long long f, ff; int n; bool bad; };
-__device__ __forceinline__ ChainRange chain_range(const ChainArgs &A, long long c) {
-    ChainRange r;
-    const ChainStates cs = chain_states(A.C, A.G, A.S, A.first, A.count, c);   // the states: the rule cpi_marginals_kernel shares
-    r.f = cs.f; r.n = cs.n;
-    r.ff = A.ffirst ? A.ffirst[cs.cc] : cs.f - cs.cc;
-    r.bad = cs.n > 1 && (r.ff < 0 || r.ff > A.F - (long long)(cs.n - 1));
-    return r;
-}
 
 __global__ __launch_bounds__(64, 2) void cpi_chain_solve_kernel(ChainArgs A) {
     constexpr int HD = chn::HESS_D, NP = HD / 2, NR = (NP + 63) / 64;   // 248 pieces of 16 bytes per row, 4 per lane
     __shared__ __attribute__((aligned(16))) double sH[4 * HD];
-    // the furthest entries chain_pick and the column reads touch, kept or not, lie inside a hess row / a prior row
-    static_assert(chn::tri(30) + 29 < HD && 30 + chn::tri(29) < HD && chn::tri(15) + 14 < chn::PRIOR_D && 15 + chn::tri(14) < chn::PRIOR_D,
-                  "a read at a constant offset from a lane's base stays inside the row");
+    static_assert(chain_reads_stay_in_rows(), "a read at a constant offset from a lane's base stays inside the row");
     const int lane = threadIdx.x, j = lane & 15, fl = lane >> 4, jc = min(j, 14);
     const long long c = (long long)blockIdx.x * 4 + fl;
     const ChainRange cr = chain_range(A, c);
@@ -197,16 +150,7 @@ __global__ __launch_bounds__(64, 2) void cpi_chain_solve_kernel(ChainArgs A) {
             const unsigned long long bal = __ballot(fail && j < 15);
             if (act && st == 0 && ((bal >> (16 * fl)) & 0xffffull)) st = s + 1;
         }
-        // W = L^-1 U: column jc in this lane (lane 15 redoes column 14)
-        chain_for<0, 15>([&](auto Kc) {
-            constexpr int K = decltype(Kc)::value;
-            u[K] = dpp_mul<K>(a[K], u[K]);
-            chain_for<K + 1, 15>([&](auto Ic) {
-                constexpr int I = decltype(Ic)::value;
-                dpp_fnmac<I>(u[I], a[K], u[K]);
-            });
-        });
-        __builtin_amdgcn_sched_barrier(0);
+        chain_w(a, u);
         double *rec = A.workspace + srow * chn::WS_D;
         if (act) {
 #pragma unroll
@@ -220,17 +164,9 @@ __global__ __launch_bounds__(64, 2) void cpi_chain_solve_kernel(ChainArgs A) {
         // lane 15: its w becomes y, and the Schur update carries the right-hand side along
 #pragma unroll
         for (int k = 0; k < 15; k++) u[k] = (j == 15) ? a[k] : u[k];
-        asm volatile("s_nop 1" : "+v"(u[0]), "+v"(u[1]), "+v"(u[2]), "+v"(u[3]), "+v"(u[4]), "+v"(u[5]), "+v"(u[6]), "+v"(u[7]),
-                                 "+v"(u[8]), "+v"(u[9]), "+v"(u[10]), "+v"(u[11]), "+v"(u[12]), "+v"(u[13]), "+v"(u[14]));
+        chain_settle(u);
         __builtin_amdgcn_sched_barrier(0);
-        chain_for<0, 15>([&](auto Ic) {
-            constexpr int I = decltype(Ic)::value;
-            chain_for<0, 15>([&](auto Kc) {
-                constexpr int K = decltype(Kc)::value;
-                dpp_fnmac<I>(nxt[I], u[K], u[K]);
-            });
-        });
-        __builtin_amdgcn_sched_barrier(0);
+        chain_schur(nxt, u);
     }
     // the records are read back by OTHER lanes of this wavefront
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");

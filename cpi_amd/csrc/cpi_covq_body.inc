@@ -1,5 +1,6 @@
-// cpi_covq_body.inc -- body of cpi_query_cov_kernel and cpi_query_cov_open_kernel (cpi_query_cov_kernels.hpp, cpi_query_open_kernels.hpp).  Expects: the
-// template parameters MODEL, AVG, the arguments QueryArgs A, QueryCovNoise NZ and QueryBase B, constexpr bool OPEN.
+// cpi_covq_body.inc -- the statements of the covariance query body (described in cpi_covq_body.hpp), pasted into the three kernels
+// over it.  Expects: the template parameters MODEL and AVG, constexpr bool OPEN, the locator type Loc, and the arguments A
+// (QueryArgs or StreamQueryArgs), QueryCovNoise NZ and QueryBase B.
     static_assert(!(AVG && MODEL == 1), "with the reading held, model 1's averaging is the identity (x + x) * 0.5");
     typedef CovDims<MODEL> D;
     constexpr int GROUP = D::GROUP;   // lanes per query
@@ -16,19 +17,6 @@
     const long long q0 = (long long)blockIdx.x * G;
     const bool valid = q0 + g < A.Q;
     const long long k = min(q0 + g, A.Q - 1);        // groups past the last query redo it and store nothing
-    const long long w = min(max((long long)A.qwin[k], 0ll), A.W - 1);
-    const double tq = A.qtime[k];
-    const int n = A.count ? min(max(A.count[w], 0), A.N) : A.N;
-    const double *kn = A.knots + (A.first ? A.first[w] : w * (long long)(A.N + 1)) * 7;
-
-    // ---- the interval (cpi_query_kernel): sum of the steps = 2^trips - 1 >= N, every probe clamped into [0, n]
-    int i = 0;
-    for (int s = A.trips - 1; s >= 0; --s) {
-        const int probe = i + (1 << s);
-        const double t = kn[min(probe, n) * 7];
-        i = (probe <= n && t <= tq) ? probe : i;
-    }
-
     const double q4[4] = { NZ.q4[0], NZ.q4[1], NZ.q4[2], NZ.q4[3] };
     const int jl = cov_col_of_lane<MODEL>(j);
     const int jj = (jl < D::NPCOL) ? jl : D::NCOL;                  // column owned by this lane; NCOL = idle
@@ -36,10 +24,14 @@
     CovLane<MODEL> Ln;
     cov_init(Ln, jj, q4);
 
-    // ---- knot i, the base row's quaternion and this lane's column of S, in flight together
-    double kt[7];
-#pragma unroll
-    for (int c = 0; c < 7; c++) kt[c] = kn[i * 7 + c];
+    const double tq = A.qtime[k];
+    const QueryAt at = Loc::find(A, k, tq);
+    const long long w = at.w;
+    const int n = at.n, i = at.i;
+    const double *kt = at.kt;
+    Loc::note_window(A, k, at, valid && j == 0);
+
+    // ---- the base row's quaternion and this lane's column of S (knot i is in flight with them)
     const bool has = OPEN || i > 0;
     const bool fromb = OPEN && i == 0;               // the state before knot 0: the base row
     double S[D::NR];
@@ -123,7 +115,7 @@
 
     // ---- columns jj < 15: the stepped column, or the gathered one bit for bit
     if (!valid || jj >= 15) return;
-    const bool bad = (tq != tq) || (OPEN && bq.x != bq.x);
+    const bool bad = (tq != tq) || (OPEN && bq.x != bq.x) || at.none;
     double v[15];
 #pragma unroll
     for (int r = 0; r < 15; r++) v[r] = bad ? __builtin_nan("") : (step ? Ln.P0[r] : S[r]);

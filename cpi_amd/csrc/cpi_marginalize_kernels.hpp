@@ -1,14 +1,14 @@
 // cpi_marginalize_kernels.hpp -- cpi_marginalize_kernel: the leading states of every chain of IMU factors eliminated into the
 // prior row of the first state that stays (cpi_chain_marginalize_batch; the arithmetic: cpi_math.hpp, chn::marginalize_chain, whose
 // lane-mapped form this is).  Part of the translation unit cpi_marginalize.hip (included there after cpi_math.hpp /
-// cpi_device_util.hpp / cpi_factor_kernels.hpp, from which it takes row_share, dpp_fmac / dpp_fnmac / dpp_mul and pivot_rsqrt, and
-// after cpi_chain_util.hpp: chain_for, chain_settle, chain_states; not a stand-alone header).
+// cpi_device_util.hpp / cpi_factor_kernels.hpp, and after cpi_chain_util.hpp, which holds what one elimination step shares with
+// cpi_chain_solve_kernel: chain_range, the staged pieces, chain_pick, chain_pivot_step, chain_w, chain_schur; not a stand-alone header).
 //
-// The mapping of cpi_chain_solve_kernel (cpi_chain_kernels.hpp, which is not a shared header: the pivot step, the staging and the
-// both-candidates read are restated here under names of their own): 16 lanes (one DPP row) per chain, 4 chains per wavefront, one
+// The mapping of cpi_chain_solve_kernel (cpi_chain_kernels.hpp): 16 lanes (one DPP row) per chain, 4 chains per wavefront, one
 // wavefront per workgroup.  Lane j < 15 keeps the FULL symmetric column j of the working block, lane 15 the right-hand side as a
-// sixteenth column; pivots, W = L^-1 U and the Schur update are the solve's DPP patterns, without damping.  LDS stages the four hess
-// rows of a trip (4 x 496 doubles, whole 16-byte pieces).  Nothing is written but out and status: no workspace, no fence, no back pass.
+// sixteenth column; pivots, W = L^-1 U and the Schur update are the solve's DPP patterns (cpi_chain_util.hpp), without damping.  LDS
+// stages the four hess rows of a trip (4 x 496 doubles, whole 16-byte pieces).  Nothing is written but out and status: no workspace,
+// no fence, no back pass.
 //
 // What differs from the solve is where a chain stops.  The trip count of a wavefront is its largest m; a chain with a smaller m
 // FREEZES its carried block from its trip m on (a select per register) and goes on executing on valid addresses -- a DPP source must
@@ -22,52 +22,17 @@
 
 namespace {
 
-struct __attribute__((packed, aligned(8))) mgz_d2u { double a, b; };
-
-__device__ __forceinline__ long long mgz_readlane64(long long v, int l) {
-    return ((long long)__builtin_amdgcn_readlane((int)(v >> 32), l) << 32) | (unsigned)__builtin_amdgcn_readlane((int)(v & 0xffffffffll), l);
-}
-// entry (i, d) of a packed symmetric matrix sits at T(d) + i or at T(i) + d: both are read at constant offsets from a lane's base, one
-// is kept (the solve's chain_pick); the one not kept lies inside the same row (static_assert in the kernel)
-__device__ __forceinline__ double mgz_pick(bool first, double x, double y) { return first ? x : y; }
-// keeps the reads of one group from being issued with the next group's
-__device__ __forceinline__ void mgz_read_fence() { asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); }
-
-// pivot step K of the augmented block (chn::factor_block); a[K] becomes R[K][j] (1 / R[K][K] in lane K).  The solve's chain_pivot_step.
-template <int K>
-__device__ __forceinline__ void mgz_pivot_step(double (&a)[15], int j, bool &fail) {
-    if constexpr (K < 15) {
-        double mine = a[K];
-        if (j == K) {
-            if (!(mine > 0.0)) fail = true;
-            mine = pivot_rsqrt(mine);
-        }
-        chain_settle(mine);
-        const double inv = row_share<K>(mine);
-        const double r = a[K] * inv, ca = -inv * r;
-        a[K] = (j == K) ? inv : r;
-#pragma unroll
-        for (int i = K + 1; i < 15; i++) dpp_fmac<K>(a[i], a[i], ca);   // rows ascend: a[K + 1], the next pivot, is the oldest write
-        asm volatile("s_nop 1");
-        __builtin_amdgcn_sched_barrier(0);
-        mgz_pivot_step<K + 1>(a, j, fail);
-    }
-}
-
 __global__ __launch_bounds__(64, 2) void cpi_marginalize_kernel(MarginalizeArgs A) {
     constexpr int HD = chn::HESS_D, PD = chn::PRIOR_D, NP = HD / 2, NR = (NP + 63) / 64;   // 248 pieces of 16 bytes per row, 4 per lane
     __shared__ __attribute__((aligned(16))) double sH[4 * HD];
-    // the furthest entries mgz_pick and the column reads touch, kept or not, lie inside a hess row / a prior row
-    static_assert(chn::tri(30) + 29 < HD && 30 + chn::tri(29) < HD && chn::tri(15) + 14 < PD && 15 + chn::tri(14) < PD,
-                  "a read at a constant offset from a lane's base stays inside the row");
+    static_assert(chain_reads_stay_in_rows(), "a read at a constant offset from a lane's base stays inside the row");
     const int lane = threadIdx.x, j = lane & 15, fl = lane >> 4, jc = min(j, 14);
     const long long c = (long long)blockIdx.x * 4 + fl;
-    const ChainStates cs = chain_states(A.C, A.G, A.S, A.first, A.count, c);   // the states: the rule the solve and the marginals share
+    const ChainRange cs = chain_range(A, c);           // the states and the factors: the solve's rule, over the whole chain
     const int n = cs.n;
-    const long long ff = A.ffirst ? A.ffirst[cs.cc] : cs.f - cs.cc;
-    const bool bad = n > 1 && (ff < 0 || ff > A.F - (long long)(n - 1));      // the solve's rule, over the whole chain
+    const long long ff = cs.ff;
     const int mraw = A.drop ? A.drop[cs.cc] : A.M;
-    const bool ok = c < A.C && !bad && mraw >= 0 && mraw < n;                  // n = 0: no m is inside [0, n)
+    const bool ok = c < A.C && !cs.bad && mraw >= 0 && mraw < n;               // n = 0: no m is inside [0, n)
     const int m = ok ? mraw : 0;
     const int mmax = wave_max(m);
     const double qnan = __builtin_nan("");
@@ -88,11 +53,11 @@ __global__ __launch_bounds__(64, 2) void cpi_marginalize_kernel(MarginalizeArgs 
             const long long row = (m > 0) ? ff + min(s, m - 1) : 0;    // m = 0: ff may be anything (a chain of one state)
 #pragma unroll
             for (int q = 0; q < 4; q++) {
-                const mgz_d2u *src = reinterpret_cast<const mgz_d2u *>(A.hess + mgz_readlane64(row, 16 * q) * HD);
+                const chain_d2u *src = reinterpret_cast<const chain_d2u *>(A.hess + readlane64(row, 16 * q) * HD);
 #pragma unroll
                 for (int r = 0; r < NR; r++) {
                     const int i = min(lane + 64 * r, NP - 1);
-                    const mgz_d2u v = src[i];
+                    const chain_d2u v = src[i];
                     sH[q * HD + 2 * i] = v.a; sH[q * HD + 2 * i + 1] = v.b;
                 }
             }
@@ -103,22 +68,22 @@ __global__ __launch_bounds__(64, 2) void cpi_marginalize_kernel(MarginalizeArgs 
             const double *Pr = A.prior + (f + min(s, m)) * PD;
             const double *colp = Pr + chn::tri(j), *rowp = Pr + j;
 #pragma unroll
-            for (int i = 0; i < 15; i++) a[i] = mgz_pick(i <= j, colp[i], rowp[chn::tri(i)]);
+            for (int i = 0; i < 15; i++) a[i] = chain_pick(i <= j, colp[i], rowp[chn::tri(i)]);
         } else {
 #pragma unroll
             for (int i = 0; i < 15; i++) a[i] = 0.0;
         }
-        mgz_read_fence();                              // one group of reads at a time
+        chain_read_fence();                            // one group of reads at a time
         double u[15], nb[15];
         {
             const double *colp = Hq + chn::tri(cj), *rowp = Hq + cj;
 #pragma unroll
             for (int i = 0; i < 15; i++) {
-                double cur = mgz_pick(i <= cj, colp[i], rowp[chn::tri(i)]);
+                double cur = chain_pick(i <= cj, colp[i], rowp[chn::tri(i)]);
                 cur = act ? cur : 0.0;
                 a[i] = (nxt[i] + cur) + a[i];
             }
-            mgz_read_fence();
+            chain_read_fence();
             // U = rows 0 .. 14 of packed column 15 + j; the carried block of the next state: rows 15 .. 29 of column 15 + j (30: g)
             const double *ucol = Hq + chn::tri(15 + jc);
             const double *bcol = Hq + chn::tri(bj) + 15, *brow = Hq + bj;
@@ -127,43 +92,27 @@ __global__ __launch_bounds__(64, 2) void cpi_marginalize_kernel(MarginalizeArgs 
                 const double uu = ucol[i];
                 u[i] = act ? uu : 0.0;
             }
-            mgz_read_fence();
+            chain_read_fence();
 #pragma unroll
             for (int i = 0; i < 15; i++) {
-                const double bb = mgz_pick(15 + i <= bj, bcol[i], brow[chn::tri(15 + i)]);
+                const double bb = chain_pick(15 + i <= bj, bcol[i], brow[chn::tri(15 + i)]);
                 nb[i] = act ? bb : 0.0;
             }
         }
         wave_lds_fence();                              // the stage is read: the next trip may write over it
         bool fail = false;
-        mgz_pivot_step<0>(a, j, fail);
+        chain_pivot_step<0>(a, j, fail);
         {
             const unsigned long long bal = __ballot(fail && j < 15);
             if (act && st == 0 && ((bal >> (16 * fl)) & 0xffffull)) st = s + 1;
         }
-        // W = L^-1 U: column jc in this lane (lane 15 redoes column 14)
-        chain_for<0, 15>([&](auto Kc) {
-            constexpr int K = decltype(Kc)::value;
-            u[K] = dpp_mul<K>(a[K], u[K]);
-            chain_for<K + 1, 15>([&](auto Ic) {
-                constexpr int I = decltype(Ic)::value;
-                dpp_fnmac<I>(u[I], a[K], u[K]);
-            });
-        });
-        __builtin_amdgcn_sched_barrier(0);
+        chain_w(a, u);
         // lane 15: its w becomes y, and the Schur update carries the right-hand side along
 #pragma unroll
         for (int k = 0; k < 15; k++) u[k] = (j == 15) ? a[k] : u[k];
         chain_settle(u);
         __builtin_amdgcn_sched_barrier(0);
-        chain_for<0, 15>([&](auto Ic) {
-            constexpr int I = decltype(Ic)::value;
-            chain_for<0, 15>([&](auto Kc) {
-                constexpr int K = decltype(Kc)::value;
-                dpp_fnmac<I>(nb[I], u[K], u[K]);
-            });
-        });
-        __builtin_amdgcn_sched_barrier(0);
+        chain_schur(nb, u);
         // a chain past its m keeps the block it carried at its trip m
 #pragma unroll
         for (int i = 0; i < 15; i++) nxt[i] = act ? nb[i] : nxt[i];

@@ -13,6 +13,7 @@ using namespace cpi;
 
 #include "cpi_device_util.hpp"
 #include "cpi_query_kernels.hpp"
+#include "cpi_covq_body.hpp"
 #include "cpi_stj_kernels.hpp"
 #include "cpi_query_open_kernels.hpp"
 

@@ -1,6 +1,6 @@
 // cpi_query_stream.hip -- translation unit of cpi_query_stream_batch: cpi_squery_mean_kernel / cpi_squery_cov_kernel /
 // cpi_squery_jac2_kernel (cpi_query_stream_kernels.hpp), the query family by absolute time over IMU stream(s) read in place -- the
-// window lookup and the search over patched stamps in front of the arithmetic of the three plain query kernels --, with their
+// window lookup and the search over patched stamps in front of the bodies of the three plain query kernels --, with their
 // launchers (cpi_args.hpp: cpi::launch).  A unit of its own: no other unit is recompiled for it, and its kernels have a resource
 // report of their own (resource_usage_query_stream.txt; cpi_amd/build.py).
 #include <hip/hip_runtime.h>
@@ -12,7 +12,9 @@
 using namespace cpi;
 
 #include "cpi_device_util.hpp"
-#include "cpi_query_kernels.hpp"       // query_flush / QRY_PITCH (its kernel template is not instantiated here)
+#include "cpi_covq_body.hpp"           // the three bodies (the window kernels beside them are not instantiated here)
+#include "cpi_stj_kernels.hpp"
+#include "cpi_query_kernels.hpp"
 #include "cpi_query_stream_kernels.hpp"
 
 namespace cpi {
@@ -30,7 +32,7 @@ void squery_mean(int model, bool jac, bool avg, const StreamQueryArgs &a, hipStr
 
 // One lane group per query; the instances of launch::query_cov.
 void squery_cov(int model, bool avg, const StreamQueryArgs &a, const double q4[4], hipStream_t st) {
-    SQueryNoise nz;
+    QueryCovNoise nz;
     for (int i = 0; i < 4; i++) nz.q4[i] = q4[i];
     const long long per = 64 / (model == CPI_MODEL_V2 ? CovDims<2>::GROUP : CovDims<1>::GROUP);
     const dim3 grid((unsigned)((a.Q + per - 1) / per)), block(64);

@@ -106,7 +106,8 @@ def test_kernels_have_units_and_reports_of_their_own():
     from cpi_amd import _lib, build
     _lib.load()
     assert "cpi_cov_kernels.hpp" in build.UNITS["cpi_running_resume_stj"] and "cpi_running_resume_stj.hip" in build.UNITS["cpi_running_resume_stj"]
-    for f in ("cpi_query_open.hip", "cpi_query_open_kernels.hpp", "cpi_query_body.inc", "cpi_covq_body.inc", "cpi_query_stj_body.inc"):
+    for f in ("cpi_query_open.hip", "cpi_query_open_kernels.hpp", "cpi_query_locate.hpp", "cpi_query_kernels.hpp", "cpi_covq_body.hpp", "cpi_covq_body.inc",
+              "cpi_stj_kernels.hpp"):
         assert f in build.UNITS["cpi_query_open"], f
     a = _rows(build.UNIT_REPORTS["cpi_running_resume_stj"])
     assert sorted(a) == ["cpi_cov_running_stj_carry_kernel<false>", "cpi_cov_running_stj_carry_kernel<true>"]
