@@ -41,7 +41,11 @@ UNIT_REPORTS = {"cpi_running_resume": os.path.join(CSRC, "resource_usage_running
                 "cpi_marginals": os.path.join(CSRC, "resource_usage_marginals.txt"),
                 "cpi_marginalize": os.path.join(CSRC, "resource_usage_marginalize.txt")}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Rpass-analysis=kernel-resource-usage"]
+# -amdgpu-kernarg-preload-count: the leading scalar / pointer parameters of a kernel (up to 16 user SGPRs less the ones the
+# kernel already takes) arrive in SGPRs with the wave instead of through a scalar-memory round trip at the head of every
+# wavefront; kernels whose first parameter is a by-value struct are compiled as before (cpi_mean_kernels.hpp: CPI_MEAN_LEAD_PARAMS)
+CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Rpass-analysis=kernel-resource-usage",
+          "-mllvm", "-amdgpu-kernarg-preload-count=16"]
 COMMON = ["cpi_args.hpp", "../../include/cpi_amd.h", "exports.map"]   # exports.map: the link step's version script
 DEVICE = COMMON + ["cpi_math.hpp", "cpi_device_util.hpp"]
 # translation unit -> the files it includes (what its object depends on)

@@ -71,9 +71,9 @@ static void launch_mean_L(int L, const PreArgs &a, hipStream_t st) {
         if (L == 1 && admitted && a.W >= wmin && a.N >= CPI_MEAN_BIG_NMIN) {
             const unsigned nb = (unsigned)((a.W + 63) / 64);
             const size_t pad = CPI_MEAN_BIG_LDS_PAD;   // unused dynamic LDS: caps the wavefronts per CU (see above)
-            if (cut == 2) hipLaunchKernelGGL((cpi_mean_kernel<MODEL, false, AVG, 1, 2, true>), dim3(nb), dim3(64), pad, st, a);
-            else if (cut == 1) hipLaunchKernelGGL((cpi_mean_kernel<MODEL, false, AVG, 1, 1, true>), dim3(nb), dim3(64), pad, st, a);
-            else hipLaunchKernelGGL((cpi_mean_kernel<MODEL, false, AVG, 1, 0, true>), dim3(nb), dim3(64), pad, st, a);
+            if (cut == 2) hipLaunchKernelGGL((cpi_mean_kernel<MODEL, false, AVG, 1, 2, true>), dim3(nb), dim3(64), pad, st, CPI_MEAN_LEAD(a), a);
+            else if (cut == 1) hipLaunchKernelGGL((cpi_mean_kernel<MODEL, false, AVG, 1, 1, true>), dim3(nb), dim3(64), pad, st, CPI_MEAN_LEAD(a), a);
+            else hipLaunchKernelGGL((cpi_mean_kernel<MODEL, false, AVG, 1, 0, true>), dim3(nb), dim3(64), pad, st, CPI_MEAN_LEAD(a), a);
             return;
         }
     }
@@ -81,9 +81,9 @@ static void launch_mean_L(int L, const PreArgs &a, hipStream_t st) {
     case LL: {                                                                                   \
         const long long nb = (a.W + (64 / LL) - 1) / (64 / LL);                                  \
         if (cut == 2) {                                                                          \
-            if constexpr (!JAC) hipLaunchKernelGGL((cpi_mean_kernel<MODEL, JAC, AVG, LL, 2>), dim3((unsigned)nb), dim3(64), 0, st, a); \
-        } else if (cut == 1) hipLaunchKernelGGL((cpi_mean_kernel<MODEL, JAC, AVG, LL, 1>), dim3((unsigned)nb), dim3(64), 0, st, a); \
-        else hipLaunchKernelGGL((cpi_mean_kernel<MODEL, JAC, AVG, LL, 0>), dim3((unsigned)nb), dim3(64), 0, st, a); \
+            if constexpr (!JAC) hipLaunchKernelGGL((cpi_mean_kernel<MODEL, JAC, AVG, LL, 2>), dim3((unsigned)nb), dim3(64), 0, st, CPI_MEAN_LEAD(a), a); \
+        } else if (cut == 1) hipLaunchKernelGGL((cpi_mean_kernel<MODEL, JAC, AVG, LL, 1>), dim3((unsigned)nb), dim3(64), 0, st, CPI_MEAN_LEAD(a), a); \
+        else hipLaunchKernelGGL((cpi_mean_kernel<MODEL, JAC, AVG, LL, 0>), dim3((unsigned)nb), dim3(64), 0, st, CPI_MEAN_LEAD(a), a); \
     } break;
     if constexpr (MODEL == 2 && JAC) { switch (L) { CPI_LAUNCH_L(1) default: break; } } else
     switch (L) {
@@ -110,12 +110,12 @@ static void launch_mean_runs_L(int L, const PreArgs &a, const RunArgs &r, hipStr
     const long long wmin = MODEL == 2 ? (long long)CPI_MEAN_BIG_W_M2 : (long long)CPI_MEAN_BIG_W;
     if (L == 1 && a.K > 0 && a.K < (1ll << 26) && a.W >= wmin && a.N >= CPI_MEAN_BIG_NMIN) {
         hipLaunchKernelGGL((cpi_mean_runs_kernel<MODEL, AVG, 1, true>), dim3((unsigned)((a.W + 63) / 64)), dim3(64),
-                           (size_t)CPI_MEAN_BIG_LDS_PAD, st, a, r);
+                           (size_t)CPI_MEAN_BIG_LDS_PAD, st, CPI_MEAN_LEAD(a), a, r);
         return;
     }
 #define CPI_LAUNCH_R(LL)                                                                         \
     case LL:                                                                                     \
-        hipLaunchKernelGGL((cpi_mean_runs_kernel<MODEL, AVG, LL, false>), dim3((unsigned)((a.W + (64 / LL) - 1) / (64 / LL))), dim3(64), 0, st, a, r); \
+        hipLaunchKernelGGL((cpi_mean_runs_kernel<MODEL, AVG, LL, false>), dim3((unsigned)((a.W + (64 / LL) - 1) / (64 / LL))), dim3(64), 0, st, CPI_MEAN_LEAD(a), a, r); \
         break;
     switch (L) {
         CPI_LAUNCH_R(1) CPI_LAUNCH_R(2) CPI_LAUNCH_R(3) CPI_LAUNCH_R(4) CPI_LAUNCH_R(5) CPI_LAUNCH_R(6) CPI_LAUNCH_R(8)
@@ -134,7 +134,7 @@ template <int MODEL, bool JAC, bool AVG>
 static void launch_mean_carry_L(int L, const PreArgs &a, const CarryArgs &c, hipStream_t st) {
 #define CPI_LAUNCH_C(LL)                                                                         \
     case LL:                                                                                     \
-        hipLaunchKernelGGL((cpi_mean_carry_kernel<MODEL, JAC, AVG, LL>), dim3((unsigned)((a.W + (64 / LL) - 1) / (64 / LL))), dim3(64), 0, st, a, c); \
+        hipLaunchKernelGGL((cpi_mean_carry_kernel<MODEL, JAC, AVG, LL>), dim3((unsigned)((a.W + (64 / LL) - 1) / (64 / LL))), dim3(64), 0, st, CPI_MEAN_LEAD(a), a, c); \
         break;
     if constexpr (MODEL == 2 && JAC) { switch (L) { CPI_LAUNCH_C(1) default: break; } } else
     switch (L) {
@@ -167,8 +167,8 @@ hipError_t mean_tiled(int model, bool avg, bool counted, int S, const TiledArgs 
                 if (e != hipSuccess) return e;                                                                    \
                 *big_lds_set |= bit;                                                                              \
             }                                                                                                     \
-            hipLaunchKernelGGL((cpi_mean_tiled_kernel<M, AV, C, true>), dim3(nb), dim3(64 * S), lds, st, a);      \
-        } else hipLaunchKernelGGL((cpi_mean_tiled_kernel<M, AV, C, false>), dim3(nb), dim3(64), 0, st, a);        \
+            hipLaunchKernelGGL((cpi_mean_tiled_kernel<M, AV, C, true>), dim3(nb), dim3(64 * S), lds, st, CPI_TILED_LEAD(a), a); \
+        } else hipLaunchKernelGGL((cpi_mean_tiled_kernel<M, AV, C, false>), dim3(nb), dim3(64), 0, st, CPI_TILED_LEAD(a), a); \
     } while (0)
     if (model == CPI_MODEL_V1) {
         if (counted) { if (avg) CPI_TILED2(1, true, true); else CPI_TILED2(1, false, true); }

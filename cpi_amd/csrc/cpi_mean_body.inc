@@ -1,7 +1,8 @@
 // cpi_mean_body.inc -- the body of cpi_mean_kernel and cpi_mean_carry_kernel (cpi_mean_kernels.hpp), included inside both.
 // Shared as text rather than through a device function so that the batch kernels compile to exactly the code they had
 // before the carry path existed (a body function changes their scalar register allocation).  In scope where it is
-// included: MODEL, JAC, AVG, L, CUT, BIG, CARRY, the kernel arguments A (PreArgs), CA (CarryArgs) and RA (RunArgs; CUT = 3 only).
+// included: MODEL, JAC, AVG, L, CUT, BIG, CARRY, the kernel arguments A (PreArgs), CA (CarryArgs) and RA (RunArgs; CUT = 3 only),
+// and the preloaded leading parameters knots, lin, W, N, first, count (CPI_MEAN_LEAD_PARAMS), read INSTEAD of their copies in A.
     static_assert(!BIG || (L == 1 && !JAC), "BIG: one lane per window, mean-only");
     constexpr int WPB = 64 / L;       // windows per wavefront
     // knots staged per lane per chunk: measured on MI355X -- 2 when a lane has several intervals (L <= 8; 20 k x 50 with
@@ -17,9 +18,9 @@
     const int lane = threadIdx.x;
     const int grp = lane / L, l = lane - grp * L;
     long long w = (long long)blockIdx.x * WPB + grp;
-    const bool valid = (w < A.W) && (grp < WPB);   // L not a power of two leaves 64 - WPB*L idle lanes
+    const bool valid = (w < W) && (grp < WPB);   // L not a power of two leaves 64 - WPB*L idle lanes
     if (grp >= WPB) w = (long long)blockIdx.x * WPB;   // idle lanes shadow the block's first window (stays near the block)
-    if (w >= A.W) w = A.W - 1;
+    if (w >= W) w = W - 1;
     constexpr bool cut = CUT != 0;
     int n;
     long long k0;
@@ -32,23 +33,23 @@
         // many runs: the run of the wavefront's first window, by a bisection on wave-uniform values (scalar loads); when the
         // run also owns the wavefront's last window -- every wavefront but the few that straddle a run boundary -- that is
         // every lane's run, otherwise each lane bisects for its own.  Then the CUT = 2 arithmetic on the run's readings.
-        const long long wb = (long long)blockIdx.x * WPB, we = min(wb + WPB, A.W) - 1;
+        const long long wb = (long long)blockIdx.x * WPB, we = min(wb + WPB, W) - 1;
         int r = run_of(RA, wb);
         if (!(RA.uoff[r + 1] > we)) r = run_of(RA, w);
-        const RunWindow c = run_window(A.knots, A.K, A.update, RA, r, w);
+        const RunWindow c = run_window(knots, A.K, A.update, RA, r, w);
         if (valid && l == 0) A.count_out[w] = c.cnt;                     // the TRUE count (cpi_stream_counts)
         k0 = c.k0;
-        n = min(c.cnt, A.N);
+        n = min(c.cnt, N);
         t_start = c.t_start;
         t_end = A.update[w];
-        tail = c.tail && c.cnt <= A.N;                                   // a truncated window has lost its tail
+        tail = c.tail && c.cnt <= N;                                   // a truncated window has lost its tail
     } else if constexpr (CUT == 2) {
         // the arithmetic of cpi_cut_windows_kernel (GraphSolver_IMU.cpp:50-69 as a closed form), per lane, in registers
-        const double ts0 = A.knots[0], ts1 = A.knots[(A.K - 1) * 7];
+        const double ts0 = knots[0], ts1 = knots[(A.K - 1) * 7];
         const double T = A.update[w], Tp = A.update[w > 0 ? w - 1 : 0];
         double stT, stP;
-        const long long cT = knots_not_after_near(A.knots, A.K, ts0, ts1, T, stT);
-        const long long cP = knots_not_after_near(A.knots, A.K, ts0, ts1, Tp, stP);
+        const long long cT = knots_not_after_near(knots, A.K, ts0, ts1, T, stT);
+        const long long cP = knots_not_after_near(knots, A.K, ts0, ts1, Tp, stP);
         const long long fp = (w > 0) ? max(cP - 1, 0ll) : 0ll;
         t_start = (w > 0) ? fmax(Tp, ts0) : ts0;
         const long long fu = max(max(cT - 1, 0ll), fp);
@@ -58,15 +59,15 @@
         const int cnt = m + (tl ? 1 : 0);
         if (valid && l == 0) A.count_out[w] = cnt;                       // the TRUE count (cpi_stream_counts)
         k0 = fp;
-        n = min(cnt, A.N);
+        n = min(cnt, N);
         t_end = T;
-        tail = tl && cnt <= A.N;                                         // a truncated window has lost its tail
+        tail = tl && cnt <= N;                                         // a truncated window has lost its tail
     } else {
-        n = A.count ? min(max(A.count[w], 0), A.N) : A.N;   // a count outside [0, N] must not corrupt the packed descriptors
-        k0 = A.first ? A.first[w] : w * (long long)(A.N + 1);
+        n = count ? min(max(count[w], 0), N) : N;   // a count outside [0, N] must not corrupt the packed descriptors
+        k0 = first ? first[w] : w * (long long)(N + 1);
         if constexpr (CUT == 1) {
             t_start = A.tstart[w]; t_end = A.tend[w];
-            tail = (t_end == t_end) && (A.count[w] <= A.N);              // NaN = no tail; a truncated window has lost it
+            tail = (t_end == t_end) && (count[w] <= N);              // NaN = no tail; a truncated window has lost it
         }
     }
     const int per = (n + L - 1) / L;
@@ -87,13 +88,13 @@
     // 13 us launch -- the 64-bit integer arithmetic costs more than the shuffle reduction and the LDS round trip.)
     segdesc[lane] = ((unsigned long long)((k0 + sb) * 7) << 16) | (unsigned long long)(unsigned)len_f;
 
-    const V3 bw = ldv3(A.lin + w * 6), ba = ldv3(A.lin + w * 6 + 3);
+    const V3 bw = ldv3(lin + w * 6), ba = ldv3(lin + w * 6 + 3);
     V3 gk = mk(0, 0, 0);
     if (MODEL == 2) gk = mul(quat_2_Rot(ldq4(A.qk + w * 4)), mk(A.grav[0], A.grav[1], A.grav[2]));
 
     double pk[7];
     {
-        const double *kb = A.knots + (k0 + sb) * 7;
+        const double *kb = knots + (k0 + sb) * 7;
 #pragma unroll
         for (int i = 0; i < 7; i++) pk[i] = kb[i];
         if (cut && s0 == 0) pk[0] = t_start;
@@ -124,7 +125,7 @@
     // several lanes per window (small, latency-bound batches) it loses (10 k windows: 192 -> 205 us), so those keep the stage.
     constexpr bool DIRECT = JAC && (MODEL == 1) && (L == 1);
     if constexpr (DIRECT) {
-        const double *kp = A.knots + (k0 + s0) * 7;
+        const double *kp = knots + (k0 + s0) * 7;
         double nx[7];
         {
             const double *kb = kp + 7 * min(1, len_f);
@@ -162,7 +163,7 @@
     unsigned voff[SEGD];   // byte offset of the element from blk0: the fast path's constant (dense layouts, uniform streams); BIG: of both paths
     int smax[SEGD];
     int tofs[SEGD];             // !BIG (BIG: the tile is flat, element e of lane i at 64 e + i)
-    const double *blk0 = A.knots + (long long)blockIdx.x * WPB * (long long)(A.N + 1) * 7;   // wave-uniform (dense layout)
+    const double *blk0 = knots + (long long)blockIdx.x * WPB * (long long)(N + 1) * 7;   // wave-uniform (dense layout)
     bool fast_stream = false;
     const long long b = k0 + sb;
     long long b0 = 0;
@@ -170,7 +171,7 @@
         // the wavefront's lowest first knot (stream windows out of time order may start below lane 0's)
         const long long bf = readfirstlane64(b);
         b0 = bf - (long long)wave_max((int)min(max(bf - b, 0ll), 0x7fffffffll));
-        blk0 = A.knots + b0 * 7;
+        blk0 = knots + b0 * 7;
     }
     if constexpr (cut) {
         // The stream entry's twin of the dense layout's fast path below: "wave-uniform base + chunk stride in SGPRs + constant
@@ -183,7 +184,7 @@
         const int nch = (maxlen + C - 1) / C;
         const bool ok = (A.K > 0) && (len == maxlen) && (b >= b0) && (b - b0 < (1ll << 24)) && (b + (long long)nch * C <= A.K - 1);
         fast_stream = __all(ok);
-        if (fast_stream) blk0 = A.knots + b0 * 7;
+        if (fast_stream) blk0 = knots + b0 * 7;
     }
     {
         // (Issuing all SEGD descriptor reads before using the first -- one LDS round trip instead of SEGD dependent ones,
@@ -200,7 +201,7 @@
             if constexpr (BIG) {
                 voff[e] = (unsigned)((base - b0 * 7 + (ok ? 7 + off : off - 7 * kn)) * 8);   // < 2^32: the launcher's admission rule
             } else {
-                sptr[e] = A.knots + base + (ok ? 7 + off : off - 7 * kn);
+                sptr[e] = knots + base + (ok ? 7 + off : off - 7 * kn);
                 voff[e] = (unsigned)((sptr[e] - blk0) * 8);   // only used when safe_overread (then 0 <= offset < 2^32)
                 tofs[e] = seg * PITCH + off;
             }
@@ -215,7 +216,7 @@
     // may never have been written -- a NaN there would reach the state through 0 * NaN on the inactive steps.  The
     // per-element path below stops at the segment's end and re-reads its last, valid knot instead.)
     const bool safe_overread = cut ? fast_stream
-                                   : ((A.first == nullptr) && (A.count == nullptr) && ((long long)(blockIdx.x + 1) * WPB + 2 < A.W));
+                                   : ((first == nullptr) && (count == nullptr) && ((long long)(blockIdx.x + 1) * WPB + 2 < W));
     auto issue = [&](int it) {
         if (safe_overread) {
             // scalar base (advanced by SALU) + constant 32-bit lane offsets: no vector arithmetic per element
@@ -321,6 +322,9 @@
     if constexpr (CARRY) { if (cbad) mean_poison(st); }
 
     if (valid && l == 0) {
+        // (Holding write_means and the four pointers in SGPRs from the prologue on takes the kernel-argument loads off the serial
+        // tail, where the compiler puts them between the loop's exit and the tree, but costs 7 SGPRs in every mean-only
+        // instantiation: not done.)
         if (A.write_means) {
             if (A.out.DT) A.out.DT[w] = st.DT;
             if (A.out.alpha) stv3(A.out.alpha + w * 3, st.alpha);

@@ -149,8 +149,17 @@ __device__ __forceinline__ RunWindow run_window(const double *stream, long long 
 // CUT = 3 (cpi_mean_runs_kernel, mean-only requests of cpi_preintegrate_streams): CUT = 2 for windows of many runs -- the
 // prologue first finds the run of its window (RunArgs), then cuts the window out of that run's readings; everything after the
 // prologue is the CUT = 2 path on the whole stream.
+// Kernel-argument preloading (gfx950 delivers the first kernel-argument dwords in SGPRs when the wave is dispatched; build.py
+// passes the backend's preload count): only leading scalar / pointer parameters are preloaded, never the fields of a by-value
+// aggregate, so what the prologue reads before its first vector load travels as leading plain parameters, in order of first use
+// (12 dwords), and the body reads these names instead of the copies in PreArgs, which follows unchanged.
+#define CPI_MEAN_LEAD_PARAMS const double *knots, const double *lin, long long W, int N, const long long *first, const int *count
+#define CPI_MEAN_LEAD(a) (a).knots, (a).lin, (a).W, (a).N, (a).first, (a).count
+// the same for cpi_mean_tiled_kernel (TiledArgs; 14 dwords)
+#define CPI_TILED_LEAD_PARAMS const double *tiles, long long ts, long long ss, long long W, int N, const int *count, const double *lin
+#define CPI_TILED_LEAD(a) (a).tiles, (a).ts, (a).ss, (a).W, (a).N, (a).count, (a).lin
 template <int MODEL, bool JAC, bool AVG, int L, int CUT, bool BIG = false>
-__global__ __launch_bounds__(64, BIG ? 2 : (((MODEL == 2 && !JAC) || (MODEL == 1 && JAC)) && L == 1 ? 2 : CPI_MEAN_WPS)) void cpi_mean_kernel(PreArgs A) {
+__global__ __launch_bounds__(64, BIG ? 2 : (((MODEL == 2 && !JAC) || (MODEL == 1 && JAC)) && L == 1 ? 2 : CPI_MEAN_WPS)) void cpi_mean_kernel(CPI_MEAN_LEAD_PARAMS, PreArgs A) {
     constexpr bool CARRY = false;
     [[maybe_unused]] const CarryArgs CA = {};
     [[maybe_unused]] const RunArgs RA = {};
@@ -158,7 +167,7 @@ __global__ __launch_bounds__(64, BIG ? 2 : (((MODEL == 2 && !JAC) || (MODEL == 1
 }
 // cpi_preintegrate_resume: the plain-knot path of cpi_mean_kernel<MODEL, JAC, AVG, L, 0> from and to carry records
 template <int MODEL, bool JAC, bool AVG, int L>
-__global__ __launch_bounds__(64, (((MODEL == 2 && !JAC) || (MODEL == 1 && JAC)) && L == 1 ? 2 : CPI_MEAN_WPS)) void cpi_mean_carry_kernel(PreArgs A, CarryArgs CA) {
+__global__ __launch_bounds__(64, (((MODEL == 2 && !JAC) || (MODEL == 1 && JAC)) && L == 1 ? 2 : CPI_MEAN_WPS)) void cpi_mean_carry_kernel(CPI_MEAN_LEAD_PARAMS, PreArgs A, CarryArgs CA) {
     constexpr bool CARRY = true;
     constexpr int CUT = 0;
     constexpr bool BIG = false;
@@ -168,7 +177,7 @@ __global__ __launch_bounds__(64, (((MODEL == 2 && !JAC) || (MODEL == 1 && JAC)) 
 // cpi_preintegrate_streams, mean-only: cpi_mean_kernel<MODEL, false, AVG, L, 3, BIG> -- its own __global__ only because the run
 // offsets travel as a second argument (RunArgs) instead of growing PreArgs
 template <int MODEL, bool AVG, int L, bool BIG>
-__global__ __launch_bounds__(64, BIG ? 2 : ((MODEL == 2 && L == 1) ? 2 : CPI_MEAN_WPS)) void cpi_mean_runs_kernel(PreArgs A, RunArgs RA) {
+__global__ __launch_bounds__(64, BIG ? 2 : ((MODEL == 2 && L == 1) ? 2 : CPI_MEAN_WPS)) void cpi_mean_runs_kernel(CPI_MEAN_LEAD_PARAMS, PreArgs A, RunArgs RA) {
     constexpr bool JAC = false;
     constexpr int CUT = 3;
     constexpr bool CARRY = false;
@@ -198,27 +207,27 @@ __global__ __launch_bounds__(64, BIG ? 2 : ((MODEL == 2 && L == 1) ? 2 : CPI_MEA
 // wavefront 0 composes the S segments in order (mean_combine / grav_combine: the composition cpi_mean_kernel uses
 // across the lanes of a window).  Each wavefront still reads one linear stream.
 template <int MODEL, bool AVG, bool COUNTED, bool SPLIT>
-__global__ __launch_bounds__(SPLIT ? 512 : 64, SPLIT ? 1 : CPI_TILED_OCC) void cpi_mean_tiled_kernel(TiledArgs A) {
+__global__ __launch_bounds__(SPLIT ? 512 : 64, SPLIT ? 1 : CPI_TILED_OCC) void cpi_mean_tiled_kernel(CPI_TILED_LEAD_PARAMS, TiledArgs A) {
     constexpr bool GSEG = SPLIT && MODEL == 2;
     constexpr int NF = GSEG ? 34 : 16;            // doubles of a parked segment
     extern __shared__ double seg[];               // [S - 1][NF][64]
     const int lane = threadIdx.x & 63;
     const int j = SPLIT ? (int)(threadIdx.x >> 6) : 0, S = SPLIT ? (int)(blockDim.x >> 6) : 1;
     const long long w = (long long)blockIdx.x * 64 + lane;
-    const bool valid = w < A.W;
-    const long long wc = valid ? w : A.W - 1;
-    const int n = valid ? (COUNTED ? min(max(A.count[wc], 0), A.N) : A.N) : 0;
-    const int nmax = COUNTED ? __builtin_amdgcn_readfirstlane(wave_max(n)) : A.N;
-    const int per = SPLIT ? (A.N + S - 1) / S : A.N;
+    const bool valid = w < W;
+    const long long wc = valid ? w : W - 1;
+    const int n = valid ? (COUNTED ? min(max(count[wc], 0), N) : N) : 0;
+    const int nmax = COUNTED ? __builtin_amdgcn_readfirstlane(wave_max(n)) : N;
+    const int per = SPLIT ? (N + S - 1) / S : N;
     const int sb = __builtin_amdgcn_readfirstlane(j * per), se = min(sb + per, nmax);   // this wavefront's steps
-    const double *tb = A.tiles + (long long)blockIdx.x * A.ts + lane;   // a step of a tile: 448 doubles = 7 fields x 64 windows
-    const V3 bw = ldv3(A.lin + wc * 6), ba = ldv3(A.lin + wc * 6 + 3);
+    const double *tb = tiles + (long long)blockIdx.x * ts + lane;   // a step of a tile: 448 doubles = 7 fields x 64 windows
+    const V3 bw = ldv3(lin + wc * 6), ba = ldv3(lin + wc * 6 + 3);
     V3 gk = mk(0, 0, 0);
     if (MODEL == 2 && j == 0) gk = mul(quat_2_Rot(ldq4(A.qk + wc * 4)), mk(A.grav[0], A.grav[1], A.grav[2]));
     auto load = [&](double (&k)[7], int s) {
         // COUNTED: past its own last knot a lane re-reads that knot (dt = 0) -- what lies behind it in the column is
         // never read.  Otherwise the row offset is wave-uniform (scalar address arithmetic).
-        const double *p = tb + (long long)(COUNTED ? min(s, n) : min(s, A.N)) * A.ss;
+        const double *p = tb + (long long)(COUNTED ? min(s, n) : min(s, N)) * ss;
         // non-temporal: every byte of a tile is read exactly once, by one wavefront (round 4, same-box A/B: 1 M x 50 582-588 ->
         // 565-569 us, model 2 561-576 -> 540 us, 100 k 60.5 -> 56 us; the same hint on the dense layout's staged loads, whose
         // 128-byte lines ARE touched again by the next chunk, costs 35 %: 619 -> 840-874 us)
