@@ -34,12 +34,20 @@ def tumbling_windows(W=32, N=47, seed=901, lo=4.0, hi=70.0):
     return kn, lin, q
 
 
-def tumbling_stream(n, phase, seed=None):
-    """make_stream(20, n, seed = 60 + n, phase) with the gyro columns and the gyro linearisation biases scaled by 25
-    (|w| dt <= 0.32): 20 windows of n whole intervals, + the tail interval when phase > 0 (the first window excepted)."""
-    s, u, lin, q = (t.numpy().copy() for t in synth.make_stream(20, n, seed=60 + n if seed is None else seed, phase=phase))
-    s[:, 1:4] *= 25.0
-    lin[:, 0:3] *= 25.0
+def tumbling_stream(n, phase, seed=None, ramp=None, U=20):
+    """make_stream(U, n, seed = 60 + n, phase) with the gyro columns and the gyro linearisation biases scaled by 25
+    (|w| dt <= 0.38): U windows of n whole intervals, + the tail interval when phase > 0 (the first window excepted).
+    ramp = (lo, hi): the scale rises along the stream instead, linspace(lo, hi) over the readings (the bias of a window with
+    the scale of the reading that opens it) -- with the rate's own swing, neighbouring windows then sit on different paths of
+    sincos_fast, and late tails leave the short polynomial."""
+    s, u, lin, q = (t.numpy().copy() for t in synth.make_stream(U, n, seed=60 + n if seed is None else seed, phase=phase))
+    if ramp is None:
+        s[:, 1:4] *= 25.0
+        lin[:, 0:3] *= 25.0
+        return s, u, lin, q
+    f = np.linspace(ramp[0], ramp[1], len(s))
+    s[:, 1:4] *= f[:, None]
+    lin[:, 0:3] *= f[np.arange(U) * n, None]
     return s, u, lin, q
 
 

@@ -130,6 +130,9 @@ def test_refusals_come_before_the_context(lib, entry):
     a = {"first": np.arange(Cn, dtype=np.int64) * G, "count": np.full(Cn, G, dtype=np.int32), "ffirst": np.arange(Cn, dtype=np.int64) * (G - 1),
          "hess": np.zeros(F * 496), "prior": np.zeros(S * 136), "lambda": np.zeros(Cn), "delta": np.zeros(S * 15),
          "status": np.zeros(Cn, dtype=np.int32), "workspace": np.zeros(lib.cpi_chain_solve_workspace_doubles(S))}
+    # status heads a buffer as long as the workspace: a workspace that begins inside status then ends inside that buffer, wherever
+    # numpy put the other arrays (with delta behind status, "delta overlaps" was reported where "status overlaps" is expected)
+    a["status"] = np.zeros(Cn + 2 * a["workspace"].size, dtype=np.int32)[:Cn]
     ptr = lambda x, off=0: None if x is None else x.ctypes.data + off
 
     def call(C_=Cn, G_=G, S_=S, F_=F, damping=0, **kw):

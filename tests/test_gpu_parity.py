@@ -14,7 +14,7 @@ import pytest
 import torch
 
 from cpi_amd import synth
-from tests.tol import REG_FACTOR, TOL_COV, TOL_FACTOR, TOL_MEAN, check_pre, cov_rel_err
+from tests.tol import REG_FACTOR, TOL_COV, TOL_FACTOR, TOL_JAC, TOL_MEAN, check_pre, cov_rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -597,6 +597,9 @@ def test_large_rotation_angles_take_the_reduced_sincos_path(eng, orc):
         ok = wmax < 1.3
         assert ok.sum() >= 8 and (wmax[ok] > 1.0).any()
         assert cov_rel_err(out["P"][ok], ref["P"][ok]) <= 1e-6
+        # the Jacobians on the same windows (model 2's follow the covariance recursion), relative to their magnitude like the means
+        for k in ("J_q", "J_a", "J_b", "H_a", "H_b") + (("O_a", "O_b") if mode[0] == 2 else ()):
+            assert np.abs(out[k][ok] - ref[k][ok]).max() <= TOL_JAC * max(1.0, np.abs(ref[k][ok]).max()), k
         m = _run(eng, mode, kn, lin, q, want=("mean",))
         assert np.abs(m["q"] - ref["q"]).max() <= 1e-9
 
