@@ -29,6 +29,11 @@ class CpiOutputs(C.Structure):
     _fields_ = [(name, C.c_void_p) for name, _ in OUT_FIELDS]
 
 
+class CpiLmParams(C.Structure):
+    """cpi_lm_params (include/cpi_amd.h: cpi_chain_accept_batch)."""
+    _fields_ = [(name, C.c_double) for name in ("lam_down", "lam_up", "lam_min", "lam_max", "abs_tol", "rel_tol")]
+
+
 class CpiError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("cpi_amd error %d: %s" % (code, msg))
@@ -204,6 +209,13 @@ def load():
     lib.cpi_chain_marginalize_batch.argtypes = [vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp]
     lib.cpi_chain_marginalize_batch_host.argtypes = [vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp]
     lib.cpi_chain_marginalize_batch.restype = lib.cpi_chain_marginalize_batch_host.restype = C.c_int
+    lib.cpi_prior_relinearize_batch.argtypes = lib.cpi_prior_relinearize_batch_host.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, vp]
+    lib.cpi_chain_cost_batch.argtypes = lib.cpi_chain_cost_batch_host.argtypes = [vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp]
+    lib.cpi_chain_accept_batch.argtypes = lib.cpi_chain_accept_batch_host.argtypes = [vp, i64, i64, i64, i64, vp, vp, vp, C.POINTER(CpiLmParams),
+                                                                                      vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    for f in (lib.cpi_prior_relinearize_batch, lib.cpi_prior_relinearize_batch_host, lib.cpi_chain_cost_batch, lib.cpi_chain_cost_batch_host,
+              lib.cpi_chain_accept_batch, lib.cpi_chain_accept_batch_host):
+        f.restype = C.c_int
     lib.cpi_preintegrate_stream_running.argtypes = lib.cpi_preintegrate_stream.argtypes
     lib.cpi_preintegrate_stream_running_host.argtypes = lib.cpi_preintegrate_stream_host.argtypes
     lib.cpi_preintegrate_streams_running.argtypes = lib.cpi_preintegrate_streams.argtypes

@@ -1504,6 +1504,132 @@ extern "C" int cpi_chain_marginalize_batch(cpi_ctx *ctx, int64_t C, int64_t G, i
     return CPI_OK;
 }
 
+// ============================================================================================
+// The Levenberg-Marquardt step per chain: cpi_prior_relinearize_batch, cpi_chain_cost_batch, cpi_chain_accept_batch (cpi_lm.hip)
+// ============================================================================================
+// what the device and the host forms refuse alike, before the context is looked at
+static int lm_prior_check(cpi_ctx *ctx, const char *who, int64_t S, int64_t P, const int32_t *idx, const double *states, const double *anchor,
+                          const double *prior0, double *prior, double *pcost) {
+    if (S < 0 || P < 0) return refuse(ctx, who, "negative size");
+    if (!idx && P > S) return refuse(ctx, who, "P > S with idx NULL (record p belongs to state p)");
+    if (P == 0) return CPI_OK;
+    if ((S > 0 && !states) || !anchor || !prior0) return refuse(ctx, who, "NULL argument");   // S == 0: every record is skipped
+    if (!prior && !pcost) return refuse(ctx, who, "prior and pcost are both NULL");
+    const size_t d = sizeof(double);
+    const Span outs[2] = { { prior, (size_t)S * 136 * d, "prior" }, { pcost, (size_t)S * d, "pcost" } };
+    const Span ins[4] = { { idx, (size_t)P * sizeof(int32_t), "" }, { states, (size_t)S * 16 * d, "" }, { anchor, (size_t)P * 16 * d, "" },
+                          { prior0, (size_t)P * 136 * d, "" } };
+    return refuse_overlaps(ctx, who, outs, 2, ins, 4);
+}
+extern "C" int cpi_prior_relinearize_batch(cpi_ctx *ctx, int64_t S, int64_t P, const int32_t *idx,
+                                           const double *states, const double *anchor, const double *prior0,
+                                           double *prior, double *pcost) {
+    static const char who[] = "cpi_prior_relinearize_batch";
+    CPI_TRY(lm_prior_check(ctx, who, S, P, idx, states, anchor, prior0, prior, pcost));
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (P == 0) return CPI_OK;
+    if (!grid_ok((P + 3) / 4)) return refuse(ctx, who, "P exceeds the 32-bit grid (4 records per workgroup)");
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    LmPriorArgs a;
+    memset(&a, 0, sizeof a);
+    a.S = S; a.P = P; a.idx = idx; a.states = states; a.anchor = anchor; a.prior0 = prior0; a.prior = prior; a.pcost = pcost;
+    launch::lm_prior(a, ctx->stream);
+    CPI_HIP(ctx, hipGetLastError());
+    return CPI_OK;
+}
+
+static int lm_sizes_check(cpi_ctx *ctx, const char *who, int64_t C, int64_t G, int64_t S, int64_t F) {
+    if (C < 0 || S < 0 || F < 0) return refuse(ctx, who, "negative size");
+    if (G < 1) return refuse(ctx, who, "G (the longest chain in states) must be >= 1");
+    if (G > 0x7fffffffLL) return refuse(ctx, who, "G exceeds 2^31 - 1 states per chain");
+    return CPI_OK;
+}
+static int lm_cost_check(cpi_ctx *ctx, const char *who, int64_t C, int64_t G, int64_t S, int64_t F, const int64_t *first, const int32_t *count,
+                         const int64_t *ffirst, const double *chi2, const double *pcost, double *cost) {
+    CPI_TRY(lm_sizes_check(ctx, who, C, G, S, F));
+    if (C == 0) return CPI_OK;
+    if (!chi2 && G > 1) return refuse(ctx, who, "chi2 is NULL (only chains of one state, G == 1, need none)");
+    if (!cost) return refuse(ctx, who, "cost is NULL");
+    const size_t d = sizeof(double);
+    const Span outs[1] = { { cost, (size_t)C * d, "cost" } };
+    const Span ins[5] = { { first, (size_t)C * sizeof(int64_t), "" }, { count, (size_t)C * sizeof(int32_t), "" }, { ffirst, (size_t)C * sizeof(int64_t), "" },
+                          { chi2, (size_t)F * d, "" }, { pcost, (size_t)S * d, "" } };
+    return refuse_overlaps(ctx, who, outs, 1, ins, 5);
+}
+static void lm_cost_args(LmCostArgs &a, int64_t C, int64_t G, int64_t S, int64_t F, const int64_t *first, const int32_t *count,
+                         const int64_t *ffirst, const double *chi2, const double *pcost, double *cost) {
+    memset(&a, 0, sizeof a);
+    a.C = C; a.G = (int)G; a.S = S; a.F = F;
+    a.first = (const long long *)first; a.count = count; a.ffirst = (const long long *)ffirst;
+    a.chi2 = chi2; a.pcost = pcost; a.cost = cost;
+}
+extern "C" int cpi_chain_cost_batch(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_t F,
+                                    const int64_t *first, const int32_t *count, const int64_t *ffirst,
+                                    const double *chi2, const double *pcost, double *cost) {
+    static const char who[] = "cpi_chain_cost_batch";
+    CPI_TRY(lm_cost_check(ctx, who, C, G, S, F, first, count, ffirst, chi2, pcost, cost));
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (C == 0) return CPI_OK;
+    if (!grid_ok((C + 3) / 4)) return refuse(ctx, who, "C exceeds the 32-bit grid (4 chains per workgroup)");
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    LmCostArgs a;
+    lm_cost_args(a, C, G, S, F, first, count, ffirst, chi2, pcost, cost);
+    launch::lm_cost(a, ctx->stream);
+    CPI_HIP(ctx, hipGetLastError());
+    return CPI_OK;
+}
+
+// NULL: the defaults of GTSAM's LevenbergMarquardtParams (lambdaFactor 10, lambdaLowerBound 0, lambdaUpperBound 1e5,
+// absoluteErrorTol / relativeErrorTol 1e-5)
+static const cpi_lm_params kLmDefaults = { 0.1, 10.0, 0.0, 1e5, 1e-5, 1e-5 };
+static int lm_accept_check(cpi_ctx *ctx, const char *who, int64_t C, int64_t G, int64_t S, int64_t F, const int64_t *first, const int32_t *count,
+                           const int64_t *ffirst, const cpi_lm_params *params, const double *chi2_new, const double *pcost_new,
+                           const double *trial, double *cost, double *states, double *chi2, double *lambda, int32_t *phase,
+                           int32_t *accepted) {
+    CPI_TRY(lm_sizes_check(ctx, who, C, G, S, F));
+    const cpi_lm_params &p = params ? *params : kLmDefaults;
+    // every test is written so that a NaN fails it
+    if (!(p.lam_down > 0.0 && p.lam_down <= 1.0 && p.lam_up >= 1.0)) return refuse(ctx, who, "params: 0 < lam_down <= 1 <= lam_up is required");
+    if (!(p.lam_min >= 0.0 && p.lam_min <= p.lam_max)) return refuse(ctx, who, "params: 0 <= lam_min <= lam_max is required");
+    if (!(p.abs_tol >= 0.0 && p.rel_tol >= 0.0)) return refuse(ctx, who, "params: a tolerance is negative or NaN");
+    if (C == 0) return CPI_OK;
+    if (!cost || !lambda || !phase) return refuse(ctx, who, "cost, lambda or phase is NULL");
+    if (S > 0 && (!states || !trial)) return refuse(ctx, who, "states or trial is NULL");
+    if (!chi2_new && G > 1) return refuse(ctx, who, "chi2_new is NULL (only chains of one state, G == 1, need none)");
+    const size_t d = sizeof(double);
+    const Span outs[6] = { { cost, (size_t)C * d, "cost" }, { states, (size_t)S * 16 * d, "states" }, { chi2, (size_t)F * d, "chi2" },
+                           { lambda, (size_t)C * d, "lambda" }, { phase, (size_t)C * sizeof(int32_t), "phase" },
+                           { accepted, (size_t)C * sizeof(int32_t), "accepted" } };
+    const Span ins[6] = { { first, (size_t)C * sizeof(int64_t), "" }, { count, (size_t)C * sizeof(int32_t), "" }, { ffirst, (size_t)C * sizeof(int64_t), "" },
+                          { chi2_new, (size_t)F * d, "" }, { pcost_new, (size_t)S * d, "" }, { trial, (size_t)S * 16 * d, "" } };
+    return refuse_overlaps(ctx, who, outs, 6, ins, 6);
+}
+extern "C" int cpi_chain_accept_batch(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_t F,
+                                      const int64_t *first, const int32_t *count, const int64_t *ffirst,
+                                      const cpi_lm_params *params,
+                                      const double *chi2_new, const double *pcost_new, const double *trial,
+                                      double *cost, double *states, double *chi2, double *lambda,
+                                      int32_t *phase, int32_t *accepted) {
+    static const char who[] = "cpi_chain_accept_batch";
+    CPI_TRY(lm_accept_check(ctx, who, C, G, S, F, first, count, ffirst, params, chi2_new, pcost_new, trial, cost, states, chi2, lambda, phase, accepted));
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (C == 0) return CPI_OK;
+    if (!grid_ok((C + 3) / 4)) return refuse(ctx, who, "C exceeds the 32-bit grid (4 chains per workgroup)");
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    LmCostArgs a;
+    lm_cost_args(a, C, G, S, F, first, count, ffirst, chi2_new, pcost_new, cost);
+    LmAcceptArgs b;
+    memset(&b, 0, sizeof b);
+    b.p = params ? *params : kLmDefaults;
+    b.trial = trial; b.states = states; b.chi2 = chi2; b.lambda = lambda; b.phase = phase; b.accepted = accepted;
+    launch::lm_accept(a, b, ctx->stream);
+    CPI_HIP(ctx, hipGetLastError());
+    return CPI_OK;
+}
+
 extern "C" size_t cpi_outputs_slab_doubles(const cpi_outputs *mask, int64_t Wb) {
     if (!mask || Wb <= 0) return 0;
     size_t n = 0;
@@ -3030,5 +3156,109 @@ extern "C" int cpi_chain_marginalize_batch_host(cpi_ctx *ctx, int64_t C, int64_t
     CPI_TRY(cpi_chain_marginalize_batch(ctx, C, G, S, F, in.first, in.count, in.ffirst, in.hess, in.prior, M, dm, dout, ds));
     CPI_TRY(st.download(out, (const double *)dout, (size_t)C * 136));
     if (status) CPI_TRY(st.download(status, (const int32_t *)ds, (size_t)C));
+    return st.finish();
+}
+
+// cpi_prior_relinearize_batch / cpi_chain_cost_batch / cpi_chain_accept_batch from host memory: every array a host array, staged whole,
+// synchronous.  Outputs and in/out arrays travel up before the kernel, so that what nobody writes comes back as the caller left it.
+extern "C" int cpi_prior_relinearize_batch_host(cpi_ctx *ctx, int64_t S, int64_t P, const int32_t *idx,
+                                                const double *states, const double *anchor, const double *prior0,
+                                                double *prior, double *pcost) {
+    static const char who[] = "cpi_prior_relinearize_batch_host";
+    CPI_TRY(lm_prior_check(ctx, who, S, P, idx, states, anchor, prior0, prior, pcost));
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (P == 0) return CPI_OK;
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    Staging st(ctx);
+    const int32_t *di;
+    const double *ds, *da, *d0, *dp = nullptr, *dc = nullptr;
+    CPI_TRY(st.upload(idx, (size_t)P, &di));
+    CPI_TRY(st.upload(S > 0 ? states : nullptr, (size_t)S * 16, &ds));
+    CPI_TRY(st.upload(anchor, (size_t)P * 16, &da));
+    CPI_TRY(st.upload(prior0, (size_t)P * 136, &d0));
+    if (S > 0 && prior) CPI_TRY(st.upload((const double *)prior, (size_t)S * 136, &dp));
+    if (S > 0 && pcost) CPI_TRY(st.upload((const double *)pcost, (size_t)S, &dc));
+    if (S == 0) return st.finish();                    // every record is skipped
+    CPI_TRY(cpi_prior_relinearize_batch(ctx, S, P, di, ds, da, d0, const_cast<double *>(dp), const_cast<double *>(dc)));
+    if (prior) CPI_TRY(st.download(prior, dp, (size_t)S * 136));
+    if (pcost) CPI_TRY(st.download(pcost, dc, (size_t)S));
+    return st.finish();
+}
+
+// first / count / ffirst and the two term arrays of a chain cost, staged whole
+struct LmTermsDev {
+    const int64_t *first, *ffirst;
+    const int32_t *count;
+    const double *chi2, *pcost;
+};
+static int stage_lm_terms(Staging &st, int64_t C, int64_t G, int64_t S, int64_t F, const int64_t *first, const int32_t *count, const int64_t *ffirst,
+                          const double *chi2, const double *pcost, LmTermsDev *d) {
+    CPI_TRY(st.upload(first, (size_t)C, &d->first));
+    CPI_TRY(st.upload(count, (size_t)C, &d->count));
+    CPI_TRY(st.upload(ffirst, (size_t)C, &d->ffirst));
+    CPI_TRY(st.upload(F > 0 ? chi2 : nullptr, (size_t)F, &d->chi2));
+    CPI_TRY(st.upload(S > 0 ? pcost : nullptr, (size_t)S, &d->pcost));
+    if (!d->chi2 && G > 1) {   // F == 0: no chain has a factor (the ranges are validated), and the device form wants a pointer it never reads
+        double *none;
+        CPI_TRY(st.alloc((size_t)1, &none));
+        d->chi2 = none;
+    }
+    return CPI_OK;
+}
+extern "C" int cpi_chain_cost_batch_host(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_t F,
+                                         const int64_t *first, const int32_t *count, const int64_t *ffirst,
+                                         const double *chi2, const double *pcost, double *cost) {
+    static const char who[] = "cpi_chain_cost_batch_host";
+    CPI_TRY(lm_cost_check(ctx, who, C, G, S, F, first, count, ffirst, chi2, pcost, cost));
+    CPI_TRY(chain_ranges_check(ctx, who, C, G, S, F, first, count, ffirst));
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (C == 0) return CPI_OK;
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    Staging st(ctx);
+    LmTermsDev in;
+    double *dc;
+    CPI_TRY(stage_lm_terms(st, C, G, S, F, first, count, ffirst, chi2, pcost, &in));
+    CPI_TRY(st.alloc((size_t)C, &dc));
+    CPI_TRY(cpi_chain_cost_batch(ctx, C, G, S, F, in.first, in.count, in.ffirst, in.chi2, in.pcost, dc));
+    CPI_TRY(st.download(cost, (const double *)dc, (size_t)C));
+    return st.finish();
+}
+extern "C" int cpi_chain_accept_batch_host(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_t F,
+                                           const int64_t *first, const int32_t *count, const int64_t *ffirst,
+                                           const cpi_lm_params *params,
+                                           const double *chi2_new, const double *pcost_new, const double *trial,
+                                           double *cost, double *states, double *chi2, double *lambda,
+                                           int32_t *phase, int32_t *accepted) {
+    static const char who[] = "cpi_chain_accept_batch_host";
+    CPI_TRY(lm_accept_check(ctx, who, C, G, S, F, first, count, ffirst, params, chi2_new, pcost_new, trial, cost, states, chi2, lambda, phase, accepted));
+    CPI_TRY(chain_ranges_check(ctx, who, C, G, S, F, first, count, ffirst));
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (C == 0) return CPI_OK;
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    Staging st(ctx);
+    LmTermsDev in;
+    const double *dt, *dcost, *dstates, *dchi2 = nullptr, *dlam;
+    const int32_t *dphase;
+    int32_t *dacc = nullptr;
+    CPI_TRY(stage_lm_terms(st, C, G, S, F, first, count, ffirst, chi2_new, pcost_new, &in));
+    CPI_TRY(st.upload(S > 0 ? trial : nullptr, (size_t)S * 16, &dt));
+    CPI_TRY(st.upload((const double *)cost, (size_t)C, &dcost));
+    CPI_TRY(st.upload(S > 0 ? (const double *)states : nullptr, (size_t)S * 16, &dstates));
+    if (F > 0 && chi2) CPI_TRY(st.upload((const double *)chi2, (size_t)F, &dchi2));
+    CPI_TRY(st.upload((const double *)lambda, (size_t)C, &dlam));
+    CPI_TRY(st.upload((const int32_t *)phase, (size_t)C, &dphase));
+    if (accepted) CPI_TRY(st.alloc((size_t)C, &dacc));
+    CPI_TRY(cpi_chain_accept_batch(ctx, C, G, S, F, in.first, in.count, in.ffirst, params, in.chi2, in.pcost, dt, const_cast<double *>(dcost),
+                                   const_cast<double *>(dstates), const_cast<double *>(dchi2), const_cast<double *>(dlam),
+                                   const_cast<int32_t *>(dphase), dacc));
+    CPI_TRY(st.download(cost, dcost, (size_t)C));
+    if (S > 0) CPI_TRY(st.download(states, dstates, (size_t)S * 16));
+    if (dchi2) CPI_TRY(st.download(chi2, dchi2, (size_t)F));
+    CPI_TRY(st.download(lambda, dlam, (size_t)C));
+    CPI_TRY(st.download(phase, dphase, (size_t)C));
+    if (accepted) CPI_TRY(st.download(accepted, (const int32_t *)dacc, (size_t)C));
     return st.finish();
 }

@@ -1,6 +1,6 @@
 // cpi_args.hpp -- kernel argument blocks and the launcher interface between the translation units of libcpi_amd.so.
 //
-// The library is seventeen translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
+// The library is eighteen translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
 //   cpi_mean.hip    cpi_mean_kernel / cpi_mean_tiled_kernel / cpi_tile_*_kernel       (cpi_mean_kernels.hpp)
 //   cpi_running.hip cpi_mean_running_kernel / cpi_mean_stream_running_kernel: a row after every interval, from plain knots /
 //                   from windows cut out of IMU stream(s) in place         (cpi_running_kernels.hpp, cpi_running_body.inc)
@@ -36,6 +36,9 @@
 //   cpi_marginalize.hip  cpi_marginalize_kernel: the leading states of every chain eliminated into a prior on the first
 //                   state that stays -- the forward half of the solve, undamped, no workspace
 //                                 (cpi_marginalize_kernels.hpp over cpi_factor_kernels.hpp's DPP multiply-adds; cpi_chain_util.hpp)
+//   cpi_lm.hip      cpi_lm_prior_kernel / cpi_lm_cost_kernel / cpi_lm_accept_kernel: the Levenberg-Marquardt step per chain -- the prior
+//                   at the current states with its cost, the objective per chain, and the decision (accept, copy, lambda, phase)
+//                                                                                  (cpi_lm_kernels.hpp; cpi_chain_util.hpp)
 //   cpi_factor.hip  evaluateError sweeps, square-root information, Hessian blocks, state prediction
 //                                                                                      (cpi_factor_kernels.hpp)
 //   cpi_abi.hip     the C-ABI of include/cpi_amd.h: argument checks, launch heuristics, device sets (RCCL), the
@@ -256,6 +259,39 @@ struct MarginalizeArgs {
     int *status;             // [C] or NULL
 };
 
+// cpi_prior_relinearize_batch: record p belongs to state idx[p] (NULL: p); an index outside [0, S) skips the record where it is read.
+struct LmPriorArgs {
+    long long S, P;
+    const int *idx;          // [P] or NULL
+    const double *states;    // [S][16]
+    const double *anchor;    // [P][16]
+    const double *prior0;    // [P][136]
+    double *prior;           // [S][136] or NULL
+    double *pcost;           // [S] or NULL
+};
+
+// cpi_chain_cost_batch / cpi_chain_accept_batch: the chains of cpi_chain_solve_batch (the same clamps; cpi_chain_util.hpp: chain_range).
+struct LmCostArgs {
+    long long C;             // chains
+    int G;                   // the longest chain in states, >= 1
+    long long S, F;          // rows of pcost / states; rows of chi2
+    const long long *first;  // [C] or NULL: chain c starts at state c * G
+    const int *count;        // [C] or NULL: every chain has G states
+    const long long *ffirst; // [C] or NULL: first[c] - c
+    const double *chi2;      // [F] or NULL (G == 1); the trial's chi2 for the accept kernel
+    const double *pcost;     // [S] or NULL; the trial's for the accept kernel
+    double *cost;            // [C]: out (cost), in/out (accept)
+};
+struct LmAcceptArgs {
+    cpi_lm_params p;         // validated by the entry (include/cpi_amd.h)
+    const double *trial;    // [S][16]
+    double *states;          // [S][16] in/out
+    double *chi2;            // [F] in/out or NULL
+    double *lambda;          // [C] in/out
+    int *phase;              // [C] in/out
+    int *accepted;           // [C] or NULL
+};
+
 struct PredictArgs {
     long long F;
     double grav[3];
@@ -342,6 +378,10 @@ void chain_solve(const ChainArgs &a, hipStream_t st);
 void chain_marginals(const MarginalsArgs &a, hipStream_t st);
 // ---- cpi_marginalize.hip (cpi_chain_marginalize_batch)
 void chain_marginalize(const MarginalizeArgs &a, hipStream_t st);
+// ---- cpi_lm.hip (cpi_prior_relinearize_batch, cpi_chain_cost_batch, cpi_chain_accept_batch)
+void lm_prior(const LmPriorArgs &a, hipStream_t st);
+void lm_cost(const LmCostArgs &a, hipStream_t st);
+void lm_accept(const LmCostArgs &a, const LmAcceptArgs &b, hipStream_t st);
 // ---- cpi_factor.hip
 void factor(int model, bool whiten, int lpf, const FactorArgs &a, hipStream_t st);            // lpf 16 | 8 | 4
 void factor_packed(int model, int lpf, const FactorArgs &a, double *packed, hipStream_t st);  // lpf 2 | 3 | 4 | 6 | 8

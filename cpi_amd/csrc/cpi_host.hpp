@@ -987,6 +987,62 @@ inline std::vector<double> chain_marginalize(const Context &ctx, int64_t C, int6
     return out;
 }
 
+// The Levenberg-Marquardt step per chain (cpi_prior_relinearize_batch_host, cpi_chain_cost_batch_host, cpi_chain_accept_batch_host: the
+// device kernels' bits), for C chains of G states back to back.
+// prior_relinearize: the priors of P records at `states` [S * 16] -- anchor [P * 16] the state each was linearised at, prior0 [P * 136]
+// = [Lam eta0; . .], idx empty (record p belongs to state p) or [P].  Returns the prior rows [S * 136] chain_solve takes and pcost [S];
+// rows of states without a record are zero.
+struct PriorRows {
+    std::vector<double> prior, pcost;
+};
+inline PriorRows prior_relinearize(const Context &ctx, const std::vector<double> &states, const std::vector<double> &anchor,
+                                   const std::vector<double> &prior0, const std::vector<int32_t> &idx = {}) {
+    const size_t S = states.size() / 16, P = anchor.size() / 16;
+    if (states.size() != S * 16 || anchor.size() != P * 16 || prior0.size() != P * 136 || (!idx.empty() && idx.size() != P) || (idx.empty() && P > S))
+        throw std::invalid_argument("cpi_host::prior_relinearize: states [S * 16], anchor [P * 16], prior0 [P * 136], idx empty (P <= S) or [P]");
+    PriorRows r;
+    r.prior.assign(S * 136, 0.0);
+    r.pcost.assign(S, 0.0);
+    if (P && S)
+        ctx.check(cpi_prior_relinearize_batch_host(ctx.get(), (int64_t)S, (int64_t)P, idx.empty() ? nullptr : idx.data(), states.data(), anchor.data(),
+                                                   prior0.data(), r.prior.data(), r.pcost.data()));
+    return r;
+}
+// chain_cost: cost[c] = 0.5 sum of the chain's chi2 rows + the sum of its pcost rows, in the fixed summation shape of include/cpi_amd.h.
+// chi2 [C * (G - 1)] (cpi_factor_cost_*), pcost empty or [C * G].
+inline std::vector<double> chain_cost(const Context &ctx, int64_t C, int64_t G, const std::vector<double> &chi2, const std::vector<double> &pcost = {}) {
+    if (C < 0 || G < 1 || chi2.size() != (size_t)(C * (G - 1)) || (!pcost.empty() && pcost.size() != (size_t)(C * G)))
+        throw std::invalid_argument("cpi_host::chain_cost: chi2 [C * (G - 1)], pcost empty or [C * G]");
+    std::vector<double> cost((size_t)C);
+    static const double none = 0.0;      // G == 1: no factor rows; G > 1 with C == 0: never read
+    ctx.check(cpi_chain_cost_batch_host(ctx.get(), C, G, C * G, C * (G - 1), nullptr, nullptr, nullptr, chi2.empty() ? &none : chi2.data(),
+                                        pcost.empty() ? nullptr : pcost.data(), cost.data()));
+    return cost;
+}
+// chain_accept: the decision, on what the loop keeps per chain.  st is updated in place as include/cpi_amd.h says (an accepted chain
+// takes the trial's rows, the new cost and a smaller lambda; a rejected one a larger lambda; phase: CPI_LM_*); returns accepted [C].
+// params NULL: the library's defaults.
+struct LmState {
+    std::vector<double> cost, states, chi2, lambda;   // [C], [C * G * 16], [C * (G - 1)] or empty (not kept), [C]
+    std::vector<int32_t> phase;                       // [C]
+};
+inline std::vector<int32_t> chain_accept(const Context &ctx, int64_t C, int64_t G, const std::vector<double> &chi2_new,
+                                         const std::vector<double> &pcost_new, const std::vector<double> &trial, LmState &st,
+                                         const cpi_lm_params *params = nullptr) {
+    if (C < 0 || G < 1 || chi2_new.size() != (size_t)(C * (G - 1)) || (!pcost_new.empty() && pcost_new.size() != (size_t)(C * G)) ||
+        trial.size() != (size_t)(C * G) * 16 || st.states.size() != trial.size() || st.cost.size() != (size_t)C || st.lambda.size() != (size_t)C ||
+        st.phase.size() != (size_t)C || (!st.chi2.empty() && st.chi2.size() != chi2_new.size()))
+        throw std::invalid_argument("cpi_host::chain_accept: chi2_new [C * (G - 1)], pcost_new empty or [C * G], trial and st.states [C * G * 16], "
+                                    "st.cost / lambda / phase [C], st.chi2 empty or [C * (G - 1)]");
+    std::vector<int32_t> accepted((size_t)C, 0);
+    static const double none = 0.0;
+    ctx.check(cpi_chain_accept_batch_host(ctx.get(), C, G, C * G, C * (G - 1), nullptr, nullptr, nullptr, params,
+                                          chi2_new.empty() ? &none : chi2_new.data(), pcost_new.empty() ? nullptr : pcost_new.data(), trial.data(),
+                                          st.cost.data(), st.states.data(), st.chi2.empty() ? nullptr : st.chi2.data(), st.lambda.data(),
+                                          st.phase.data(), accepted.data()));
+    return accepted;
+}
+
 // ---- the caller's loop for MANY windows at once --------------------------------------------------------------------
 // What GraphSolver keeps between two states is a deque of IMU readings (GraphSolver.h: imu_times / imu_linaccs /
 // imu_angvel, filled by addmeasurement_imu); createimufactor_cpi_v1 / _v2 (GraphSolver_IMU.cpp:34-134) walk it up to the

@@ -1858,6 +1858,86 @@ CPI_HD int marginalize_chain(int n, int m, const double *hess, const double *pri
         for (int i = 0; i < PRIOR_D; i++) out[i] = NAN;
     return status;
 }
+
+// ------------------------------------------------------------------------------------------
+// The Levenberg-Marquardt step per chain (cpi_lm_kernels.hpp; tests/hostsim/hostsim_lm.cpp is the host restatement): the prior at the
+// current states with its cost, the objective of a chain, and the decision.
+//
+// cpi_prior_relinearize_batch, one record: xi = local_coordinates(state, anchor); P0 = [Lam eta0; . .] in the packing of a prior row.
+//   eta_i = the fma chain k = 0 .. 14 ascending that STARTS FROM eta0_i: acc = fma(Lam[i][k], xi[k], acc)      (prior_eta_row)
+//   t_i   = eta_i + eta0_i
+//   pcost = 0.5 * (the fma chain i = 0 .. 14 ascending from +0.0: acc = fma(xi[i], t_i, acc))                 (prior_cost)
+//         = 0.5 xi^T Lam xi + eta0^T xi: the prior's cost up to the constant that marginalisation drops.
+// eta is the negative gradient, the sign convention of the solve.  Entry 135 of P0 is never read.
+CPI_HD double prior_eta_row(const double *P0, const double *xi, int i) {
+    double acc = P0[tri(15) + i];
+    for (int k = 0; k < 15; k++) acc = fma(sym_at(P0, i, k), xi[k], acc);
+    return acc;
+}
+CPI_HD double prior_cost(const double *xi, const double *t) {
+    double acc = 0.0;
+    for (int i = 0; i < 15; i++) acc = fma(xi[i], t[i], acc);
+    return 0.5 * acc;
+}
+// row: NULL or [136] (the Lam bits copied, eta, entry 135 = 0.0); pcost: NULL or one double
+CPI_HD void prior_relinearize(const double *xi, const double *P0, double *row, double *pcost) {
+    double eta[15], t[15];
+    for (int i = 0; i < 15; i++) {
+        eta[i] = prior_eta_row(P0, xi, i);
+        t[i] = eta[i] + P0[tri(15) + i];
+    }
+    if (row) {
+        for (int i = 0; i < tri(15); i++) row[i] = P0[i];
+        for (int i = 0; i < 15; i++) row[tri(15) + i] = eta[i];
+        row[PRIOR_D - 1] = 0.0;
+    }
+    if (pcost) *pcost = prior_cost(xi, t);
+}
+
+// cpi_chain_cost_batch, one chain of n states: cost = 0.5 sum_k chi2[k] + sum_s pcost[s] in a FIXED shape (tests reproduce it bit for
+// bit).  Sixteen slots q: a_q = the plain sum from +0.0 of chi2[k], k = q, q + 16, ... < n - 1 ascending; b_q the same over pcost[s],
+// s < n; v_q = 0.5 * a_q + b_q with the product and the sum each rounded; then the butterfly v_q = v_q + v_{q ^ 8}, ^ 4, ^ 2, ^ 1 (the
+// sums commute: every slot ends with the same bits).  chi2 / pcost: the chain's rows or NULL (no term).  n = 0 gives +0.0.
+CPI_HD double chain_cost_slot(int n, const double *chi2, const double *pcost, int q) {
+    double a = 0.0, b = 0.0;
+    if (chi2) for (int k = q; k < n - 1; k += 16) a = a + chi2[k];
+    if (pcost) for (int s = q; s < n; s += 16) b = b + pcost[s];
+    double h = 0.5 * a;
+    CPI_ROUNDED(h);
+    return h + b;
+}
+CPI_HD double chain_cost(int n, const double *chi2, const double *pcost) {
+    double v[16], w[16];
+    for (int q = 0; q < 16; q++) v[q] = chain_cost_slot(n, chi2, pcost, q);
+    for (int s = 8; s >= 1; s >>= 1) {
+        for (int q = 0; q < 16; q++) w[q] = v[q] + v[q ^ s];
+        for (int q = 0; q < 16; q++) v[q] = w[q];
+    }
+    return v[0];
+}
+
+// cpi_chain_accept_batch, the rule of one running chain with states: cur = cost[c], nw = the trial's cost.  Returns 1 when the step
+// is accepted (the caller copies the rows and writes cost = nw); lambda and phase are updated in place (phase: 0 running, 1 converged,
+// 2 gave up -- CPI_LM_* of include/cpi_amd.h).  Every comparison is false for NaN: a NaN nw or cur is a rejection that raises lambda
+// until lam_max is passed.
+struct LmParams { double lam_down, lam_up, lam_min, lam_max, abs_tol, rel_tol; };
+CPI_HD int lm_decide(double cur, double nw, const LmParams &p, double &lambda, int &phase) {
+    if (nw < cur) {
+        const double l = lambda * p.lam_down;
+        lambda = (l > p.lam_min) ? l : p.lam_min;
+        const double dec = cur - nw;
+        if (dec <= p.abs_tol || dec <= p.rel_tol * fabs(cur)) phase = 1;
+        return 1;
+    }
+    const double ra = p.rel_tol * fabs(cur), tol = (p.abs_tol > ra) ? p.abs_tol : ra;
+    if (fabs(nw - cur) <= tol) {
+        phase = 1;                                    // stalled inside the tolerance: lambda stays
+    } else {
+        const double l = lambda * p.lam_up;
+        if (!(l <= p.lam_max)) phase = 2; else lambda = l;
+    }
+    return 0;
+}
 }  // namespace chn
 
 }  // namespace cpi

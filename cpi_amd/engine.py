@@ -10,12 +10,13 @@
 PyTorch is used for device memory and streams only.
 """
 import ctypes as C
+from ctypes import byref
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import OUT_FIELDS, CpiError, CpiOutputs, CpiParams
+from ._lib import OUT_FIELDS, CpiError, CpiLmParams, CpiOutputs, CpiParams
 
 DEFAULT_SIGMAS = (0.005, 4e-6, 0.01, 2e-4)   # ADIS16448, cpi_compare/launch/synthetic_test.launch:13-17
 DEFAULT_GRAV = (0.0, 0.0, 9.8)
@@ -1294,9 +1295,10 @@ class Engine:
         idx_i = (f[:, None] + k)[k < nf[:, None]]
         return idx_i.to(torch.int32).contiguous(), (idx_i + 1).to(torch.int32).contiguous()
 
-    def _chain_args(self, hess, C, G, first, count, ffirst, prior, lam, damping, out, status, cuda):
+    @staticmethod
+    def _chain_ranges(C, G, first, count, ffirst, cuda):
+        """What every entry of the chain family checks of first / count / ffirst; returns C."""
         where = "CUDA" if cuda else "CPU"
-        assert damping in self.DAMPING, "damping: 'identity' or 'diagonal'"
         for name, t, dt in (("first", first, torch.int64), ("count", count, torch.int32), ("ffirst", ffirst, torch.int64)):
             assert t is None or (t.dtype == dt and t.is_contiguous() and t.is_cuda == cuda and t.dim() == 1), \
                 "%s: a contiguous %s %s tensor [C]" % (name, str(dt).split(".")[1], where)
@@ -1305,6 +1307,12 @@ class Engine:
         assert C is not None, "C: the number of chains (or first / count / ffirst, which have it)"
         assert all(t is None or t.shape[0] == C for t in (first, count, ffirst)), "first / count / ffirst: [C]"
         assert G is not None and G >= 1, "G: the longest chain in states, >= 1"
+        return int(C)
+
+    def _chain_args(self, hess, C, G, first, count, ffirst, prior, lam, damping, out, status, cuda):
+        where = "CUDA" if cuda else "CPU"
+        assert damping in self.DAMPING, "damping: 'identity' or 'diagonal'"
+        C = self._chain_ranges(C, G, first, count, ffirst, cuda)
         if hess is not None:
             self._trial_tensor(hess, 496, cuda, "hess")
         if prior is not None:
@@ -1478,6 +1486,217 @@ class Engine:
         return out
 
 
+    # ------------------------------------------------------------------ the Levenberg-Marquardt step per chain
+    LM_DEFAULTS = (0.1, 10.0, 0.0, 1e5, 1e-5, 1e-5)     # cpi_lm_params NULL: the defaults of GTSAM's LevenbergMarquardtParams
+    LM_RUNNING, LM_CONVERGED, LM_GAVE_UP = 0, 1, 2
+
+    @staticmethod
+    def _lm_params(params):
+        """None (the library's defaults), a dict with any of lam_down, lam_up, lam_min, lam_max, abs_tol, rel_tol, or six numbers."""
+        if params is None:
+            return None
+        if isinstance(params, CpiLmParams):
+            return params
+        names = [n for n, _ in CpiLmParams._fields_]
+        vals = dict(zip(names, Engine.LM_DEFAULTS))
+        if isinstance(params, dict):
+            assert set(params) <= set(names), "params: keys among %s" % ", ".join(names)
+            vals.update(params)
+        else:
+            assert len(params) == 6, "params: None, a dict, or the six numbers of cpi_lm_params"
+            vals = dict(zip(names, params))
+        p = CpiLmParams()
+        for n in names:
+            setattr(p, n, float(vals[n]))
+        return p
+
+    @staticmethod
+    def _lm_vector(t, n, dt, cuda, name):
+        assert t.dtype == dt and t.is_contiguous() and t.is_cuda == cuda and t.shape == (n,), \
+            "%s: a contiguous %s %s tensor [%d]" % (name, str(dt).split(".")[1], "CUDA" if cuda else "CPU", n)
+
+    def _prior_relinearize(self, fn, states, anchor, prior0, idx, out, pcost, want_prior, want_cost, cuda):
+        self._trial_tensor(states, 16, cuda, "states")
+        S, P = states.shape[0], anchor.shape[0]
+        self._trial_tensor(anchor, 16, cuda, "anchor")
+        self._trial_tensor(prior0, 136, cuda, "prior0", P)
+        if idx is not None:
+            self._lm_vector(idx, P, torch.int32, cuda, "idx")
+        else:
+            assert P <= S, "idx=None: record p belongs to state p, so P <= S"
+        dev = states.device
+        # rows of states without a record are not written: zeros in what this call allocates (no prior there, no cost)
+        if out is None and want_prior:
+            out = torch.zeros((S, 136), dtype=torch.float64, device=dev)
+        if pcost is None and want_cost:
+            pcost = torch.zeros((S,), dtype=torch.float64, device=dev)
+        assert out is not None or pcost is not None, "at least one of the prior rows and pcost"
+        if out is not None:
+            self._trial_tensor(out, 136, cuda, "out", S)
+        if pcost is not None:
+            self._lm_vector(pcost, S, torch.float64, cuda, "pcost")
+        self._sync_stream()
+        self._check(fn(self.ctx, S, P, _ptr(idx), _ptr(states), _ptr(anchor), _ptr(prior0), _ptr(out), _ptr(pcost)))
+        return out, pcost
+
+    def prior_relinearize(self, states, anchor, prior0, idx=None, out=None, pcost=None, want_prior=True, want_cost=True):
+        """cpi_prior_relinearize_batch: the priors of P records at the current states and their cost.  states [S,16]; anchor [P,16] the
+        state each prior was linearised at; prior0 [P,136] = [Lam eta0; . .] (a row of chain_marginalize as it is; eta0 = 0 for a
+        Gaussian centred on anchor); idx None (record p belongs to state p) or int32 [P] (an index outside [0, S) skips the record).
+        Returns (prior [S,136], pcost [S]): row s = [Lam, eta = eta0 + Lam xi, 0] with xi = local_coordinates(states[s], anchor[p]) --
+        what chain_solve takes as prior --, pcost[s] = 0.5 xi^T Lam xi + eta0^T xi.  out= / pcost= re-use tensors (graph capture);
+        want_prior=False / want_cost=False leave that output out (None is returned in its place) unless a tensor is given for it.
+        Rows of states without a record are not written: zeros in what this call allocates.  Asynchronous."""
+        return self._prior_relinearize(self.lib.cpi_prior_relinearize_batch, states, anchor, prior0, idx, out, pcost, want_prior, want_cost, True)
+
+    def prior_relinearize_host(self, states, anchor, prior0, idx=None, out=None, pcost=None, want_prior=True, want_cost=True):
+        """prior_relinearize on CPU tensors (cpi_prior_relinearize_batch_host): synchronous, the device form's bits."""
+        return self._prior_relinearize(self.lib.cpi_prior_relinearize_batch_host, states, anchor, prior0, idx, out, pcost, want_prior, want_cost,
+                                       False)
+
+    def _lm_sizes(self, C, G, first, count, ffirst, chi2, pcost, S, cuda):
+        C_ = self._chain_ranges(C, G, first, count, ffirst, cuda)
+        if chi2 is not None:
+            self._lm_vector(chi2, chi2.shape[0] if chi2.dim() == 1 else -1, torch.float64, cuda, "chi2")
+        if pcost is not None:
+            self._lm_vector(pcost, pcost.shape[0] if pcost.dim() == 1 else -1, torch.float64, cuda, "pcost")
+        if S is None:
+            S = pcost.shape[0] if pcost is not None else (C_ * int(G) if first is None else None)
+        assert S is not None, "S: the number of state rows -- from pcost, from C * G when first is None, else the caller's"
+        assert pcost is None or pcost.shape[0] == S, "pcost: [S]"
+        return C_, int(G), int(S), (chi2.shape[0] if chi2 is not None else 0)
+
+    def _chain_cost(self, fn, chi2, pcost, C, G, first, count, ffirst, S, out, cuda):
+        C_, G_, S, F = self._lm_sizes(C, G, first, count, ffirst, chi2, pcost, S, cuda)
+        if out is None:
+            out = torch.empty((C_,), dtype=torch.float64, device=self.device if cuda else "cpu")
+        self._lm_vector(out, C_, torch.float64, cuda, "out")
+        self._sync_stream()
+        self._check(fn(self.ctx, C_, G_, S, F, _ptr(first), _ptr(count), _ptr(ffirst), _ptr(chi2), _ptr(pcost), _ptr(out)))
+        return out
+
+    def chain_cost(self, chi2, pcost=None, C=None, G=None, first=None, count=None, ffirst=None, S=None, out=None):
+        """cpi_chain_cost_batch: cost [C], cost[c] = 0.5 sum of the chain's chi2 rows + the sum of its pcost rows -- the objective per
+        chain, in a fixed summation shape (the same inputs give the same bits, whatever C or the chain's position).  chi2 [F] from
+        factor_cost (None only with G == 1), pcost None or [S] from prior_relinearize; C, G, first, count, ffirst: those of
+        chain_solve.  S, the number of state rows the chains are clipped to: pcost's rows, else C * G when first is None, else the
+        caller's S=.  A chain without states gives 0, one whose factor rows leave chi2 gives NaN.  Asynchronous."""
+        return self._chain_cost(self.lib.cpi_chain_cost_batch, chi2, pcost, C, G, first, count, ffirst, S, out, True)
+
+    def chain_cost_host(self, chi2, pcost=None, C=None, G=None, first=None, count=None, ffirst=None, S=None, out=None):
+        """chain_cost on CPU tensors (cpi_chain_cost_batch_host): every chain's state and factor range is validated (CpiError names the
+        chain), synchronous, the device form's bits."""
+        return self._chain_cost(self.lib.cpi_chain_cost_batch_host, chi2, pcost, C, G, first, count, ffirst, S, out, False)
+
+    def _chain_accept(self, fn, chi2_new, pcost_new, trial, cost, states, lam, phase, C, G, first, count, ffirst, chi2, accepted, params, cuda):
+        self._trial_tensor(states, 16, cuda, "states")
+        S = states.shape[0]
+        self._trial_tensor(trial, 16, cuda, "trial", S)
+        C_, G_, S, F = self._lm_sizes(C, G, first, count, ffirst, chi2_new, pcost_new, S, cuda)
+        assert pcost_new is None or pcost_new.shape[0] == S, "pcost_new: [S] with the S of states"
+        for name, t, dt in (("cost", cost, torch.float64), ("lam", lam, torch.float64), ("phase", phase, torch.int32)):
+            self._lm_vector(t, C_, dt, cuda, name)
+        if accepted is not None:
+            self._lm_vector(accepted, C_, torch.int32, cuda, "accepted")
+        if chi2 is not None:
+            self._lm_vector(chi2, F, torch.float64, cuda, "chi2")
+        p = self._lm_params(params)
+        self._sync_stream()
+        self._check(fn(self.ctx, C_, G_, S, F, _ptr(first), _ptr(count), _ptr(ffirst), None if p is None else byref(p), _ptr(chi2_new),
+                       _ptr(pcost_new), _ptr(trial), _ptr(cost), _ptr(states), _ptr(chi2), _ptr(lam), _ptr(phase), _ptr(accepted)))
+        return accepted
+
+    def chain_accept(self, chi2_new, pcost_new, trial, cost, states, lam, phase, C=None, G=None, first=None, count=None, ffirst=None,
+                     chi2=None, accepted=None, params=None):
+        """cpi_chain_accept_batch: the decision of a Levenberg-Marquardt step, per chain and on the device.  chi2_new [F] / pcost_new
+        (None or [S]) / trial [S,16]: the trial's; cost [C], states [S,16], lam [C], phase [C] int32 are updated IN PLACE, chi2 [F]
+        too when given.  A running chain (phase 0) whose trial cost -- the value chain_cost gives, same bits -- is below cost[c] takes
+        the trial's rows, the new cost and lam * lam_down (not below lam_min); otherwise lam * lam_up, or phase LM_GAVE_UP once that
+        passes lam_max; phase LM_CONVERGED when the decrease (or the rejected difference) is inside abs_tol or rel_tol * |cost|.  A NaN
+        cost is a rejection.  A chain whose phase is not 0 is left alone.  params: None (the library's defaults: 0.1, 10, 0, 1e5, 1e-5,
+        1e-5), a dict with any of lam_down, lam_up, lam_min, lam_max, abs_tol, rel_tol, or the six numbers.  accepted: an int32 [C]
+        tensor to fill with 1 / 0, which is also what is returned.  Asynchronous."""
+        return self._chain_accept(self.lib.cpi_chain_accept_batch, chi2_new, pcost_new, trial, cost, states, lam, phase, C, G, first, count,
+                                  ffirst, chi2, accepted, params, True)
+
+    def chain_accept_host(self, chi2_new, pcost_new, trial, cost, states, lam, phase, C=None, G=None, first=None, count=None, ffirst=None,
+                          chi2=None, accepted=None, params=None):
+        """chain_accept on CPU tensors (cpi_chain_accept_batch_host): every chain's state and factor range is validated (CpiError names
+        the chain), synchronous, the device form's bits."""
+        return self._chain_accept(self.lib.cpi_chain_accept_batch_host, chi2_new, pcost_new, trial, cost, states, lam, phase, C, G, first,
+                                  count, ffirst, chi2, accepted, params, False)
+
+    def chain_lm(self, model, meas, lin, q_k_lin, states, R_tri, C, G, first=None, count=None, ffirst=None, idx_i=None, idx_j=None,
+                 prior0=None, anchor=None, prior_idx=None, lam=1e-3, iterations=10, params=None, damping="diagonal", grav=DEFAULT_GRAV,
+                 cost_history=None, buffers=None, init=True):
+        """Levenberg-Marquardt on C chains of IMU factors, every chain with a lambda, a cost and a phase of its own: the loop of
+        INTEGRATION.md 3p issued eagerly -- a thin composition of the entries, no kernel of its own, no host read, every buffer
+        allocated before the first iteration.  Before the loop (init): factor_cost, prior_relinearize and chain_cost at `states`; per
+        iteration: prior_relinearize(states) -> factor_hessian -> chain_solve -> retract -> factor_cost(trial) ->
+        prior_relinearize(trial, pcost only) -> chain_accept.
+          meas, lin, q_k_lin, R_tri, idx_i, idx_j   the F factors as factor_hessian / factor_cost take them (idx None: chain_indices)
+          states [S,16]                             updated IN PLACE (an accepted chain's rows are replaced)
+          prior0 / anchor / prior_idx               the priors as prior_relinearize takes them; None: no priors
+          lam                                       the initial lambda: a number, or a float64 CUDA tensor [C] that is updated in place
+          cost_history                              None or a float64 CUDA tensor [iterations + 1, C]: row 0 the initial cost, row i
+                                                    the cost after iteration i (device copies; nothing is read on the host)
+          buffers                                   None or a dict: filled with the buffers of the first call and re-used by later ones
+                                                    (init=False skips the part before the loop: one iteration under graph capture).
+                                                    Its keys are interface: "cost", "lam" [C] float64, "phase", "accepted", "status"
+                                                    [C] int32 -- what the loop keeps per chain and a caller may read or reset --,
+                                                    "chi2", "chi2_new" [F], "hess" [F,496], "delta" [S,15], "trial" [S,16],
+                                                    "workspace", "idx_i", "idx_j", and with priors "prior" [S,136], "pcost",
+                                                    "pcost_new" [S]
+        Returns (states, cost [C], lam [C], phase [C] int32: LM_RUNNING, LM_CONVERGED, LM_GAVE_UP)."""
+        F, S, dev = lin.shape[0], states.shape[0], self.device
+        C_ = self._chain_ranges(C, G, first, count, ffirst, True)
+        b = buffers if buffers is not None else {}
+        if not b:
+            f64 = dict(dtype=torch.float64, device=dev)
+            if torch.is_tensor(lam):
+                self._lm_vector(lam, C_, torch.float64, True, "lam")
+                b["lam"] = lam
+            else:
+                b["lam"] = torch.full((C_,), float(lam), **f64)
+            b.update(cost=torch.zeros((C_,), **f64), phase=torch.zeros((C_,), dtype=torch.int32, device=dev),
+                     accepted=torch.zeros((C_,), dtype=torch.int32, device=dev), status=torch.zeros((C_,), dtype=torch.int32, device=dev),
+                     chi2=torch.zeros((F,), **f64), chi2_new=torch.zeros((F,), **f64), hess=torch.zeros((F, 496), **f64),
+                     delta=torch.zeros((S, 15), **f64), trial=torch.zeros((S, 16), **f64),
+                     workspace=torch.empty((self.chain_solve_workspace_doubles(S),), **f64))
+            if prior0 is not None:
+                b.update(prior=torch.zeros((S, 136), **f64), pcost=torch.zeros((S,), **f64), pcost_new=torch.zeros((S,), **f64))
+            if idx_i is None or idx_j is None:
+                ii, jj = self.chain_indices(C_, G, first, count)
+                b["idx_i"], b["idx_j"] = ii.to(dev), jj.to(dev)
+            else:
+                b["idx_i"], b["idx_j"] = idx_i, idx_j
+        chain = dict(C=C_, G=G, first=first, count=count, ffirst=ffirst)
+        sweep = dict(idx_i=b["idx_i"], idx_j=b["idx_j"], grav=grav)
+        priors = prior0 is not None
+        if init:
+            self.factor_cost(model, meas, lin, q_k_lin, states, R_tri, want_total=False, out={"chi2": b["chi2"]}, **sweep)
+            if priors:
+                self.prior_relinearize(states, anchor, prior0, idx=prior_idx, pcost=b["pcost"], want_prior=False)
+            self.chain_cost(b["chi2"], b.get("pcost"), out=b["cost"], **chain)
+            if cost_history is not None:
+                cost_history[0].copy_(b["cost"])
+        for it in range(iterations):
+            if priors:
+                self.prior_relinearize(states, anchor, prior0, idx=prior_idx, out=b["prior"], want_cost=False)
+            self.factor_hessian(model, meas, lin, q_k_lin, states, R_tri, out=b["hess"], **sweep)
+            self.chain_solve(b["hess"], prior=b.get("prior"), lam=b["lam"], damping=damping, out=b["delta"], status=b["status"],
+                             workspace=b["workspace"], **chain)
+            self.retract(states, b["delta"], out=b["trial"])
+            self.factor_cost(model, meas, lin, q_k_lin, b["trial"], R_tri, want_total=False, out={"chi2": b["chi2_new"]}, **sweep)
+            if priors:
+                self.prior_relinearize(b["trial"], anchor, prior0, idx=prior_idx, pcost=b["pcost_new"], want_prior=False)
+            self.chain_accept(b["chi2_new"], b.get("pcost_new"), b["trial"], b["cost"], states, b["lam"], b["phase"], chi2=b["chi2"],
+                              accepted=b["accepted"], params=params, **chain)
+            if cost_history is not None:
+                cost_history[it + 1].copy_(b["cost"])
+        return states, b["cost"], b["lam"], b["phase"]
+
+
 def unpack_factor(packed, meas):
     """Dense (err [F,15], H1 [F,225], H2 [F,225], column-major) from the packed evaluation and the measurement it was
     computed from -- the block table of include/cpi_amd.h (ImuFactorCPIv1.cpp:109-143,169-185)."""
@@ -1542,6 +1761,26 @@ def chain_marginals(*args, **kw):
 def chain_marginalize(*args, **kw):
     """Engine.chain_marginalize on the default engine."""
     return default_engine().chain_marginalize(*args, **kw)
+
+
+def prior_relinearize(*args, **kw):
+    """Engine.prior_relinearize on the default engine."""
+    return default_engine().prior_relinearize(*args, **kw)
+
+
+def chain_cost(*args, **kw):
+    """Engine.chain_cost on the default engine."""
+    return default_engine().chain_cost(*args, **kw)
+
+
+def chain_accept(*args, **kw):
+    """Engine.chain_accept on the default engine."""
+    return default_engine().chain_accept(*args, **kw)
+
+
+def chain_lm(*args, **kw):
+    """Engine.chain_lm on the default engine."""
+    return default_engine().chain_lm(*args, **kw)
 
 
 # ---------------------------------------------------------------------- reference-shaped classes

@@ -78,7 +78,11 @@ extern "C" {
                                chains: the diagonal and first off-diagonal blocks of the inverse, from the factor the solve
                                left in its workspace); cpi_chain_marginalize_batch, cpi_chain_marginalize_batch_host (the
                                oldest states of a chain eliminated into a prior on the first state that stays: the step of a
-                               fixed-lag smoother between two optimisations) */
+                               fixed-lag smoother between two optimisations); cpi_prior_relinearize_batch,
+                               cpi_chain_cost_batch, cpi_chain_accept_batch, cpi_prior_relinearize_batch_host,
+                               cpi_chain_cost_batch_host, cpi_chain_accept_batch_host (the Levenberg-Marquardt
+                               step per chain on the device: the prior at the current states with its cost, the objective
+                               per chain, and the decision -- accept or reject, copy, lambda, phase) */
 
 enum { CPI_OK = 0, CPI_ERR_INVALID = 1, CPI_ERR_HIP = 2, CPI_ERR_NO_DEVICE = 3, CPI_ERR_RCCL = 4 };
 enum {
@@ -995,6 +999,81 @@ int cpi_chain_marginalize_batch(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, i
                                 int32_t M, const int32_t *drop,
                                 double *out, int32_t *status);
 
+/* The Levenberg-Marquardt step PER CHAIN, without the host looking at anything: the loop linearise -> relinearise the prior -> solve
+ * -> retract -> cost -> accept closes on the device.  Replaces: the outer loop of GTSAM's
+ * LevenbergMarquardtOptimizer (the error of the graph with its prior factor, the comparison of the trial's error with the current
+ * one, the lambda update and the convergence test of checkConvergence), per chain instead of per graph.  GTSAM is absent from the
+ * reference tree: PARITY UNPINNED; the three entries are checked against long-double restatements of the definitions below and, where
+ * the summation order is fixed, bit for bit.  Out of scope: a gain-ratio (model-fidelity) acceptance rule, the minDiagonal /
+ * maxDiagonal clamps, robust kernels, skipping the work of converged chains in the other sweeps.
+ *
+ * cpi_prior_relinearize_batch: the prior of P records at the current states, and its cost.
+ *   idx     NULL or [P] DEVICE int32: record p belongs to state idx[p]; NULL: to state p, and P <= S is required.  A record whose index
+ *           is outside [0, S) is skipped: it reads and writes nothing.  Duplicate indices are the caller's error (the contents are
+ *           unspecified; no access goes out of bounds).
+ *   states  [S][16];  anchor [P][16]: the state the prior was linearised at (x_lin of INTEGRATION.md 3o, or the centre of a Gaussian)
+ *   prior0  [P][136]: [Lam eta0; . .] in the packing of prior; entry 135 is never read.  A row of cpi_chain_marginalize_batch goes in
+ *           as it is; a Gaussian prior has eta0 = 0.
+ * Per record, with s = idx[p]:
+ *     xi    = localCoordinates(states[s], anchor[p])                 (the function of cpi_local_batch)
+ *     eta_i = the fma chain k = 0 .. 14 ascending STARTING FROM eta0_i: acc = fma(Lam[i][k], xi[k], acc)
+ *     t_i   = eta_i + eta0_i
+ *     pcost = 0.5 * (the fma chain i = 0 .. 14 ascending from +0.0: acc = fma(xi[i], t_i, acc))
+ *           = 0.5 xi^T Lam xi + eta0^T xi: the prior's cost up to the constant that marginalisation drops
+ *   prior   NULL or [S][136]: row s receives the Lam bits copied, eta, and entry 135 as 0.0
+ *   pcost   NULL or [S]: element s.  At least one of prior / pcost must be given.
+ * Rows of states without a record are not written (the caller zeroes the arrays once).  eta is the negative gradient, the sign
+ * convention of the solve; where states[s] and anchor[p] give xi = 0 the row is prior0 with entry 135 zeroed and pcost is 0.  NaN in
+ * a record reaches that record's outputs only.  Refused: negative sizes, P > S with idx NULL, a NULL anchor / prior0 when
+ * P > 0 (a NULL states when S > 0 too), prior and pcost both NULL, an output overlapping an input or the other output ("overlaps").  P == 0 is a no-op. */
+int cpi_prior_relinearize_batch(cpi_ctx *ctx, int64_t S, int64_t P, const int32_t *idx,
+                                const double *states, const double *anchor, const double *prior0,
+                                double *prior, double *pcost);
+
+/* cpi_chain_cost_batch: cost[c] = 0.5 sum_k chi2[ffirst_c + k] + sum_s pcost[first_c + s], the objective per chain.  C G S F first
+ * count ffirst: those of cpi_chain_solve_batch, with the same defaults and clamps.  chi2 [F] (cpi_factor_cost_*; NULL only when
+ * G == 1), pcost NULL (no priors) or [S], cost [C].  The reduction has a FIXED shape: sixteen slots q = 0 .. 15, a_q the plain sum from
+ * +0.0 of the chain's chi2 at k = q, q + 16, ... ascending, b_q the same over pcost, v_q = 0.5 * a_q + b_q (the product and the sum
+ * each rounded), then v_q = v_q + v_{q ^ 8}, ^ 4, ^ 2, ^ 1.  A chain without states gives +0.0; a chain whose factor rows leave
+ * [0, F) (the solve's status -1 rule) gives NaN and reads nothing; NaN in any term gives NaN for that chain alone.
+ * Refused: negative sizes, G < 1 or G > 2^31 - 1, a NULL cost, a NULL chi2 when G > 1, cost overlapping an input.  C == 0 is a no-op. */
+int cpi_chain_cost_batch(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_t F,
+                         const int64_t *first, const int32_t *count, const int64_t *ffirst,
+                         const double *chi2, const double *pcost, double *cost);
+
+/* cpi_chain_accept_batch: the decision.  params is a HOST pointer; NULL means { 0.1, 10, 0, 1e5, 1e-5, 1e-5 }: lambdaFactor 10 (down
+ * by its inverse), lambdaLowerBound 0, lambdaUpperBound 1e5, absoluteErrorTol 1e-5, relativeErrorTol 1e-5 -- the defaults of GTSAM's
+ * LevenbergMarquardtParams.  cost [C], states [S][16], lambda [C], phase [C] are in/out and required; chi2 [F] is in/out, or NULL
+ * when the caller does not keep the current chi2; accepted is NULL or [C], out.  chi2_new / pcost_new / trial: the trial's.
+ * Per chain (n_c: its clamped number of states):
+ *     phase[c] != 0 on entry     -> nothing of the chain is written; accepted[c] = 0
+ *     n_c == 0                   -> phase[c] = CPI_LM_CONVERGED, accepted[c] = 0, nothing else
+ *     new = the value cpi_chain_cost_batch gives for (chi2_new, pcost_new), same bits;  cur = cost[c]
+ *     new < cur (false for any NaN):
+ *         the chain's rows of trial -> states and of chi2_new -> chi2, bit for bit; cost[c] = new
+ *         lambda[c] = max(lambda[c] * lam_down, lam_min); accepted[c] = 1
+ *         dec = cur - new; if dec <= abs_tol or dec <= rel_tol * |cur|: phase[c] = CPI_LM_CONVERGED
+ *     otherwise (reject): states, chi2, cost untouched; accepted[c] = 0
+ *         if |new - cur| <= max(abs_tol, rel_tol * |cur|): phase[c] = CPI_LM_CONVERGED (stalled inside the tolerance; lambda untouched)
+ *         else l = lambda[c] * lam_up; if !(l <= lam_max): phase[c] = CPI_LM_GAVE_UP, lambda untouched; else lambda[c] = l
+ * A failed solve (NaN delta, NaN trial, NaN cost) is a rejection with a larger lambda; a chain whose current cost is NaN climbs to
+ * CPI_LM_GAVE_UP; neither disturbs another chain.  Rows of states that belong to no chain are not written.
+ * Refused: the sizes as above; params outside 0 < lam_down <= 1 <= lam_up, 0 <= lam_min <= lam_max, a negative tolerance or a NaN in
+ * any of them; a NULL cost / states / lambda / phase / trial, a NULL chi2_new when G > 1; trial / chi2_new / pcost_new or the
+ * ranges overlapping an in/out array, or in/out arrays overlapping each other ("overlaps").  C == 0 is a no-op.
+ *
+ * Common to the three: every refusal is CPI_ERR_INVALID and comes before the context is looked at; the library allocates nothing;
+ * one kernel on the context's stream, no host synchronisation: a capture is a chain without parallel branches.  A chain's or a
+ * record's bits depend on its own data only, not on C, P or its position. */
+typedef struct { double lam_down, lam_up, lam_min, lam_max, abs_tol, rel_tol; } cpi_lm_params;
+enum { CPI_LM_RUNNING = 0, CPI_LM_CONVERGED = 1, CPI_LM_GAVE_UP = 2 };
+int cpi_chain_accept_batch(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_t F,
+                           const int64_t *first, const int32_t *count, const int64_t *ffirst,
+                           const cpi_lm_params *params,
+                           const double *chi2_new, const double *pcost_new, const double *trial,
+                           double *cost, double *states, double *chi2, double *lambda,
+                           int32_t *phase, int32_t *accepted);
+
 /* ---- Device sets: the 8-GPU path of a single-process host (nothing in the reference, which is a
  * single-threaded CPU program).  Windows (and factors) are independent units: rank r of n owns the contiguous block
  * [lo, hi) = cpi_shard_bounds(W, r, n) (block size ceil(W / n); trailing ranks may be short or empty), runs the ordinary
@@ -1226,6 +1305,23 @@ int cpi_chain_marginalize_batch_host(cpi_ctx *ctx, int64_t C, int64_t G, int64_t
                                      const double *hess, const double *prior,
                                      int32_t M, const int32_t *drop,
                                      double *out, int32_t *status);
+
+/* cpi_prior_relinearize_batch, cpi_chain_cost_batch and cpi_chain_accept_batch from host memory: every pointer a host pointer (idx
+ * too), synchronous; the device forms' bits.  The outputs and in/out arrays travel up before the kernel, so that what nobody writes
+ * comes back as the caller left it.  The two chain entries validate every chain's state range and factor range first as
+ * cpi_chain_solve_batch_host does, and the text names the chain. */
+int cpi_prior_relinearize_batch_host(cpi_ctx *ctx, int64_t S, int64_t P, const int32_t *idx,
+                                     const double *states, const double *anchor, const double *prior0,
+                                     double *prior, double *pcost);
+int cpi_chain_cost_batch_host(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_t F,
+                              const int64_t *first, const int32_t *count, const int64_t *ffirst,
+                              const double *chi2, const double *pcost, double *cost);
+int cpi_chain_accept_batch_host(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_t F,
+                                const int64_t *first, const int32_t *count, const int64_t *ffirst,
+                                const cpi_lm_params *params,
+                                const double *chi2_new, const double *pcost_new, const double *trial,
+                                double *cost, double *states, double *chi2, double *lambda,
+                                int32_t *phase, int32_t *accepted);
 
 #ifdef __cplusplus
 }
