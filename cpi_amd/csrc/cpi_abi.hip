@@ -1630,6 +1630,46 @@ extern "C" int cpi_chain_accept_batch(cpi_ctx *ctx, int64_t C, int64_t G, int64_
     return CPI_OK;
 }
 
+// ============================================================================================
+// cpi_state_fix_batch: absolute measurements of states added to their rows and to their cost (cpi_fix.hip)
+// ============================================================================================
+static const int kFixZ[4] = { 3, 3, 4, 7 }, kFixR[4] = { 6, 6, 6, 21 };
+// what the device and the host forms refuse alike, before the context is looked at
+static int fix_check(cpi_ctx *ctx, const char *who, int64_t S, int64_t M, int32_t kind, const int64_t *mfirst, const double *states, const double *z,
+                     const double *R, const double *weight, const double *base, const double *pcost_base, double *out, double *pcost, double *chi2) {
+    if (S < 0 || M < 0) return refuse(ctx, who, "negative size");
+    if (kind < CPI_FIX_POSITION || kind > CPI_FIX_POSE) return refuse(ctx, who, "unknown kind (CPI_FIX_POSITION .. CPI_FIX_POSE)");
+    if (!mfirst || !states) return refuse(ctx, who, "mfirst or states is NULL");
+    if (M > 0 && (!z || !R)) return refuse(ctx, who, "z or R is NULL with M > 0");
+    if (!out && !pcost && !chi2) return refuse(ctx, who, "out, pcost and chi2 are all NULL");
+    const size_t d = sizeof(double);
+    const Span outs[3] = { { out, (size_t)S * 136 * d, "out" }, { pcost, (size_t)S * d, "pcost" }, { chi2, (size_t)M * d, "chi2" } };
+    const Span ins[7] = { { mfirst, (size_t)(S + 1) * sizeof(int64_t), "" }, { states, (size_t)S * 16 * d, "" }, { z, (size_t)M * kFixZ[kind] * d, "" },
+                          { R, (size_t)M * kFixR[kind] * d, "" }, { weight, (size_t)M * d, "" }, { base, (size_t)S * 136 * d, "" },
+                          { pcost_base, (size_t)S * d, "" } };
+    return refuse_overlaps(ctx, who, outs, 3, ins, 7);
+}
+extern "C" int cpi_state_fix_batch(cpi_ctx *ctx, int64_t S, int64_t M, int32_t kind, const int64_t *mfirst,
+                                   const double *states, const double *z, const double *R,
+                                   const double *weight, const double *base,
+                                   const double *pcost_base, double *out,
+                                   double *pcost, double *chi2) {
+    static const char who[] = "cpi_state_fix_batch";
+    CPI_TRY(fix_check(ctx, who, S, M, kind, mfirst, states, z, R, weight, base, pcost_base, out, pcost, chi2));
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (S == 0) return CPI_OK;
+    if (!grid_ok((S + 3) / 4)) return refuse(ctx, who, "S exceeds the 32-bit grid (4 states per workgroup)");
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    FixArgs a;
+    memset(&a, 0, sizeof a);
+    a.S = S; a.M = M; a.mfirst = (const long long *)mfirst; a.states = states; a.z = z; a.R = R; a.weight = weight; a.base = base;
+    a.pcost_base = pcost_base; a.out = out; a.pcost = pcost; a.chi2 = chi2;
+    launch::state_fix(kind, a, ctx->stream);
+    CPI_HIP(ctx, hipGetLastError());
+    return CPI_OK;
+}
+
 extern "C" size_t cpi_outputs_slab_doubles(const cpi_outputs *mask, int64_t Wb) {
     if (!mask || Wb <= 0) return 0;
     size_t n = 0;
@@ -3260,5 +3300,42 @@ extern "C" int cpi_chain_accept_batch_host(cpi_ctx *ctx, int64_t C, int64_t G, i
     CPI_TRY(st.download(lambda, dlam, (size_t)C));
     CPI_TRY(st.download(phase, dphase, (size_t)C));
     if (accepted) CPI_TRY(st.download(accepted, (const int32_t *)dacc, (size_t)C));
+    return st.finish();
+}
+
+// cpi_state_fix_batch from host memory: every array a host array, staged whole, synchronous.  mfirst is validated first.
+extern "C" int cpi_state_fix_batch_host(cpi_ctx *ctx, int64_t S, int64_t M, int32_t kind, const int64_t *mfirst,
+                                        const double *states, const double *z, const double *R,
+                                        const double *weight, const double *base,
+                                        const double *pcost_base, double *out,
+                                        double *pcost, double *chi2) {
+    static const char who[] = "cpi_state_fix_batch_host";
+    CPI_TRY(fix_check(ctx, who, S, M, kind, mfirst, states, z, R, weight, base, pcost_base, out, pcost, chi2));
+    for (int64_t s = 0; s < S; s++)
+        if (mfirst[s] < 0 || mfirst[s + 1] > M || mfirst[s + 1] < mfirst[s])
+            return refuse(ctx, who, ("the fixes of state " + std::to_string(s) + " leave [0, M] or mfirst decreases there").c_str());
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (S == 0) return CPI_OK;
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    Staging st(ctx);
+    const int64_t *df;
+    const double *ds, *dz, *dR, *dw, *db, *dpb;
+    double *dout = nullptr, *dpc = nullptr, *dchi = nullptr;
+    CPI_TRY(st.upload(mfirst, (size_t)S + 1, &df));
+    CPI_TRY(st.upload(states, (size_t)S * 16, &ds));
+    CPI_TRY(st.upload(M > 0 ? z : nullptr, (size_t)M * kFixZ[kind], &dz));
+    CPI_TRY(st.upload(M > 0 ? R : nullptr, (size_t)M * kFixR[kind], &dR));
+    CPI_TRY(st.upload(M > 0 ? weight : nullptr, (size_t)M, &dw));
+    CPI_TRY(st.upload(base, (size_t)S * 136, &db));
+    CPI_TRY(st.upload(pcost_base, (size_t)S, &dpb));
+    if (out) CPI_TRY(st.alloc((size_t)S * 136, &dout));
+    if (pcost) CPI_TRY(st.alloc((size_t)S, &dpc));
+    if (chi2 && M > 0) CPI_TRY(st.alloc((size_t)M, &dchi));
+    if (!dout && !dpc && !dchi) return st.finish();    // chi2 alone with M == 0: nothing to write
+    CPI_TRY(cpi_state_fix_batch(ctx, S, M, kind, df, ds, dz, dR, dw, db, dpb, dout, dpc, dchi));
+    if (out) CPI_TRY(st.download(out, (const double *)dout, (size_t)S * 136));
+    if (pcost) CPI_TRY(st.download(pcost, (const double *)dpc, (size_t)S));
+    if (dchi) CPI_TRY(st.download(chi2, (const double *)dchi, (size_t)M));
     return st.finish();
 }

@@ -1,6 +1,6 @@
 // cpi_args.hpp -- kernel argument blocks and the launcher interface between the translation units of libcpi_amd.so.
 //
-// The library is eighteen translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
+// The library is nineteen translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
 //   cpi_mean.hip    cpi_mean_kernel / cpi_mean_tiled_kernel / cpi_tile_*_kernel       (cpi_mean_kernels.hpp)
 //   cpi_running.hip cpi_mean_running_kernel / cpi_mean_stream_running_kernel: a row after every interval, from plain knots /
 //                   from windows cut out of IMU stream(s) in place         (cpi_running_kernels.hpp, cpi_running_body.inc)
@@ -39,6 +39,8 @@
 //   cpi_lm.hip      cpi_lm_prior_kernel / cpi_lm_cost_kernel / cpi_lm_accept_kernel: the Levenberg-Marquardt step per chain -- the prior
 //                   at the current states with its cost, the objective per chain, and the decision (accept, copy, lambda, phase)
 //                                                                                  (cpi_lm_kernels.hpp; cpi_chain_util.hpp)
+//   cpi_fix.hip     cpi_fix_kernel<kind>: absolute measurements of states (position, velocity, orientation, pose) added to their
+//                   rows [Lam eta] and to their cost                                                   (cpi_fix_kernels.hpp)
 //   cpi_factor.hip  evaluateError sweeps, square-root information, Hessian blocks, state prediction
 //                                                                                      (cpi_factor_kernels.hpp)
 //   cpi_abi.hip     the C-ABI of include/cpi_amd.h: argument checks, launch heuristics, device sets (RCCL), the
@@ -292,6 +294,21 @@ struct LmAcceptArgs {
     int *accepted;           // [C] or NULL
 };
 
+// cpi_state_fix_batch: state s owns the fixes mfirst[s] .. mfirst[s + 1] - 1 (clamped into [0, M] where they are read).
+struct FixArgs {
+    long long S, M;
+    const long long *mfirst; // [S + 1]
+    const double *states;    // [S][16]
+    const double *z;         // [M][3 | 3 | 4 | 7]
+    const double *R;         // [M][6 | 6 | 6 | 21]
+    const double *weight;    // [M] or NULL
+    const double *base;      // [S][136] or NULL
+    const double *pcost_base;// [S] or NULL
+    double *out;             // [S][136] or NULL
+    double *pcost;           // [S] or NULL
+    double *chi2;            // [M] or NULL
+};
+
 struct PredictArgs {
     long long F;
     double grav[3];
@@ -382,6 +399,8 @@ void chain_marginalize(const MarginalizeArgs &a, hipStream_t st);
 void lm_prior(const LmPriorArgs &a, hipStream_t st);
 void lm_cost(const LmCostArgs &a, hipStream_t st);
 void lm_accept(const LmCostArgs &a, const LmAcceptArgs &b, hipStream_t st);
+// ---- cpi_fix.hip (cpi_state_fix_batch)
+void state_fix(int kind, const FixArgs &a, hipStream_t st);                                   // kind: CPI_FIX_*
 // ---- cpi_factor.hip
 void factor(int model, bool whiten, int lpf, const FactorArgs &a, hipStream_t st);            // lpf 16 | 8 | 4
 void factor_packed(int model, int lpf, const FactorArgs &a, double *packed, hipStream_t st);  // lpf 2 | 3 | 4 | 6 | 8

@@ -1043,6 +1043,34 @@ inline std::vector<int32_t> chain_accept(const Context &ctx, int64_t C, int64_t 
     return accepted;
 }
 
+// state_fix: absolute measurements of states (cpi_state_fix_batch_host: the device kernel's bits).  kind CPI_FIX_*; z [M * 3 | 3 | 4 | 7]
+// and R [M * 6 | 6 | 6 | 21] (the packed upper-triangular square-root information) for M fixes sorted by state, mfirst [S + 1] the
+// first fix of every state; weight empty or [M]; base empty or [S * 136], pcost_base empty or [S]: what an earlier sensor or
+// prior_relinearize wrote.  Returns the rows [S * 136] chain_solve takes as prior, pcost [S] and chi2 [M] (without the weight).
+struct FixRows {
+    std::vector<double> rows, pcost, chi2;
+};
+inline FixRows state_fix(const Context &ctx, int32_t kind, const std::vector<double> &states, const std::vector<double> &z, const std::vector<double> &R,
+                         const std::vector<int64_t> &mfirst, const std::vector<double> &weight = {}, const std::vector<double> &base = {},
+                         const std::vector<double> &pcost_base = {}) {
+    static const size_t zn[4] = {3, 3, 4, 7}, rn[4] = {6, 6, 6, 21};
+    if (kind < CPI_FIX_POSITION || kind > CPI_FIX_POSE) throw std::invalid_argument("cpi_host::state_fix: kind is CPI_FIX_POSITION .. CPI_FIX_POSE");
+    const size_t S = states.size() / 16, M = z.size() / zn[kind];
+    if (states.size() != S * 16 || z.size() != M * zn[kind] || R.size() != M * rn[kind] || mfirst.size() != S + 1 || (!weight.empty() && weight.size() != M) ||
+        (!base.empty() && base.size() != S * 136) || (!pcost_base.empty() && pcost_base.size() != S))
+        throw std::invalid_argument("cpi_host::state_fix: states [S * 16], z [M * 3 | 3 | 4 | 7], R [M * 6 | 6 | 6 | 21], mfirst [S + 1], weight empty or [M], "
+                                    "base empty or [S * 136], pcost_base empty or [S]");
+    FixRows r;
+    r.rows.assign(S * 136, 0.0);
+    r.pcost.assign(S, 0.0);
+    r.chi2.assign(M, 0.0);
+    if (S)
+        ctx.check(cpi_state_fix_batch_host(ctx.get(), (int64_t)S, (int64_t)M, kind, mfirst.data(), states.data(), M ? z.data() : nullptr, M ? R.data() : nullptr,
+                                           weight.empty() ? nullptr : weight.data(), base.empty() ? nullptr : base.data(),
+                                           pcost_base.empty() ? nullptr : pcost_base.data(), r.rows.data(), r.pcost.data(), M ? r.chi2.data() : nullptr));
+    return r;
+}
+
 // ---- the caller's loop for MANY windows at once --------------------------------------------------------------------
 // What GraphSolver keeps between two states is a deque of IMU readings (GraphSolver.h: imu_times / imu_linaccs /
 // imu_angvel, filled by addmeasurement_imu); createimufactor_cpi_v1 / _v2 (GraphSolver_IMU.cpp:34-134) walk it up to the

@@ -1938,6 +1938,123 @@ CPI_HD int lm_decide(double cur, double nw, const LmParams &p, double &lambda, i
     }
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------
+// cpi_state_fix_batch (cpi_fix_kernels.hpp; tests/hostsim/hostsim_fix.cpp is the host restatement): absolute measurements of a state --
+// position, velocity, orientation, pose -- added to its row [Lam eta; . .] and to its cost.  Kind K fixes d = Fix<K>::D tangent rows
+// sel(0) < .. < sel(d - 1) (tangent order theta bg v ba p):
+//     K  z row              d   sel                   e
+//     0  [3] p              3   12 13 14              z - x.p
+//     1  [3] v              3   6 7 8                 z - x.v
+//     2  [4] JPL quaternion 3   0 1 2                 2 vec(quat_multiply(z, quat_inv(x.q)))
+//     3  [7] q then p       6   0 1 2 12 13 14        the rotation's three, then the position's three
+// quat_multiply gives the product with w >= 0 (it negates a product whose w is negative, then normalises), so z and -z give the same
+// e and e is the matching part of local_coordinates(x, x with z put in) for every z: the chart of every prior of the library, its
+// Jacobian taken flat (identity) as prior_relinearize takes it.  A zero or NaN quaternion normalises to NaN.
+// R [d (d + 1) / 2]: the upper-triangular square-root information in the packing of R_tri, entry (i, k), i <= k, at i + k (k + 1) / 2.
+// THE ORDER OF EVERY SUM (tests reproduce it bit for bit); fma(a, b, c) is one rounding of a b + c:
+//     wh_i   = the fma chain k = i .. d - 1 ascending from +0.0: acc = fma(R[i][k], e[k], acc)                      (fix_vectors)
+//     chi2   = (..(wh_0 wh_0 + wh_1 wh_1) + ..) + wh_{d-1} wh_{d-1}, every square rounded by itself (no fused multiply-add)
+//     u_a    = the fma chain i = 0 .. a ascending from +0.0: acc = fma(R[i][a], wh_i, acc)           (R^T wh)
+//     G_ab   = the fma chain i = 0 .. a ascending from +0.0: acc = fma(R[i][a], R[i][b], acc), a <= b  (R^T R)    (fix_term)
+// and onto the row, the fixes of a state in ascending m, starting from the base row's entry (or +0.0) and pcost_base (or +0.0):
+//     Lam[sel_a][sel_b] = fma(w_m, G_ab, Lam[sel_a][sel_b]);  eta[sel_a] = fma(w_m, u_a, eta[sel_a]);  pcost = fma(0.5 w_m, chi2, pcost)
+// (0.5 w_m is exact).  eta = Lam (z - x) is the sign chain_solve expects.  chi2 is reported without the weight.
+// The row's d (d + 1) / 2 + d entries that a kind touches are numbered t = 0 .. NT - 1: t < RN is the packed index of (a, b) in the
+// d x d triangle, t >= RN is eta's entry a = t - RN; the kernel deals them over sixteen lanes, t = lane and t = lane + 16.
+enum { FIX_POSITION = 0, FIX_VELOCITY = 1, FIX_ORIENTATION = 2, FIX_POSE = 3 };
+template <int K>
+struct Fix {
+    static constexpr int D = (K == FIX_POSE) ? 6 : 3, ZN = (K == FIX_POSE) ? 7 : ((K == FIX_ORIENTATION) ? 4 : 3), RN = D * (D + 1) / 2, NT = RN + D;
+    CPI_HD static constexpr int sel(int a) {
+        return (K == FIX_POSITION) ? 12 + a : (K == FIX_VELOCITY) ? 6 + a : (K == FIX_ORIENTATION) ? a : (a < 3 ? a : 9 + a);
+    }
+    // where entry t lives in the 136 doubles of a row
+    CPI_HD static int slot(int t) {
+        if (t >= RN) return tri(15) + sel(t - RN);
+        const int b = (t >= 1) + (t >= 3) + (t >= 6) + (t >= 10) + (t >= 15), a = t - tri(b);
+        return tri(sel(b)) + sel(a);
+    }
+};
+template <int K>
+CPI_HD void fix_residual(const NavState &x, const double *z, double *e) {
+    if (K == FIX_POSITION) { e[0] = z[0] - x.p.x; e[1] = z[1] - x.p.y; e[2] = z[2] - x.p.z; }
+    if (K == FIX_VELOCITY) { e[0] = z[0] - x.v.x; e[1] = z[1] - x.v.y; e[2] = z[2] - x.v.z; }
+    if (K == FIX_ORIENTATION || K == FIX_POSE) {
+        const Q4 qd = quat_multiply(ldq(z), quat_inv(x.q));
+        e[0] = 2 * qd.x; e[1] = 2 * qd.y; e[2] = 2 * qd.z;
+    }
+    if (K == FIX_POSE) { e[3] = z[4] - x.p.x; e[4] = z[5] - x.p.y; e[5] = z[6] - x.p.z; }
+}
+// wh = R e, u = R^T wh; returns chi2
+template <int D>
+CPI_HD double fix_vectors(const double *R, const double *e, double *wh, double *u) {
+#pragma unroll
+    for (int i = 0; i < D; i++) {
+        double acc = 0.0;
+#pragma unroll
+        for (int k = i; k < D; k++) acc = fma(R[tri(k) + i], e[k], acc);
+        wh[i] = acc;
+    }
+    double chi2 = wh[0] * wh[0];
+    CPI_ROUNDED(chi2);
+#pragma unroll
+    for (int i = 1; i < D; i++) {
+        double sq = wh[i] * wh[i];
+        CPI_ROUNDED(sq);
+        chi2 = chi2 + sq;
+    }
+#pragma unroll
+    for (int a = 0; a < D; a++) {
+        double acc = 0.0;
+#pragma unroll
+        for (int i = 0; i <= a; i++) acc = fma(R[tri(a) + i], wh[i], acc);
+        u[a] = acc;
+    }
+    return chi2;
+}
+// entry t of a fix: G_ab for t < RN (R is read at run-time indices: a pointer to memory, not to registers), else u_{t - RN}
+template <int D>
+CPI_HD double fix_term(const double *R, const double *u, int t) {
+    const int RN = D * (D + 1) / 2;
+    if (t >= RN) {
+        double v = u[0];
+#pragma unroll
+        for (int k = 1; k < D; k++) {
+            v = (t - RN == k) ? u[k] : v;
+            CPI_ROUNDED(v);                            // a chain of selects on registers: left alone, it is turned into u[t - RN] from scratch
+        }
+        return v;
+    }
+    const int b = (t >= 1) + (t >= 3) + (t >= 6) + (t >= 10) + (t >= 15), a = t - tri(b);
+    double acc = 0.0;
+    for (int i = 0; i <= a; i++) acc = fma(R[tri(a) + i], R[tri(b) + i], acc);
+    return acc;
+}
+// One state with its n fixes on host arrays: z [n][ZN], R [n][RN], weight NULL or [n], base NULL or [136]; row NULL or [136], pcost
+// NULL or one double, chi2 NULL or [n].  The statement the kernel is the lane-mapped form of.
+template <int K>
+CPI_HD void state_fix(const NavState &x, long long n, const double *z, const double *R, const double *weight, const double *base,
+                      double pcost_base, double *row, double *pcost, double *chi2) {
+    typedef Fix<K> T;
+    double acc[T::NT], pc = pcost_base;
+    for (int t = 0; t < T::NT; t++) acc[t] = base ? base[T::slot(t)] : 0.0;
+    for (long long m = 0; m < n; m++) {
+        const double *Rm = R + m * T::RN, w = weight ? weight[m] : 1.0;
+        double e[T::D], wh[T::D], u[T::D];
+        fix_residual<K>(x, z + m * T::ZN, e);
+        const double c2 = fix_vectors<T::D>(Rm, e, wh, u);
+        if (chi2) chi2[m] = c2;
+        pc = fma(0.5 * w, c2, pc);
+        for (int t = 0; t < T::NT; t++) acc[t] = fma(w, fix_term<T::D>(Rm, u, t), acc[t]);
+    }
+    if (row) {
+        for (int i = 0; i < PRIOR_D - 1; i++) row[i] = base ? base[i] : 0.0;
+        for (int t = 0; t < T::NT; t++) row[T::slot(t)] = acc[t];
+        row[PRIOR_D - 1] = 0.0;
+    }
+    if (pcost) *pcost = pc;
+}
 }  // namespace chn
 
 }  // namespace cpi

@@ -1626,9 +1626,87 @@ class Engine:
         return self._chain_accept(self.lib.cpi_chain_accept_batch_host, chi2_new, pcost_new, trial, cost, states, lam, phase, C, G, first,
                                   count, ffirst, chi2, accepted, params, False)
 
+    # ------------------------------------------------------------------ absolute measurements of states
+    FIX_KINDS = {"position": 0, "velocity": 1, "orientation": 2, "pose": 3}
+    _FIX_Z, _FIX_R = (3, 3, 4, 7), (6, 6, 6, 21)
+
+    @staticmethod
+    def fix_offsets(idx, S):
+        """mfirst [S + 1] int64 for cpi_state_fix_batch from a NON-DECREASING integer tensor idx [M], idx[m] the state of fix m: state s
+        owns the fixes mfirst[s] .. mfirst[s + 1] - 1.  Computed on idx's device with searchsorted: no host read, so nothing is checked --
+        an index that decreases, is below 0 or is S or more is the caller's error: such fixes are counted to state 0 or to no state
+        and the offsets no longer describe idx (the entry itself stays inside its arrays whatever mfirst holds)."""
+        assert idx.dim() == 1 and not idx.is_floating_point(), "idx: an integer tensor [M], non-decreasing"
+        return torch.searchsorted(idx.contiguous(), torch.arange(int(S) + 1, dtype=idx.dtype, device=idx.device)).to(torch.int64)
+
+    def _state_fix(self, fn, states, kind, z, R, mfirst, weight, base, pcost_base, out, pcost, chi2, want_rows, want_cost, cuda):
+        k = self.FIX_KINDS.get(kind, kind) if isinstance(kind, str) else int(kind)
+        assert k in (0, 1, 2, 3), "kind: 'position', 'velocity', 'orientation', 'pose' or CPI_FIX_* (0 .. 3)"
+        self._trial_tensor(states, 16, cuda, "states")
+        S, M = states.shape[0], z.shape[0]
+        self._trial_tensor(z, self._FIX_Z[k], cuda, "z")
+        self._trial_tensor(R, self._FIX_R[k], cuda, "R", M)
+        self._lm_vector(mfirst, S + 1, torch.int64, cuda, "mfirst")
+        if weight is not None:
+            self._lm_vector(weight, M, torch.float64, cuda, "weight")
+        if base is not None:
+            self._trial_tensor(base, 136, cuda, "base", S)
+        if pcost_base is not None:
+            self._lm_vector(pcost_base, S, torch.float64, cuda, "pcost_base")
+        dev = states.device
+        if out is None and want_rows:
+            out = torch.empty((S, 136), dtype=torch.float64, device=dev)      # every row is written
+        if pcost is None and want_cost:
+            pcost = torch.empty((S,), dtype=torch.float64, device=dev)
+        assert out is not None or pcost is not None or chi2 is not None, "at least one of the rows, pcost and chi2"
+        if out is not None:
+            self._trial_tensor(out, 136, cuda, "out", S)
+        if pcost is not None:
+            self._lm_vector(pcost, S, torch.float64, cuda, "pcost")
+        if chi2 is not None:
+            self._lm_vector(chi2, M, torch.float64, cuda, "chi2")
+        self._sync_stream()
+        self._check(fn(self.ctx, S, M, k, _ptr(mfirst), _ptr(states), _ptr(z), _ptr(R), _ptr(weight), _ptr(base), _ptr(pcost_base), _ptr(out),
+                       _ptr(pcost), _ptr(chi2)))
+        return out, pcost
+
+    def state_fix(self, states, kind, z, R, mfirst, weight=None, base=None, pcost_base=None, out=None, pcost=None, chi2=None, want_rows=True,
+                  want_cost=True):
+        """cpi_state_fix_batch: absolute measurements of states added to their rows [Lam eta] and to their cost.  states [S,16]; kind
+        'position' (z [M,3] = p), 'velocity' (z [M,3] = v), 'orientation' (z [M,4], a JPL quaternion as in a state row) or 'pose'
+        (z [M,7], q then p), or the enum value 0 .. 3; R [M,6] ([M,21] for a pose): the upper-triangular square-root information of
+        every fix in the packing of R_tri (pack_tri of a d x d upper triangle); mfirst int64 [S+1]: state s owns the fixes mfirst[s] ..
+        mfirst[s+1] - 1 (fix_offsets makes it from the state index of every fix); weight None or [M].  Returns (rows [S,136], pcost
+        [S]): rows[s] = base[s] (or 0) + sum w R^T R on the fixed tangent rows with eta += w R^T R e -- what chain_solve takes as prior
+        --, pcost[s] = pcost_base[s] (or 0) + sum 0.5 w |R e|^2.  Every state is written, never in place: chain a second sensor, or
+        the carried prior of prior_relinearize, through base= / pcost_base=.  chi2= an [M] tensor to fill with |R e|^2 of every fix
+        WITHOUT the weight (a gate).  out= / pcost= re-use tensors (graph capture); want_rows=False / want_cost=False leave that output
+        out (None is returned in its place) unless a tensor is given for it; without rows no row is read or written.  Asynchronous."""
+        return self._state_fix(self.lib.cpi_state_fix_batch, states, kind, z, R, mfirst, weight, base, pcost_base, out, pcost, chi2, want_rows,
+                               want_cost, True)
+
+    def state_fix_host(self, states, kind, z, R, mfirst, weight=None, base=None, pcost_base=None, out=None, pcost=None, chi2=None, want_rows=True,
+                       want_cost=True):
+        """state_fix on CPU tensors (cpi_state_fix_batch_host): mfirst is validated (CpiError names the state), synchronous, the device
+        form's bits."""
+        return self._state_fix(self.lib.cpi_state_fix_batch_host, states, kind, z, R, mfirst, weight, base, pcost_base, out, pcost, chi2,
+                               want_rows, want_cost, False)
+
+    def _lm_fixes(self, x, fixes, pair, base, rows):
+        """The fixes of chain_lm in list order at the states x, ping-pong through the two buffers of pair (the entry is never in place):
+        rows [S,136] on top of base when rows, else pcost [S] on top of base.  Returns the tensor the last call wrote."""
+        for k, f in enumerate(fixes):
+            dst = pair[k % 2]
+            if rows:
+                self.state_fix(x, f["kind"], f["z"], f["R"], f["mfirst"], weight=f.get("weight"), base=base, out=dst, want_cost=False)
+            else:
+                self.state_fix(x, f["kind"], f["z"], f["R"], f["mfirst"], weight=f.get("weight"), pcost_base=base, pcost=dst, want_rows=False)
+            base = dst
+        return base
+
     def chain_lm(self, model, meas, lin, q_k_lin, states, R_tri, C, G, first=None, count=None, ffirst=None, idx_i=None, idx_j=None,
                  prior0=None, anchor=None, prior_idx=None, lam=1e-3, iterations=10, params=None, damping="diagonal", grav=DEFAULT_GRAV,
-                 cost_history=None, buffers=None, init=True):
+                 cost_history=None, buffers=None, init=True, fixes=None):
         """Levenberg-Marquardt on C chains of IMU factors, every chain with a lambda, a cost and a phase of its own: the loop of
         INTEGRATION.md 3p issued eagerly -- a thin composition of the entries, no kernel of its own, no host read, every buffer
         allocated before the first iteration.  Before the loop (init): factor_cost, prior_relinearize and chain_cost at `states`; per
@@ -1637,6 +1715,10 @@ class Engine:
           meas, lin, q_k_lin, R_tri, idx_i, idx_j   the F factors as factor_hessian / factor_cost take them (idx None: chain_indices)
           states [S,16]                             updated IN PLACE (an accepted chain's rows are replaced)
           prior0 / anchor / prior_idx               the priors as prior_relinearize takes them; None: no priors
+          fixes                                     None or a list of dicts with kind, z, R, mfirst and optionally weight, as state_fix
+                                                    takes them: absolute measurements of the states.  Every prior_relinearize of the
+                                                    loop is followed by the fixes in list order -- rows before factor_hessian, pcost
+                                                    only in the two cost evaluations
           lam                                       the initial lambda: a number, or a float64 CUDA tensor [C] that is updated in place
           cost_history                              None or a float64 CUDA tensor [iterations + 1, C]: row 0 the initial cost, row i
                                                     the cost after iteration i (device copies; nothing is read on the host)
@@ -1646,7 +1728,8 @@ class Engine:
                                                     [C] int32 -- what the loop keeps per chain and a caller may read or reset --,
                                                     "chi2", "chi2_new" [F], "hess" [F,496], "delta" [S,15], "trial" [S,16],
                                                     "workspace", "idx_i", "idx_j", and with priors "prior" [S,136], "pcost",
-                                                    "pcost_new" [S]
+                                                    "pcost_new" [S], and with fixes "fix_rows" (two [S,136]) and
+                                                    "fix_pcost" (two [S]), added to a dict that a call without fixes filled
         Returns (states, cost [C], lam [C], phase [C] int32: LM_RUNNING, LM_CONVERGED, LM_GAVE_UP)."""
         F, S, dev = lin.shape[0], states.shape[0], self.device
         C_ = self._chain_ranges(C, G, first, count, ffirst, True)
@@ -1670,6 +1753,9 @@ class Engine:
                 b["idx_i"], b["idx_j"] = ii.to(dev), jj.to(dev)
             else:
                 b["idx_i"], b["idx_j"] = idx_i, idx_j
+        if fixes and "fix_rows" not in b:                                     # also a buffers dict that a call without fixes filled
+            b.update(fix_rows=[torch.zeros((S, 136), dtype=torch.float64, device=dev) for _ in range(2)],
+                     fix_pcost=[torch.zeros((S,), dtype=torch.float64, device=dev) for _ in range(2)])
         chain = dict(C=C_, G=G, first=first, count=count, ffirst=ffirst)
         sweep = dict(idx_i=b["idx_i"], idx_j=b["idx_j"], grav=grav)
         priors = prior0 is not None
@@ -1677,20 +1763,22 @@ class Engine:
             self.factor_cost(model, meas, lin, q_k_lin, states, R_tri, want_total=False, out={"chi2": b["chi2"]}, **sweep)
             if priors:
                 self.prior_relinearize(states, anchor, prior0, idx=prior_idx, pcost=b["pcost"], want_prior=False)
-            self.chain_cost(b["chi2"], b.get("pcost"), out=b["cost"], **chain)
+            self.chain_cost(b["chi2"], self._lm_fixes(states, fixes or (), b.get("fix_pcost"), b.get("pcost"), False), out=b["cost"], **chain)
             if cost_history is not None:
                 cost_history[0].copy_(b["cost"])
         for it in range(iterations):
             if priors:
                 self.prior_relinearize(states, anchor, prior0, idx=prior_idx, out=b["prior"], want_cost=False)
+            rows = self._lm_fixes(states, fixes or (), b.get("fix_rows"), b.get("prior"), True)
             self.factor_hessian(model, meas, lin, q_k_lin, states, R_tri, out=b["hess"], **sweep)
-            self.chain_solve(b["hess"], prior=b.get("prior"), lam=b["lam"], damping=damping, out=b["delta"], status=b["status"],
+            self.chain_solve(b["hess"], prior=rows, lam=b["lam"], damping=damping, out=b["delta"], status=b["status"],
                              workspace=b["workspace"], **chain)
             self.retract(states, b["delta"], out=b["trial"])
             self.factor_cost(model, meas, lin, q_k_lin, b["trial"], R_tri, want_total=False, out={"chi2": b["chi2_new"]}, **sweep)
             if priors:
                 self.prior_relinearize(b["trial"], anchor, prior0, idx=prior_idx, pcost=b["pcost_new"], want_prior=False)
-            self.chain_accept(b["chi2_new"], b.get("pcost_new"), b["trial"], b["cost"], states, b["lam"], b["phase"], chi2=b["chi2"],
+            pcost_new = self._lm_fixes(b["trial"], fixes or (), b.get("fix_pcost"), b.get("pcost_new"), False)
+            self.chain_accept(b["chi2_new"], pcost_new, b["trial"], b["cost"], states, b["lam"], b["phase"], chi2=b["chi2"],
                               accepted=b["accepted"], params=params, **chain)
             if cost_history is not None:
                 cost_history[it + 1].copy_(b["cost"])
@@ -1781,6 +1869,21 @@ def chain_accept(*args, **kw):
 def chain_lm(*args, **kw):
     """Engine.chain_lm on the default engine."""
     return default_engine().chain_lm(*args, **kw)
+
+
+def state_fix(*args, **kw):
+    """Engine.state_fix on the default engine."""
+    return default_engine().state_fix(*args, **kw)
+
+
+def state_fix_host(*args, **kw):
+    """Engine.state_fix_host on the default engine."""
+    return default_engine().state_fix_host(*args, **kw)
+
+
+def fix_offsets(idx, S):
+    """Engine.fix_offsets."""
+    return Engine.fix_offsets(idx, S)
 
 
 # ---------------------------------------------------------------------- reference-shaped classes

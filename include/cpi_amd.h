@@ -82,7 +82,10 @@ extern "C" {
                                cpi_chain_cost_batch, cpi_chain_accept_batch, cpi_prior_relinearize_batch_host,
                                cpi_chain_cost_batch_host, cpi_chain_accept_batch_host (the Levenberg-Marquardt
                                step per chain on the device: the prior at the current states with its cost, the objective
-                               per chain, and the decision -- accept or reject, copy, lambda, phase) */
+                               per chain, and the decision -- accept or reject, copy, lambda, phase);
+                               cpi_state_fix_batch, cpi_state_fix_batch_host (absolute measurements of states --
+                               position, velocity, orientation, pose fixes -- added to their rows [Lam eta] and to their
+                               cost: how a GPS fix, a zero-velocity update or a mocap pose enters that loop) */
 
 enum { CPI_OK = 0, CPI_ERR_INVALID = 1, CPI_ERR_HIP = 2, CPI_ERR_NO_DEVICE = 3, CPI_ERR_RCCL = 4 };
 enum {
@@ -1074,6 +1077,54 @@ int cpi_chain_accept_batch(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_
                            double *cost, double *states, double *chi2, double *lambda,
                            int32_t *phase, int32_t *accepted);
 
+/* cpi_state_fix_batch: absolute measurements ("fixes") of states -- a GPS position, a zero-velocity update, an attitude, a mocap
+ * pose -- added to the states' rows [Lam eta; . .] (the packing of prior: what cpi_chain_solve_batch takes) and to their cost (the
+ * pcost of cpi_chain_cost_batch).  Replaces: GTSAM's PriorFactor<Point3 / Rot3 / Pose3> / GPSFactor linearised and summed into the
+ * Hessian of a state, per state instead of per graph.  GTSAM is absent from the reference tree: PARITY UNPINNED; checked against a
+ * long-double restatement of the definitions below and, where the summation order is fixed, bit for bit.  Out of scope: robust kernels
+ * inside the library (weight is the caller's hook), relative (between-state) measurements, mixed kinds in one call (a second kind is
+ * a second call), the exact right Jacobian of the rotation residual (it is taken flat, as cpi_prior_relinearize_batch takes it).
+ *
+ *   kind                 z row                              d   tangent rows sel (order theta bg v ba p)   residual e
+ *   CPI_FIX_POSITION     [3] p                              3   12 13 14                                   z - x.p
+ *   CPI_FIX_VELOCITY     [3] v                              3   6 7 8                                      z - x.v
+ *   CPI_FIX_ORIENTATION  [4] JPL quaternion (a state's)     3   0 1 2                                      2 vec(qd), qd = quat_multiply(z, inv(x.q)),
+ *                                                                                                          negated when qd.w < 0
+ *   CPI_FIX_POSE         [7] q then p                       6   0 1 2 12 13 14                             the two above
+ * e is the matching part of localCoordinates(x, x with z put in) -- the chart of every prior of the library -- with its Jacobian
+ * taken flat (identity).  z and -z are one attitude and give the same e: the product is negated when its w is negative, which is
+ * also what the library's localCoordinates (cpi_local_batch) does.  A zero-norm or NaN measurement gives NaN.
+ *   mfirst  [S + 1] DEVICE int64: state s owns the fixes mfirst[s] .. mfirst[s + 1] - 1 (sorted by state, CSR).  Every range is
+ *           clamped into [0, M] where it is read: a broken mfirst gives unspecified contents, no access out of bounds.
+ *   states  [S][16];  z [M][3 | 3 | 4 | 7];  R [M][6 | 6 | 6 | 21]: the upper-triangular square-root information (R^T R = the inverse
+ *           covariance of z) in the packing of R_tri, entry (i, k), i <= k, at i + k (k + 1) / 2;  weight NULL (1) or [M]
+ *   base    NULL (zeros) or [S][136];  pcost_base NULL (zeros) or [S]
+ * Per fix m of state s, in ascending m, with fma(a, b, c) one rounding of a b + c:
+ *     wh_i  = the fma chain k = i .. d - 1 ascending from +0.0: acc = fma(R[i][k], e[k], acc)
+ *     chi2  = (..(wh_0 wh_0 + wh_1 wh_1) + ..) + wh_{d-1} wh_{d-1}, every square rounded by itself
+ *     u_a   = the fma chain i = 0 .. a ascending from +0.0: acc = fma(R[i][a], wh_i, acc)
+ *     G_ab  = the fma chain i = 0 .. a ascending from +0.0: acc = fma(R[i][a], R[i][b], acc), a <= b
+ *     Lam[sel_a][sel_b] = fma(w_m, G_ab, Lam[sel_a][sel_b]);  eta[sel_a] = fma(w_m, u_a, eta[sel_a]);  pcost = fma(0.5 w_m, chi2, pcost)
+ *   out     NULL or [S][136]: for EVERY s in [0, S), out[s] = (base ? base[s] : 0) + the fixes of s; entry 135 is written as 0.0
+ *   pcost   NULL or [S]: for every s, (pcost_base ? pcost_base[s] : 0) + sum 0.5 w chi2
+ *   chi2    NULL or [M]: chi2[m] WITHOUT the weight, so that a gate does not depend on it
+ * eta = Lam (z - x) is the negative gradient, the sign convention of the solve.  A state without fixes gets its base row and
+ * pcost_base bit for bit (entry 135 aside), zeros when they are NULL.  The sweep is dense over S and never in place: a second
+ * sensor is a second call with the first call's out / pcost as base / pcost_base, and the carried prior comes in as the base that
+ * cpi_prior_relinearize_batch wrote; an in-place add would accumulate from one iteration of the loop to the next.  With out NULL
+ * (the cost-only calls of an iteration) no row is read or written.  A NaN or zero-norm measurement makes that state's row and pcost
+ * NaN and touches no other state; cpi_chain_cost_batch turns it into a rejection of that chain.
+ * Refused (CPI_ERR_INVALID, before the context is looked at): negative sizes, an unknown kind, a NULL mfirst / states, a NULL z / R
+ * when M > 0, out, pcost and chi2 all NULL, an output that overlaps an input or another output ("overlaps").  S == 0 is a no-op.
+ * The library allocates nothing; one kernel on the context's stream, no host synchronisation: a capture is a chain
+ * without parallel branches.  A state's bits depend on its own data only, not on S or its position. */
+enum { CPI_FIX_POSITION = 0, CPI_FIX_VELOCITY = 1, CPI_FIX_ORIENTATION = 2, CPI_FIX_POSE = 3 };
+int cpi_state_fix_batch(cpi_ctx *ctx, int64_t S, int64_t M, int32_t kind, const int64_t *mfirst,
+                        const double *states, const double *z, const double *R,
+                        const double *weight, const double *base,
+                        const double *pcost_base, double *out,
+                        double *pcost, double *chi2);
+
 /* ---- Device sets: the 8-GPU path of a single-process host (nothing in the reference, which is a
  * single-threaded CPU program).  Windows (and factors) are independent units: rank r of n owns the contiguous block
  * [lo, hi) = cpi_shard_bounds(W, r, n) (block size ceil(W / n); trailing ranks may be short or empty), runs the ordinary
@@ -1322,6 +1373,14 @@ int cpi_chain_accept_batch_host(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, i
                                 const double *chi2_new, const double *pcost_new, const double *trial,
                                 double *cost, double *states, double *chi2, double *lambda,
                                 int32_t *phase, int32_t *accepted);
+
+/* cpi_state_fix_batch from host memory: every pointer a host pointer (mfirst too), synchronous; the device form's bits.  mfirst is
+ * validated first -- non-decreasing and inside [0, M] -- and the text names the state. */
+int cpi_state_fix_batch_host(cpi_ctx *ctx, int64_t S, int64_t M, int32_t kind, const int64_t *mfirst,
+                             const double *states, const double *z, const double *R,
+                             const double *weight, const double *base,
+                             const double *pcost_base, double *out,
+                             double *pcost, double *chi2);
 
 #ifdef __cplusplus
 }
