@@ -1067,7 +1067,10 @@ int cpi_chain_cost_batch(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_t 
  *
  * Common to the three: every refusal is CPI_ERR_INVALID and comes before the context is looked at; the library allocates nothing;
  * one kernel on the context's stream, no host synchronisation: a capture is a chain without parallel branches.  A chain's or a
- * record's bits depend on its own data only, not on C, P or its position. */
+ * record's bits depend on its own data only, not on C, P or its position.  Alignment, for these three, cpi_state_fix_batch and every
+ * other entry of the optimiser's loop (the factor sweeps, cpi_retract_batch, cpi_chain_solve / marginals / marginalize_batch): a
+ * double array needs the alignment of a double (8 bytes) and no more -- [S][136] may be carved out of a workspace at an odd double
+ * offset. */
 typedef struct { double lam_down, lam_up, lam_min, lam_max, abs_tol, rel_tol; } cpi_lm_params;
 enum { CPI_LM_RUNNING = 0, CPI_LM_CONVERGED = 1, CPI_LM_GAVE_UP = 2 };
 int cpi_chain_accept_batch(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_t F,

@@ -17,9 +17,11 @@ products of size 1, not of 1e-9):
     final  max |local(final state, the CPU loop's)_i| / sigma_i, sigma from chain_marginals at the final states
 Gates = 100 x the floor, the rule of tests/tol.py and tests/lm_cases.py; a floor is the largest value measured over every case of the
 tests and never below one unit.  Measured (profiles/state_fix.md):
-    host twin (tests/hostsim/hostsim_fix.cpp, x86-64)    Lam 3.5   eta 3.0   pcost 1.7   chi2 3.3
-    device (MI355X)                                      Lam 4.5   eta 3.0   pcost 2.4   chi2 3.3   final 4.3e-13 sigma (dense; ragged 1.8e-13)
-A wrong term shows as 1e13 units and more (the mutation checks of tests/test_fix_cpu.py)."""
+    host twin (tests/hostsim/hostsim_fix.cpp, x86-64)    Lam 7.0   eta 6.3   pcost 4.3   chi2 4.7
+    device (MI355X)                                      Lam 7.0   eta 6.3   pcost 4.3   chi2 4.7   final 4.3e-13 sigma (dense; ragged 1.8e-13)
+All four are set by the 1027 states of edge_case("many", .) -- the largest of 4560 fixes, where the nine states of case() gave 3.5, 3.0,
+1.7, 3.3 on the host and 4.5, 3.0, 2.4, 3.3 on the device; the builders at GPS-sized positions and with float32-rounded, scaled or
+axis-aligned quaternions stay below those.  A wrong term shows as 1e13 units and more (the mutation checks of tests/test_fix_cpu.py)."""
 import functools
 
 import numpy as np
@@ -36,8 +38,8 @@ ZN = (3, 3, 4, 7)
 RN = (6, 6, 6, 21)
 SEL = ((12, 13, 14), (6, 7, 8), (0, 1, 2), (0, 1, 2, 12, 13, 14))
 
-FLOOR_HOST = dict(Lam=3.5, eta=3.0, pcost=1.7, chi2=3.3)
-FLOOR_DEVICE = dict(Lam=4.5, eta=3.0, pcost=2.4, chi2=3.3)
+FLOOR_HOST = dict(Lam=7.0, eta=6.3, pcost=4.3, chi2=4.7)
+FLOOR_DEVICE = dict(Lam=7.0, eta=6.3, pcost=4.3, chi2=4.7)
 FLOOR_FINAL_DEVICE = 4.3e-13  # sigma: both loops reach the minimum itself, what is left is rounding (as lm_cases.FLOOR_FINAL_DEVICE)
 GATE_HOST = {k: 100 * max(v, 1.0) for k, v in FLOOR_HOST.items()}
 GATE_DEVICE = {k: 100 * max(v, 1.0) for k, v in FLOOR_DEVICE.items()}
@@ -170,6 +172,77 @@ def case(kind, S, seed=3):
     """The first S states of the nine of COUNTS: a state's data does not depend on S."""
     full = Case(kind, COUNTS, seed) if S == len(COUNTS) else case(kind, len(COUNTS), seed)
     return full if S == len(COUNTS) else full.head(S)
+
+
+# --------------------------------------------------------------------------------------------- the cases at the edges of the contract
+# Variations of the nine-state Case(kind, COUNTS): the mix of 0 / 1 / 2 / 17 fixes per wavefront stays (tests/test_fix_cpu.py holds the
+# host twin to the reference on each of them, tests/test_gpu_fix_edges.py the device).
+EARTH = np.array([4.2e6, 1.7e5, 4.8e6])      # an ECEF position: a GPS fix is 6e6 m from the origin
+MANY, MANY_SEED = 1027, 101                  # 257 workgroups of four states, the last one short
+Z_SCALES, X_SCALES = (0.5, 2.0, 1e-3, 1e3, 1.0 + 1e-7), (1.0, 3.0, 0.25)
+EDGE_BUILDERS = (("earth", (0, 3)), ("float32", (2, 3)), ("scaled", (2, 3)), ("identity", (2, 3)), ("many", (0, 1, 2, 3)))
+
+
+def _zp(kind):
+    """The columns of z that hold a position."""
+    return slice(0, 3) if kind == 0 else slice(4, 7)
+
+
+def _f32(a):
+    return a.astype(np.float32).astype(np.float64)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_case(name, kind):
+    """One of EDGE_BUILDERS:
+      earth     kinds 0, 3: EARTH added to the states' positions and to the position part of z (z - p stays exact in double)
+      float32   kinds 2, 3: the state and z quaternions rounded to float32 and back: unit to 1e-8 only
+      scaled    kinds 2, 3: z scaled by Z_SCALES[m % 5], the state quaternion by X_SCALES[s % 3] (residual_ld normalises the product)
+      identity  kinds 2, 3: the state quaternions np.eye(4)[(s + 3) % 4], z the owner's quaternion, negated for odd m: the product has
+                no rounding and the rotation residual is exactly +-0.0
+      many      every kind: MANY states (COUNTS tiled), a problem of its own seed"""
+    assert kind in dict(EDGE_BUILDERS)[name], (name, kind)
+    if name == "many":
+        c = Case(kind, np.tile(COUNTS, 115)[:MANY], seed=MANY_SEED)
+        nine = case(kind, len(COUNTS))
+        for a, b in ((c.states[:9], nine.states), (c.z[:int(c.mfirst[9])], nine.z), (c.R[:int(c.mfirst[9])], nine.R)):
+            assert not np.isin(a, b).any(), "the first nine states repeat the nine-state case"
+        return c
+    c = Case(kind, COUNTS)
+    own = c.owner()
+    if name == "earth":
+        c.states[:, 13:16] += EARTH
+        c.z[:, _zp(kind)] += EARTH
+        assert np.abs(c.states[:, 13:16]).max() > 4e6
+    elif name == "float32":
+        c.states[:, :4], c.z[:, :4] = _f32(c.states[:, :4]), _f32(c.z[:, :4])
+        n = np.linalg.norm(c.states[:, :4], axis=1)
+        assert (np.abs(n - 1) < 1e-7).all() and (n != 1.0).any()
+    elif name == "scaled":
+        c.z[:, :4] *= np.asarray(Z_SCALES)[np.arange(c.M) % 5][:, None]
+        c.states[:, :4] *= np.asarray(X_SCALES)[np.arange(c.S) % 3][:, None]
+    elif name == "identity":
+        c.states[:, :4] = np.eye(4)[(np.arange(c.S) + 3) % 4]
+        c.z[:, :4] = c.states[own, :4] * np.where(np.arange(c.M) % 2, -1.0, 1.0)[:, None]
+    return c
+
+
+def reversed_case(c):
+    """(the case with its states in reverse order, order [S], fixes [M]: where every state and fix of it sits in c)."""
+    order = np.arange(c.S - 1, -1, -1)
+    fixes = np.concatenate([np.arange(c.mfirst[s], c.mfirst[s + 1]) for s in order]).astype(np.int64)
+    mv = c.head(c.S)
+    mv.counts = c.counts[order]
+    mv.mfirst = offsets(mv.counts)
+    mv.states, mv.base, mv.pcost_base = c.states[order], c.base[order], c.pcost_base[order]
+    mv.z, mv.R, mv.weight = c.z[fixes], c.R[fixes], c.weight[fixes]
+    return mv, order, fixes
+
+
+def touched(kind):
+    """The entries of a row [136] that a kind writes: (Lam slots, eta slots)."""
+    d, sel = D[kind], SEL[kind]
+    return [slot(sel[a], sel[b]) for a in range(d) for b in range(a, d)], [slot(sel[a], 15) for a in range(d)]
 
 
 def reference(c, weight=True, base=True):

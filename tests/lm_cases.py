@@ -18,7 +18,8 @@ Gates = 100 x the floor, the rule of tests/tol.py; a floor is the largest value 
 one unit.  Measured (profiles/chain_lm.md):
     host twin (tests/hostsim/hostsim_lm.cpp, x86-64)    eta 79   pcost 6.1   cost 2.0
     device (MI355X)                                      eta 86   pcost 13    cost 2.0   final 1.93e-13 sigma
-A wrong term shows as 1e13 units and more (the mutation checks of tests/test_lm_cpu.py)."""
+hard_prior_case (GPS-sized positions, float32-rounded and scaled quaternions) stays below them: eta 5.6 / pcost 4.1 on the host twin,
+10.6 / 5.8 on the device.  A wrong term shows as 1e13 units and more (the mutation checks of tests/test_lm_cpu.py)."""
 import functools
 from fractions import Fraction
 
@@ -147,6 +148,26 @@ def prior_case(S, seed=11):
             P[:15, 15] = P[15, :15] = np.diag(P)[:15] * 0.01 * rng.standard_normal(15)
         P[15, 15] = np.nan
         prior0[p] = cc.pack_upper(P)
+    return states, anchor, prior0
+
+
+HARD_OFFSET = np.array([4.2e6, -1.7e5, 4.8e6])
+
+
+@functools.lru_cache(maxsize=None)
+def hard_prior_case(S, seed=11):
+    """prior_case(S) away from its comfortable range: the positions of state and anchor moved by the same HARD_OFFSET (a GPS position),
+    the quaternions of odd records rounded to float32 (unit to 1e-8 only), those of every third record scaled -- the state's by 0.5 and
+    the anchor's by 2 where p % 6 == 0, the other way round where p % 6 == 3.  localCoordinates normalises the product, so the
+    reference (xi from the oracle) is the contract's."""
+    states, anchor, prior0 = (a.copy() for a in prior_case(S, seed))
+    p = np.arange(S)
+    for a in (states, anchor):
+        a[:, 13:16] += HARD_OFFSET
+        a[p % 2 == 1, :4] = a[p % 2 == 1, :4].astype(np.float32).astype(np.float64)
+    for a, (s0, s3) in ((states, (0.5, 2.0)), (anchor, (2.0, 0.5))):
+        a[p % 6 == 0, :4] *= s0
+        a[p % 6 == 3, :4] *= s3
     return states, anchor, prior0
 
 
@@ -327,6 +348,45 @@ def rule_table(outside=True):
     cost = np.array([(new[c] + r[4]) if r[4] is not None else r[5] for c, r in enumerate(RULES)])
     case = AcceptCase(call, chi2_new, pcost_new, cost, [r[6] for r in RULES], [r[7] for r in RULES], params=RULE_PARAMS)
     return case, [r[8] for r in RULES]
+
+
+# The equalities and infinities of the rule, and chains on both sides of the copy loop's trip of 128 sixteen-byte pieces (16 states);
+# the columns of RULES, the parameters of RULE_PARAMS (lam_up 10, lam_max 1e5, abs_tol = rel_tol = 1e-5).  1e4 * 10 is 1e5 without
+# rounding; 2e-5 - 1e-5 is the double 1e-5 without rounding (a binary doubling).  cur = +inf over a finite new is an accept that
+# CONVERGES by the rule as written: dec = inf <= rel_tol * |cur| = inf.
+INF = float("inf")
+RULES_EDGE = [
+    ("lambda * lam_up == lam_max",  3, [1.0, 2.0], 0.25, -1.0, None, 1e4, 0, (0, RUNNING, 1e5)),
+    ("cur - new == abs_tol",        2, [0.0], 1e-5, None, 2e-5, 2.0, 0, (1, CONVERGED, 0.2)),
+    ("cur +inf, new finite",        3, [1.0, 2.0], 0.25, None, INF, 1.0, 0, (1, CONVERGED, 0.1)),
+    ("new -inf",                    3, [1.0, 2.0], -INF, None, 5.0, 1.0, 0, (1, RUNNING, 0.1)),
+    ("cur == new == +inf",          3, [1.0, 2.0], INF, None, INF, 1.0, 0, (0, RUNNING, 10.0)),
+    ("lambda 0 on a reject",        3, [1.0, 2.0], 0.25, -1.0, None, 0.0, 0, (0, RUNNING, 0.0)),
+    ("16 states accepted",          16, [1.0] * 15, 0.25, 1.0, None, 1.0, 0, (1, RUNNING, 0.1)),
+    ("17 states accepted",          17, [1.0] * 16, 0.25, 1.0, None, 1.0, 0, (1, RUNNING, 0.1)),
+    ("32 states accepted",          32, [1.0] * 31, 0.25, 1.0, None, 1.0, 0, (1, RUNNING, 0.1)),
+]
+
+
+def edge_rule_table():
+    """(AcceptCase, [the (accepted, phase, lambda) every rule of RULES_EDGE must give]) -- one chain per rule, gap rows between the
+    chains; every expected triple is the one lm_rule gives (asserted here)."""
+    b = cc.Batch([r[1] for r in RULES_EDGE], seed=2, layout="gaps")
+    call = cc.Call.explicit(b)
+    chi2_new, pcost_new = np.full(b.F, np.nan), np.full(b.S, np.nan)
+    for c, r in enumerate(RULES_EDGE):
+        chi2_new[b.ffirst[c]:b.ffirst[c] + r[1] - 1] = r[2]
+        pcost_new[b.first[c]:b.first[c] + r[1]] = 0.0
+        pcost_new[b.first[c]] = r[3]
+    new = chain_costs(call, chi2_new, pcost_new)
+    cost = np.array([(new[c] + r[4]) if r[4] is not None else r[5] for c, r in enumerate(RULES_EDGE)])
+    p = dict(DEFAULTS, **RULE_PARAMS)
+    for c, r in enumerate(RULES_EDGE):
+        acc, _, lam, ph = lm_rule(cost[c], new[c], r[6], p)
+        assert (acc, ph, lam) == r[8], (r[0], acc, ph, lam)
+    assert 1e4 * p["lam_up"] == p["lam_max"] and cost[1] - new[1] == p["abs_tol"]
+    case = AcceptCase(call, chi2_new, pcost_new, cost, [r[6] for r in RULES_EDGE], [r[7] for r in RULES_EDGE], params=RULE_PARAMS)
+    return case, [r[8] for r in RULES_EDGE]
 
 
 def ragged_accept_case(layout="tile", seed=4):

@@ -10,18 +10,22 @@
 4. Mutations of the twin, built in tmp_path, that must fail: a dropped sign flip, sel of the pose kind shifted by one block, the
    entries of the second round of sixteen lanes skipped.
 5. The end-to-end problem of tests/test_gpu_fix.py has positive definite undamped systems.
+6. The edges of the contract on the twin: the builders of fx.edge_case against the reference (the honesty condition of
+   tests/test_gpu_fix_edges.py), and the checks of tests/fix_edge_checks.py -- an exactly zero residual, a broken mfirst on padded
+   arrays, one NaN in every place -- each of which fails on a twin with the defect it is there for: no clamp, a position residual that
+   reads x.v, chi2 multiplied by the weight.
 The figures are printed before anything is asserted (pytest -s shows them; profiles/state_fix.md records them)."""
 import ctypes as C
 import inspect
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 from tests import fix_cases as fx
+from tests import fix_edge_checks as fe
 from tests import test_marginals_cpu as tm
 from tests.test_lm_cpu import same_bits
 
@@ -198,13 +202,14 @@ def hf():
     return _bind(_LIB)
 
 
-def _mutant(tmp_path, old, new):
-    text = open(_MATH).read()
-    assert text.count(old) == 1, old
+def _mutant(tmp_path, old, new, twin=False):
+    """The twin with old replaced by new in cpi_math.hpp -- or, with twin=True, in hostsim_fix.cpp itself (its range handling)."""
+    text, src = open(_MATH).read(), open(_SRC).read()
+    assert (src if twin else text).count(old) == 1, old
     os.makedirs(tmp_path / "cpi_amd" / "csrc")
     os.makedirs(tmp_path / "tests" / "hostsim")
-    (tmp_path / "cpi_amd" / "csrc" / "cpi_math.hpp").write_text(text.replace(old, new))
-    shutil.copy(_SRC, tmp_path / "tests" / "hostsim" / "hostsim_fix.cpp")
+    (tmp_path / "cpi_amd" / "csrc" / "cpi_math.hpp").write_text(text if twin else text.replace(old, new))
+    (tmp_path / "tests" / "hostsim" / "hostsim_fix.cpp").write_text(src.replace(old, new) if twin else src)
     out = str(tmp_path / "libmutant.so")
     tm._build(str(tmp_path / "tests" / "hostsim" / "hostsim_fix.cpp"), out)
     return _bind(out)
@@ -340,6 +345,104 @@ def test_the_stand_alone_twin_program(tmp_path):
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wno-unknown-pragmas", "-ffp-contract=off", "-DHOSTSIM_FIX_MAIN", "-o", exe, _SRC])
     p = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=60)
     assert p.returncode == 0, p.stdout
+
+
+# ---------------------------------------------------------------- the edges of the contract, on the twin
+EDGE_CASES = [(name, kind) for name, kinds in fx.EDGE_BUILDERS for kind in kinds]
+
+
+@pytest.mark.parametrize("name,kind", EDGE_CASES, ids=["%s-%s" % (n, fx.KINDS[k]) for n, k in EDGE_CASES])
+def test_twin_on_the_edge_builders(hf, name, kind):
+    """The honesty condition of the builders of tests/fix_cases.py: the reference and the twin agree within GATE_HOST on each of them
+    before any number from the device is believed; the documented order bit for bit (the nine-state builders)."""
+    c = fx.edge_case(name, kind)
+    worst = {}
+    for weight, base in ((True, True), (False, False)):
+        out, pcost, chi2 = twin(hf, c, weight, base)
+        if name != "many":
+            d_out, d_pc, d_chi2 = fx.documented(c, twin_residual(hf, c), weight, base)
+            assert same_bits(out, d_out) and same_bits(pcost, d_pc) and same_bits(chi2, d_chi2), (weight, base)
+        for k, v in fx.metrics(out, pcost, chi2, fx.reference(c, weight, base)).items():
+            worst[k] = max(worst.get(k, 0.0), v)
+    print("twin, %s, %s: %s (gates %s)" % (name, fx.KINDS[kind], ", ".join("%s %.3g" % kv for kv in sorted(worst.items())), fx.GATE_HOST))
+    for k, v in worst.items():
+        assert v <= fx.GATE_HOST[k], (k, v)
+    if name == "many":                                                        # a state's bits: not S, nor where it sits
+        assert c.S == fx.MANY and set(c.counts.tolist()) == {0, 1, 2, 17}
+        out, pcost, chi2 = twin(hf, c)
+        o, p, x2 = twin(hf, c.head(9))
+        assert same_bits(o, out[:9]) and same_bits(p, pcost[:9]) and same_bits(x2, chi2[:len(x2)])
+        mv, order, fixes = fx.reversed_case(c)
+        o, p, x2 = twin(hf, mv)
+        assert same_bits(o, np.ascontiguousarray(out[order])) and same_bits(p, np.ascontiguousarray(pcost[order])) and same_bits(x2, np.ascontiguousarray(chi2[fixes]))
+    if name == "identity":                                                    # the premise: a rotation residual of exactly 0, both signs
+        e = twin_residual(hf, c)[:, :3]
+        assert (e == 0.0).all() and np.signbit(e).any() and not np.signbit(e).all()
+    if name == "earth":                                                       # z - p is exact: the residuals of the nine-state case to 1e-9
+        e, e0 = twin_residual(hf, c)[:, -3:], twin_residual(hf, fx.case(kind, 9))[:, -3:]
+        assert np.abs(e - e0).max() < 2e-9 and np.abs(e).max() < 1.0
+
+
+@pytest.mark.parametrize("kind", [2, 3], ids=fx.KINDS[2:])
+def test_twin_exact_zero_residual(hf, kind):
+    m = fe.check_exact_zero(lambda c: twin(hf, c), kind)
+    for k, v in m.items():
+        assert v <= fx.GATE_HOST[k], (k, v)
+
+
+def twin_padded(h, p, mfirst):
+    """hsf_state_fix on the interiors of the padded arrays of fe.Padded -> the whole buffers (out, pcost, chi2)."""
+    c, P = p.c, fe.PAD
+    out, pcost = np.full((c.S + 2, 136), np.nan), np.full(c.S + 2, np.nan)
+    out[[0, -1]], pcost[[0, -1]] = fe.GUARD, fe.GUARD
+    chi2 = p.big["chi2"].copy()
+    mf = np.ascontiguousarray(mfirst, dtype=np.int64)
+    z, R, w = p.big["z"], p.big["R"], p.big["weight"]
+    assert h.hsf_state_fix(c.S, c.M, c.kind, _ptr(mf), _ptr(c.states), _ptr(z, P * z.strides[0]), _ptr(R, P * R.strides[0]), _ptr(w, P * 8),
+                           _ptr(c.base), _ptr(c.pcost_base), _ptr(out, 136 * 8), _ptr(pcost, 8), _ptr(chi2, P * 8)) == 0
+    return out, pcost, chi2
+
+
+@pytest.mark.parametrize("kind", [0, 3], ids=["position", "pose"])
+def test_twin_broken_mfirst_stays_inside(hf, lib, kind):
+    fe.check_broken_mfirst(lambda p, mf: twin_padded(hf, p, mf), kind)
+    c = fx.case(kind, 9)                                                      # the host form refuses each of them, naming a state
+    for what, mf, _ in fe.broken_mfirsts(c):
+        a = [np.ascontiguousarray(x) for x in (mf, c.states, c.z, c.R, c.weight, c.base, c.pcost_base, np.zeros((c.S, 136)), np.zeros(c.S), np.zeros(c.M))]
+        rc = lib.cpi_state_fix_batch_host(None, c.S, c.M, kind, *[_ptr(x) for x in a])
+        print("%s: %s" % (what, _err(lib)))
+        assert rc == 1 and re.search(r"the fixes of state \d+ ", _err(lib)), what
+
+
+@pytest.mark.parametrize("kind", range(4), ids=fx.KINDS)
+def test_twin_nan_stays_where_it_is(hf, kind):
+    assert fe.check_nan_locality(lambda c: twin(hf, c), kind) >= 24
+
+
+EDGE_MUTATIONS = {
+    "a missing mfirst clamp": ("{ return v < 0 ? 0 : (v > M ? M : v); }", "{ return v; }", True, "mfirst"),
+    "a position residual that reads x.v": ("e[0] = z[0] - x.p.x; e[1] = z[1] - x.p.y; e[2] = z[2] - x.p.z; }\n    if (K == FIX_VELOCITY)",
+                                           "e[0] = z[0] - x.v.x; e[1] = z[1] - x.v.y; e[2] = z[2] - x.v.z; }\n    if (K == FIX_VELOCITY)", False, "nan"),
+    "chi2 multiplied by the weight": ("if (chi2) chi2[m] = c2;", "if (chi2) chi2[m] = w * c2;", False, "nan"),
+}
+
+
+@pytest.mark.parametrize("what", list(EDGE_MUTATIONS))
+def test_the_edge_checks_fail_when_they_should(hf, tmp_path, what):
+    """The twin with one defect, built in tmp_path: the check of the edge family named in EDGE_MUTATIONS passes on the twin and fails on
+    the mutant.  (The padded arrays keep a twin without the clamp inside its allocations: it reads a NaN pad or writes over a guard.)"""
+    old, new, in_twin, family = EDGE_MUTATIONS[what]
+    mutant = _mutant(tmp_path, old, new, twin=in_twin)
+    check = {"mfirst": lambda h: fe.check_broken_mfirst(lambda p, mf: twin_padded(h, p, mf), 0),
+             "nan": lambda h: fe.check_nan_locality(lambda c: twin(h, c), 0)}[family]
+    check(hf)
+    with pytest.raises(AssertionError):
+        check(mutant)
+    if family == "nan":                                                       # ... and the reference comparison of the builders sees it too
+        c = fx.edge_case("earth", 0)
+        m = fx.metrics(*twin(mutant, c), fx.reference(c))
+        print("%s, earth: %s" % (what, m))
+        assert max(m.values()) > 1e3 * max(fx.GATE_HOST.values())
 
 
 # ---------------------------------------------------------------- the end-to-end problem

@@ -9,6 +9,9 @@
 4. Mutations of the twin, built in tmp_path, that must fail: eta0 with the wrong sign, <= for < in the accept test, a butterfly stride
    dropped, lambda raised on accept.
 5. The rule table of chain_accept on the twin, one chain per rule.
+6. The edges that tests/test_gpu_lm_edges.py runs on the device, settled on the twin first: lc.hard_prior_case against the reference,
+   and lc.RULES_EDGE -- the rule's equalities and infinities and chains around the copy loop's trip --, which a twin with < in place
+   of <= at lam_max fails while it still passes the table of RULES.
 The figures are printed before anything is asserted (pytest -s shows them; profiles/chain_lm.md records them)."""
 import ctypes as C
 import inspect
@@ -463,6 +466,45 @@ def test_twin_rule_table(hl):
     check_accept(twin_accept(hl, case, with_chi2=False, with_accepted=False), case.expected(with_chi2=False))
 
 
+def test_twin_prior_on_the_hard_case(hl):
+    """The honesty condition of lc.hard_prior_case: the twin against the restatement bit for bit and against the longdouble reference
+    within the host gates, at GPS-sized positions, float32-rounded and scaled quaternions."""
+    S = 65
+    states, anchor, prior0 = lc.hard_prior_case(S)
+    easy = lc.prior_case(S)
+    assert np.abs(states[:, 13:16]).max() > 4e6 and np.array_equal(prior0, easy[2], equal_nan=True)
+    n = np.linalg.norm(states[:, :4], axis=1)
+    assert (np.abs(n[1::6] - 1) < 1e-7).all() and (n[1::6] != 1).any() and (np.abs(n[0::6] - 0.5) < 1e-7).all() and (np.abs(n[3::6] - 2) < 1e-6).all()
+    xi = np.zeros((S, 15))
+    assert hl.hsl_local(S, _ptr(states), _ptr(anchor), _ptr(xi)) == 0
+    prior, pcost = twin_prior(hl, S, None, states, anchor, prior0)
+    rows, pc = lc.prior_documented(xi, prior0)
+    assert same_bits(prior, rows) and same_bits(pcost, pc)
+    assert same_bits(prior[:, :120], prior0[:, :120]) and (prior[:, 135] == 0.0).all()
+    at = np.arange(S) % 4 == 0
+    m_eta, m_pc = lc.prior_metrics(prior, pcost, lc.oracle_local(states, anchor), prior0, skip=at)
+    print("twin, the hard prior case, S %d: eta %.3g units (gate %.0f), pcost %.3g units (gate %.0f); at the anchor |xi| max %.3g"
+          % (S, m_eta, lc.GATE_ETA_HOST, m_pc, lc.GATE_PCOST_HOST, np.abs(xi[at]).max()))
+    assert m_eta <= lc.GATE_ETA_HOST and m_pc <= lc.GATE_PCOST_HOST
+
+
+def test_twin_edge_rule_table(hl):
+    """The equalities and infinities of the rule and the chains around the copy loop's trip (lc.RULES_EDGE): the triples as written
+    there, the rows bit for bit and every sentinel around them."""
+    case, want = lc.edge_rule_table()
+    got = twin_accept(hl, case)
+    for c, (rule, (acc, phase, lam)) in enumerate(zip(lc.RULES_EDGE, want)):
+        print("%-28s accepted %d phase %d lambda %g cost %g" % (rule[0], got[5][c], got[4][c], got[3][c], got[0][c]))
+        assert (got[5][c], got[4][c], got[3][c]) == (acc, phase, lam), rule[0]
+    check_accept(got, case.expected())
+    b = case.call.b
+    for c in (6, 7, 8):                                                       # 16, 17 and 32 states: the trial's rows, the sentinels on either side
+        rows = b.rows(c)
+        assert same_bits(got[1][rows], case.trial[rows])
+        assert same_bits(got[1][rows.start - 2:rows.start], case.states[rows.start - 2:rows.start])
+        assert same_bits(got[1][rows.stop:rows.stop + 2], case.states[rows.stop:rows.stop + 2])
+
+
 @pytest.mark.parametrize("layout", ["tile", "gaps", "reverse"])
 def test_twin_accept_ragged(hl, layout):
     case = lc.ragged_accept_case(layout)
@@ -508,6 +550,20 @@ def test_a_wrong_term_fails_its_gate(hl, tmp_path, what):
     failed = {"eta0 added with the wrong sign": m[1] > 1e3 * lc.GATE_PCOST_HOST, "a butterfly stride dropped": m[2] > 1e3 * lc.GATE_COST_HOST,
               "<= in place of < in the accept test": not m[3], "lambda raised on accept": not m[3]}[what]
     assert failed, m
+
+
+def test_a_strict_comparison_at_lam_max_fails_the_edge_table(hl, tmp_path):
+    """< in place of <= at lam_max: the table of RULES keeps holding (no rule of it sits on the bound), the edge table does not."""
+    mutant = _mutant(tmp_path, "if (!(l <= p.lam_max)) phase = 2;", "if (!(l < p.lam_max)) phase = 2;")
+    plain, _ = lc.rule_table()
+    edge, want = lc.edge_rule_table()
+    check_accept(twin_accept(hl, edge), edge.expected())
+    check_accept(twin_accept(mutant, plain), plain.expected())
+    got = twin_accept(mutant, edge)
+    print("the mutant on 'lambda * lam_up == lam_max': phase %d lambda %g (the rule: %s)" % (got[4][0], got[3][0], want[0]))
+    assert (got[4][0], got[3][0]) == (lc.GAVE_UP, 1e4)
+    with pytest.raises(AssertionError):
+        check_accept(got, edge.expected())
 
 
 def test_the_stand_alone_twin_program(tmp_path):
