@@ -72,7 +72,7 @@ UNITS = {
     "cpi_marginalize": DEVICE + ["cpi_marginalize.hip", "cpi_factor_kernels.hpp", "cpi_chain_util.hpp", "cpi_marginalize_kernels.hpp"],
     "cpi_lm": DEVICE + ["cpi_lm.hip", "cpi_factor_kernels.hpp", "cpi_chain_util.hpp", "cpi_lm_kernels.hpp"],
     "cpi_fix": DEVICE + ["cpi_fix.hip", "cpi_fix_kernels.hpp"],
-    "cpi_abi": COMMON + ["cpi_abi.hip", "../../include/cpi_amd_test.h"],   # the test header: -DCPI_TEST_HOOKS builds only
+    "cpi_abi": COMMON + ["cpi_abi.hip", "cpi_capture_overlap.hpp", "../../include/cpi_amd_test.h"],   # the test header: -DCPI_TEST_HOOKS builds only
 }
 EXP_EXTRA = {"cpi_mean": ["cpi_mean_experimental.hpp"]}   # additional includes under -DCPI_EXPERIMENTS
 EXP_UNITS = ("cpi_mean", "cpi_abi")                        # the units that differ in an experiments build

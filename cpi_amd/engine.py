@@ -133,6 +133,10 @@ class Engine:
     def synchronize(self):
         self._check(self.lib.cpi_ctx_synchronize(self.ctx))
 
+    def set_capture_overlap(self, depth):
+        """cpi_ctx_set_capture_overlap: how many captured, provably disjoint batch calls may be unordered in a HIP graph (1 = none)."""
+        self._check(self.lib.cpi_ctx_set_capture_overlap(self.ctx, int(depth)))
+
     # ------------------------------------------------------------------ preintegration
     @staticmethod
     def make_params(model=1, imu_avg=False, state_transition_jacobians=True, sigmas=DEFAULT_SIGMAS,

@@ -157,6 +157,25 @@ int cpi_ctx_create(int device, void *stream, cpi_ctx **out);
 void cpi_ctx_destroy(cpi_ctx *ctx);
 /* Later calls on ctx are issued on `stream` (a hipStream_t of the context's device).  The caller orders the two streams. */
 int cpi_ctx_set_stream(cpi_ctx *ctx, void *stream);
+/* Captured batch calls.  While ctx's stream is being captured into a HIP graph, consecutive cpi_preintegrate_batch calls that
+ * issue one kernel (means, or means + analytic Jacobians; no covariance) are left UNORDERED in the graph, up to `depth` of them at
+ * a time, when the library can prove from the arguments that the memory they touch is disjoint: no array one call writes
+ * (W x n x 8 bytes per non-NULL output) overlaps an array the other reads or writes (knots, lin, q_k_lin, count, outputs).
+ * Their kernels may then run concurrently when the graph is replayed.  What a caller may rely on:
+ *   - results are bit for bit those of the serial order (calls that share memory stay ordered; a call with a `first` array,
+ *     whose knot span the host cannot see, is ordered against everything);
+ *   - everything the caller captures on the stream before such calls happens before them, and everything captured after them
+ *     (any other entry of this library, a copy, a kernel, an event record, hipStreamEndCapture) happens after ALL of them;
+ *   - at most `depth` calls are in flight; call i is ordered behind call i - depth and everything before it;
+ *   - eager (non-captured) execution is never relaxed.
+ * depth 1 = every node depends on the previous one (the shape before this entry existed); clamped to [1, 4]; default 2 (the fastest
+ * measured, profiles/capture_overlap.md), or
+ * CPI_AMD_CAPTURE_OVERLAP=<depth> read once by cpi_ctx_create.  A process that sets GPU_MAX_HW_QUEUES below 4 keeps depth 1
+ * (parallel branches of a graph need four hardware queues); the library never sets that variable.  Two cases keep the serial
+ * shape because overlap was measured not to pay there (profiles/capture_overlap.md): launches of more than one wavefront per
+ * SIMD (1 024 wavefronts), and captures in which several contexts of the process take part (the caller spread the calls by hand).  A caller that writes one of
+ * the arrays from ANOTHER stream of the same capture orders the streams with events as before. */
+int cpi_ctx_set_capture_overlap(cpi_ctx *ctx, int32_t depth);
 const char *cpi_last_error(const cpi_ctx *ctx); /* ctx may be NULL: last error of a failed create */
 int cpi_abi_version(void);
 const char *cpi_build_id(void);   /* sha256[:16] of the sources this library was built from (cpi_amd/build.py: source_id) */
