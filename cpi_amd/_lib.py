@@ -123,6 +123,7 @@ def load():
     lib.cpi_ctx_synchronize.argtypes = [vp]
     lib.cpi_ctx_set_stream.argtypes = [vp, vp]
     lib.cpi_ctx_set_capture_overlap.argtypes = [vp, i32]
+    lib.cpi_ctx_set_capture_strands.argtypes = [vp, i32]
     lib.cpi_preintegrate_batch.argtypes = [vp, C.POINTER(CpiParams), i64, i32, dp, vp, vp, dp, dp, C.POINTER(CpiOutputs)]
     lib.cpi_preintegrate_tiled_batch.argtypes = [vp, C.POINTER(CpiParams), i64, i32, dp, vp, dp, dp, C.POINTER(CpiOutputs)]
     lib.cpi_tile_knots.argtypes = [vp, i64, i32, dp, dp]

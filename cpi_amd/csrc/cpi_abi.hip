@@ -62,12 +62,16 @@ struct cpi_ctx {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     unsigned big_lds_set = 0;   // bit per kernel instantiation whose dynamic-LDS limit was raised on this device
     struct HostPipe *pipe = nullptr;   // staging of the host-pointer entries (created at their first use)
-    // Captured single-kernel cpi_preintegrate_batch calls on provably disjoint memory are left unordered in the graph, up to
-    // overlap_depth of them (1 = the serial shape); the window is the bookkeeping of the current run of such calls
-    // (cpi_capture_overlap.hpp, capture_overlap_begin / _end below).  Parallel branches of a graph need >= 4 hardware queues.
-    int overlap_depth = 1;
+    // Captured single-kernel cpi_preintegrate_batch calls on provably disjoint memory are left unordered in the graph: on
+    // overlap_n strands, or (the opt-in look-back shape) up to overlap_n of them at a time; 1 = the serial shape.  The window /
+    // the strands are the bookkeeping of the current run of such calls (cpi_capture_overlap.hpp, capture_overlap_begin / _end
+    // below); only the one overlap_shape names is ever open.  Parallel branches of a graph need >= 4 hardware queues.
+    overlap::Shape overlap_shape = overlap::kShapeLookback;
+    int overlap_n = 1;
     bool overlap_allowed = true;
     overlap::Window<hipGraphNode_t> window;
+    overlap::Strands<hipGraphNode_t> strands;
+    void close_window() { window.close(); strands.close(); }
     std::vector<hipGraphNode_t> ov_found, ov_preds;   // scratch of a call: the stream's dependencies as found; the planned predecessors
 };
 static thread_local std::string g_create_err;
@@ -120,10 +124,11 @@ extern "C" int cpi_ctx_create(int device, void *stream, cpi_ctx **out) {
     cpi_ctx *c = new cpi_ctx();
     c->device = device;
     c->stream = (hipStream_t)stream;
-    // the context's capture-overlap depth is settled once, here (cpi_capture_overlap.hpp: Policy); no launch path reads the environment
-    const overlap::Policy pol = overlap::policy_from_environment();
+    // the context's capture shape is settled once, here (cpi_capture_overlap.hpp: CapturePolicy); no launch path reads the environment
+    const overlap::CapturePolicy pol = overlap::capture_policy_from_environment();
     c->overlap_allowed = pol.allowed;
-    c->overlap_depth = pol.depth;
+    c->overlap_shape = pol.shape;
+    c->overlap_n = pol.n;
     *out = c;
     return CPI_OK;
 }
@@ -145,14 +150,22 @@ extern "C" void cpi_ctx_destroy(cpi_ctx *ctx) {
 }
 extern "C" int cpi_ctx_set_stream(cpi_ctx *ctx, void *stream) {
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
-    if (ctx->stream != (hipStream_t)stream) ctx->window.close();   // the window describes one stream's capture
+    if (ctx->stream != (hipStream_t)stream) ctx->close_window();   // the window describes one stream's capture
     ctx->stream = (hipStream_t)stream;
     return CPI_OK;
 }
 extern "C" int cpi_ctx_set_capture_overlap(cpi_ctx *ctx, int32_t depth) {
     if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
-    ctx->overlap_depth = ctx->overlap_allowed ? overlap::clamp_depth(depth) : 1;
-    ctx->window.close();
+    ctx->overlap_shape = overlap::kShapeLookback;
+    ctx->overlap_n = ctx->overlap_allowed ? overlap::clamp_depth(depth) : 1;
+    ctx->close_window();
+    return CPI_OK;
+}
+extern "C" int cpi_ctx_set_capture_strands(cpi_ctx *ctx, int32_t n) {
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    ctx->overlap_shape = overlap::kShapeStrands;
+    ctx->overlap_n = ctx->overlap_allowed ? overlap::clamp_strands(n) : 1;
+    ctx->close_window();
     return CPI_OK;
 }
 extern "C" const char *cpi_last_error(const cpi_ctx *ctx) { return ctx ? ctx->err.c_str() : g_create_err.c_str(); }
@@ -364,9 +377,11 @@ static int cut_launch(cpi_ctx *ctx, const StreamCut &sc, const double *stream, i
 }
 // ---- captured batch calls: independent launches overlap in the graph ----------------------
 // While the context's stream is capturing, a cpi_preintegrate_batch call that issues exactly one kernel and touches no
-// context-owned memory need not wait for the up to overlap_depth - 1 such calls captured right before it when its footprint is
-// disjoint from theirs.  capture_overlap_begin replaces the stream's capture dependencies by the planned predecessors, the
-// kernel is launched as always, capture_overlap_end reads the new node back and leaves the window's frontier on the stream.
+// context-owned memory need not wait for every such call captured before it: on the strand shape it follows the one strand its
+// footprint conflicts with (or the least recently extended one), on the look-back shape it skips the up to overlap_n - 1 calls
+// right before it whose footprints are disjoint from its own.  capture_overlap_begin replaces the stream's capture
+// dependencies by the planned predecessors, the kernel is launched as always, capture_overlap_end reads the new node back and
+// leaves the window's frontier on the stream.
 // Nothing here can fail a call: any error or surprise of the capture queries puts the dependencies back as found (so the
 // launch, and whatever follows, is ordered behind everything before it -- the serial shape) and closes the window.
 static void overlap_give_up(cpi_ctx *ctx, bool restore) {
@@ -376,22 +391,23 @@ static void overlap_give_up(cpi_ctx *ctx, bool restore) {
                                                  hipStreamAddCaptureDependencies);
         (void)hipGetLastError();
     }
-    ctx->window.close();
+    ctx->close_window();
 }
 // true: the launch that follows is part of the window and capture_overlap_end must be called after it
-static bool capture_overlap_begin(cpi_ctx *ctx, const overlap::Footprint &fp) {
-    if (ctx->overlap_depth <= 1 || !ctx->stream) return false;   // the serial shape asks the runtime nothing
+template <class Win>   // overlap::Window or overlap::Strands: the context's shape
+static bool capture_overlap_begin(cpi_ctx *ctx, Win &win, const overlap::Footprint &fp) {
+    if (ctx->overlap_n <= 1 || !ctx->stream) return false;   // the serial shape asks the runtime nothing
     hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
     unsigned long long id = 0;
     const hipGraphNode_t *deps = nullptr;
     size_t ndeps = 0;
     if (hipStreamGetCaptureInfo_v2(ctx->stream, &status, &id, nullptr, &deps, &ndeps) != hipSuccess) { overlap_give_up(ctx, false); return false; }
-    if (status != hipStreamCaptureStatusActive || (ndeps && !deps)) { ctx->window.close(); return false; }
+    if (status != hipStreamCaptureStatusActive || (ndeps && !deps)) { win.close(); return false; }
     // several contexts inside one capture: the caller spread the calls by hand, every context keeps the serial shape
-    if (!overlap::capture_registry().sole(id, ctx)) { ctx->window.close(); return false; }
+    if (!overlap::capture_registry().sole(id, ctx)) { win.close(); return false; }
     ctx->ov_found.assign(deps, deps + ndeps);   // (the runtime's array is valid until the next call on the stream)
-    if (!ctx->window.continues(id, ctx->ov_found.data(), ndeps)) ctx->window.open_at(id, ctx->overlap_depth, ctx->ov_found.data(), ndeps);
-    ctx->window.plan(fp, ctx->ov_preds);
+    if (!win.continues(id, ctx->ov_found.data(), ndeps)) win.open_at(id, ctx->overlap_n, ctx->ov_found.data(), ndeps);
+    win.plan(fp, ctx->ov_preds);
     if (overlap::same_set(ctx->ov_preds, ctx->ov_found.data(), ndeps)) return true;   // (a window's first call; a chain) nothing to change
     if (hipStreamUpdateCaptureDependencies(ctx->stream, ctx->ov_preds.empty() ? nullptr : ctx->ov_preds.data(), ctx->ov_preds.size(),
                                            hipStreamSetCaptureDependencies) != hipSuccess) {
@@ -400,7 +416,8 @@ static bool capture_overlap_begin(cpi_ctx *ctx, const overlap::Footprint &fp) {
     }
     return true;
 }
-static void capture_overlap_end(cpi_ctx *ctx, const overlap::Footprint &fp) {
+template <class Win>
+static void capture_overlap_end(cpi_ctx *ctx, Win &win, const overlap::Footprint &fp) {
     hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
     unsigned long long id = 0;
     const hipGraphNode_t *deps = nullptr;
@@ -409,9 +426,9 @@ static void capture_overlap_end(cpi_ctx *ctx, const overlap::Footprint &fp) {
         status != hipStreamCaptureStatusActive || ndeps != 1 || !deps) { overlap_give_up(ctx, true); return; }
     const hipGraphNode_t node = deps[0];
     for (hipGraphNode_t p : ctx->ov_preds) if (p == node) { overlap_give_up(ctx, true); return; }   // the launch captured nothing
-    ctx->window.commit(node, fp);
-    const std::vector<hipGraphNode_t> &fr = ctx->window.frontier();
-    if (fr.size() == 1) return;   // the new node alone: what the stream holds already
+    win.commit(node, fp);
+    const std::vector<hipGraphNode_t> &fr = win.frontier();
+    if (fr.size() == 1 && fr[0] == node) return;   // the new node alone: what the stream holds already
     if (hipStreamUpdateCaptureDependencies(ctx->stream, const_cast<hipGraphNode_t *>(fr.data()), fr.size(), hipStreamSetCaptureDependencies) != hipSuccess)
         overlap_give_up(ctx, true);
 }
@@ -458,7 +475,7 @@ static int preintegrate_impl(cpi_ctx *ctx, const char *who, const cpi_params *pr
 
     DeviceGuard guard_;
     CPI_HIP(ctx, guard_.enter(ctx->device));
-    if (!overlap_ok) ctx->window.close();
+    if (!overlap_ok) ctx->close_window();
     if (sc && !fused_cut) {
         CPI_TRY(cut_launch(ctx, *sc, knots, W, N));
         first = reinterpret_cast<const int64_t *>(sc->first); count = sc->count;
@@ -510,17 +527,18 @@ static int preintegrate_impl(cpi_ctx *ctx, const char *who, const cpi_params *pr
 #endif
         if (done < W) {
             if (fused_cut && sc->runs) launch::mean_runs(prm->model, avg, LL, m, *sc->runs, mean_stream);
-            else if (overlap_ok && ctx->overlap_depth > 1 && !overlap::launch_is_latency_bound((W + (64 / LL) - 1) / (64 / LL))) {
-                ctx->window.close();   // a launch that fills the SIMDs several times over has no idle head and tail to hide
+            else if (overlap_ok && ctx->overlap_n > 1 && !overlap::launch_is_latency_bound((W + (64 / LL) - 1) / (64 / LL))) {
+                ctx->close_window();   // a launch that fills the SIMDs several times over has no idle head and tail to hide
                 launch::mean(prm->model, mean_jac, avg, LL, m, mean_stream);
-            } else if (overlap_ok && ctx->overlap_depth > 1) {
+            } else if (overlap_ok && ctx->overlap_n > 1) {
                 const void *outs[kOutFields];
                 for (int k = 0; k < kOutFields; k++) outs[k] = out_field_c(out, k);
                 const overlap::Footprint fp = overlap::make_footprint(W, N, knots, first, count, lin, q_k_lin, outs, OUT_N, kOutFields);
-                const bool in_window = capture_overlap_begin(ctx, fp);
+                const bool strands = ctx->overlap_shape == overlap::kShapeStrands;
+                const bool in_window = strands ? capture_overlap_begin(ctx, ctx->strands, fp) : capture_overlap_begin(ctx, ctx->window, fp);
                 launch::mean(prm->model, mean_jac, avg, LL, m, mean_stream);
                 const hipError_t launched = hipGetLastError();   // taken before the capture queries, which clear their own errors
-                if (in_window) capture_overlap_end(ctx, fp);
+                if (in_window) { if (strands) capture_overlap_end(ctx, ctx->strands, fp); else capture_overlap_end(ctx, ctx->window, fp); }
                 CPI_HIP(ctx, launched);
             } else launch::mean(prm->model, mean_jac, avg, LL, m, mean_stream);
         }

@@ -1,10 +1,12 @@
 // cpi_capture_overlap.hpp -- which captured cpi_preintegrate_batch calls may run unordered in a HIP graph, decided on the host.
-// Plain C++ (no HIP): cpi_abi.hip drives it with hipGraphNode_t, tests/cpp/test_capture_overlap_cpu.cpp with fake node ids.
+// Plain C++ (no HIP): cpi_abi.hip drives it with hipGraphNode_t, tests/cpp/test_capture_overlap_cpu.cpp and
+// tests/cpp/test_capture_strands_cpu.cpp with fake node ids.
 //
-// Two parts:
+// Three parts:
 //   Footprint  the byte ranges a call reads and writes, and the conflict test between two calls;
 //   Window     the bookkeeping of consecutive eligible calls captured on one stream: the predecessors of the next call and
-//              the dependency set ("frontier") the stream is left with after it.
+//              the dependency set ("frontier") the stream is left with after it -- the look-back shape, an opt-in;
+//   Strands    the same bookkeeping for the shape a context starts with: one chain per strand (at the end of this file).
 // The rule: call i of a window may be unordered only with calls i-1 ... i-D+1, and only
 // with those whose footprint is disjoint from its own; it has a path from every earlier call of the window and from the
 // base (the stream's dependency set when the window opened).  Realised with at most 2D-1 edges per call:
@@ -25,7 +27,7 @@ namespace cpi {
 namespace overlap {
 
 constexpr int kMaxDepth = 4;
-constexpr int kDefaultDepth = 2;   // measured: profiles/capture_overlap.md (3 and 4 are slower than the serial shape)
+constexpr int kDefaultDepth = 2;   // of the look-back shape; measured: profiles/capture_overlap.md (3 and 4 are slower than the serial shape)
 inline int clamp_depth(long long d) { return d < 1 ? 1 : (d > kMaxDepth ? kMaxDepth : (int)d); }
 
 // What a new context starts with; read ONCE per context, at its creation -- no launch path reads the environment.
@@ -196,6 +198,177 @@ private:
     Footprint fp_[kRing];
     uint32_t anc_[kRing] = {}, pending_anc_ = 0;   // bit d: the call d before this one is an ancestor (d < 32)
 };
+
+// ---- strands: one chain of calls per strand, no cross edges except at joins --------------------------------------
+// The look-back rule above makes every node of an all-disjoint walk join D branches; measured, those cross-branch edges cost
+// more than a third launch in flight returns.  Strands keep the same two guarantees with ONE in-edge per call:
+//   summary    per strand, the union of what its calls have read / written since the window opened or was last joined, as two
+//              RangeSets of fixed capacity: look-back unbounded in calls, bounded in memory, nothing allocated per call;
+//   placement  a call that conflicts with no strand's summary goes to the least recently extended strand (empty ones first);
+//              one that conflicts with exactly one strand goes behind that strand's tail; one that conflicts with several
+//              strands, or is unknown while several are non-empty, or whose ranges no longer fit the summary, is a JOIN: its
+//              predecessors are the tails of all non-empty strands, and the window restarts behind it (base = {the join});
+//   preds      of any other call: its strand's tail, or the base while the strand is empty;
+//   frontier   the tails of the non-empty strands; the base while there is none.
+// Two calls without a path between them lie on different strands of one window between two joins, so neither conflicted with
+// the other's strand summary when it was placed: their footprints are disjoint.  Everything behind a join descends from it.
+constexpr int kMaxStrands = 4;
+constexpr int kReadRanges = 64, kWriteRanges = 32;
+inline int clamp_strands(long long n) { return n < 1 ? 1 : (n > kMaxStrands ? kMaxStrands : (int)n); }
+
+// A sorted array of coalesced byte ranges: overlapping, touching and identical ranges merge, so no two entries share or touch.
+template <int Cap>
+class RangeSet {
+public:
+    int size() const { return n_; }
+    const Range &operator[](int i) const { return r_[i]; }
+    void clear() { n_ = 0; }
+    bool overlaps(const Range &x) const {
+        if (x.hi <= x.lo) return false;
+        int i = 0;
+        while (i < n_ && r_[i].hi <= x.lo) i++;   // (entries are disjoint and sorted: the first one that ends behind x.lo decides)
+        return i < n_ && r_[i].lo < x.hi;
+    }
+    // false: the set is full and x starts a new entry -- nothing was changed
+    bool add(const Range &x) {
+        if (x.hi <= x.lo) return true;
+        int i = 0;
+        while (i < n_ && r_[i].hi < x.lo) i++;    // [i, j): the entries x overlaps or touches
+        int j = i;
+        while (j < n_ && r_[j].lo <= x.hi) j++;
+        if (i == j) {
+            if (n_ == Cap) return false;
+            for (int k = n_; k > i; k--) r_[k] = r_[k - 1];
+            r_[i] = x;
+            n_++;
+            return true;
+        }
+        Range m = {x.lo < r_[i].lo ? x.lo : r_[i].lo, x.hi > r_[j - 1].hi ? x.hi : r_[j - 1].hi};
+        r_[i] = m;
+        for (int k = j; k < n_; k++) r_[i + 1 + (k - j)] = r_[k];
+        n_ -= j - i - 1;
+        return true;
+    }
+
+private:
+    int n_ = 0;
+    Range r_[Cap];
+};
+
+// RCap / WCap: the summaries' capacities (the test instantiates a small one so that overflow joins occur)
+template <class Node, int RCap = kReadRanges, int WCap = kWriteRanges>
+class Strands {
+public:
+    bool is_open() const { return open_; }
+    void close() { open_ = false; }
+    long long calls() const { return n_; }
+    long long joins() const { return joins_; }
+    int last_strand() const { return last_; }   // where the call committed last went; -1: it was a join
+    const std::vector<Node> &base() const { return base_; }
+    const std::vector<Node> &frontier() const { return frontier_; }
+
+    bool continues(unsigned long long capture_id, const Node *deps, size_t ndeps) const {
+        return open_ && capture_id == id_ && same_set(frontier_, deps, ndeps);
+    }
+    void open_at(unsigned long long capture_id, int strands, const Node *deps, size_t ndeps) {
+        open_ = true; id_ = capture_id; S_ = clamp_strands(strands); n_ = 0; joins_ = 0; last_ = -1;
+        base_.assign(deps, deps + ndeps);
+        restart();
+    }
+    void plan(const Footprint &fp, std::vector<Node> &preds) {
+        preds.clear();
+        int hit = -1, nhit = 0, nonempty = 0, lru = 0;
+        for (int s = 0; s < S_; s++) {
+            if (!st_[s].empty) nonempty++;
+            if (conflicts(st_[s], fp)) { nhit++; hit = s; }
+            if (st_[s].stamp < st_[lru].stamp) lru = s;   // (empty strands carry stamp 0: they come first, lowest index first)
+        }
+        target_ = nhit == 0 ? lru : hit;
+        if (nhit >= 2 || (fp.unknown && nonempty >= 2)) target_ = -1;
+        if (target_ >= 0) {   // the summary as it would be: kept aside, the strand's own stays untouched until commit
+            pending_ = st_[target_];
+            pending_.everything = pending_.everything || fp.unknown;
+            bool fits = true;
+            if (!fp.unknown) {
+                for (int k = 0; k < fp.nr && fits; k++) fits = pending_.reads.add(fp.r[k]);
+                for (int k = 0; k < fp.nw && fits; k++) fits = pending_.writes.add(fp.w[k]);
+            }
+            if (!fits) target_ = -1;
+        }
+        if (target_ >= 0) {
+            if (!st_[target_].empty) preds.push_back(st_[target_].tail);
+        } else {
+            for (int s = 0; s < S_; s++) if (!st_[s].empty) preds.push_back(st_[s].tail);
+        }
+        if (preds.empty()) preds = base_;
+    }
+    void commit(Node node, const Footprint &) {
+        n_++;
+        last_ = target_;
+        if (target_ < 0) {
+            joins_++;
+            base_.assign(1, node);
+            restart();
+            return;
+        }
+        st_[target_] = pending_;
+        st_[target_].empty = false; st_[target_].tail = node; st_[target_].stamp = ++clock_;
+        frontier_.clear();
+        for (int s = 0; s < S_; s++) if (!st_[s].empty) frontier_.push_back(st_[s].tail);
+    }
+
+private:
+    struct Strand {
+        bool empty = true, everything = false;   // everything: holds a call of unknown footprint -- conflicts with every call
+        Node tail = Node();
+        unsigned long long stamp = 0;            // when it was extended last (0: not since the window restarted)
+        RangeSet<RCap> reads;
+        RangeSet<WCap> writes;
+    };
+    static bool conflicts(const Strand &s, const Footprint &fp) {
+        if (s.empty) return false;
+        if (s.everything || fp.unknown) return true;
+        for (int k = 0; k < fp.nw; k++) if (s.reads.overlaps(fp.w[k]) || s.writes.overlaps(fp.w[k])) return true;
+        for (int k = 0; k < fp.nr; k++) if (s.writes.overlaps(fp.r[k])) return true;
+        return false;
+    }
+    void restart() {
+        for (int s = 0; s < kMaxStrands; s++) { st_[s].empty = true; st_[s].everything = false; st_[s].stamp = 0; st_[s].reads.clear(); st_[s].writes.clear(); }
+        clock_ = 0;
+        frontier_ = base_;
+    }
+
+    bool open_ = false;
+    unsigned long long id_ = 0, clock_ = 0;
+    int S_ = 1, target_ = -1, last_ = -1;
+    long long n_ = 0, joins_ = 0;
+    std::vector<Node> base_, frontier_;
+    Strand st_[kMaxStrands], pending_;
+};
+
+// Which shape a new context captures with; read ONCE per context, at its creation (policy_from above stays the look-back
+// shape's own reading of its variable).
+//   GPU_MAX_HW_QUEUES below 4     serial for good (allowed = false, n = 1)
+//   CPI_AMD_CAPTURE_STRANDS set   strands, clamped to [1, kMaxStrands]
+//   CPI_AMD_CAPTURE_OVERLAP set   otherwise: the look-back shape at that depth, clamped to [1, kMaxDepth]
+//   neither                       kDefaultShape at kDefaultStrands / kDefaultDepth
+enum Shape { kShapeLookback = 0, kShapeStrands = 1 };
+constexpr int kDefaultStrands = 4;   // measured: profiles/capture_strands.md (the fastest on the headline, not slower than 2 on twelve disjoint sets)
+constexpr Shape kDefaultShape = kShapeStrands;
+struct CapturePolicy {
+    bool allowed;
+    Shape shape;
+    int n;   // strands, or the look-back depth; 1 = the serial chain in either shape
+};
+inline CapturePolicy capture_policy_from(const char *hw_queues, const char *strands, const char *depth) {
+    if (hw_queues && *hw_queues && atoll(hw_queues) < 4) return {false, kDefaultShape, 1};
+    if (strands && *strands) return {true, kShapeStrands, clamp_strands(atoll(strands))};
+    if (depth && *depth) return {true, kShapeLookback, clamp_depth(atoll(depth))};
+    return {true, kDefaultShape, kDefaultShape == kShapeStrands ? kDefaultStrands : kDefaultDepth};
+}
+inline CapturePolicy capture_policy_from_environment() {
+    return capture_policy_from(getenv("GPU_MAX_HW_QUEUES"), getenv("CPI_AMD_CAPTURE_STRANDS"), getenv("CPI_AMD_CAPTURE_OVERLAP"));
+}
 
 }  // namespace overlap
 }  // namespace cpi

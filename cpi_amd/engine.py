@@ -137,6 +137,10 @@ class Engine:
         """cpi_ctx_set_capture_overlap: how many captured, provably disjoint batch calls may be unordered in a HIP graph (1 = none)."""
         self._check(self.lib.cpi_ctx_set_capture_overlap(self.ctx, int(depth)))
 
+    def set_capture_strands(self, n):
+        """cpi_ctx_set_capture_strands: captured, provably disjoint batch calls form n chains in a HIP graph (1 = one chain, the serial order)."""
+        self._check(self.lib.cpi_ctx_set_capture_strands(self.ctx, int(n)))
+
     # ------------------------------------------------------------------ preintegration
     @staticmethod
     def make_params(model=1, imu_avg=False, state_transition_jacobians=True, sigmas=DEFAULT_SIGMAS,

@@ -168,14 +168,26 @@ int cpi_ctx_set_stream(cpi_ctx *ctx, void *stream);
  *     (any other entry of this library, a copy, a kernel, an event record, hipStreamEndCapture) happens after ALL of them;
  *   - at most `depth` calls are in flight; call i is ordered behind call i - depth and everything before it;
  *   - eager (non-captured) execution is never relaxed.
- * depth 1 = every node depends on the previous one (the shape before this entry existed); clamped to [1, 4]; default 2 (the fastest
- * measured, profiles/capture_overlap.md), or
- * CPI_AMD_CAPTURE_OVERLAP=<depth> read once by cpi_ctx_create.  A process that sets GPU_MAX_HW_QUEUES below 4 keeps depth 1
+ * depth 1 = every node depends on the previous one (the shape before this entry existed); clamped to [1, 4]; 2 is the fastest
+ * depth measured (profiles/capture_overlap.md).  This "look-back" shape is an opt-in: through this entry, or through
+ * CPI_AMD_CAPTURE_OVERLAP=<depth> read once by cpi_ctx_create; a new context starts with the strand shape of
+ * cpi_ctx_set_capture_strands below, which gives every call ONE predecessor and was measured faster.  A process that sets GPU_MAX_HW_QUEUES below 4 keeps depth 1
  * (parallel branches of a graph need four hardware queues); the library never sets that variable.  Two cases keep the serial
  * shape because overlap was measured not to pay there (profiles/capture_overlap.md): launches of more than one wavefront per
  * SIMD (1 024 wavefronts), and captures in which several contexts of the process take part (the caller spread the calls by hand).  A caller that writes one of
  * the arrays from ANOTHER stream of the same capture orders the streams with events as before. */
 int cpi_ctx_set_capture_overlap(cpi_ctx *ctx, int32_t depth);
+/* The same relaxation in another graph shape, and the one a new context starts with: `n` STRANDS (clamped to [1, 4]; 1 = the
+ * serial chain).  Every captured call of the kind above gets exactly one predecessor: the last call of the one strand whose
+ * calls (all of them, since the strands were last joined) touch memory that conflicts with its own, or of the least recently
+ * extended strand when it conflicts with none.  A call that conflicts with several strands, or whose footprint the host cannot
+ * bound while several strands are in use, joins them: it follows the last call of every strand and everything later follows it.
+ * The guarantees are those listed above, with "at most n calls are in flight" in place of the depth's.
+ * cpi_ctx_set_capture_overlap selects the look-back shape, this entry the strand shape; the later call holds.  At cpi_ctx_create:
+ * GPU_MAX_HW_QUEUES below 4 keeps the chain; else CPI_AMD_CAPTURE_STRANDS=<n> selects strands; else CPI_AMD_CAPTURE_OVERLAP=<depth>
+ * selects the look-back shape (=2 is the graph of the library before this entry existed); neither set: 4 strands, the fastest
+ * measured on 10 000-window batches (profiles/capture_strands.md). */
+int cpi_ctx_set_capture_strands(cpi_ctx *ctx, int32_t n);
 const char *cpi_last_error(const cpi_ctx *ctx); /* ctx may be NULL: last error of a failed create */
 int cpi_abi_version(void);
 const char *cpi_build_id(void);   /* sha256[:16] of the sources this library was built from (cpi_amd/build.py: source_id) */
