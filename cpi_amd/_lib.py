@@ -220,6 +220,9 @@ def load():
         f.restype = C.c_int
     lib.cpi_state_fix_batch.argtypes = lib.cpi_state_fix_batch_host.argtypes = [vp, i64, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.cpi_state_fix_batch.restype = lib.cpi_state_fix_batch_host.restype = C.c_int
+    lib.cpi_state_between_batch.argtypes = lib.cpi_state_between_batch_host.argtypes = [vp, i64, i64, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp,
+                                                                                        vp, vp, vp]
+    lib.cpi_state_between_batch.restype = lib.cpi_state_between_batch_host.restype = C.c_int
     lib.cpi_preintegrate_stream_running.argtypes = lib.cpi_preintegrate_stream.argtypes
     lib.cpi_preintegrate_stream_running_host.argtypes = lib.cpi_preintegrate_stream_host.argtypes
     lib.cpi_preintegrate_streams_running.argtypes = lib.cpi_preintegrate_streams.argtypes

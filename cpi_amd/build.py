@@ -41,7 +41,8 @@ UNIT_REPORTS = {"cpi_running_resume": os.path.join(CSRC, "resource_usage_running
                 "cpi_marginals": os.path.join(CSRC, "resource_usage_marginals.txt"),
                 "cpi_marginalize": os.path.join(CSRC, "resource_usage_marginalize.txt"),
                 "cpi_lm": os.path.join(CSRC, "resource_usage_lm.txt"),
-                "cpi_fix": os.path.join(CSRC, "resource_usage_fix.txt")}
+                "cpi_fix": os.path.join(CSRC, "resource_usage_fix.txt"),
+                "cpi_between": os.path.join(CSRC, "resource_usage_between.txt")}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -amdgpu-kernarg-preload-count: the leading scalar / pointer parameters of a kernel (up to 16 user SGPRs less the ones the
 # kernel already takes) arrive in SGPRs with the wave instead of through a scalar-memory round trip at the head of every
@@ -72,6 +73,7 @@ UNITS = {
     "cpi_marginalize": DEVICE + ["cpi_marginalize.hip", "cpi_factor_kernels.hpp", "cpi_chain_util.hpp", "cpi_marginalize_kernels.hpp"],
     "cpi_lm": DEVICE + ["cpi_lm.hip", "cpi_factor_kernels.hpp", "cpi_chain_util.hpp", "cpi_lm_kernels.hpp"],
     "cpi_fix": DEVICE + ["cpi_fix.hip", "cpi_fix_kernels.hpp"],
+    "cpi_between": DEVICE + ["cpi_between.hip", "cpi_between_kernels.hpp"],
     "cpi_abi": COMMON + ["cpi_abi.hip", "cpi_capture_overlap.hpp", "../../include/cpi_amd_test.h"],   # the test header: -DCPI_TEST_HOOKS builds only
 }
 EXP_EXTRA = {"cpi_mean": ["cpi_mean_experimental.hpp"]}   # additional includes under -DCPI_EXPERIMENTS

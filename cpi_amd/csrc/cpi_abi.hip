@@ -1781,6 +1781,51 @@ extern "C" int cpi_state_fix_batch(cpi_ctx *ctx, int64_t S, int64_t M, int32_t k
     return CPI_OK;
 }
 
+// ============================================================================================
+// cpi_state_between_batch: measurements between the two states of an IMU factor added to its 31 x 31 row and to its chi2 (cpi_between.hip)
+// ============================================================================================
+static const int kBetweenZ[3] = { 3, 4, 7 }, kBetweenR[3] = { 6, 6, 21 };
+// what the device and the host forms refuse alike, before the context is looked at
+static int between_check(cpi_ctx *ctx, const char *who, int64_t F, int64_t M, int32_t kind, const int64_t *mfirst, const double *states, int64_t S,
+                         const int32_t *idx_i, const int32_t *idx_j, const double *z, const double *R, const double *weight, const double *hess_base,
+                         const double *chi2_base, double *hess, double *chi2, double *chi2_m) {
+    if (F < 0 || M < 0 || S < 0) return refuse(ctx, who, "negative size");
+    if (kind < CPI_BETWEEN_POSITION || kind > CPI_BETWEEN_POSE) return refuse(ctx, who, "unknown kind (CPI_BETWEEN_POSITION .. CPI_BETWEEN_POSE)");
+    if (!mfirst || !states) return refuse(ctx, who, "mfirst or states is NULL");
+    if (M > 0 && (!z || !R)) return refuse(ctx, who, "z or R is NULL with M > 0");
+    if (!hess && !chi2 && !chi2_m) return refuse(ctx, who, "hess, chi2 and chi2_m are all NULL");
+    if (F > 0 && (S < 1 || (!idx_i && S < F) || (!idx_j && S < F + 1)))
+        return refuse(ctx, who, "too few states: S >= 1, and >= F + 1 when idx_i / idx_j are NULL (chained states f, f + 1)");
+    const size_t d = sizeof(double);
+    // hess == hess_base and chi2 == chi2_base exactly are the in-place forms: the base then is no input of its own
+    const Span outs[3] = { { hess, (size_t)F * 496 * d, "hess" }, { chi2, (size_t)F * d, "chi2" }, { chi2_m, (size_t)M * d, "chi2_m" } };
+    const Span ins[9] = { { mfirst, (size_t)(F + 1) * sizeof(int64_t), "" }, { states, (size_t)S * 16 * d, "" },
+                          { idx_i, (size_t)F * sizeof(int32_t), "" }, { idx_j, (size_t)F * sizeof(int32_t), "" },
+                          { z, (size_t)M * kBetweenZ[kind] * d, "" }, { R, (size_t)M * kBetweenR[kind] * d, "" }, { weight, (size_t)M * d, "" },
+                          { hess_base == hess ? nullptr : hess_base, (size_t)F * 496 * d, "" }, { chi2_base == chi2 ? nullptr : chi2_base, (size_t)F * d, "" } };
+    return refuse_overlaps(ctx, who, outs, 3, ins, 9);
+}
+extern "C" int cpi_state_between_batch(cpi_ctx *ctx, int64_t F, int64_t M, int32_t kind, const int64_t *mfirst,
+                                       const double *states, int64_t S, const int32_t *idx_i, const int32_t *idx_j,
+                                       const double *z, const double *R, const double *weight,
+                                       const double *hess_base, const double *chi2_base,
+                                       double *hess, double *chi2, double *chi2_m) {
+    static const char who[] = "cpi_state_between_batch";
+    CPI_TRY(between_check(ctx, who, F, M, kind, mfirst, states, S, idx_i, idx_j, z, R, weight, hess_base, chi2_base, hess, chi2, chi2_m));
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (F == 0) return CPI_OK;
+    if (!grid_ok((F + 3) / 4)) return refuse(ctx, who, "F exceeds the 32-bit grid (4 factors per workgroup)");
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    BetweenArgs a;
+    memset(&a, 0, sizeof a);
+    a.F = F; a.M = M; a.S = S; a.mfirst = (const long long *)mfirst; a.states = states; a.idx_i = idx_i; a.idx_j = idx_j; a.z = z; a.R = R;
+    a.weight = weight; a.hess_base = hess_base; a.chi2_base = chi2_base; a.hess = hess; a.chi2 = chi2; a.chi2_m = chi2_m;
+    launch::state_between(kind, a, ctx->stream);
+    CPI_HIP(ctx, hipGetLastError());
+    return CPI_OK;
+}
+
 extern "C" size_t cpi_outputs_slab_doubles(const cpi_outputs *mask, int64_t Wb) {
     if (!mask || Wb <= 0) return 0;
     size_t n = 0;
@@ -3448,5 +3493,51 @@ extern "C" int cpi_state_fix_batch_host(cpi_ctx *ctx, int64_t S, int64_t M, int3
     if (out) CPI_TRY(st.download(out, (const double *)dout, (size_t)S * 136));
     if (pcost) CPI_TRY(st.download(pcost, (const double *)dpc, (size_t)S));
     if (dchi) CPI_TRY(st.download(chi2, (const double *)dchi, (size_t)M));
+    return st.finish();
+}
+
+// cpi_state_between_batch from host memory: every array a host array, staged whole, synchronous.  mfirst and the state indices are
+// validated first.  hess == hess_base / chi2 == chi2_base (in place) run in place on the staged copy.
+extern "C" int cpi_state_between_batch_host(cpi_ctx *ctx, int64_t F, int64_t M, int32_t kind, const int64_t *mfirst,
+                                            const double *states, int64_t S, const int32_t *idx_i, const int32_t *idx_j,
+                                            const double *z, const double *R, const double *weight,
+                                            const double *hess_base, const double *chi2_base,
+                                            double *hess, double *chi2, double *chi2_m) {
+    static const char who[] = "cpi_state_between_batch_host";
+    CPI_TRY(between_check(ctx, who, F, M, kind, mfirst, states, S, idx_i, idx_j, z, R, weight, hess_base, chi2_base, hess, chi2, chi2_m));
+    for (int64_t f = 0; f < F; f++)
+        if (mfirst[f] < 0 || mfirst[f + 1] > M || mfirst[f + 1] < mfirst[f])
+            return refuse(ctx, who, ("the measurements of factor " + std::to_string(f) + " leave [0, M] or mfirst decreases there").c_str());
+    if (F > 0) CPI_TRY(check_state_indices(ctx, who, F, S, idx_i, idx_j));
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (F == 0) return CPI_OK;
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    Staging st(ctx);
+    const int64_t *df;
+    const int32_t *di, *dj;
+    const double *ds, *dz, *dR, *dw, *db = nullptr, *dcb = nullptr;
+    double *dh = nullptr, *dc = nullptr, *dm = nullptr;
+    CPI_TRY(st.upload(mfirst, (size_t)F + 1, &df));
+    CPI_TRY(st.upload(states, (size_t)S * 16, &ds));
+    CPI_TRY(st.upload(idx_i, (size_t)F, &di));
+    CPI_TRY(st.upload(idx_j, (size_t)F, &dj));
+    CPI_TRY(st.upload(M > 0 ? z : nullptr, (size_t)M * kBetweenZ[kind], &dz));
+    CPI_TRY(st.upload(M > 0 ? R : nullptr, (size_t)M * kBetweenR[kind], &dR));
+    CPI_TRY(st.upload(M > 0 ? weight : nullptr, (size_t)M, &dw));
+    if (hess) {
+        CPI_TRY(st.upload(hess_base, (size_t)F * 496, &db));
+        if (hess == hess_base) dh = const_cast<double *>(db); else CPI_TRY(st.alloc((size_t)F * 496, &dh));
+    }
+    if (chi2) {
+        CPI_TRY(st.upload(chi2_base, (size_t)F, &dcb));
+        if (chi2 == chi2_base) dc = const_cast<double *>(dcb); else CPI_TRY(st.alloc((size_t)F, &dc));
+    }
+    if (chi2_m && M > 0) CPI_TRY(st.alloc((size_t)M, &dm));
+    if (!dh && !dc && !dm) return st.finish();    // chi2_m alone with M == 0: nothing to write
+    CPI_TRY(cpi_state_between_batch(ctx, F, M, kind, df, ds, S, di, dj, dz, dR, dw, db, dcb, dh, dc, dm));
+    if (hess) CPI_TRY(st.download(hess, (const double *)dh, (size_t)F * 496));
+    if (chi2) CPI_TRY(st.download(chi2, (const double *)dc, (size_t)F));
+    if (dm) CPI_TRY(st.download(chi2_m, (const double *)dm, (size_t)M));
     return st.finish();
 }

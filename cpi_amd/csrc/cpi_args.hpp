@@ -41,6 +41,8 @@
 //                                                                                  (cpi_lm_kernels.hpp; cpi_chain_util.hpp)
 //   cpi_fix.hip     cpi_fix_kernel<kind>: absolute measurements of states (position, velocity, orientation, pose) added to their
 //                   rows [Lam eta] and to their cost                                                   (cpi_fix_kernels.hpp)
+//   cpi_between.hip cpi_between_kernel<kind>: measurements between the two states of an IMU factor (position, orientation, pose)
+//                   added to the factor's 31 x 31 row and to its chi2                              (cpi_between_kernels.hpp)
 //   cpi_factor.hip  evaluateError sweeps, square-root information, Hessian blocks, state prediction
 //                                                                                      (cpi_factor_kernels.hpp)
 //   cpi_abi.hip     the C-ABI of include/cpi_amd.h: argument checks, launch heuristics, device sets (RCCL), the
@@ -309,6 +311,23 @@ struct FixArgs {
     double *chi2;            // [M] or NULL
 };
 
+// cpi_state_between_batch: factor f owns the measurements mfirst[f] .. mfirst[f + 1] - 1 (clamped into [0, M] where they are read)
+// between the states idx_i[f] and idx_j[f] (f and f + 1 where NULL; clamped into [0, S)).
+struct BetweenArgs {
+    long long F, M, S;
+    const long long *mfirst; // [F + 1]
+    const double *states;    // [S][16]
+    const int *idx_i, *idx_j;// [F] or NULL
+    const double *z;         // [M][3 | 4 | 7]
+    const double *R;         // [M][6 | 6 | 21]
+    const double *weight;    // [M] or NULL
+    const double *hess_base; // [F][496] or NULL; == hess: the in-place form
+    const double *chi2_base; // [F] or NULL
+    double *hess;            // [F][496] or NULL
+    double *chi2;            // [F] or NULL
+    double *chi2_m;          // [M] or NULL
+};
+
 struct PredictArgs {
     long long F;
     double grav[3];
@@ -401,6 +420,8 @@ void lm_cost(const LmCostArgs &a, hipStream_t st);
 void lm_accept(const LmCostArgs &a, const LmAcceptArgs &b, hipStream_t st);
 // ---- cpi_fix.hip (cpi_state_fix_batch)
 void state_fix(int kind, const FixArgs &a, hipStream_t st);                                   // kind: CPI_FIX_*
+// ---- cpi_between.hip (cpi_state_between_batch)
+void state_between(int kind, const BetweenArgs &a, hipStream_t st);                           // kind: CPI_BETWEEN_*
 // ---- cpi_factor.hip
 void factor(int model, bool whiten, int lpf, const FactorArgs &a, hipStream_t st);            // lpf 16 | 8 | 4
 void factor_packed(int model, int lpf, const FactorArgs &a, double *packed, hipStream_t st);  // lpf 2 | 3 | 4 | 6 | 8

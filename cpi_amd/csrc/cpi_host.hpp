@@ -1071,6 +1071,39 @@ inline FixRows state_fix(const Context &ctx, int32_t kind, const std::vector<dou
     return r;
 }
 
+// state_between: measurements between the two consecutive states of IMU factors (cpi_state_between_batch_host: the device kernel's
+// bits).  kind CPI_BETWEEN_*; z [M * 3 | 4 | 7] and R [M * 6 | 6 | 21] (the packed upper-triangular square-root information) for M
+// measurements sorted by factor, mfirst [F + 1] the first measurement of every factor; idx_i / idx_j empty (factor f joins the states
+// f and f + 1) or [F]; weight empty or [M]; hess_base empty or [F * 496] (what factor_hessian wrote), chi2_base empty or [F].  Returns
+// the rows [F * 496] chain_solve takes as hess, chi2 [F] and chi2_m [M] (without the weight).
+struct BetweenRows {
+    std::vector<double> rows, chi2, chi2_m;
+};
+inline BetweenRows state_between(const Context &ctx, int32_t kind, const std::vector<double> &states, const std::vector<double> &z,
+                                 const std::vector<double> &R, const std::vector<int64_t> &mfirst, const std::vector<int32_t> &idx_i = {},
+                                 const std::vector<int32_t> &idx_j = {}, const std::vector<double> &weight = {},
+                                 const std::vector<double> &hess_base = {}, const std::vector<double> &chi2_base = {}) {
+    static const size_t zn[3] = {3, 4, 7}, rn[3] = {6, 6, 21};
+    if (kind < CPI_BETWEEN_POSITION || kind > CPI_BETWEEN_POSE)
+        throw std::invalid_argument("cpi_host::state_between: kind is CPI_BETWEEN_POSITION .. CPI_BETWEEN_POSE");
+    const size_t S = states.size() / 16, M = z.size() / zn[kind], F = mfirst.empty() ? 0 : mfirst.size() - 1;
+    if (states.size() != S * 16 || z.size() != M * zn[kind] || R.size() != M * rn[kind] || mfirst.size() != F + 1 || (!idx_i.empty() && idx_i.size() != F) ||
+        (!idx_j.empty() && idx_j.size() != F) || (!weight.empty() && weight.size() != M) || (!hess_base.empty() && hess_base.size() != F * 496) ||
+        (!chi2_base.empty() && chi2_base.size() != F))
+        throw std::invalid_argument("cpi_host::state_between: states [S * 16], z [M * 3 | 4 | 7], R [M * 6 | 6 | 21], mfirst [F + 1], idx_i / idx_j empty or "
+                                    "[F], weight empty or [M], hess_base empty or [F * 496], chi2_base empty or [F]");
+    BetweenRows r;
+    r.rows.assign(F * 496, 0.0);
+    r.chi2.assign(F, 0.0);
+    r.chi2_m.assign(M, 0.0);
+    if (F)
+        ctx.check(cpi_state_between_batch_host(ctx.get(), (int64_t)F, (int64_t)M, kind, mfirst.data(), states.data(), (int64_t)S,
+                                               idx_i.empty() ? nullptr : idx_i.data(), idx_j.empty() ? nullptr : idx_j.data(), M ? z.data() : nullptr,
+                                               M ? R.data() : nullptr, weight.empty() ? nullptr : weight.data(), hess_base.empty() ? nullptr : hess_base.data(),
+                                               chi2_base.empty() ? nullptr : chi2_base.data(), r.rows.data(), r.chi2.data(), M ? r.chi2_m.data() : nullptr));
+    return r;
+}
+
 // ---- the caller's loop for MANY windows at once --------------------------------------------------------------------
 // What GraphSolver keeps between two states is a deque of IMU readings (GraphSolver.h: imu_times / imu_linaccs /
 // imu_angvel, filled by addmeasurement_imu); createimufactor_cpi_v1 / _v2 (GraphSolver_IMU.cpp:34-134) walk it up to the

@@ -2055,6 +2055,190 @@ CPI_HD void state_fix(const NavState &x, long long n, const double *z, const dou
     }
     if (pcost) *pcost = pc;
 }
+
+// ------------------------------------------------------------------------------------------
+// cpi_state_between_batch (cpi_between_kernels.hpp; tests/hostsim/hostsim_between.cpp is the host restatement): measurements between the
+// two states x_i, x_j that IMU factor f joins -- the position of j in body i, the relative rotation, or both -- added to the factor's
+// augmented 31 x 31 row [G g; g^T f] of cpi_factor_hessian_* and to its chi2.  With R_i = quat_2_Rot(x_i.q), R_j likewise,
+// R_ij = R_j R_i^T, y = R_i (p_j - p_i), the residual has d = Between<K>::D rows and the touched columns of the 31 are col(0 .. NC - 1):
+//     K  z row                      d   e                                                    col
+//     0  [3] p_j in body i          3   z - y                                                0 1 2 | 12 13 14 | 27 28 29 | 30
+//     1  [4] JPL q_j (x) inv(q_i)   3   2 vec(quat_multiply(z, inv(quat_multiply(q_j, inv(q_i)))))  0 1 2 | 15 16 17 | 30
+//     2  [7] q then p               6   the rotation's three, then the position's three      0 1 2 | 12 13 14 | 15 16 17 | 27 28 29 | 30
+// The Jacobian J [d][NC - 1] along retract_state, the rotation residual's own right Jacobian taken flat (exact where e_th = 0), the
+// position blocks exact everywhere, structural zeros as +0.0:
+//     rotation rows   theta_i: R_ij      theta_j: -I       p_i, p_j: 0
+//     position rows   theta_i: -[y x]    p_i: R_i          p_j: -R_i         theta_j: 0
+// THE ORDER OF EVERY SUM (tests reproduce it bit for bit from e and J); fma(a, b, c) is one rounding of a b + c:
+//     d_p    = p_j - p_i;  y_r = the fma chain k = 0, 1, 2 from +0.0: acc = fma(R_i[r][k], d_p[k], acc);  e_p = z_p - y
+//     R_ij[a][b] = the fma chain k = 0, 1, 2 from +0.0: acc = fma(R_j[a][k], R_i[b][k], acc)
+//     wh_r   = the fma chain k = r .. d - 1 ascending from +0.0: acc = fma(R[r][k], e[k], acc);  chi2 as fix_vectors    (fix_vectors)
+//     A_rc   = the fma chain k = r .. d - 1 ascending from +0.0: acc = fma(R[r][k], J[k][c], acc), c < NC - 1;  A_r,NC-1 = -wh_r
+//     P_ab   = the fma chain r = 0 .. d - 1 ascending from +0.0: acc = fma(A_ra, A_rb, acc), a <= b < NC
+// and onto the row, the measurements of a factor in ascending m, starting from the base row's entry (or +0.0) and chi2_base (or +0.0):
+//     row[col_a + col_b (col_b + 1) / 2] = fma(w_m, P_ab, row[..]);  chi2 = fma(w_m, chi2_m, chi2)
+// The NT = NC (NC + 1) / 2 touched entries are numbered t = 0 .. NT - 1, the packed index of (a, b) in the NC x NC triangle; the kernel
+// deals them over sixteen lanes, t = lane + 16 r.
+enum { BETWEEN_POSITION = 0, BETWEEN_ORIENTATION = 1, BETWEEN_POSE = 2 };
+template <int K>
+struct Between {
+    static constexpr bool ROT = K != BETWEEN_POSITION, POS = K != BETWEEN_ORIENTATION;
+    static constexpr int D = (ROT && POS) ? 6 : 3, ZN = (ROT ? 4 : 0) + (POS ? 3 : 0), RN = D * (D + 1) / 2;
+    static constexpr int NB = 1 + (ROT ? 1 : 0) + (POS ? 2 : 0), NC = 3 * NB + 1, NT = NC * (NC + 1) / 2;
+    static constexpr int PR = ROT ? 3 : 0, ZP = ROT ? 4 : 0;    // the first position row of e, the first position entry of z
+    // block g of the touched columns: 0 theta_i, 1 p_i, 2 theta_j, 3 p_j
+    CPI_HD static constexpr int block(int g) { return (K == BETWEEN_POSE) ? g : (K == BETWEEN_POSITION) ? (g == 2 ? 3 : g) : (g == 1 ? 2 : 0); }
+    CPI_HD static constexpr int col(int c) {
+        return (c >= NC - 1) ? 30 : ((block(c / 3) == 0) ? 0 : (block(c / 3) == 1) ? 12 : (block(c / 3) == 2) ? 15 : 27) + c % 3;
+    }
+    // (a, b), a <= b, of entry t, and where it lives in the 496 doubles of a row
+    CPI_HD static void ab(int t, int &a, int &b) {
+        b = 0;
+#pragma unroll
+        for (int k = 1; k < NC; k++) b += (t >= tri(k));
+        a = t - tri(b);
+    }
+    CPI_HD static int slot(int t) {
+        int a, b;
+        ab(t, a, b);
+        return tri(col(b)) + col(a);
+    }
+};
+// what the measurements of a factor share: it depends on the two states alone
+struct BetweenGeo { M3 Ri, Rij; V3 y; Q4 qji; };
+template <int K>
+CPI_HD BetweenGeo between_geometry(const NavState &xi, const NavState &xj) {
+    typedef Between<K> T;
+    BetweenGeo g;
+    g.Ri = quat_2_Rot(xi.q);
+    if (T::ROT) {
+        const M3 Rj = quat_2_Rot(xj.q);
+#pragma unroll
+        for (int a = 0; a < 3; a++)
+#pragma unroll
+            for (int b = 0; b < 3; b++) {
+                double acc = 0.0;
+#pragma unroll
+                for (int k = 0; k < 3; k++) acc = fma(Rj.m[a][k], g.Ri.m[b][k], acc);
+                g.Rij.m[a][b] = acc;
+            }
+        g.qji = quat_inv(quat_multiply(xj.q, quat_inv(xi.q)));
+    }
+    if (T::POS) {
+        const double d[3] = { xj.p.x - xi.p.x, xj.p.y - xi.p.y, xj.p.z - xi.p.z };
+        double y[3];
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            double acc = 0.0;
+#pragma unroll
+            for (int k = 0; k < 3; k++) acc = fma(g.Ri.m[r][k], d[k], acc);
+            y[r] = acc;
+        }
+        g.y = mk(y[0], y[1], y[2]);
+    }
+    return g;
+}
+template <int K>
+CPI_HD void between_residual(const BetweenGeo &g, const double *z, double *e) {
+    typedef Between<K> T;
+    if (T::ROT) {
+        const Q4 qd = quat_multiply(ldq(z), g.qji);
+        e[0] = 2 * qd.x; e[1] = 2 * qd.y; e[2] = 2 * qd.z;
+    }
+    if (T::POS) { e[T::PR] = z[T::ZP] - g.y.x; e[T::PR + 1] = z[T::ZP + 1] - g.y.y; e[T::PR + 2] = z[T::ZP + 2] - g.y.z; }
+}
+// one of three by a run-time index, as selects on registers (left alone, the chain is turned into an indexed read from scratch)
+CPI_HD double between_pick(double a, double b, double c, int w) {
+    double v = a;
+    v = (w == 1) ? b : v;
+    CPI_ROUNDED(v);
+    v = (w == 2) ? c : v;
+    CPI_ROUNDED(v);
+    return v;
+}
+// column c < NC - 1 of the Jacobian: Jc [d]
+template <int K>
+CPI_HD void between_jcol(const BetweenGeo &g, int c, double *Jc) {
+    typedef Between<K> T;
+    const int w = c % 3, blk = c / 3;
+    int kind = T::block(0);
+#pragma unroll
+    for (int k = 1; k < T::NB; k++) kind = (blk == k) ? T::block(k) : kind;
+    if (T::ROT) {
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            const double th_i = between_pick(g.Rij.m[r][0], g.Rij.m[r][1], g.Rij.m[r][2], w), th_j = (r == w) ? -1.0 : 0.0;
+            Jc[r] = (kind == 0) ? th_i : ((kind == 2) ? th_j : 0.0);
+        }
+    }
+    if (T::POS) {
+        // -[y x], row by row
+        const double sk[3][3] = { { 0.0, g.y.z, -g.y.y }, { -g.y.z, 0.0, g.y.x }, { g.y.y, -g.y.x, 0.0 } };
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            const double th_i = between_pick(sk[r][0], sk[r][1], sk[r][2], w), p_i = between_pick(g.Ri.m[r][0], g.Ri.m[r][1], g.Ri.m[r][2], w);
+            Jc[T::PR + r] = (kind == 0) ? th_i : ((kind == 1) ? p_i : ((kind == 3) ? -p_i : 0.0));
+        }
+    }
+}
+// column c of the whitened [A | b]: Ac [d].  R [RN] and Jc [d] are read at compile-time indices (registers).
+template <int D>
+CPI_HD void between_acol(const double *R, const double *Jc, double *Ac) {
+#pragma unroll
+    for (int r = 0; r < D; r++) {
+        double acc = 0.0;
+#pragma unroll
+        for (int k = r; k < D; k++) acc = fma(R[tri(k) + r], Jc[k], acc);
+        Ac[r] = acc;
+    }
+}
+// P_ab of the columns Aa, Ab [d] at stride `pitch`
+template <int D>
+CPI_HD double between_term(const double *Aa, const double *Ab, int pitch) {
+    double acc = 0.0;
+#pragma unroll
+    for (int r = 0; r < D; r++) acc = fma(Aa[r * pitch], Ab[r * pitch], acc);
+    return acc;
+}
+// One factor with its n measurements on host arrays: z [n][ZN], R [n][RN], weight NULL or [n], base NULL or [496] (row may be base
+// itself: the in-place form); row NULL or [496], chi2 NULL or one double, chi2_m NULL or [n].  The statement the kernel is the
+// lane-mapped form of.
+template <int K>
+CPI_HD void factor_between(const NavState &xi, const NavState &xj, long long n, const double *z, const double *R, const double *weight,
+                           const double *base, double chi2_base, double *row, double *chi2, double *chi2_m) {
+    typedef Between<K> T;
+    double acc[T::NT], c2sum = chi2_base;
+    for (int t = 0; t < T::NT; t++) acc[t] = base ? base[T::slot(t)] : 0.0;
+    if (n > 0) {
+        const BetweenGeo g = between_geometry<K>(xi, xj);
+        double A[T::D][T::NC];
+        for (long long m = 0; m < n; m++) {
+            const double *Rm = R + m * T::RN, w = weight ? weight[m] : 1.0;
+            double e[T::D], wh[T::D], u[T::D], Jc[T::D], Ac[T::D];
+            between_residual<K>(g, z + m * T::ZN, e);
+            const double c2 = fix_vectors<T::D>(Rm, e, wh, u);
+            if (chi2_m) chi2_m[m] = c2;
+            c2sum = fma(w, c2, c2sum);
+            for (int c = 0; c < T::NC - 1; c++) {
+                between_jcol<K>(g, c, Jc);
+                between_acol<T::D>(Rm, Jc, Ac);
+                for (int r = 0; r < T::D; r++) A[r][c] = Ac[r];
+            }
+            for (int r = 0; r < T::D; r++) A[r][T::NC - 1] = -wh[r];
+            for (int t = 0; t < T::NT; t++) {
+                int a, b;
+                T::ab(t, a, b);
+                acc[t] = fma(w, between_term<T::D>(&A[0][a], &A[0][b], T::NC), acc[t]);
+            }
+        }
+    }
+    if (row) {
+        if (row != base)
+            for (int i = 0; i < 496; i++) row[i] = base ? base[i] : 0.0;
+        for (int t = 0; t < T::NT; t++) row[T::slot(t)] = acc[t];
+    }
+    if (chi2) *chi2 = c2sum;
+}
 }  // namespace chn
 
 }  // namespace cpi

@@ -1712,9 +1712,83 @@ class Engine:
             base = dst
         return base
 
+    # ------------------------------------------------------------------ measurements between the two states of a factor
+    BETWEEN_KINDS = {"position": 0, "orientation": 1, "pose": 2}
+    _BETWEEN_Z, _BETWEEN_R = (3, 4, 7), (6, 6, 21)
+
+    def _state_between(self, fn, states, kind, z, R, mfirst, idx_i, idx_j, weight, hess_base, chi2_base, out, chi2, chi2_m, want_rows, want_cost,
+                       cuda):
+        k = self.BETWEEN_KINDS.get(kind, kind) if isinstance(kind, str) else int(kind)
+        assert k in (0, 1, 2), "kind: 'position', 'orientation', 'pose' or CPI_BETWEEN_* (0 .. 2)"
+        self._trial_tensor(states, 16, cuda, "states")
+        S, M, F = states.shape[0], z.shape[0], mfirst.shape[0] - 1
+        self._trial_tensor(z, self._BETWEEN_Z[k], cuda, "z")
+        self._trial_tensor(R, self._BETWEEN_R[k], cuda, "R", M)
+        self._lm_vector(mfirst, F + 1, torch.int64, cuda, "mfirst")
+        for name, idx in (("idx_i", idx_i), ("idx_j", idx_j)):
+            if idx is not None:
+                self._lm_vector(idx, F, torch.int32, cuda, name)
+        if weight is not None:
+            self._lm_vector(weight, M, torch.float64, cuda, "weight")
+        if hess_base is not None:
+            self._trial_tensor(hess_base, 496, cuda, "hess_base", F)
+        if chi2_base is not None:
+            self._lm_vector(chi2_base, F, torch.float64, cuda, "chi2_base")
+        dev = states.device
+        if out is None and want_rows:
+            out = torch.empty((F, 496), dtype=torch.float64, device=dev)      # every row is written
+        if chi2 is None and want_cost:
+            chi2 = torch.empty((F,), dtype=torch.float64, device=dev)
+        assert out is not None or chi2 is not None or chi2_m is not None, "at least one of the rows, chi2 and chi2_m"
+        if out is not None:
+            self._trial_tensor(out, 496, cuda, "out", F)
+        if chi2 is not None:
+            self._lm_vector(chi2, F, torch.float64, cuda, "chi2")
+        if chi2_m is not None:
+            self._lm_vector(chi2_m, M, torch.float64, cuda, "chi2_m")
+        if F == 0:                                                            # a no-op: empty tensors have no address to pass
+            return out, chi2
+        self._sync_stream()
+        self._check(fn(self.ctx, F, M, k, _ptr(mfirst), _ptr(states), S, _ptr(idx_i), _ptr(idx_j), _ptr(z), _ptr(R), _ptr(weight), _ptr(hess_base),
+                       _ptr(chi2_base), _ptr(out), _ptr(chi2), _ptr(chi2_m)))
+        return out, chi2
+
+    def state_between(self, states, kind, z, R, mfirst, idx_i=None, idx_j=None, weight=None, hess_base=None, chi2_base=None, out=None, chi2=None,
+                      chi2_m=None, want_rows=True, want_cost=True):
+        """cpi_state_between_batch: measurements between the two consecutive states of every IMU factor (odometry) added to the factor's
+        row of factor_hessian and to its chi2.  states [S,16]; kind 'position' (z [M,3]: the position of state j in the body frame of
+        state i), 'orientation' (z [M,4]: the JPL quaternion q_j (x) inv(q_i)) or 'pose' (z [M,7], q then p), or the enum value 0 .. 2;
+        R [M,6] ([M,21] for a pose): the upper-triangular square-root information in the packing of R_tri; mfirst int64 [F+1]: factor f
+        owns the measurements mfirst[f] .. mfirst[f+1] - 1 (fix_offsets makes it from the factor index of every measurement); idx_i /
+        idx_j int32 [F] as factor_hessian takes them (None: f and f + 1); weight None or [M].  Returns (rows [F,496], chi2 [F]):
+        rows[f] = hess_base[f] (or 0) + sum w [A | b]^T [A | b] on the touched columns, chi2[f] = chi2_base[f] (or 0) + sum w |R e|^2.
+        IN PLACE: out=hess_base and chi2=chi2_base (the same tensors) are allowed and touch only what the measurements touch.  chi2_m=
+        an [M] tensor to fill with |R e|^2 of every measurement WITHOUT the weight (a gate).  want_rows=False / want_cost=False leave
+        that output out (None is returned in its place) unless a tensor is given for it; without rows no row is read or written.
+        Asynchronous."""
+        return self._state_between(self.lib.cpi_state_between_batch, states, kind, z, R, mfirst, idx_i, idx_j, weight, hess_base, chi2_base, out,
+                                   chi2, chi2_m, want_rows, want_cost, True)
+
+    def state_between_host(self, states, kind, z, R, mfirst, idx_i=None, idx_j=None, weight=None, hess_base=None, chi2_base=None, out=None,
+                           chi2=None, chi2_m=None, want_rows=True, want_cost=True):
+        """state_between on CPU tensors (cpi_state_between_batch_host): mfirst and the indices are validated (CpiError names the factor),
+        synchronous, the device form's bits."""
+        return self._state_between(self.lib.cpi_state_between_batch_host, states, kind, z, R, mfirst, idx_i, idx_j, weight, hess_base, chi2_base,
+                                   out, chi2, chi2_m, want_rows, want_cost, False)
+
+    def _lm_betweens(self, x, betweens, idx_i, idx_j, hess, chi2):
+        """The betweens of chain_lm in list order at the states x, IN PLACE: onto the rows hess [F,496] when given, else onto chi2 [F]."""
+        for b in betweens:
+            if hess is not None:
+                self.state_between(x, b["kind"], b["z"], b["R"], b["mfirst"], idx_i, idx_j, weight=b.get("weight"), hess_base=hess, out=hess,
+                                   want_cost=False)
+            else:
+                self.state_between(x, b["kind"], b["z"], b["R"], b["mfirst"], idx_i, idx_j, weight=b.get("weight"), chi2_base=chi2, chi2=chi2,
+                                   want_rows=False)
+
     def chain_lm(self, model, meas, lin, q_k_lin, states, R_tri, C, G, first=None, count=None, ffirst=None, idx_i=None, idx_j=None,
                  prior0=None, anchor=None, prior_idx=None, lam=1e-3, iterations=10, params=None, damping="diagonal", grav=DEFAULT_GRAV,
-                 cost_history=None, buffers=None, init=True, fixes=None):
+                 cost_history=None, buffers=None, init=True, fixes=None, betweens=None):
         """Levenberg-Marquardt on C chains of IMU factors, every chain with a lambda, a cost and a phase of its own: the loop of
         INTEGRATION.md 3p issued eagerly -- a thin composition of the entries, no kernel of its own, no host read, every buffer
         allocated before the first iteration.  Before the loop (init): factor_cost, prior_relinearize and chain_cost at `states`; per
@@ -1727,6 +1801,12 @@ class Engine:
                                                     takes them: absolute measurements of the states.  Every prior_relinearize of the
                                                     loop is followed by the fixes in list order -- rows before factor_hessian, pcost
                                                     only in the two cost evaluations
+          betweens                                  None or a list of dicts with kind, z, R, mfirst and optionally weight, as
+                                                    state_between takes them: measurements between the two states of the factors
+                                                    (mfirst indexes the F factors).  Issued IN PLACE in list order after every
+                                                    factor_hessian (onto the rows) and after every factor_cost (onto chi2, the current
+                                                    and the trial one) with the loop's idx_i / idx_j; no buffer of
+                                                    their own.  Without them the launches are those of a call without the argument
           lam                                       the initial lambda: a number, or a float64 CUDA tensor [C] that is updated in place
           cost_history                              None or a float64 CUDA tensor [iterations + 1, C]: row 0 the initial cost, row i
                                                     the cost after iteration i (device copies; nothing is read on the host)
@@ -1769,6 +1849,7 @@ class Engine:
         priors = prior0 is not None
         if init:
             self.factor_cost(model, meas, lin, q_k_lin, states, R_tri, want_total=False, out={"chi2": b["chi2"]}, **sweep)
+            self._lm_betweens(states, betweens or (), b["idx_i"], b["idx_j"], None, b["chi2"])
             if priors:
                 self.prior_relinearize(states, anchor, prior0, idx=prior_idx, pcost=b["pcost"], want_prior=False)
             self.chain_cost(b["chi2"], self._lm_fixes(states, fixes or (), b.get("fix_pcost"), b.get("pcost"), False), out=b["cost"], **chain)
@@ -1779,10 +1860,12 @@ class Engine:
                 self.prior_relinearize(states, anchor, prior0, idx=prior_idx, out=b["prior"], want_cost=False)
             rows = self._lm_fixes(states, fixes or (), b.get("fix_rows"), b.get("prior"), True)
             self.factor_hessian(model, meas, lin, q_k_lin, states, R_tri, out=b["hess"], **sweep)
+            self._lm_betweens(states, betweens or (), b["idx_i"], b["idx_j"], b["hess"], None)
             self.chain_solve(b["hess"], prior=rows, lam=b["lam"], damping=damping, out=b["delta"], status=b["status"],
                              workspace=b["workspace"], **chain)
             self.retract(states, b["delta"], out=b["trial"])
             self.factor_cost(model, meas, lin, q_k_lin, b["trial"], R_tri, want_total=False, out={"chi2": b["chi2_new"]}, **sweep)
+            self._lm_betweens(b["trial"], betweens or (), b["idx_i"], b["idx_j"], None, b["chi2_new"])
             if priors:
                 self.prior_relinearize(b["trial"], anchor, prior0, idx=prior_idx, pcost=b["pcost_new"], want_prior=False)
             pcost_new = self._lm_fixes(b["trial"], fixes or (), b.get("fix_pcost"), b.get("pcost_new"), False)
@@ -1892,6 +1975,16 @@ def state_fix_host(*args, **kw):
 def fix_offsets(idx, S):
     """Engine.fix_offsets."""
     return Engine.fix_offsets(idx, S)
+
+
+def state_between(*args, **kw):
+    """Engine.state_between on the default engine."""
+    return default_engine().state_between(*args, **kw)
+
+
+def state_between_host(*args, **kw):
+    """Engine.state_between_host on the default engine."""
+    return default_engine().state_between_host(*args, **kw)
 
 
 # ---------------------------------------------------------------------- reference-shaped classes

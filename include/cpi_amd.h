@@ -85,7 +85,10 @@ extern "C" {
                                per chain, and the decision -- accept or reject, copy, lambda, phase);
                                cpi_state_fix_batch, cpi_state_fix_batch_host (absolute measurements of states --
                                position, velocity, orientation, pose fixes -- added to their rows [Lam eta] and to their
-                               cost: how a GPS fix, a zero-velocity update or a mocap pose enters that loop) */
+                               cost: how a GPS fix, a zero-velocity update or a mocap pose enters that loop);
+                               cpi_state_between_batch, cpi_state_between_batch_host (measurements between the two
+                               consecutive states an IMU factor joins -- relative position, orientation, pose -- added to
+                               the factor's row of cpi_factor_hessian_* and to its chi2: how odometry enters that loop) */
 
 enum { CPI_OK = 0, CPI_ERR_INVALID = 1, CPI_ERR_HIP = 2, CPI_ERR_NO_DEVICE = 3, CPI_ERR_RCCL = 4 };
 enum {
@@ -1116,7 +1119,8 @@ int cpi_chain_accept_batch(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_
  * pcost of cpi_chain_cost_batch).  Replaces: GTSAM's PriorFactor<Point3 / Rot3 / Pose3> / GPSFactor linearised and summed into the
  * Hessian of a state, per state instead of per graph.  GTSAM is absent from the reference tree: PARITY UNPINNED; checked against a
  * long-double restatement of the definitions below and, where the summation order is fixed, bit for bit.  Out of scope: robust kernels
- * inside the library (weight is the caller's hook), relative (between-state) measurements, mixed kinds in one call (a second kind is
+ * inside the library (weight is the caller's hook), measurements between non-adjacent states (the between-state measurements of
+ * consecutive states are cpi_state_between_batch below), mixed kinds in one call (a second kind is
  * a second call), the exact right Jacobian of the rotation residual (it is taken flat, as cpi_prior_relinearize_batch takes it).
  *
  *   kind                 z row                              d   tangent rows sel (order theta bg v ba p)   residual e
@@ -1158,6 +1162,68 @@ int cpi_state_fix_batch(cpi_ctx *ctx, int64_t S, int64_t M, int32_t kind, const 
                         const double *weight, const double *base,
                         const double *pcost_base, double *out,
                         double *pcost, double *chi2);
+
+/* cpi_state_between_batch: measurements BETWEEN the two consecutive states x_i, x_j that IMU factor f joins -- a relative pose from
+ * scan matching or visual odometry between two keyframes, a body-frame displacement from wheel odometry, a relative rotation --
+ * added to the factor's augmented 31 x 31 row of cpi_factor_hessian_* ([G g; g^T f], hess [F][496]) and to its chi2
+ * (cpi_factor_cost_*), so that cpi_chain_solve / marginals / marginalize / cost / accept_batch work as they are and the graph stays
+ * block-tridiagonal.  Replaces: GTSAM's BetweenFactor<Pose3 / Rot3> (and a body-frame displacement factor) linearised and summed into
+ * the Hessian of the pair, per factor instead of per graph.  GTSAM is absent from the reference tree: PARITY UNPINNED; checked against
+ * a long-double restatement of the definitions below, central differences through a long-double retract and, where the summation
+ * order is fixed, bit for bit.  Out of scope: measurements between non-adjacent states (loop closures, landmarks), robust kernels
+ * inside the library (weight is the caller's hook), mixed kinds in one call, the exact right Jacobian of the rotation residual.
+ *
+ * With R_i = quat_2_Rot(x_i.q) (global to body i, JPL), R_ij = quat_2_Rot(x_j.q) R_i^T, y = R_i (p_j - p_i); tangent order theta bg v ba
+ * p, state_i columns 0-14, state_j 15-29, the b column 30:
+ *   kind                     z row                           d   residual e                                  touched columns of 31
+ *   CPI_BETWEEN_POSITION     [3] position of j in body i     3   e_p = z - y                                  0 1 2 12 13 14 27 28 29 30       (55 of 496)
+ *   CPI_BETWEEN_ORIENTATION  [4] JPL quaternion q_j (x) inv(q_i)  3   e_th = 2 vec(qd), qd = quat_multiply(z, inv(quat_multiply(x_j.q, inv(x_i.q)))),
+ *                                                                negated when qd.w < 0                        0 1 2 15 16 17 30                (28 of 496)
+ *   CPI_BETWEEN_POSE         [7] q then p                    6   the two above, rotation first                0 1 2 12 13 14 15 16 17 27 28 29 30  (91 of 496)
+ * The Jacobian J [d][30], derivatives along cpi_retract_batch (the map every H1 / H2 of the library is a derivative along), checked
+ * against central differences (tests/test_between_cpu.py):
+ *   d e_p / d theta_i = -[y x]      d e_p / d p_i = R_i        d e_p / d p_j = -R_i
+ *   d e_th / d theta_i = R_ij       d e_th / d theta_j = -I
+ * The rotation residual's own right Jacobian is taken flat (identity), the rule of cpi_state_fix_batch and
+ * cpi_prior_relinearize_batch: the rotation blocks are exact where e_th = 0; the position blocks are exact everywhere.  z and -z are
+ * one rotation and give the same e.  A zero-norm or NaN z quaternion gives NaN.
+ *   mfirst  [F + 1] DEVICE int64: factor f owns the measurements mfirst[f] .. mfirst[f + 1] - 1 (sorted by factor, CSR; the array
+ *           Engine.fix_offsets builds).  Every range is clamped into [0, M] where it is read.
+ *   states  [S][16];  idx_i / idx_j [F] int32 or NULL (f and f + 1: S >= F + 1) as in the factor sweeps, clamped into [0, S)
+ *   z [M][3 | 4 | 7];  R [M][6 | 6 | 21]: the upper-triangular square-root information in the packing of R_tri, entry (r, k), r <= k,
+ *           at r + k (k + 1) / 2;  weight NULL (1) or [M]
+ *   hess_base NULL (zeros) or [F][496];  chi2_base NULL (zeros) or [F]
+ * Per measurement m of factor f, in ascending m, with fma(a, b, c) one rounding of a b + c, b = -R e and [A | b] = [R J | -R e] over
+ * the NC touched columns (structural zeros of J enter as +0.0):
+ *     y_r    = the fma chain k = 0, 1, 2 from +0.0: acc = fma(R_i[r][k], (p_j - p_i)[k], acc);   e_p = z_p - y
+ *     R_ij[a][b] = the fma chain k = 0, 1, 2 from +0.0: acc = fma(R_j[a][k], R_i[b][k], acc)
+ *     wh_r   = the fma chain k = r .. d - 1 ascending from +0.0: acc = fma(R[r][k], e[k], acc)
+ *     chi2_m = (..(wh_0 wh_0 + wh_1 wh_1) + ..) + wh_{d-1} wh_{d-1}, every square rounded by itself
+ *     A_rc   = the fma chain k = r .. d - 1 ascending from +0.0: acc = fma(R[r][k], J[k][c], acc);  the b column: A_r = -wh_r
+ *     P_ab   = the fma chain r = 0 .. d - 1 ascending from +0.0: acc = fma(A_ra, A_rb, acc), a <= b touched columns
+ *     hess[f][(a, b)] = fma(w_m, P_ab, hess[f][(a, b)]);   chi2[f] = fma(w_m, chi2_m, chi2[f])
+ * i.e. G += w A^T A, g += w A^T b (minus the gradient of 0.5 w chi2: the sign of cpi_factor_hessian_*), entry (30, 30) += w b^T b.
+ *   hess    NULL or [F][496]: for EVERY f in [0, F), hess[f] = (hess_base ? hess_base[f] : 0) + the measurements of f; only the
+ *           touched entries differ from the base.  NULL: the cost-only call of a trial step, no row is read or written
+ *   chi2    NULL or [F]: for every f, (chi2_base ? chi2_base[f] : 0) + sum w chi2_m (cpi_chain_cost_batch halves the sum)
+ *   chi2_m  NULL or [M]: |R e|^2 WITHOUT the weight, so that a gate does not depend on it
+ * A factor without measurements gets its base row and base chi2 bit for bit, zeros when they are NULL.
+ * IN PLACE: hess == hess_base and chi2 == chi2_base EXACTLY (the same pointer) are allowed and give the same bits as the out-of-place
+ * call; then only the touched entries of factors with measurements are read and written.  This differs from cpi_state_fix_batch
+ * deliberately: cpi_factor_hessian_* and cpi_factor_cost_* rewrite their arrays every iteration, so an in-place add does not
+ * accumulate from one iteration to the next.  A second sensor is a second call.  A NaN or zero-norm measurement makes that factor's
+ * row and chi2 NaN and touches no other factor.
+ * Refused (CPI_ERR_INVALID, before the context is looked at): negative sizes, an unknown kind, a NULL mfirst / states, a NULL z / R
+ * when M > 0, hess, chi2 and chi2_m all NULL, too few states, any other overlap of an output with an input or another output
+ * ("overlaps").  F == 0 is a no-op.  The library allocates nothing; one kernel on the context's stream, no host synchronisation: a
+ * capture is a chain without parallel branches.  A factor's bits depend on its own data only, not on F or its position.  A double
+ * array needs the alignment of a double (8 bytes) and no more. */
+enum { CPI_BETWEEN_POSITION = 0, CPI_BETWEEN_ORIENTATION = 1, CPI_BETWEEN_POSE = 2 };
+int cpi_state_between_batch(cpi_ctx *ctx, int64_t F, int64_t M, int32_t kind, const int64_t *mfirst,
+                            const double *states, int64_t S, const int32_t *idx_i, const int32_t *idx_j,
+                            const double *z, const double *R, const double *weight,
+                            const double *hess_base, const double *chi2_base,
+                            double *hess, double *chi2, double *chi2_m);
 
 /* ---- Device sets: the 8-GPU path of a single-process host (nothing in the reference, which is a
  * single-threaded CPU program).  Windows (and factors) are independent units: rank r of n owns the contiguous block
@@ -1415,6 +1481,15 @@ int cpi_state_fix_batch_host(cpi_ctx *ctx, int64_t S, int64_t M, int32_t kind, c
                              const double *weight, const double *base,
                              const double *pcost_base, double *out,
                              double *pcost, double *chi2);
+
+/* cpi_state_between_batch from host memory: every pointer a host pointer (mfirst and the indices too), synchronous; the device form's
+ * bits, the in-place forms included.  mfirst -- non-decreasing and inside [0, M] -- and the state indices are validated first, and
+ * the text names the factor. */
+int cpi_state_between_batch_host(cpi_ctx *ctx, int64_t F, int64_t M, int32_t kind, const int64_t *mfirst,
+                                 const double *states, int64_t S, const int32_t *idx_i, const int32_t *idx_j,
+                                 const double *z, const double *R, const double *weight,
+                                 const double *hess_base, const double *chi2_base,
+                                 double *hess, double *chi2, double *chi2_m);
 
 #ifdef __cplusplus
 }
