@@ -30,7 +30,17 @@ Central differences: step FD_STEP = 1e-6 on every tangent entry, in longdouble. 
 the third derivative (1e-12 x the size of the entry for a rotation, 0 for the linear position entries), the rounding 2^-64 / h x the
 size of the residual's terms (5e-14 x).  Measured over every case, relative to 1 + the largest entry: the Jacobian 2.5e-13 (position),
 6.1e-14 (orientation), 2.4e-13 (pose); g against the gradient of the cost 6.7e-13 (position), 1.0e-12 (pose): FLOOR_FD is the largest.
-A wrong sign or a transposed block shows as O(1) (0.9 to 16 in the mutation checks)."""
+A wrong sign or a transposed block shows as O(1) (0.9 to 16 in the mutation checks).
+The edge builders (edge_case; tests/between_edge_checks.py) have floors of their own, FLOOR_EDGE_HOST / FLOOR_EDGE_DEVICE, the largest
+value over the kinds of a builder against the same longdouble reference, and gates by the same rule, 100 x max(floor, 1).  Measured on
+the host twin (x86-64) / on the MI355X:
+    identity   G 4.41 / 4.41   g, f, chi2, chi2_m 0 / 0: every residual is exactly zero
+    pi         G 4.62 / 4.62   g 0.393 / 0.393   f 0.147 / 0.147   chi2 0.181 / 0.181   chi2_m 0.147 / 0.147   (exact products: the same bits)
+    scaled     G 4.96 / 4.96   g 0.337 / 0.67    f 0.108 / 0.129   chi2 0.072 / 0.144   chi2_m 0.102 / 0.582
+    long       G 10.9 / 10.8   g 0.176 / 0.16    f 0.0847 / 0.0847 chi2 0.0847 / 0.0847 chi2_m 0.381 / 0.381
+Only the fold of 300 (long) leaves the range of FLOOR_HOST / FLOOR_DEVICE by more than a fraction of a unit: G 10.9 against 5.9, the
+rounding of 300 fma steps onto one entry; its G gate is 1090 (host) / 1080 (device), every other gate of the builders is the 100 units of
+the rule or, for G, below GATE_HOST's 590."""
 import functools
 
 import numpy as np
@@ -55,6 +65,13 @@ FLOOR_HOST = dict(G=5.9, g=0.46, f=0.11, chi2=0.098, chi2_m=0.25)
 FLOOR_DEVICE = dict(G=5.9, g=0.60, f=0.11, chi2=0.12, chi2_m=0.22)
 GATE_HOST = {k: 100 * max(v, 1.0) for k, v in FLOOR_HOST.items()}
 GATE_DEVICE = {k: 100 * max(v, 1.0) for k, v in FLOOR_DEVICE.items()}
+# the edge builders (edge_case), each with a floor of its own: the largest value over its kinds, measured against the longdouble reference
+FLOOR_EDGE_HOST = dict(identity=dict(G=4.41, g=0.0, f=0.0, chi2=0.0, chi2_m=0.0), pi=dict(G=4.62, g=0.393, f=0.147, chi2=0.181, chi2_m=0.147),
+                       scaled=dict(G=4.96, g=0.337, f=0.108, chi2=0.072, chi2_m=0.102), long=dict(G=10.9, g=0.176, f=0.0847, chi2=0.0847, chi2_m=0.381))
+FLOOR_EDGE_DEVICE = dict(identity=dict(G=4.41, g=0.0, f=0.0, chi2=0.0, chi2_m=0.0), pi=dict(G=4.62, g=0.393, f=0.147, chi2=0.181, chi2_m=0.147),
+                         scaled=dict(G=4.96, g=0.67, f=0.129, chi2=0.144, chi2_m=0.582), long=dict(G=10.8, g=0.16, f=0.0847, chi2=0.0847, chi2_m=0.381))
+GATE_EDGE_HOST = {n: {k: 100 * max(v, 1.0) for k, v in fl.items()} for n, fl in FLOOR_EDGE_HOST.items()}
+GATE_EDGE_DEVICE = {n: {k: 100 * max(v, 1.0) for k, v in fl.items()} for n, fl in FLOOR_EDGE_DEVICE.items()}
 FD_STEP = 1e-6
 FLOOR_FD = 1.1e-12
 GATE_FD = 100 * FLOOR_FD
@@ -64,7 +81,7 @@ GATE_FINAL_DEVICE = 100 * FLOOR_FINAL_DEVICE
 # measurements per factor: 0, 1, 2 and 17 dealt so that every wavefront of four factors mixes them; the last two factors have none
 COUNTS = fx.COUNTS
 SIZES = fx.SIZES
-# explicit state indices of the nine factors over twelve states: factors 2 and 5 join the same pair (7, 2), state 7 is in four factors
+# explicit state indices of the nine factors over twelve states: factors 2 and 5 join the same pair (7, 2), state 7 is state i of three factors
 IDX_I = (3, 0, 7, 7, 1, 7, 9, 4, 10)
 IDX_J = (4, 5, 2, 8, 6, 2, 1, 11, 0)
 EARTH = np.array([4.2e6, 1.7e5, 4.8e6]) * (5e6 / 4.8e6)      # positions of 5e6 m
@@ -179,7 +196,8 @@ def exact_z(kind, xi, xj):
 class Case:
     """One call: states [S, 16], idx_i / idx_j [F] or None, mfirst [F + 1], z [M, ZN], R [M, RN], weight [M], base [F, 496], chi2_base [F]."""
 
-    def __init__(self, kind, counts, variant="chain", seed=5):
+    def __init__(self, kind, counts, variant="chain", seed=5, idx=None, S=12):
+        """idx: (idx_i, idx_j) of the explicit variant over S states where the nine pairs of IDX_I / IDX_J do not reach (edge_case("many"))."""
         assert variant in VARIANTS
         rng = np.random.default_rng(seed + 17 * kind + 101 * VARIANTS.index(variant))
         self.kind, self.variant, self.counts = kind, variant, np.asarray(counts, dtype=np.int64)
@@ -187,9 +205,9 @@ class Case:
         self.F, self.mfirst = F, offsets(counts)
         M = self.M = int(self.mfirst[-1])
         explicit = variant == "explicit"
-        S = self.S = 12 if explicit else F + 1
-        self.idx_i = np.array(IDX_I[:F], dtype=np.int32) if explicit else None
-        self.idx_j = np.array(IDX_J[:F], dtype=np.int32) if explicit else None
+        S = self.S = S if explicit else F + 1
+        self.idx_i = np.array(IDX_I[:F] if idx is None else idx[0], dtype=np.int32) if explicit else None
+        self.idx_j = np.array(IDX_J[:F] if idx is None else idx[1], dtype=np.int32) if explicit else None
         self.states = np.zeros((S, 16))
         for s in range(S):
             self.states[s, :4] = fx._unit_quat(rng)
@@ -267,6 +285,85 @@ def all_cases(kind):
     return out
 
 
+# --------------------------------------------------------------------------------------------- the edge builders
+PI_Z = tuple(tuple(s * v for v in np.eye(4)[a]) for a in range(3) for s in (1.0, -1.0))     # +x -x +y -y +z -z: qd.w == 0 exactly
+Z_SCALES = (0.5, 3.0, 1e-150)
+LONG_COUNTS = (0, 300, 1, 33, 0)
+MANY, MANY_SEED, MANY_S = 1027, 61, 40      # 257 workgroups of four factors, the last one with three live factors
+EDGE_BUILDERS = (("identity", (0, 1, 2)), ("pi", (1, 2)), ("scaled", (1, 2)), ("long", (0, 1, 2)), ("many", (0, 1, 2)))
+
+
+def _on_the_grid(c, rng):
+    """Identity quaternions and positions that are multiples of 0.25: R_i = I, y = p_j - p_i and every product of quaternions exact."""
+    c.states[:, :4] = [0.0, 0.0, 0.0, 1.0]
+    c.states[:, 13:16] = 0.25 * rng.integers(-40, 41, (c.S, 3))
+    fi, fj = c.pairs()
+    own = c.owner()
+    return c.states[fj[own], 13:16] - c.states[fi[own], 13:16]
+
+
+@functools.lru_cache(maxsize=None)
+def edge_case(name, kind):
+    """One of EDGE_BUILDERS (the tests leave what comes back unchanged):
+      identity  every kind: the nine chained factors, state quaternions [0, 0, 0, 1], positions multiples of 0.25, z quaternion
+                [0, 0, 0, 1], z_p = p_j - p_i: every residual is exactly +-0.0
+      pi        kinds 1, 2: the same states, z quaternion PI_Z[m % 6] (+-1 on one axis): qd.w == 0 exactly, a rotation of exactly pi, where
+                "negated when qd.w < 0" leaves e_th = 2 vec(qd) as it is; z_p off the exact value by multiples of 0.25; the pose kind with
+                a diagonal R, so that the rotation and the position rows of [A | b] do not mix
+      scaled    kinds 1, 2: the nine chained factors, z quaternion times Z_SCALES[m % 3] (residual_ld normalises the product)
+      long      every kind: LONG_COUNTS measurements per factor, a fold of 300
+      many      every kind: MANY factors over MANY_S states, the pairs of IDX_I / IDX_J continued by a seeded draw (i != j), COUNTS tiled"""
+    assert kind in dict(EDGE_BUILDERS)[name], (name, kind)
+    rng = np.random.default_rng(1000 + 10 * [n for n, _ in EDGE_BUILDERS].index(name) + kind)
+    if name == "long":
+        return Case(kind, LONG_COUNTS, seed=MANY_SEED + 1)
+    if name == "many":
+        i = rng.integers(0, MANY_S, MANY)
+        j = (i + 1 + rng.integers(0, MANY_S - 1, MANY)) % MANY_S
+        i[:9], j[:9] = IDX_I, IDX_J
+        assert (i != j).all()
+        return Case(kind, np.tile(COUNTS, MANY // len(COUNTS) + 1)[:MANY], "explicit", seed=MANY_SEED, idx=(i, j), S=MANY_S)
+    c = Case(kind, COUNTS)
+    if name == "scaled":
+        c.z[:, :4] *= np.asarray(Z_SCALES)[np.arange(c.M) % 3][:, None]
+        return c
+    dp = _on_the_grid(c, rng)
+    if ROT[kind]:
+        c.z[:, :4] = [0.0, 0.0, 0.0, 1.0] if name == "identity" else np.asarray(PI_Z)[np.arange(c.M) % 6]
+    if POS[kind]:
+        c.z[:, ZN[kind] - 3:] = dp if name == "identity" else dp + 0.25 * rng.integers(1, 9, (c.M, 3))
+    if name == "pi" and kind == 2:
+        for k in range(6):
+            c.R[:, tri(k):tri(k) + k] = 0.0
+    return c
+
+
+def reversed_case(c):
+    """(the case with its factors in reverse order, order [F], meas [M]: where every factor and measurement of it sits in c); the states
+    stay where they are, so the case has explicit indices."""
+    assert c.idx_i is not None
+    order = np.arange(c.F - 1, -1, -1)
+    meas = np.concatenate([np.arange(c.mfirst[f], c.mfirst[f + 1]) for f in order]).astype(np.int64)
+    mv = c.head(c.F)
+    mv.counts = c.counts[order]
+    mv.mfirst = offsets(mv.counts)
+    mv.base, mv.chi2_base = c.base[order], c.chi2_base[order]
+    mv.idx_i, mv.idx_j = c.idx_i[order].copy(), c.idx_j[order].copy()
+    mv.z, mv.R, mv.weight = c.z[meas], c.R[meas], c.weight[meas]
+    return mv, order, meas
+
+
+def without(c, drop):
+    """The case with the measurements drop [M] bool deleted."""
+    v = c.head(c.F)
+    own = c.owner()
+    v.counts = np.bincount(own[~drop], minlength=c.F).astype(np.int64)
+    v.mfirst = offsets(v.counts)
+    v.M = int(v.mfirst[-1])
+    v.z, v.R, v.weight = (np.ascontiguousarray(a[~drop]) for a in (c.z, c.R, c.weight))
+    return v
+
+
 # --------------------------------------------------------------------------------------------- reference and metrics
 def reference(c, weight=True, base=True):
     """By the table of the contract in longdouble -> dict(hess [F, 496], chi2 [F], chi2_m [M]) and the units u_hess, u_chi2, u_chi2_m
@@ -296,6 +393,12 @@ def reference(c, weight=True, base=True):
             chi2[f] += w * chi2_m[m]
             u_chi2[f] += abs(w) * u_chi2_m[m]
     return dict(hess=hess, chi2=chi2, chi2_m=chi2_m, u_hess=u_hess, u_chi2=u_chi2, u_chi2_m=u_chi2_m)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_reference(name, kind, weight=True, base=True):
+    """reference() of an edge builder, computed once and shared (the tests leave it unchanged)."""
+    return reference(edge_case(name, kind), weight, base)
 
 
 _IB = np.array([b for b in range(31) for a in range(b + 1)])

@@ -128,6 +128,31 @@ int main() {
     std::vector<double> z(M * 3, 0.5), R(M * 6, 1.0), out(F * 496), c2(F);
     if (hsb_state_between(F, M, 0, broken.data(), st.data(), S, bi.data(), bj.data(), z.data(), R.data(), nullptr, nullptr, nullptr, out.data(), c2.data(), nullptr)) return 2;
     if (hsb_state_between(F, M, 9, mf.data(), st.data(), S, nullptr, nullptr, z.data(), R.data(), nullptr, nullptr, nullptr, out.data(), c2.data(), nullptr) != 1) ok = false;
+    // the padded arrays of tests/between_edge_checks.py: z, R, weight and chi2_m with PAD measurements on either side, the states with
+    // PADS states, NaN in the input pads and -7 in chi2_m; an mfirst and indices that leave their ranges by less than the pads.  The
+    // clamp keeps every access inside the interiors: nothing comes back NaN and no pad of chi2_m is written.
+    {
+        const long long PAD = 4, PADS = 2;
+        const double nan = NAN;
+        std::vector<double> bz((M + 2 * PAD) * 7, nan), bR((M + 2 * PAD) * 21, nan), bw(M + 2 * PAD, nan), bs((S + 2 * PADS) * 16, nan), bm(M + 2 * PAD, -7.0);
+        for (long long i = 0; i < M * 7; i++) bz[PAD * 7 + i] = (i % 7 == 3) ? 1.0 : 0.25;
+        for (long long i = 0; i < M * 21; i++) bR[PAD * 21 + i] = 1.0;
+        for (long long i = 0; i < M; i++) bw[PAD + i] = 0.5;
+        for (long long i = 0; i < S * 16; i++) bs[PADS * 16 + i] = st[i];
+        std::vector<long long> pm(mf);
+        pm[0] = -3; pm[2] = pm[1] - 1; pm[F] = M + 3;
+        std::vector<int> pi = {-1, 1, (int)S + 1, 3, 4}, pj = {1, (int)S, 3, -2, 5};
+        std::vector<double> po(F * 496, nan), pc(F, nan);
+        if (hsb_state_between(F, M, 2, pm.data(), bs.data() + PADS * 16, S, pi.data(), pj.data(), bz.data() + PAD * 7, bR.data() + PAD * 21, bw.data() + PAD,
+                              nullptr, nullptr, po.data(), pc.data(), bm.data() + PAD)) return 2;
+        bool inside = true;
+        for (double v : po) inside = inside && v == v;
+        for (double v : pc) inside = inside && v == v;
+        for (long long i = 0; i < PAD; i++) inside = inside && bm[i] == -7.0 && bm[PAD + M + i] == -7.0;
+        for (long long i = 0; i < M; i++) inside = inside && bm[PAD + i] == bm[PAD + i];
+        printf("padded arrays, broken mfirst and indices: everything stays inside %d\n", (int)inside);
+        ok = ok && inside;
+    }
     return ok ? 0 : 1;
 }
 #endif

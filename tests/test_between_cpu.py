@@ -230,39 +230,55 @@ def hb():
     return _bind(_LIB)
 
 
-def _mutant(tmp_path, old, new):
-    """The twin with old replaced by new in cpi_math.hpp."""
+def _mutant(tmp_path, old, new, twin=False):
+    """The twin with old replaced by new in cpi_math.hpp -- or, with twin=True, in hostsim_between.cpp itself (its ranges and pointers)."""
     text, src = open(_MATH).read(), open(_SRC).read()
-    assert text.count(old) == 1, old
+    assert (src if twin else text).count(old) == 1, old
     os.makedirs(tmp_path / "cpi_amd" / "csrc")
     os.makedirs(tmp_path / "tests" / "hostsim")
-    (tmp_path / "cpi_amd" / "csrc" / "cpi_math.hpp").write_text(text.replace(old, new))
-    (tmp_path / "tests" / "hostsim" / "hostsim_between.cpp").write_text(src)
+    (tmp_path / "cpi_amd" / "csrc" / "cpi_math.hpp").write_text(text if twin else text.replace(old, new))
+    (tmp_path / "tests" / "hostsim" / "hostsim_between.cpp").write_text(src.replace(old, new) if twin else src)
     out = str(tmp_path / "libmutant.so")
     tm._build(str(tmp_path / "tests" / "hostsim" / "hostsim_between.cpp"), out)
     return _bind(out)
 
 
-def twin(h, c, weight=True, base=True, rows=True, cost=True, inplace=False, z=None, mfirst=None):
-    """hsb_state_between on case c -> (hess [F, 496], chi2 [F], chi2_m [M]) with sentinels behind every array (None where not asked for)."""
+def twin(h, c, weight=True, base=True, rows=True, cost=True, inplace=False, z=None, mfirst=None, alias=None, bases=None, padded=None):
+    """hsb_state_between on case c -> (hess [F, 496], chi2 [F], chi2_m [M]) with sentinels behind every array (None where not asked for).
+    alias = (hess in place, chi2 in place) and bases = (hess_base given, chi2_base given) where the two arrays differ (inplace and base
+    set both).  padded: a between_edge_checks.Padded of the case -- z, R, weight, the states and chi2_m are the interiors of its arrays,
+    the inputs are compared with what they were, and chi2_m comes back as the WHOLE buffer [M + 2 PAD]."""
     hess = np.full((c.F + 1, 496), bc.SENTINEL) if rows else None
     chi2 = np.full(c.F + 1, bc.SENTINEL) if cost else None
     chi2_m = np.full(c.M + 1, bc.SENTINEL)
-    hb_, cb_ = (c.base, c.chi2_base) if base else (None, None)
-    if inplace:
-        assert base
-        if rows:
-            hess[:c.F] = c.base
-            hb_ = hess
-        if cost:
-            chi2[:c.F] = c.chi2_base
-            cb_ = chi2
+    a_h, a_c = (inplace, inplace) if alias is None else alias
+    b_h, b_c = (base, base) if bases is None else bases
+    hb_, cb_ = (c.base if b_h else None), (c.chi2_base if b_c else None)
+    if a_h and rows:
+        assert b_h
+        hess[:c.F] = c.base
+        hb_ = hess
+    if a_c and cost:
+        assert b_c
+        chi2[:c.F] = c.chi2_base
+        cb_ = chi2
     z = np.ascontiguousarray(c.z if z is None else z)
     mf = np.ascontiguousarray(c.mfirst if mfirst is None else mfirst, dtype=np.int64)
-    assert h.hsb_state_between(c.F, c.M, c.kind, _ptr(mf), _ptr(c.states), c.S, _ptr(c.idx_i), _ptr(c.idx_j), _ptr(z), _ptr(c.R),
-                               _ptr(c.weight) if weight else None, _ptr(hb_), _ptr(cb_), _ptr(hess), _ptr(chi2), _ptr(chi2_m)) == 0
-    assert chi2_m[c.M] == bc.SENTINEL and (hess is None or (hess[c.F] == bc.SENTINEL).all()) and (chi2 is None or chi2[c.F] == bc.SENTINEL)
-    return (None if hess is None else hess[:c.F]), (None if chi2 is None else chi2[:c.F]), chi2_m[:c.M]
+    if padded is not None:
+        p, big = padded, padded.big
+        was = {k: v.copy() for k, v in big.items()}
+        x2 = big["chi2_m"].copy()
+        inner = lambda a, n: _ptr(a, n * a.strides[0])
+        assert h.hsb_state_between(c.F, c.M, c.kind, _ptr(mf), inner(big["states"], p.PADS), c.S, _ptr(c.idx_i), _ptr(c.idx_j), inner(big["z"], p.PAD),
+                                   inner(big["R"], p.PAD), inner(big["weight"], p.PAD) if weight else None, _ptr(hb_), _ptr(cb_), _ptr(hess), _ptr(chi2),
+                                   inner(x2, p.PAD)) == 0
+        assert all(same_bits(big[k], was[k]) for k in big), "an input was written"
+        chi2_m = np.concatenate([x2, [bc.SENTINEL]])
+    else:
+        assert h.hsb_state_between(c.F, c.M, c.kind, _ptr(mf), _ptr(c.states), c.S, _ptr(c.idx_i), _ptr(c.idx_j), _ptr(z), _ptr(c.R),
+                                   _ptr(c.weight) if weight else None, _ptr(hb_), _ptr(cb_), _ptr(hess), _ptr(chi2), _ptr(chi2_m)) == 0
+    assert chi2_m[-1] == bc.SENTINEL and (hess is None or (hess[c.F] == bc.SENTINEL).all()) and (chi2 is None or chi2[c.F] == bc.SENTINEL)
+    return (None if hess is None else hess[:c.F]), (None if chi2 is None else chi2[:c.F]), chi2_m[:-1]
 
 
 def twin_e_J(h, kind, xi, xj, z):

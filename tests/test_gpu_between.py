@@ -38,28 +38,52 @@ def _t(a, dev):
     return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
-def _banded(n, cols, dev, fill=None):
-    """An output of n rows between two guard rows, NaN-filled (or holding `fill`: the in-place form) -> (the buffer, the view)."""
-    buf = torch.full((n + 2,) + cols, GUARD, dtype=torch.float64, device=dev)
+def _banded(n, cols, dev, fill=None, odd=False):
+    """An output of n rows between two guard rows, NaN-filled (or holding `fill`: the in-place form) -> (the buffer, the view).  odd: the
+    view starts at an address that is 8 but not 16 bytes aligned."""
+    width = int(np.prod(cols, dtype=np.int64))
+    shift = (width + 1) % 2 if odd else 0
+    flat = torch.full(((n + 2) * width + shift,), GUARD, dtype=torch.float64, device=dev)
+    buf = flat[shift:].view((n + 2,) + cols)
     buf[1:n + 1] = float("nan") if fill is None else _t(fill, dev)
+    assert not odd or buf[1:n + 1].data_ptr() % 16 == 8
     return buf, buf[1:n + 1]
 
 
-def dev_between(eng, c, weight=True, base=True, rows=True, cost=True, chi2_m=True, host=False, inplace=False, z=None):
-    """state_between on case c -> (hess [F, 496], chi2 [F], chi2_m [M]) as numpy (None where not asked for), outputs between guard rows."""
+def dev_between(eng, c, weight=True, base=True, rows=True, cost=True, chi2_m=True, host=False, inplace=False, z=None, alias=None, bases=None,
+                padded=None, wrap=None):
+    """state_between on case c -> (hess [F, 496], chi2 [F], chi2_m [M]) as numpy (None where not asked for), outputs between guard rows.
+    alias = (hess in place, chi2 in place) and bases = (hess_base given, chi2_base given) where the two arrays differ (inplace and base
+    set both).  padded: a between_edge_checks.Padded of the case -- z, R, weight, the states and chi2_m are the interiors of its arrays,
+    the inputs are compared with what they were, and chi2_m comes back as the WHOLE buffer [M + 2 PAD].  wrap: what every float64 input
+    goes through (tests/test_gpu_lm_edges.odd); the outputs then start at 8 mod 16 as well."""
     dev = "cpu" if host else eng.device
-    hb, hv = _banded(c.F, (496,), dev, c.base if inplace else None) if rows else (None, None)
-    cb, cv = _banded(c.F, (), dev, c.chi2_base if inplace else None) if cost else (None, None)
-    xb, xv = _banded(c.M, (), dev) if chi2_m else (None, None)
+    a_h, a_c = (inplace, inplace) if alias is None else alias
+    b_h, b_c = (base, base) if bases is None else bases
+    odd = wrap is not None
+    w = (lambda t: t) if wrap is None else wrap
+    hb, hv = _banded(c.F, (496,), dev, c.base if a_h else None, odd) if rows else (None, None)
+    cb, cv = _banded(c.F, (), dev, c.chi2_base if a_c else None, odd) if cost else (None, None)
+    xb, xv = _banded(c.M, (), dev, None, odd) if chi2_m else (None, None)
     fn = eng.state_between_host if host else eng.state_between
-    b_rows = (hv if inplace else _t(c.base, dev)) if base and rows else None
-    b_chi2 = (cv if inplace else _t(c.chi2_base, dev)) if base and cost else None
-    got = fn(_t(c.states, dev), bc.KINDS[c.kind] if c.F % 2 else c.kind, _t(c.z if z is None else z, dev), _t(c.R, dev), _t(c.mfirst, dev),
-             idx_i=_t(c.idx_i, dev), idx_j=_t(c.idx_j, dev), weight=_t(c.weight, dev) if weight else None, hess_base=b_rows, chi2_base=b_chi2,
-             out=hv, chi2=cv, chi2_m=xv, want_rows=rows, want_cost=cost)
+    b_rows = (hv if a_h else w(_t(c.base, dev))) if b_h and rows else None
+    b_chi2 = (cv if a_c else w(_t(c.chi2_base, dev))) if b_c and cost else None
+    states, zt, Rt, wt = (w(_t(a, dev)) for a in (c.states, c.z if z is None else z, c.R, c.weight))
+    if padded is not None:
+        p = padded
+        big = {k: _t(v, dev) for k, v in p.big.items()}
+        states, zt, Rt, wt = big["states"][p.PADS:p.PADS + c.S], big["z"][p.PAD:p.PAD + c.M], big["R"][p.PAD:p.PAD + c.M], big["weight"][p.PAD:p.PAD + c.M]
+        xb, xv = big["chi2_m"], big["chi2_m"][p.PAD:p.PAD + c.M]
+    got = fn(states, bc.KINDS[c.kind] if c.F % 2 else c.kind, zt, Rt, _t(c.mfirst, dev), idx_i=_t(c.idx_i, dev), idx_j=_t(c.idx_j, dev),
+             weight=wt if weight else None, hess_base=b_rows, chi2_base=b_chi2, out=hv, chi2=cv, chi2_m=xv, want_rows=rows, want_cost=cost)
     if not host:
         torch.cuda.synchronize()
     assert (got[0] is None) == (not rows) and (got[1] is None) == (not cost)
+    if padded is not None:
+        assert all(same_bits(big[k].cpu().numpy(), v) for k, v in padded.big.items() if k != "chi2_m"), "an input was written"
+        for buf, n in ((hb, c.F), (cb, c.F)):
+            assert buf is None or ((buf[0] == GUARD).all() and (buf[n + 1] == GUARD).all())
+        return tuple(None if v is None else v.cpu().numpy() for v in (hv, cv, xb))
     for buf, n in ((hb, c.F), (cb, c.F), (xb, c.M)):
         assert buf is None or ((buf[0] == GUARD).all() and (buf[n + 1] == GUARD).all())
     return tuple(None if v is None else v.cpu().numpy() for v in (hv, cv, xv))
@@ -183,8 +207,12 @@ def problem(eng, pipe, request):
     count / ffirst and compacted factor rows; "dense": the eight chains of six.  A Gaussian prior on every chain's first state, centred
     on the unperturbed state, and the betweens of bc.e2e_betweens at the device's unperturbed states: a relative pose on every factor, a
     body-frame displacement on every second one."""
+    return make_problem(eng, pipe, request.param == "ragged")
+
+
+def make_problem(eng, pipe, ragged):
+    """The dict of the fixture `problem` (tests/test_gpu_between_edges.py takes one layout at a time)."""
     C, G, dev = pipe.C, pipe.G, eng.device
-    ragged = request.param == "ragged"
     L = fx.layout(ragged)
     P0 = np.zeros((C, 16, 16))
     P0[:, np.arange(15), np.arange(15)] = 0.1 * cc.SCALES ** 2
