@@ -10,7 +10,7 @@ from ._lib import CpiError, LIB_PATH  # noqa: F401
 def __getattr__(name):  # lazy: importing the package must not need torch / a GPU
     if name in ("Engine", "CpiV1", "CpiV2", "ForsterDiscrete", "ImuFactorCPIv1", "ImuFactorCPIv2", "default_engine", "unpack_factor",
                 "pack_sym", "pack_tri", "unpack_sym", "unpack_tri", "retract", "local_coordinates", "factor_cost", "chain_solve", "chain_marginals",
-                "chain_marginalize", "prior_relinearize", "chain_cost", "chain_accept", "chain_lm", "state_fix", "state_fix_host", "fix_offsets",
+                "chain_marginalize", "chain_condense", "chain_expand", "chain_solve_segmented", "prior_relinearize", "chain_cost", "chain_accept", "chain_lm", "state_fix", "state_fix_host", "fix_offsets",
                 "state_between", "state_between_host"):
         from . import engine
         return getattr(engine, name)

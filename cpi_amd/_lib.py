@@ -211,6 +211,16 @@ def load():
     lib.cpi_chain_marginalize_batch.argtypes = [vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp]
     lib.cpi_chain_marginalize_batch_host.argtypes = [vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp]
     lib.cpi_chain_marginalize_batch.restype = lib.cpi_chain_marginalize_batch_host.restype = C.c_int
+    lib.cpi_chain_condense_states.argtypes = [i64, i64]
+    lib.cpi_chain_condense_states.restype = i64
+    lib.cpi_chain_condense_workspace_doubles.argtypes = [i64]
+    lib.cpi_chain_condense_workspace_doubles.restype = C.c_size_t
+    lib.cpi_chain_condense_batch.argtypes = [vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp]
+    lib.cpi_chain_condense_batch_host.argtypes = [vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp]
+    lib.cpi_chain_expand_batch.argtypes = [vp, i64, i64, i64, vp, vp, i64, vp, vp, vp]
+    lib.cpi_chain_expand_batch_host.argtypes = [vp, i64, i64, i64, vp, vp, i64, vp, vp, vp]
+    lib.cpi_chain_condense_batch.restype = lib.cpi_chain_condense_batch_host.restype = C.c_int
+    lib.cpi_chain_expand_batch.restype = lib.cpi_chain_expand_batch_host.restype = C.c_int
     lib.cpi_prior_relinearize_batch.argtypes = lib.cpi_prior_relinearize_batch_host.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, vp]
     lib.cpi_chain_cost_batch.argtypes = lib.cpi_chain_cost_batch_host.argtypes = [vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp]
     lib.cpi_chain_accept_batch.argtypes = lib.cpi_chain_accept_batch_host.argtypes = [vp, i64, i64, i64, i64, vp, vp, vp, C.POINTER(CpiLmParams),

@@ -7,7 +7,7 @@
     python -m cpi_amd.build --test-hooks         # additionally libcpi_amd_test.so (-DCPI_TEST_HOOKS: the two entries of
                                                  # include/cpi_amd_test.h; the PRODUCT library exports nothing but include/cpi_amd.h)
 
-The library is nineteen translation units (cpi_amd/csrc/cpi_args.hpp) compiled IN PARALLEL into cpi_amd/csrc/_obj/*.o and
+The library is twenty translation units (cpi_amd/csrc/cpi_args.hpp) compiled IN PARALLEL into cpi_amd/csrc/_obj/*.o and
 linked into one shared object; an object is rebuilt only when the sources it includes (or the flags) change, so touching
 one kernel family costs one TU.  hipcc cross-compiles gfx950 without a GPU present; the .so is git-ignored but ships to
 the GPU box.
@@ -40,6 +40,7 @@ UNIT_REPORTS = {"cpi_running_resume": os.path.join(CSRC, "resource_usage_running
                 "cpi_chain": os.path.join(CSRC, "resource_usage_chain.txt"),
                 "cpi_marginals": os.path.join(CSRC, "resource_usage_marginals.txt"),
                 "cpi_marginalize": os.path.join(CSRC, "resource_usage_marginalize.txt"),
+                "cpi_condense": os.path.join(CSRC, "resource_usage_condense.txt"),
                 "cpi_lm": os.path.join(CSRC, "resource_usage_lm.txt"),
                 "cpi_fix": os.path.join(CSRC, "resource_usage_fix.txt"),
                 "cpi_between": os.path.join(CSRC, "resource_usage_between.txt")}
@@ -71,6 +72,7 @@ UNITS = {
     "cpi_chain": DEVICE + ["cpi_chain_util.hpp", "cpi_chain.hip", "cpi_factor_kernels.hpp", "cpi_chain_kernels.hpp"],
     "cpi_marginals": DEVICE + ["cpi_marginals.hip", "cpi_factor_kernels.hpp", "cpi_chain_util.hpp", "cpi_marginals_kernels.hpp"],
     "cpi_marginalize": DEVICE + ["cpi_marginalize.hip", "cpi_factor_kernels.hpp", "cpi_chain_util.hpp", "cpi_marginalize_kernels.hpp"],
+    "cpi_condense": DEVICE + ["cpi_condense.hip", "cpi_factor_kernels.hpp", "cpi_chain_util.hpp", "cpi_condense_kernels.hpp"],
     "cpi_lm": DEVICE + ["cpi_lm.hip", "cpi_factor_kernels.hpp", "cpi_chain_util.hpp", "cpi_lm_kernels.hpp"],
     "cpi_fix": DEVICE + ["cpi_fix.hip", "cpi_fix_kernels.hpp"],
     "cpi_between": DEVICE + ["cpi_between.hip", "cpi_between_kernels.hpp"],
@@ -257,7 +259,7 @@ def _build_locked(force, report, experiments, test_hooks):
     for variant, wanted in (("", True), ("exp", experiments), ("test", test_hooks)):
         if wanted and (force or stale(VARIANTS[variant][0], variant=variant)):
             todo.append(variant)
-    # every object of every wanted variant in ONE pool (the default build's nineteen units + the units a variant compiles with its own
+    # every object of every wanted variant in ONE pool (the default build's twenty units + the units a variant compiles with its own
     # define): __graft_entry__.build() rebuilds three libraries in the time of the slowest translation unit
     jobs = {}
     for variant in todo:

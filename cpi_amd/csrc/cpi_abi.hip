@@ -1616,6 +1616,109 @@ extern "C" int cpi_chain_marginalize_batch(cpi_ctx *ctx, int64_t C, int64_t G, i
 }
 
 // ============================================================================================
+// cpi_chain_condense_batch / cpi_chain_expand_batch: segments of chains condensed in parallel (cpi_condense_kernel / cpi_expand_kernel,
+// cpi_condense.hip)
+// ============================================================================================
+extern "C" int64_t cpi_chain_condense_states(int64_t G, int64_t K) {
+    if (G < 2 || K < 1) return G < 0 ? 0 : (G < 2 ? G : 0);   // K < 1 is refused by the entries: no layout
+    return (G - 2) / K + 2;
+}
+extern "C" size_t cpi_chain_condense_workspace_doubles(int64_t S) { return launch::condense_workspace_doubles(S > 0 ? (long long)S : 0); }
+
+// what the device and the host forms refuse alike, before the context is looked at; host: no workspace
+static int condense_check(cpi_ctx *ctx, const char *who, int64_t C, int64_t G, int64_t S, int64_t F, const int64_t *first, const int32_t *count,
+                          const int64_t *ffirst, const double *hess, const double *prior, const double *lambda, int32_t damping, int64_t K,
+                          double *rhess, double *rprior, int32_t *rcount, int32_t *status, double *workspace, bool host) {
+    if (C < 0 || S < 0 || F < 0) return refuse(ctx, who, "negative size");
+    if (G < 1) return refuse(ctx, who, "G (the longest chain in states) must be >= 1");
+    if (G > 0x7fffffffLL) return refuse(ctx, who, "G exceeds 2^31 - 1 states per chain");
+    if (K < 1) return refuse(ctx, who, "K (the factors of a segment) must be >= 1");
+    if (damping != CPI_DAMP_IDENTITY && damping != CPI_DAMP_DIAGONAL) return refuse(ctx, who, "damping must be CPI_DAMP_IDENTITY or CPI_DAMP_DIAGONAL");
+    if (C == 0) return CPI_OK;
+    const int64_t Gr = cpi_chain_condense_states(G, K);
+    if (!hess && G > 1) return refuse(ctx, who, "hess is NULL (only chains of one state, G == 1, need none)");
+    if (!rhess && G > 1) return refuse(ctx, who, "rhess is NULL (only chains of one state, G == 1, need none)");
+    if (!rprior) return refuse(ctx, who, "rprior is NULL");
+    if (!rcount) return refuse(ctx, who, "rcount is NULL");
+    if (!host && !workspace) return refuse(ctx, who, "workspace is NULL");
+    const size_t d = sizeof(double);
+    const Span outs[5] = { { rhess, (size_t)C * (size_t)(Gr - 1) * 496 * d, "rhess" }, { rprior, (size_t)C * (size_t)Gr * 136 * d, "rprior" },
+                           { rcount, (size_t)C * sizeof(int32_t), "rcount" }, { status, (size_t)C * (size_t)(Gr - 1) * sizeof(int32_t), "status" },
+                           { workspace, workspace ? cpi_chain_condense_workspace_doubles(S) * d : 0, "workspace" } };
+    const Span ins[6] = { { first, (size_t)C * sizeof(int64_t), "" }, { count, (size_t)C * sizeof(int32_t), "" }, { ffirst, (size_t)C * sizeof(int64_t), "" },
+                          { hess, (size_t)F * 496 * d, "" }, { prior, (size_t)S * 136 * d, "" }, { lambda, (size_t)C * d, "" } };
+    return refuse_overlaps(ctx, who, outs, 5, ins, 6);
+}
+// K as the kernels take it: a K beyond the longest chain's factors cuts nothing, and max(G - 1, 1) cuts the same
+static int condense_k(int64_t G, int64_t K) { return (int)(K < (G > 2 ? G - 1 : 1) ? K : (G > 2 ? G - 1 : 1)); }
+
+extern "C" int cpi_chain_condense_batch(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_t F,
+                                        const int64_t *first, const int32_t *count, const int64_t *ffirst,
+                                        const double *hess, const double *prior, const double *lambda, int32_t damping, int64_t K,
+                                        double *rhess, double *rprior, int32_t *rcount,
+                                        int32_t *status, double *workspace) {
+    static const char who[] = "cpi_chain_condense_batch";
+    CPI_TRY(condense_check(ctx, who, C, G, S, F, first, count, ffirst, hess, prior, lambda, damping, K, rhess, rprior, rcount, status, workspace, false));
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (C == 0) return CPI_OK;
+    const int64_t Gr = cpi_chain_condense_states(G, K);
+    if (C > 0x7fffffffffffffffLL / Gr || !grid_ok((launch::condense_groups(C, (int)Gr) + 3) / 4))
+        return refuse(ctx, who, "C x segments exceeds the 32-bit grid (4 segments per workgroup)");
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    CondenseArgs a;
+    memset(&a, 0, sizeof a);
+    a.C = C; a.G = (int)G; a.S = S; a.F = F;
+    a.first = (const long long *)first; a.count = count; a.ffirst = (const long long *)ffirst;
+    a.hess = hess; a.prior = prior; a.lambda = lambda; a.diagonal = damping == CPI_DAMP_DIAGONAL;
+    a.K = condense_k(G, K); a.Gr = (int)Gr;
+    a.rhess = rhess; a.rprior = rprior; a.rcount = rcount; a.status = status; a.workspace = workspace;
+    launch::chain_condense(a, ctx->stream);
+    CPI_HIP(ctx, hipGetLastError());
+    return CPI_OK;
+}
+
+static int expand_check(cpi_ctx *ctx, const char *who, int64_t C, int64_t G, int64_t S, const int64_t *first, const int32_t *count, int64_t K,
+                        const double *rdelta, const double *workspace, double *delta) {
+    if (C < 0 || S < 0) return refuse(ctx, who, "negative size");
+    if (G < 1) return refuse(ctx, who, "G (the longest chain in states) must be >= 1");
+    if (G > 0x7fffffffLL) return refuse(ctx, who, "G exceeds 2^31 - 1 states per chain");
+    if (K < 1) return refuse(ctx, who, "K (the factors of a segment) must be >= 1");
+    if (C == 0) return CPI_OK;
+    if (!rdelta) return refuse(ctx, who, "rdelta is NULL");
+    if (!workspace) return refuse(ctx, who, "workspace is NULL");
+    if (!delta) return refuse(ctx, who, "delta is NULL");
+    const size_t d = sizeof(double);
+    const Span outs[1] = { { delta, (size_t)S * 15 * d, "delta" } };
+    const Span ins[4] = { { first, (size_t)C * sizeof(int64_t), "" }, { count, (size_t)C * sizeof(int32_t), "" },
+                          { rdelta, (size_t)C * (size_t)cpi_chain_condense_states(G, K) * 15 * d, "" },
+                          { workspace, cpi_chain_condense_workspace_doubles(S) * d, "" } };
+    return refuse_overlaps(ctx, who, outs, 1, ins, 4);
+}
+
+extern "C" int cpi_chain_expand_batch(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S,
+                                      const int64_t *first, const int32_t *count, int64_t K,
+                                      const double *rdelta, const double *workspace, double *delta) {
+    static const char who[] = "cpi_chain_expand_batch";
+    CPI_TRY(expand_check(ctx, who, C, G, S, first, count, K, rdelta, workspace, delta));
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (C == 0) return CPI_OK;
+    const int64_t Gr = cpi_chain_condense_states(G, K);
+    if (C > 0x7fffffffffffffffLL / Gr || !grid_ok((launch::condense_groups(C, (int)Gr) + 3) / 4))
+        return refuse(ctx, who, "C x segments exceeds the 32-bit grid (4 segments per workgroup)");
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    ExpandArgs a;
+    memset(&a, 0, sizeof a);
+    a.C = C; a.G = (int)G; a.S = S;
+    a.first = (const long long *)first; a.count = count; a.K = condense_k(G, K); a.Gr = (int)Gr;
+    a.rdelta = rdelta; a.workspace = workspace; a.delta = delta;
+    launch::chain_expand(a, ctx->stream);
+    CPI_HIP(ctx, hipGetLastError());
+    return CPI_OK;
+}
+
+// ============================================================================================
 // The Levenberg-Marquardt step per chain: cpi_prior_relinearize_batch, cpi_chain_cost_batch, cpi_chain_accept_batch (cpi_lm.hip)
 // ============================================================================================
 // what the device and the host forms refuse alike, before the context is looked at
@@ -3352,6 +3455,94 @@ extern "C" int cpi_chain_marginalize_batch_host(cpi_ctx *ctx, int64_t C, int64_t
     CPI_TRY(cpi_chain_marginalize_batch(ctx, C, G, S, F, in.first, in.count, in.ffirst, in.hess, in.prior, M, dm, dout, ds));
     CPI_TRY(st.download(out, (const double *)dout, (size_t)C * 136));
     if (status) CPI_TRY(st.download(status, (const int32_t *)ds, (size_t)C));
+    return st.finish();
+}
+
+// cpi_chain_condense_batch from host memory: every array a host array, staged whole, synchronous.  The ranges are validated as in
+// cpi_chain_solve_batch_host.  The workspace stays on the device: workspace_out NULL, or cpi_chain_condense_workspace_doubles(S) HOST
+// doubles that receive it (what cpi_chain_expand_batch_host takes).  The reduced arrays travel up before the kernel, so that the rows
+// nobody writes come back as the caller left them.
+extern "C" int cpi_chain_condense_batch_host(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_t F,
+                                             const int64_t *first, const int32_t *count, const int64_t *ffirst,
+                                             const double *hess, const double *prior, const double *lambda, int32_t damping, int64_t K,
+                                             double *rhess, double *rprior, int32_t *rcount,
+                                             int32_t *status, double *workspace_out) {
+    static const char who[] = "cpi_chain_condense_batch_host";
+    CPI_TRY(condense_check(ctx, who, C, G, S, F, first, count, ffirst, hess, prior, lambda, damping, K, rhess, rprior, rcount, status, workspace_out, true));
+    CPI_TRY(chain_ranges_check(ctx, who, C, G, S, F, first, count, ffirst));
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (C == 0) return CPI_OK;
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    Staging st(ctx);
+    ChainsDev in;
+    const int64_t Gr = cpi_chain_condense_states(G, K);
+    const size_t nh = (size_t)C * (size_t)(Gr - 1) * 496, np = (size_t)C * (size_t)Gr * 136, nw = cpi_chain_condense_workspace_doubles(S);
+    const double *dl, *dh0 = nullptr, *dp0, *dw0 = nullptr;
+    double *dh = nullptr, *dw = nullptr;
+    int32_t *dc, *ds = nullptr;
+    CPI_TRY(stage_chains(st, C, G, S, F, first, count, ffirst, hess, prior, &in, false));
+    CPI_TRY(st.upload(lambda, (size_t)C, &dl));
+    if (nh > 0) {
+        CPI_TRY(st.upload((const double *)rhess, nh, &dh0));
+        dh = const_cast<double *>(dh0);
+    } else {
+        CPI_TRY(st.alloc((size_t)1, &dh));
+    }
+    CPI_TRY(st.upload((const double *)rprior, np, &dp0));
+    if (workspace_out) {
+        CPI_TRY(st.upload((const double *)workspace_out, nw, &dw0));
+        dw = const_cast<double *>(dw0);
+    } else {
+        CPI_TRY(st.alloc(nw, &dw));
+    }
+    CPI_TRY(st.alloc((size_t)C, &dc));
+    if (status && Gr > 1) CPI_TRY(st.alloc((size_t)C * (size_t)(Gr - 1), &ds));
+    CPI_TRY(cpi_chain_condense_batch(ctx, C, G, S, F, in.first, in.count, in.ffirst, in.hess, in.prior, dl, damping, K, dh, const_cast<double *>(dp0), dc, ds, dw));
+    if (nh > 0) CPI_TRY(st.download(rhess, (const double *)dh, nh));
+    CPI_TRY(st.download(rprior, dp0, np));
+    CPI_TRY(st.download(rcount, (const int32_t *)dc, (size_t)C));
+    if (ds) CPI_TRY(st.download(status, (const int32_t *)ds, (size_t)C * (size_t)(Gr - 1)));
+    if (workspace_out) CPI_TRY(st.download(workspace_out, (const double *)dw, nw));
+    return st.finish();
+}
+
+// cpi_chain_expand_batch from host memory: every array a host array (the workspace too: what cpi_chain_condense_batch_host returned),
+// staged whole, synchronous.  The state ranges are validated.  delta travels up before the kernel.
+extern "C" int cpi_chain_expand_batch_host(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S,
+                                           const int64_t *first, const int32_t *count, int64_t K,
+                                           const double *rdelta, const double *workspace, double *delta) {
+    static const char who[] = "cpi_chain_expand_batch_host";
+    CPI_TRY(expand_check(ctx, who, C, G, S, first, count, K, rdelta, workspace, delta));
+    for (int64_t c = 0; c < C; c++) {
+        const int64_t f = first ? first[c] : c * G;
+        int64_t n = count ? count[c] : G;
+        n = n < 0 ? 0 : (n > G ? G : n);
+        if (f < 0 || f > S || n > S - f)
+            return fail(ctx, CPI_ERR_INVALID, std::string(who) + ": the states of chain " + std::to_string(c) + " leave [0, S)");
+    }
+    if (!ctx) return fail(nullptr, CPI_ERR_INVALID, "ctx is NULL");
+    if (C == 0) return CPI_OK;
+    DeviceGuard guard_;
+    CPI_HIP(ctx, guard_.enter(ctx->device));
+    Staging st(ctx);
+    const int64_t Gr = cpi_chain_condense_states(G, K);
+    const int64_t *df;
+    const int32_t *dn;
+    const double *dr, *dw, *dd0 = nullptr;
+    double *dd = nullptr;
+    CPI_TRY(st.upload(first, (size_t)C, &df));
+    CPI_TRY(st.upload(count, (size_t)C, &dn));
+    CPI_TRY(st.upload(rdelta, (size_t)C * (size_t)Gr * 15, &dr));
+    CPI_TRY(st.upload(workspace, cpi_chain_condense_workspace_doubles(S), &dw));
+    if (S > 0) {
+        CPI_TRY(st.upload((const double *)delta, (size_t)S * 15, &dd0));
+        dd = const_cast<double *>(dd0);
+    } else {
+        CPI_TRY(st.alloc((size_t)1, &dd));
+    }
+    CPI_TRY(cpi_chain_expand_batch(ctx, C, G, S, df, dn, K, dr, dw, dd));
+    if (S > 0) CPI_TRY(st.download(delta, (const double *)dd, (size_t)S * 15));
     return st.finish();
 }
 

@@ -1,6 +1,6 @@
 // cpi_args.hpp -- kernel argument blocks and the launcher interface between the translation units of libcpi_amd.so.
 //
-// The library is nineteen translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
+// The library is twenty translation units, compiled in parallel by cpi_amd/build.py and linked into one shared object:
 //   cpi_mean.hip    cpi_mean_kernel / cpi_mean_tiled_kernel / cpi_tile_*_kernel       (cpi_mean_kernels.hpp)
 //   cpi_running.hip cpi_mean_running_kernel / cpi_mean_stream_running_kernel: a row after every interval, from plain knots /
 //                   from windows cut out of IMU stream(s) in place         (cpi_running_kernels.hpp, cpi_running_body.inc)
@@ -36,6 +36,10 @@
 //   cpi_marginalize.hip  cpi_marginalize_kernel: the leading states of every chain eliminated into a prior on the first
 //                   state that stays -- the forward half of the solve, undamped, no workspace
 //                                 (cpi_marginalize_kernels.hpp over cpi_factor_kernels.hpp's DPP multiply-adds; cpi_chain_util.hpp)
+//   cpi_condense.hip  cpi_condense_kernel / cpi_expand_kernel: chains cut into segments of K factors, every segment's interior states
+//                   eliminated by a 16-lane group of its own into one 31 x 31 factor row between its ends, and the solution of the
+//                   short chain of segment ends substituted back -- parallelism ALONG a chain
+//                                   (cpi_condense_kernels.hpp over cpi_factor_kernels.hpp's DPP multiply-adds; cpi_chain_util.hpp)
 //   cpi_lm.hip      cpi_lm_prior_kernel / cpi_lm_cost_kernel / cpi_lm_accept_kernel: the Levenberg-Marquardt step per chain -- the prior
 //                   at the current states with its cost, the objective per chain, and the decision (accept, copy, lambda, phase)
 //                                                                                  (cpi_lm_kernels.hpp; cpi_chain_util.hpp)
@@ -263,6 +267,40 @@ struct MarginalizeArgs {
     int *status;             // [C] or NULL
 };
 
+// cpi_chain_condense_batch: the chains of cpi_chain_solve_batch (the same clamps) cut into segments of K factors; Gr reduced states per
+// chain slot (cpi_chain_condense_states(G, K)).  The reduced arrays are in the tile layout: state j of chain c at row c * Gr + j.
+struct CondenseArgs {
+    long long C;             // chains
+    int G;                   // the longest chain in states, >= 1
+    long long S, F;          // rows of prior / workspace records; rows of hess
+    const long long *first;  // [C] or NULL: chain c starts at state c * G
+    const int *count;        // [C] or NULL: every chain has G states
+    const long long *ffirst; // [C] or NULL: first[c] - c
+    const double *hess;      // [F][496]
+    const double *prior;     // [S][136] or NULL
+    const double *lambda;    // [C] or NULL (0)
+    int diagonal;            // CPI_DAMP_DIAGONAL
+    int K, Gr;               // factors per segment (1 <= K <= max(G - 1, 1)); reduced states per chain slot
+    double *rhess;           // [C * (Gr - 1)][496]
+    double *rprior;          // [C * Gr][136]
+    int *rcount;             // [C]
+    int *status;             // [C * (Gr - 1)] or NULL, per segment
+    double *workspace;       // [S][chn::CS_D]; interior records only
+};
+
+// cpi_chain_expand_batch: C, G, S, first, count, K as the condense that wrote workspace had them.
+struct ExpandArgs {
+    long long C;
+    int G;
+    long long S;
+    const long long *first;
+    const int *count;
+    int K, Gr;
+    const double *rdelta;     // [C * Gr][15]: the reduced solve's delta
+    const double *workspace;  // [S][chn::CS_D], read only
+    double *delta;            // [S][15]
+};
+
 // cpi_prior_relinearize_batch: record p belongs to state idx[p] (NULL: p); an index outside [0, S) skips the record where it is read.
 struct LmPriorArgs {
     long long S, P;
@@ -414,6 +452,11 @@ void chain_solve(const ChainArgs &a, hipStream_t st);
 void chain_marginals(const MarginalsArgs &a, hipStream_t st);
 // ---- cpi_marginalize.hip (cpi_chain_marginalize_batch)
 void chain_marginalize(const MarginalizeArgs &a, hipStream_t st);
+// ---- cpi_condense.hip (cpi_chain_condense_batch, cpi_chain_expand_batch)
+size_t condense_workspace_doubles(long long S);
+long long condense_groups(long long C, int Gr);   // 16-lane groups of a launch, 4 per workgroup
+void chain_condense(const CondenseArgs &a, hipStream_t st);
+void chain_expand(const ExpandArgs &a, hipStream_t st);
 // ---- cpi_lm.hip (cpi_prior_relinearize_batch, cpi_chain_cost_batch, cpi_chain_accept_batch)
 void lm_prior(const LmPriorArgs &a, hipStream_t st);
 void lm_cost(const LmCostArgs &a, hipStream_t st);

@@ -987,6 +987,66 @@ inline std::vector<double> chain_marginalize(const Context &ctx, int64_t C, int6
     return out;
 }
 
+// Long chains, solved in parallel ALONG the chain (cpi_chain_condense_batch_host, cpi_chain_expand_batch_host: the device kernels'
+// bits).  C chains of G states back to back, hess / prior / lambda / diagonal as chain_solve takes them, K >= 1 the factors of a
+// segment.  chain_condense eliminates the states between the ends of every segment: the reduced chains of Gr =
+// cpi_chain_condense_states(G, K) states each, for chain_solve(ctx, C, Gr, rhess, rprior) WITHOUT lambda (the damping is in the
+// reduced system), and the workspace chain_expand substitutes back from.  status: per segment, [C * (Gr - 1)], the codes of
+// include/cpi_amd.h.  chain_expand returns delta [C * G * 15] from the reduced solve's rdelta [C * Gr * 15].
+struct CondensedChains {
+    int64_t Gr = 0;
+    std::vector<double> rhess, rprior, workspace;
+    std::vector<int32_t> rcount, status;
+};
+inline CondensedChains chain_condense(const Context &ctx, int64_t C, int64_t G, int64_t K, const std::vector<double> &hess,
+                                      const std::vector<double> &prior = {}, const std::vector<double> &lambda = {}, bool diagonal = false) {
+    if (C < 0 || G < 1 || K < 1 || hess.size() != (size_t)(C * (G - 1)) * 496 || (!prior.empty() && prior.size() != (size_t)(C * G) * 136) ||
+        (!lambda.empty() && lambda.size() != (size_t)C))
+        throw std::invalid_argument("cpi_host::chain_condense: K >= 1, hess [C * (G - 1) * 496], prior empty or [C * G * 136], lambda empty or [C]");
+    CondensedChains r;
+    r.Gr = cpi_chain_condense_states(G, K);
+    r.rhess.assign((size_t)(C * (r.Gr - 1)) * 496 + 1, 0.0);       // + 1: G == 1 has no reduced factor, and data() stays a pointer
+    r.rprior.assign((size_t)(C * r.Gr) * 136, 0.0);
+    r.workspace.assign(cpi_chain_condense_workspace_doubles(C * G), 0.0);
+    r.rcount.assign((size_t)C, 0);
+    r.status.assign((size_t)(C * (r.Gr - 1)), 0);
+    static const double none = 0.0;      // G == 1: no factor rows; G > 1 with C == 0: never read
+    ctx.check(cpi_chain_condense_batch_host(ctx.get(), C, G, C * G, C * (G - 1), nullptr, nullptr, nullptr, hess.empty() ? &none : hess.data(),
+                                            prior.empty() ? nullptr : prior.data(), lambda.empty() ? nullptr : lambda.data(),
+                                            diagonal ? CPI_DAMP_DIAGONAL : CPI_DAMP_IDENTITY, K, r.rhess.data(), r.rprior.data(), r.rcount.data(),
+                                            r.status.empty() ? nullptr : r.status.data(), r.workspace.data()));
+    r.rhess.pop_back();
+    return r;
+}
+inline std::vector<double> chain_expand(const Context &ctx, int64_t C, int64_t G, int64_t K, const std::vector<double> &rdelta,
+                                        const std::vector<double> &workspace) {
+    if (C < 0 || G < 1 || K < 1 || rdelta.size() != (size_t)(C * cpi_chain_condense_states(G, K)) * 15 ||
+        workspace.size() < cpi_chain_condense_workspace_doubles(C * G))
+        throw std::invalid_argument("cpi_host::chain_expand: K >= 1, rdelta [C * Gr * 15], workspace as chain_condense returned it");
+    std::vector<double> delta((size_t)(C * G) * 15 + 1, 0.0);
+    ctx.check(cpi_chain_expand_batch_host(ctx.get(), C, G, C * G, nullptr, nullptr, K, rdelta.empty() ? delta.data() + delta.size() - 1 : rdelta.data(),
+                                          workspace.data(), delta.data()));
+    delta.pop_back();
+    return delta;
+}
+// The three calls: condense at segment length K, the reduced solve, expand.  Returns delta [C * G * 15], chain_solve's result to
+// rounding; status, when given, receives the REDUCED solve's per-chain codes (a failed chain's rows are NaN).
+inline std::vector<double> chain_solve_segmented(const Context &ctx, int64_t C, int64_t G, int64_t K, const std::vector<double> &hess,
+                                                 const std::vector<double> &prior = {}, const std::vector<double> &lambda = {},
+                                                 bool diagonal = false, std::vector<int32_t> *status = nullptr) {
+    const CondensedChains r = chain_condense(ctx, C, G, K, hess, prior, lambda, diagonal);
+    std::vector<double> rdelta((size_t)(C * r.Gr) * 15 + 1, 0.0);
+    std::vector<int32_t> st((size_t)C + 1, 0);
+    static const double none = 0.0;
+    ctx.check(cpi_chain_solve_batch_host(ctx.get(), C, r.Gr, C * r.Gr, C * (r.Gr - 1), nullptr, r.rcount.data(), nullptr,
+                                         r.rhess.empty() ? &none : r.rhess.data(), r.rprior.empty() ? &none : r.rprior.data(), nullptr,
+                                         CPI_DAMP_IDENTITY, rdelta.data(), st.data()));
+    rdelta.pop_back();
+    st.pop_back();
+    if (status) *status = st;
+    return chain_expand(ctx, C, G, K, rdelta, r.workspace);
+}
+
 // The Levenberg-Marquardt step per chain (cpi_prior_relinearize_batch_host, cpi_chain_cost_batch_host, cpi_chain_accept_batch_host: the
 // device kernels' bits), for C chains of G states back to back.
 // prior_relinearize: the priors of P records at `states` [S * 16] -- anchor [P * 16] the state each was linearised at, prior0 [P * 136]

@@ -1859,6 +1859,113 @@ CPI_HD int marginalize_chain(int n, int m, const double *hess, const double *pri
     return status;
 }
 
+// cpi_chain_condense_batch / cpi_chain_expand_batch: a run of consecutive factors with the states between its two ends eliminated is
+// again a 31 x 31 factor row between those ends.  One SEGMENT of nf factors: its left end a is local state 0, its interiors the local
+// states t = 1 .. nf - 1, hess its nf factor rows, prior NULL or the rows from state a on, ws the records from state a on (CS_D doubles
+// each; only those of the interiors are touched).  M starts as factor 0, in five pieces: AA = M_aa with m_a as column 15, V = M_at
+// (V[j][k]: a-index j, t-index k), N = M_tt with m_t as column 15 (the solve's carried block), c, and raw, the diagonal of the trailing
+// block as the factor has it.  Per interior t, in this order (the kernel, cpi_condense_kernels.hpp, is the lane-mapped form):
+//   A        = (N + H_t[0:15, 0:15 | 30]) + Pr_t, damped by the solve's rule: d_j = (raw_j + H_t[j][j]) + Pr_t[j][j] WITHOUT the Schur term
+//   pivots   factor_block(A);  Wn = L^-1 U_t and Wa = L^-1 V^T (solve_w: column c of Wa is row c of V)
+//   c        = c + H_t[30][30], then c = fma(-y_k, y_k, c), k = 0 .. 14
+//   N        = H_t[15:30, 15:30 | 30] - Wn^T [Wn y]                                                               (schur)
+//   AA      -= Wa^T [Wa y]                                                                                         (schur)
+//   V[j][k]  = the fma chain r = 0 .. 14 from +0.0 of fma(-Wn[r][k], Wa[r][j], .):  M_a,t+1 = -Wa^T Wn
+// and the record of state t: [R y] and Wn as solve_chain leaves them, then Wa row-major at CS_A.  out [496]: the packed row.  A segment
+// of one factor returns its row bit for bit.  Returns 0, or t for the first interior whose block was not positive definite (out is
+// all NaN then).
+static const int CS_A = WS_D, CS_D = WS_D + 225;
+CPI_HD int condense_segment(int nf, const double *hess, const double *prior, double lam, int diagonal, double *ws, double *out) {
+    double AA[15][16], V[15][15], N[15][16], raw[15], c;
+    int status = 0;
+    for (int i = 0; i < 15; i++) {
+        for (int j = 0; j < 16; j++) {
+            AA[i][j] = sym_at(hess, i, (j < 15) ? j : 30);
+            N[i][j] = sym_at(hess, 15 + i, (j < 15) ? 15 + j : 30);
+        }
+        for (int k = 0; k < 15; k++) V[i][k] = hess[tri(15 + k) + i];
+        raw[i] = hess[tri(15 + i) + 15 + i];
+    }
+    c = hess[tri(30) + 30];
+    for (int t = 1; t < nf; t++) {
+        const double *H = hess + (long long)t * HESS_D, *Pr = prior ? prior + (long long)t * PRIOR_D : nullptr;
+        double A[15][16], U[15][15], Wa[15][15];
+        for (int j = 0; j < 16; j++)
+            for (int i = 0; i < 15; i++) A[i][j] = (N[i][j] + sym_at(H, i, (j < 15) ? j : 30)) + (Pr ? sym_at(Pr, i, j) : 0.0);
+        for (int j = 0; j < 15; j++) {
+            const double d = (raw[j] + H[tri(j) + j]) + (Pr ? Pr[tri(j) + j] : 0.0);
+            A[j][j] = diagonal ? fma(lam, d, A[j][j]) : A[j][j] + lam;
+        }
+        if (!factor_block(A) && status == 0) status = t;
+        for (int i = 0; i < 15; i++) {
+            for (int k = 0; k < 15; k++) { U[i][k] = H[tri(15 + k) + i]; Wa[i][k] = V[k][i]; }
+            for (int j = 0; j < 16; j++) N[i][j] = sym_at(H, 15 + i, (j < 15) ? 15 + j : 30);
+            raw[i] = H[tri(15 + i) + 15 + i];
+        }
+        solve_w(A, U);
+        solve_w(A, Wa);
+        c = c + H[tri(30) + 30];
+        for (int k = 0; k < 15; k++) c = fma(-A[k][15], A[k][15], c);
+        schur(U, A, N);
+        schur(Wa, A, AA);
+        for (int j = 0; j < 15; j++)
+            for (int k = 0; k < 15; k++) {
+                double a = 0.0;
+                for (int r = 0; r < 15; r++) a = fma(-U[r][k], Wa[r][j], a);
+                V[j][k] = a;
+            }
+        double *rec = ws + (long long)t * CS_D;
+        for (int k = 0; k < 15; k++) {
+            for (int j = k; j < 16; j++) rec[row_off(k) + j - k] = A[k][j];
+            for (int cc = 0; cc < 15; cc++) { rec[WS_R + k * 15 + cc] = U[k][cc]; rec[CS_A + k * 15 + cc] = Wa[k][cc]; }
+        }
+    }
+    for (int j = 0; j < 15; j++) {
+        for (int i = 0; i <= j; i++) { out[tri(j) + i] = AA[i][j]; out[tri(15 + j) + 15 + i] = N[i][j]; }
+        for (int i = 0; i < 15; i++) out[tri(15 + j) + i] = V[i][j];
+    }
+    for (int i = 0; i < 15; i++) { out[tri(30) + i] = AA[i][15]; out[tri(30) + 15 + i] = N[i][15]; }
+    out[tri(30) + 30] = c;
+    if (status)
+        for (int i = 0; i < HESS_D; i++) out[i] = NAN;
+    return status;
+}
+// The prior row of a state that stays (a separator): Pr_s with the damping of the solve baked into its diagonal -- lambda, or
+// fma(lambda, d_j, .) with d_j = (Hp[15 + j][15 + j] + Hn[j][j]) + Pr_s[j][j], Hp / Hn the factors that end / begin at the state (NULL:
+// +0.0), Pr NULL: zeros.  damped = 0 (lambda is NULL): the values pass through as they are.  Entry 135 is written as 0.0.
+CPI_HD void condense_separator(const double *Hp, const double *Hn, const double *Pr, int damped, double lam, int diagonal, double *out) {
+    for (int j = 0; j < 16; j++)
+        for (int i = 0; i < 15 && i <= j; i++) {
+            double x = Pr ? Pr[tri(j) + i] : 0.0;
+            if (damped && i == j) {
+                const double d = ((Hp ? Hp[tri(15 + j) + 15 + j] : 0.0) + (Hn ? Hn[tri(j) + j] : 0.0)) + (Pr ? Pr[tri(j) + j] : 0.0);
+                x = diagonal ? fma(lam, d, x) : x + lam;
+            }
+            out[tri(j) + i] = x;
+        }
+    out[PRIOR_D - 1] = 0.0;
+}
+// Back into the interiors of a segment of nf factors, t = nf - 1 .. 1: t_k = y_k - sum_c Wa[k][c] da[c] - sum_c Wn[k][c] dn[c] (c
+// ascending, fused, Wa first), then the solve's substitution with R.  da / db: the delta rows of the two ends; ws / delta from the left
+// end on, as condense_segment has them (the rows of the ends are not written).
+CPI_HD void expand_segment(int nf, const double *ws, const double *da, const double *db, double *delta) {
+    const double *dn = db;
+    for (int s = nf - 1; s >= 1; s--) {
+        const double *rec = ws + (long long)s * CS_D;
+        double t[15], *x = delta + (long long)s * 15;
+        for (int k = 0; k < 15; k++) {
+            t[k] = rec[row_off(k) + 15 - k];
+            for (int c = 0; c < 15; c++) t[k] = fma(-da[c], rec[CS_A + k * 15 + c], t[k]);
+            for (int c = 0; c < 15; c++) t[k] = fma(-dn[c], rec[WS_R + k * 15 + c], t[k]);
+        }
+        for (int k = 14; k >= 0; k--) {
+            x[k] = t[k] * rec[row_off(k)];
+            for (int i = 0; i < k; i++) t[i] = fma(-x[k], rec[row_off(i) + k - i], t[i]);
+        }
+        dn = x;
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // The Levenberg-Marquardt step per chain (cpi_lm_kernels.hpp; tests/hostsim/hostsim_lm.cpp is the host restatement): the prior at the
 // current states with its cost, the objective of a chain, and the decision.

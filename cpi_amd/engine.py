@@ -1494,6 +1494,154 @@ class Engine:
         return out
 
 
+    # ------------------------------------------------------------------ long chains: segments condensed in parallel along the chain
+    def chain_condense_states(self, G, K):
+        """Gr, the reduced states of a chain slot of G states cut into segments of K factors (cpi_chain_condense_states)."""
+        return int(self.lib.cpi_chain_condense_states(int(G), int(K)))
+
+    def chain_condense_workspace_doubles(self, S):
+        """Doubles of the workspace of chain_condense for S states (cpi_chain_condense_workspace_doubles)."""
+        return int(self.lib.cpi_chain_condense_workspace_doubles(int(S)))
+
+    def chain_condense_buffers(self, C, G, S, K, cuda=True):
+        """Every buffer chain_solve_segmented needs for C chains of at most G states over S state rows at segment length K, as a dict
+        (allocate once, pass as buffers=: the three calls then allocate nothing and capture into a graph)."""
+        dev = self.device if cuda else "cpu"
+        Gr = self.chain_condense_states(G, K)
+        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+        i32 = lambda n: torch.zeros((n,), dtype=torch.int32, device=dev)
+        return dict(rhess=f64(C * (Gr - 1), 496), rprior=f64(C * Gr, 136), rcount=i32(C), seg_status=i32(C * (Gr - 1)),
+                    workspace=f64(self.chain_condense_workspace_doubles(S)), rdelta=f64(C * Gr, 15), status=i32(C),
+                    solve_workspace=f64(self.chain_solve_workspace_doubles(C * Gr)))
+
+    def _condense_args(self, hess, K, C, G, first, count, ffirst, prior, lam, damping, S, rhess, rprior, rcount, status, workspace, cuda):
+        where = "CUDA" if cuda else "CPU"
+        dev = self.device if cuda else "cpu"
+        assert damping in self.DAMPING, "damping: 'identity' or 'diagonal'"
+        assert int(K) >= 1, "K: the factors of a segment, >= 1"
+        C = self._chain_ranges(C, G, first, count, ffirst, cuda)
+        G, K = int(G), int(K)
+        if hess is not None:
+            self._trial_tensor(hess, 496, cuda, "hess")
+        if prior is not None:
+            self._trial_tensor(prior, 136, cuda, "prior")
+        S = int(S) if S is not None else (prior.shape[0] if prior is not None else C * G)
+        assert prior is None or prior.shape[0] == S, "prior: [S, 136]"
+        if lam is not None:
+            if not torch.is_tensor(lam):
+                lam = torch.full((C,), float(lam), dtype=torch.float64, device=dev)
+            elif lam.numel() == 1 and C != 1:
+                lam = lam.reshape(1).expand(C).contiguous()      # torch ops on the tensor's device: no host read
+            lam = lam.reshape(-1)
+            assert lam.dtype == torch.float64 and lam.is_contiguous() and lam.is_cuda == cuda and lam.shape == (C,), \
+                "lam: a number, or a float64 %s tensor with one element or C" % where
+        Gr = self.chain_condense_states(G, K)
+        if rhess is None:
+            rhess = torch.empty((C * (Gr - 1), 496), dtype=torch.float64, device=dev)
+        if rprior is None:
+            rprior = torch.empty((C * Gr, 136), dtype=torch.float64, device=dev)
+        if rcount is None:
+            rcount = torch.zeros((C,), dtype=torch.int32, device=dev)
+        self._trial_tensor(rhess, 496, cuda, "rhess", C * (Gr - 1))
+        self._trial_tensor(rprior, 136, cuda, "rprior", C * Gr)
+        for name, t, rows in (("rcount", rcount, C), ("status", status, C * (Gr - 1))):
+            assert t is None or (t.dtype == torch.int32 and t.is_contiguous() and t.is_cuda == cuda and t.shape == (rows,)), \
+                "%s: a contiguous int32 %s tensor [%d]" % (name, where, rows)
+        need = self.chain_condense_workspace_doubles(S)
+        if workspace is None:
+            workspace = torch.empty((need,), dtype=torch.float64, device=dev)
+        assert (workspace.dtype == torch.float64 and workspace.is_cuda == cuda and workspace.is_contiguous() and workspace.dim() == 1
+                and workspace.numel() >= need), "workspace: %s float64, chain_condense_workspace_doubles(S) elements" % where
+        F = hess.shape[0] if hess is not None else 0
+        return C, G, S, F, K, lam, Gr, rhess, rprior, rcount, workspace
+
+    def chain_condense(self, hess, K, C=None, G=None, first=None, count=None, ffirst=None, prior=None, lam=None, damping="identity", S=None,
+                       rhess=None, rprior=None, rcount=None, status=None, workspace=None):
+        """cpi_chain_condense_batch: every chain cut into segments of K factors and the states between the two ends of each segment
+        eliminated, one 16-lane group per segment -- parallel ALONG the chain.  hess, C, G, first, count, ffirst, prior, lam, damping:
+        those of chain_solve (the damping is baked into the reduced system).  Returns (rhess [C (Gr - 1), 496], rprior [C Gr, 136],
+        rcount [C] int32, Gr, workspace): the reduced chains in the tile layout, for chain_solve(rhess, C=C, G=Gr, count=rcount,
+        prior=rprior) with lam=None, and the records chain_expand reads.  S (the state rows) comes from prior, else C * G.  status:
+        an int32 [C (Gr - 1)] tensor to fill, per segment slot (0; s + 1: the block of interior state s of the chain was not positive
+        definite; -1: the factor rows leave hess); such a segment's rhess row is NaN.  Rows of reduced slots beyond rcount[c] are not
+        written.  Pass rhess, rprior, rcount and workspace (chain_condense_workspace_doubles(S) elements) for graph capture.
+        Asynchronous."""
+        C_, G_, S_, F, K_, lam, Gr, rhess, rprior, rcount, workspace = self._condense_args(
+            hess, K, C, G, first, count, ffirst, prior, lam, damping, S, rhess, rprior, rcount, status, workspace, True)
+        self._sync_stream()
+        self._check(self.lib.cpi_chain_condense_batch(self.ctx, C_, G_, S_, F, _ptr(first), _ptr(count), _ptr(ffirst), _ptr(hess), _ptr(prior),
+                                                      _ptr(lam), self.DAMPING[damping], K_, _ptr(rhess), _ptr(rprior), _ptr(rcount),
+                                                      _ptr(status), _ptr(workspace)))
+        return rhess, rprior, rcount, Gr, workspace
+
+    def chain_condense_host(self, hess, K, C=None, G=None, first=None, count=None, ffirst=None, prior=None, lam=None, damping="identity",
+                            S=None, rhess=None, rprior=None, rcount=None, status=None, workspace=None):
+        """chain_condense on CPU tensors (cpi_chain_condense_batch_host): every chain's state and factor range is validated (CpiError
+        names the chain), synchronous, the device form's bits; the workspace comes back as a CPU tensor for chain_expand_host."""
+        C_, G_, S_, F, K_, lam, Gr, rhess, rprior, rcount, workspace = self._condense_args(
+            hess, K, C, G, first, count, ffirst, prior, lam, damping, S, rhess, rprior, rcount, status, workspace, False)
+        self._sync_stream()
+        self._check(self.lib.cpi_chain_condense_batch_host(self.ctx, C_, G_, S_, F, _ptr(first), _ptr(count), _ptr(ffirst), _ptr(hess),
+                                                           _ptr(prior), _ptr(lam), self.DAMPING[damping], K_, _ptr(rhess), _ptr(rprior),
+                                                           _ptr(rcount), _ptr(status), _ptr(workspace)))
+        return rhess, rprior, rcount, Gr, workspace
+
+    def _expand_args(self, rdelta, workspace, K, C, G, first, count, out, S, cuda):
+        where = "CUDA" if cuda else "CPU"
+        assert int(K) >= 1, "K: the factors of a segment, >= 1"
+        C = self._chain_ranges(C, G, first, count, None, cuda)
+        G, K = int(G), int(K)
+        Gr = self.chain_condense_states(G, K)
+        self._trial_tensor(rdelta, 15, cuda, "rdelta", C * Gr)
+        S = int(S) if S is not None else (out.shape[0] if out is not None else C * G)
+        if out is None:
+            # rows of no chain are not written: they read NaN rather than whatever the allocator left there
+            out = torch.full((S, 15), float("nan"), dtype=torch.float64, device=self.device if cuda else "cpu")
+        self._trial_tensor(out, 15, cuda, "out", S)
+        assert (workspace.dtype == torch.float64 and workspace.is_cuda == cuda and workspace.is_contiguous() and workspace.dim() == 1
+                and workspace.numel() >= self.chain_condense_workspace_doubles(S)), \
+            "workspace: the %s float64 workspace of chain_condense" % where
+        return C, G, S, K, out
+
+    def chain_expand(self, rdelta, workspace, K, C=None, G=None, first=None, count=None, out=None, S=None):
+        """cpi_chain_expand_batch: the reduced solve's delta rows rdelta [C Gr, 15] copied to the segment ends and substituted back into
+        the interiors of every segment, one 16-lane group per segment.  workspace, K, C, G, first, count: those of the chain_condense
+        that wrote the workspace.  Returns delta [S, 15] (S from out, else C * G); rows of no chain are not written (NaN in a tensor
+        this call allocates); a chain whose reduced solve failed is NaN in every row.  Asynchronous."""
+        C_, G_, S_, K_, out = self._expand_args(rdelta, workspace, K, C, G, first, count, out, S, True)
+        self._sync_stream()
+        self._check(self.lib.cpi_chain_expand_batch(self.ctx, C_, G_, S_, _ptr(first), _ptr(count), K_, _ptr(rdelta), _ptr(workspace), _ptr(out)))
+        return out
+
+    def chain_expand_host(self, rdelta, workspace, K, C=None, G=None, first=None, count=None, out=None, S=None):
+        """chain_expand on CPU tensors (cpi_chain_expand_batch_host): every chain's state range is validated, synchronous, the device
+        form's bits."""
+        C_, G_, S_, K_, out = self._expand_args(rdelta, workspace, K, C, G, first, count, out, S, False)
+        self._sync_stream()
+        self._check(self.lib.cpi_chain_expand_batch_host(self.ctx, C_, G_, S_, _ptr(first), _ptr(count), K_, _ptr(rdelta), _ptr(workspace), _ptr(out)))
+        return out
+
+    def chain_solve_segmented(self, hess, K, C=None, G=None, first=None, count=None, ffirst=None, prior=None, lam=None, damping="identity",
+                              out=None, status=None, buffers=None):
+        """chain_solve for LONG chains, in three calls on the stream: chain_condense at segment length K, chain_solve of the reduced
+        chains (lam=None: the damping is in the reduced system), chain_expand.  Arguments as chain_solve.  Returns (delta [S, 15],
+        status [C] int32): the reduced solve's status -- 0, or j + 1 for the REDUCED state j whose block was not positive definite,
+        which is also what a failed or refused segment causes (buffers["seg_status"] says which); such a chain's rows are NaN.
+        buffers: the dict of chain_condense_buffers(C, G, S, K) (allocated when None); with it, a tensor lam, out and status given,
+        nothing is allocated and the three calls capture into one graph.  Asynchronous."""
+        C_ = self._chain_ranges(C, G, first, count, ffirst, True)
+        S = out.shape[0] if out is not None else (prior.shape[0] if prior is not None else C_ * int(G))
+        b = buffers if buffers is not None else self.chain_condense_buffers(C_, G, S, K)
+        if status is None:
+            status = b["status"]
+        rhess, rprior, rcount, Gr, ws = self.chain_condense(hess, K, C=C_, G=G, first=first, count=count, ffirst=ffirst, prior=prior, lam=lam,
+                                                            damping=damping, S=S, rhess=b["rhess"], rprior=b["rprior"], rcount=b["rcount"],
+                                                            status=b["seg_status"], workspace=b["workspace"])
+        self.chain_solve(rhess if Gr > 1 else None, C=C_, G=Gr, count=rcount, prior=rprior, out=b["rdelta"], status=status,
+                         workspace=b["solve_workspace"])
+        out = self.chain_expand(b["rdelta"], ws, K, C=C_, G=G, first=first, count=count, out=out, S=S)
+        return out, status
+
     # ------------------------------------------------------------------ the Levenberg-Marquardt step per chain
     LM_DEFAULTS = (0.1, 10.0, 0.0, 1e5, 1e-5, 1e-5)     # cpi_lm_params NULL: the defaults of GTSAM's LevenbergMarquardtParams
     LM_RUNNING, LM_CONVERGED, LM_GAVE_UP = 0, 1, 2
@@ -1940,6 +2088,21 @@ def chain_marginals(*args, **kw):
 def chain_marginalize(*args, **kw):
     """Engine.chain_marginalize on the default engine."""
     return default_engine().chain_marginalize(*args, **kw)
+
+
+def chain_condense(*args, **kw):
+    """Engine.chain_condense on the default engine."""
+    return default_engine().chain_condense(*args, **kw)
+
+
+def chain_expand(*args, **kw):
+    """Engine.chain_expand on the default engine."""
+    return default_engine().chain_expand(*args, **kw)
+
+
+def chain_solve_segmented(*args, **kw):
+    """Engine.chain_solve_segmented on the default engine."""
+    return default_engine().chain_solve_segmented(*args, **kw)
 
 
 def prior_relinearize(*args, **kw):

@@ -78,7 +78,11 @@ extern "C" {
                                chains: the diagonal and first off-diagonal blocks of the inverse, from the factor the solve
                                left in its workspace); cpi_chain_marginalize_batch, cpi_chain_marginalize_batch_host (the
                                oldest states of a chain eliminated into a prior on the first state that stays: the step of a
-                               fixed-lag smoother between two optimisations); cpi_prior_relinearize_batch,
+                               fixed-lag smoother between two optimisations); cpi_chain_condense_states,
+                               cpi_chain_condense_workspace_doubles, cpi_chain_condense_batch, cpi_chain_expand_batch,
+                               cpi_chain_condense_batch_host, cpi_chain_expand_batch_host (segment condensation: the interior
+                               states of every run of K factors eliminated in parallel into one factor row between its ends,
+                               and the back-substitution: parallelism along a chain); cpi_prior_relinearize_batch,
                                cpi_chain_cost_batch, cpi_chain_accept_batch, cpi_prior_relinearize_batch_host,
                                cpi_chain_cost_batch_host, cpi_chain_accept_batch_host (the Levenberg-Marquardt
                                step per chain on the device: the prior at the current states with its cost, the objective
@@ -946,7 +950,8 @@ int cpi_factor_cost_tri_batch(cpi_ctx *ctx, int32_t model, const double grav[3],
  * A chain's bits depend on its own data only, not on C or on its position.  Chains that share states are the caller's error: the
  * contents are unspecified, no access goes out of bounds.  One kernel on the context's stream, no host synchronisation: capturable.
  * 16 lanes work on a chain, 4 chains share a wavefront; there is no parallelism ALONG a chain, so one long chain runs at the
- * latency of its states in sequence (profiles/chain_solve.md).
+ * latency of its states in sequence (profiles/chain_solve.md).  cpi_chain_condense_batch below cuts long chains into segments that
+ * are eliminated in parallel and hands this entry a short chain.
  * Refused before the context is looked at (CPI_ERR_INVALID): NULL hess when G > 1, NULL delta / workspace, negative sizes, G < 1 or
  * G > 2^31 - 1, a damping other than the two, any output that overlaps an input or another output ("overlaps" in cpi_last_error).  C == 0 is a
  * no-op. */
@@ -1035,6 +1040,70 @@ int cpi_chain_marginalize_batch(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, i
                                 const double *hess, const double *prior,
                                 int32_t M, const int32_t *drop,
                                 double *out, int32_t *status);
+
+/* Segment condensation: long chains solved in parallel ALONG the chain.  A run of consecutive IMU factors with the states between its
+ * two ends eliminated is again a 31 x 31 factor row between two states, in the packing of hess.  Every chain is cut into segments of
+ * K factors; each segment's interior states are eliminated by a 16-lane group of its own (cpi_chain_condense_batch); the short
+ * reduced chain of segment ends goes to cpi_chain_solve_batch as it is; and the result is substituted back into the interiors, again
+ * one group per segment (cpi_chain_expand_batch).  A chain of 549 states at K = 23 is 24 independent eliminations of 22 states, one
+ * solve of 25 states and 24 independent back-substitutions, where the solve alone walks 549 dependent steps forward and 549 back.
+ * Replaces: nothing in the reference tree (GTSAM's elimination ordering is absent from it: PARITY UNPINNED); checked against the
+ * long-double dense solve of the definition of cpi_chain_solve_batch.  The reduced chain is also the exact linear counterpart of
+ * cpi_merge_batch -- the keyframe-rate system of an IMU-rate chain: cpi_chain_marginals_batch on it gives the full chain's cov rows
+ * at the kept states.  Out of scope: a segment option of the Levenberg-Marquardt loop; marginals of interior states (the reduced
+ * chain's marginals are the separators'); a K per chain or separators chosen by the caller; condensing the reduced chain again
+ * (recursion); any change of a default.
+ * Chains, H_k, Pr_s, D_s, U_s, g_s, lambda_c and the two dampings are those of cpi_chain_solve_batch, with the same clamps and the
+ * same refusal of factor rows that leave [0, F).
+ * LAYOUT.  The separators of a chain of n >= 2 states are the states 0, K, 2K, ... below n - 1, plus the last state n - 1; segment j
+ * spans the factors between separator j and separator j + 1 (the last one may be shorter than K); m = ceil((n - 1) / K) + 1 reduced
+ * states, m = n for n < 2.  Gr = cpi_chain_condense_states(G, K) = ceil((G - 1) / K) + 1 for G >= 2 and G below that.  The reduced
+ * arrays are in the tile layout that NULL first / ffirst mean to the solve: reduced state j of chain c is row c * Gr + j, reduced
+ * factor j is row c * (Gr - 1) + j.
+ * CONDENSE.  For a segment with left separator a and interiors t = a + 1 .. b - 1, M = H_a to begin with (blocks M_aa, M_at, M_tt, m_a,
+ * m_t and the scalar c), and per interior t
+ *     D  = M_tt + H_t[0:15, 0:15] + Pr_t[0:15, 0:15] + damping_t          g = m_t + H_t[0:15, 30] + Pr_t[0:15, 15]
+ *     L  = chol(D),  Wa = L^-1 M_at^T,  Wn = L^-1 U_t,  y = L^-1 g
+ *     M_aa -= Wa^T Wa     M_a,t+1 = -Wa^T Wn     M_t+1,t+1 = H_t[15:30, 15:30] - Wn^T Wn
+ *     m_a  -= Wa^T y      m_t+1   = H_t[15:30, 30] - Wn^T y      c += H_t[30, 30] - y^T y
+ * damping_t = lambda_c I, or lambda_c diag(D_t) with D_t the FULL block of the solve's definition (H_{t-1}[15:30, 15:30] + H_t[0:15,
+ * 0:15] + Pr_t: the diagonal WITHOUT the Schur term, as the solve takes it).  The final M is reduced factor row j.  The prior row of
+ * separator s is Pr_s with its damping on the diagonal -- lambda_c, or lambda_c diag(D_s) from H_{s-1}, H_s and Pr_s --, entry 135
+ * written as 0.0 (that of the input is never read); with lambda NULL the values pass through as they are.  The damping is baked in:
+ * the reduced chain is solved with lambda = NULL, and its system is exactly the Schur complement of the damped full system onto the
+ * separators, for both dampings.  A segment of one factor (K = 1, or a short tail) is H_k bit for bit.
+ * EXPAND.  Every separator's delta row is the reduced solve's row, copied; for the interiors t = b - 1 .. a + 1:
+ * delta_t = L_t^-T (y_t - Wa_t delta_a - Wn_t delta_{t+1}).
+ *   C G S F first count ffirst hess prior lambda damping: those of cpi_chain_solve_batch
+ *   K        >= 1, the factors of a segment, one value per call
+ *   rhess    [C * (Gr - 1)][496]; rprior [C * Gr][136]; rcount [C]: rcount[c] = m_c.  Rows of reduced slots beyond m_c are not written.
+ *   status   NULL or [C * (Gr - 1)], per segment slot: 0 the segment succeeded (a slot beyond the chain's segments: 0 as well); s + 1:
+ *            the block of interior state s (an index within the chain) had a pivot that is not > 0; -1: the chain's factor rows leave
+ *            [0, F).  Separators are not factorised here: the reduced solve reports them.  A failed or refused segment writes NaN
+ *            into its rhess row: the reduced solve then fails that chain and only that chain, and the expansion carries the NaN into
+ *            every row of the chain.
+ *   workspace  cpi_chain_condense_workspace_doubles(S) doubles of the caller's: one record of 585 doubles per state, indexed by state
+ *            -- L's triangle with the reciprocal pivots and y as the solve stores them, then Wn, then Wa.  Only the records of interior
+ *            states are written or read.
+ *   rdelta   [C * Gr][15]: the delta of the reduced solve;  delta [S][15]: rows of no chain are not written.
+ * The caller runs cpi_chain_condense_batch, then cpi_chain_solve_batch(ctx, C, Gr, C * Gr, C * (Gr - 1), NULL, rcount, NULL, rhess,
+ * rprior, NULL, damping, rdelta, rstatus, a solve workspace for C * Gr states), then cpi_chain_expand_batch with the C, G, S, first,
+ * count and K of the condense.  A chain's bits depend on its own data and on K only, not on C or on its position.  One kernel each on
+ * the context's stream, 16 lanes per segment and 4 segments per wavefront; the library allocates nothing and reads nothing back:
+ * both are capturable, and a capture of the three calls is a chain without parallel branches (profiles/chain_condense.md).
+ * Refused before the context is looked at (CPI_ERR_INVALID): negative sizes, G < 1 or G > 2^31 - 1, K < 1, a damping other than the
+ * two, NULL hess or rhess when G > 1, NULL rprior / rcount / workspace (condense), NULL rdelta / workspace / delta (expand), any
+ * output that overlaps an input or another output ("overlaps" in cpi_last_error).  C == 0 is a no-op. */
+int64_t cpi_chain_condense_states(int64_t G, int64_t K);
+size_t cpi_chain_condense_workspace_doubles(int64_t S);
+int cpi_chain_condense_batch(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_t F,
+                             const int64_t *first, const int32_t *count, const int64_t *ffirst,
+                             const double *hess, const double *prior, const double *lambda, int32_t damping, int64_t K,
+                             double *rhess, double *rprior, int32_t *rcount,
+                             int32_t *status, double *workspace);
+int cpi_chain_expand_batch(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S,
+                           const int64_t *first, const int32_t *count, int64_t K,
+                           const double *rdelta, const double *workspace, double *delta);
 
 /* The Levenberg-Marquardt step PER CHAIN, without the host looking at anything: the loop linearise -> relinearise the prior -> solve
  * -> retract -> cost -> accept closes on the device.  Replaces: the outer loop of GTSAM's
@@ -1456,6 +1525,19 @@ int cpi_chain_marginalize_batch_host(cpi_ctx *ctx, int64_t C, int64_t G, int64_t
                                      const double *hess, const double *prior,
                                      int32_t M, const int32_t *drop,
                                      double *out, int32_t *status);
+
+/* cpi_chain_condense_batch and cpi_chain_expand_batch from host memory: every pointer a host pointer, synchronous; the device forms'
+ * bits.  Every chain's state range (condense: and factor range) is validated first as in cpi_chain_solve_batch_host, and the text
+ * names the chain.  The workspace is a HOST array too: workspace_out (NULL: not wanted) receives the records the condense left, and
+ * the expand form takes that array.  Rows that are not written keep the caller's values. */
+int cpi_chain_condense_batch_host(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S, int64_t F,
+                                  const int64_t *first, const int32_t *count, const int64_t *ffirst,
+                                  const double *hess, const double *prior, const double *lambda, int32_t damping, int64_t K,
+                                  double *rhess, double *rprior, int32_t *rcount,
+                                  int32_t *status, double *workspace_out);
+int cpi_chain_expand_batch_host(cpi_ctx *ctx, int64_t C, int64_t G, int64_t S,
+                                const int64_t *first, const int32_t *count, int64_t K,
+                                const double *rdelta, const double *workspace, double *delta);
 
 /* cpi_prior_relinearize_batch, cpi_chain_cost_batch and cpi_chain_accept_batch from host memory: every pointer a host pointer (idx
  * too), synchronous; the device forms' bits.  The outputs and in/out arrays travel up before the kernel, so that what nobody writes
